@@ -15,11 +15,15 @@ ppr order 10 alpha 0.2 rmax 1e-5 top-k 32 (scripts/run_mag.sh:7 of the reference
 HIP; under `torch.distributed.run` (WORLD_SIZE set) it is one of the ranks.  N = 1 runs the
 same rank code in-process.
 
-Prints ONE JSON line on rank 0 (see the driver contract in the task statement), carrying
-`roofline` (HBM, algorithmic bytes of SURVEY.md 8d / kernel time from HIP events on the
-launch stream), `issue_bound` (edge inserts per clock and CU against the measured LDS-atomic
-insert rate), `host_api` (the metric's own clock: host buffers in -> host buffers out through
-gp_gfpush, N = 1) and, at N = 1, `cpu_baseline` (the CPU checker timed on this box's cores).
+Prints ONE JSON line on rank 0, carrying `roofline` (HBM, algorithmic bytes of SURVEY.md 8d /
+kernel time from HIP events on the launch stream) and `issue_bound` (edge inserts per clock and
+CU against the measured LDS-atomic insert rate), both derived from the timed steps' own counters.
+
+A plain run does only what that line needs: set up, warm up, time `--steps` steps, write the
+last step's rows if `--dump-outputs DIR` is given, print.  `--full` adds the measurements that
+take runs of their own (N = 1): `cold_call` (a fresh child process), `host_api` (the metric's
+own clock: host buffers in -> host buffers out through gp_gfpush), `next_rows` (the
+augmentation / propagation kernels) and `cpu_baseline` (the CPU checker timed on the host).
 """
 from __future__ import annotations
 
@@ -58,6 +62,67 @@ WORKLOADS = {
 
 # S of the reference's ONE call per process (model.py:244-248 with the shipped --unlabel_num)
 REFERENCE_S = {"mag": 10400, "amazon2m": 12350, "reddit": 12050, "pubmed": 1559, "cora": 1639, "small": 2048}
+
+# --dump-outputs writes at most this many bytes (the .npy headers fit in what is left of 64 MB)
+DUMP_BUDGET_BYTES = 60 * 2**20
+
+
+def host_threads() -> int:
+    """CPU threads this process may use: OMP_NUM_THREADS when the environment sets it, else the CPUs it may run on
+    (os.cpu_count() counts the whole machine, and a pool sized by it only slows itself down where the process gets fewer)."""
+    try:
+        n = int(os.environ.get("OMP_NUM_THREADS", ""))
+        if n > 0:
+            return n
+    except ValueError:
+        pass
+    try:
+        return len(os.sched_getaffinity(0)) or 1
+    except (AttributeError, OSError):
+        return os.cpu_count() or 1
+
+
+# values this close (relative) count as one: the kernel's fp64 atomic sums differ from run to run in the last bits
+TIE_RTOL = 1e-12
+
+
+def canonical_rows(row, col, val, filled, K: int, rtol: float = TIE_RTOL):
+    """The part of a batch of top-K rows that the computation determines, in an order that does not depend on the launch.
+    The kernel returns a row's set in no fixed slot order, and it breaks ties at the K-th value by the order in which its
+    atomics land, while those sums themselves jitter in the last bits: on the MAG line ~1 % of the rows hold a different
+    member of a K-th-value tie group from one run to the next.  So: slots by value, descending; values within `rtol` form
+    a group, ordered by column; in a full row (filled == K) the group of the K-th value has col -1 (which of the tied
+    nodes is kept is not determined), its values stay.  Slots at or past `filled` are 0.  Returns float64 (rows, K) arrays."""
+    S = len(filled)
+    keep = np.arange(K)[None, :] < filled[:, None]
+    r, c, v = (np.where(keep, a.reshape(S, K), 0) for a in (row, col, val))
+    o = np.argsort(-v, axis=1, kind="stable")                            # filled slots (v > 0) first, largest value first
+    r, c, v = (np.take_along_axis(a, o, axis=1) for a in (r, c, v))
+    new_group = v[:, :-1] - v[:, 1:] > rtol * v[:, :-1]
+    grp = np.concatenate([np.zeros((S, 1), np.int64), np.cumsum(new_group, axis=1)], axis=1)
+    grp = np.where(keep, grp, K + 1)
+    o = np.lexsort((c, grp), axis=1)                                      # within a group: by column
+    r, c, v, grp = (np.take_along_axis(a, o, axis=1) for a in (r, c, v, grp))
+    c = np.where((filled == K)[:, None] & (grp == grp[:, K - 1:K]), -1, c)
+    return r.astype(np.float64), c.astype(np.float64), v.astype(np.float64)
+
+
+def dump_outputs(out_dir: str, row, col, val, filled, K: int) -> None:
+    """What the last timed step handed its caller, as float64 DIR/{row,col,val,filled}.npy in the form of canonical_rows
+    (row / col / val are (rows, K)).  Above DUMP_BUDGET_BYTES a fixed, seeded sample of rows is written, their positions in
+    sample_rows.npy."""
+    filled = filled.cpu().numpy().astype(np.int64)
+    S = len(filled)
+    r, c, v = canonical_rows(*(t[:S * K].cpu().numpy() for t in (row, col, val)), filled, K)
+    arrays = {"row": r, "col": c, "val": v, "filled": filled.astype(np.float64)}
+    max_rows = DUMP_BUDGET_BYTES // (8 * (3 * K + 1))
+    if S > max_rows:
+        pick = np.sort(np.random.default_rng(0).choice(S, max_rows, replace=False))
+        arrays = {name: a[pick] for name, a in arrays.items()}
+        arrays["sample_rows"] = pick.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 def kernel_source_sha16() -> str:
@@ -312,6 +377,10 @@ def parse_args():
     ap.add_argument("--diag-flags", type=int, default=0, help="GRANDPLUS_DIAG=1 builds only: bit 0 skips TOP-K (instruction attribution)")
     ap.add_argument("--no-cold-call", action="store_true", help="skip the cold_call block (a fresh child process: constructor + one reference-sized call)")
     ap.add_argument("--cold-call-child", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--full", action="store_true", help="also run the side measurements (cold_call, host_api, next_rows, cpu_baseline; "
+                    "N = 1); a plain run times the steps and prints the headline line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the rows of the last step "
+                    "as float64 DIR/<name>.npy (at most 64 MB: a fixed, seeded sample of rows above that)")
     return ap.parse_args()
 
 
@@ -376,7 +445,7 @@ def run_rank(args, platform=CudaPlatform, cold=None) -> int:
     recipe = RECIPES[rkey]
     coef = recipe.coef()
     K = recipe.top_k
-    threads = max(1, (os.cpu_count() or 1) // world)
+    threads = max(1, host_threads() // world)
     t0 = time.perf_counter()
     indptr, indices = load_graph(source, threads)
     n_nodes = len(indptr) - 1
@@ -488,6 +557,10 @@ def run_rank(args, platform=CudaPlatform, cold=None) -> int:
         km[rank] = avg_ms
         dist.all_reduce(km, op=dist.ReduceOp.SUM)
         per_rank_ms = [round(float(x), 3) for x in km.tolist()]
+    if args.dump_outputs and rank == 0:
+        from grand_plus_amd.sharded import unpack_gathered
+        got = (packed.row, packed.col, packed.val, packed.filled) if world == 1 else unpack_gathered(gathered, world, per, K, S_step)
+        dump_outputs(args.dump_outputs, *got, K)
 
     if rank == 0:
         rows_total = S_step * args.steps
@@ -505,10 +578,10 @@ def run_rank(args, platform=CudaPlatform, cold=None) -> int:
             "prewarm_step_ms_median": None if pre_med is None else round(pre_med, 3),
             "anomaly": bool(pre_med is not None and world == 1 and avg_ms > 1.5 * pre_med),
             "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "f64",
+            "scaling": "weak", "vs_baseline": None, "dtype": "f64", "full": bool(args.full),
             "data": "synthetic" if source.startswith("synth:") else "fixture graph (tests/golden), seeds cycled",
             "value_clock": "inputs resident in HBM when the timed region starts (task contract); the metric's own clock -- host buffers in -> "
-                           "host buffers out through gp_gfpush, PCIe included -- is host_api.rows_per_s in this same line",
+                           "host buffers out through gp_gfpush, PCIe included -- is host_api.rows_per_s in the line of a --full run",
             "rccl_ranks": rccl_ranks, "kernel_ms_per_rank": per_rank_ms,
             "config": {"workload": desc, "recipe": f"{recipe.prop_mode} order {recipe.order} alpha {recipe.alpha} rmax {recipe.rmax} K {K}",
                        "seeds_per_gpu": per, "rows_per_step": S_step, "n_nodes": n_nodes, "nnz": int(len(indices)),
@@ -573,7 +646,7 @@ def run_rank(args, platform=CudaPlatform, cold=None) -> int:
             names = ["agg_init", "agg_insert", "agg_scan", "sel_hist", "sel_pick", "sel_compact", "sel_collect", "final"]
             line["detail"]["diag_topk_sub_share"] = {n: round(stats["diag_sub"][i] / tot, 3) for i, n in enumerate(names)}
             line["detail"]["diag_counts_per_row"] = {"agg_parts": round(stats["diag_sub"][8] / stats["rows"], 2), "sel_passes_hbm": round(stats["diag_sub"][9] / stats["rows"], 2), "sel_passes_lds": round(stats["diag_sub"][10] / stats["rows"], 2)}
-        if world == 1 and not args.no_host_api:
+        if args.full and world == 1 and not args.no_host_api:
             # The metric's own clock: the gfpush_omp call, host buffers in -> host buffers out
             # (model.py:268), through gp_gfpush: seed upload, kernel, one packed D2H, scatter of the v > 0 slots.
             hs = all_seeds[args.warmup * S_step:args.warmup * S_step + per].astype(np.int64)
@@ -591,9 +664,9 @@ def run_rank(args, platform=CudaPlatform, cold=None) -> int:
                                 "what": "Graph.gfpush_omp (gp_gfpush): int64 seeds on the host -> numpy row/col/value filled in place, median of 3 calls after one warm-up"}
         if cold is not None:
             line["cold_call"] = cold
-        if world == 1 and not args.no_next_rows:
+        if args.full and world == 1 and not args.no_next_rows:
             line["next_rows"] = next_rows(graph, packed, per, K, n_nodes, len(indices), dev)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cb = cpu_baseline(indptr, indices, all_seeds[args.warmup * S_step:], recipe, args.cpu_budget_s)
             line["cpu_baseline"] = cb
             # like clocks: the CPU number is host buffers in -> host buffers out, so it is compared with the host-API rate
@@ -616,7 +689,7 @@ def main():
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus))
     cold = None
-    if "WORLD_SIZE" not in os.environ and args.gpus == 1 and not args.no_cold_call:
+    if args.full and "WORLD_SIZE" not in os.environ and args.gpus == 1 and not args.no_cold_call:
         cold = cold_call(args.workload)                      # (a child process, started before this one touches HIP)
     sys.exit(run_rank(args, cold=cold))
 

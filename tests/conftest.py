@@ -8,8 +8,9 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 
-# generated synthetic graphs are kept for the session (the MAG shape is 0.8 GB and several tests use it)
-os.environ.setdefault("GRANDPLUS_SYNTH_CACHE", os.path.join("/dev/shm" if os.path.isdir("/dev/shm") else "/tmp", "gp_synth_tests"))
+# generated synthetic graphs are kept for the session (the MAG shape is 0.8 GB and several tests use it); one directory per
+# user, so that a cache another account left behind is neither read nor in the way
+os.environ.setdefault("GRANDPLUS_SYNTH_CACHE", os.path.join("/dev/shm" if os.path.isdir("/dev/shm") else "/tmp", f"gp_synth_tests-{os.getuid()}"))
 
 
 def pytest_configure(config):

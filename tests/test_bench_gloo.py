@@ -111,3 +111,95 @@ def test_bench_has_no_cpu_path_of_its_own(monkeypatch):
     assert not hasattr(bench, "_GRAPH_FACTORY") and "GRANDPLUS_BENCH_DEVICE" not in open(bench.__file__).read()
     monkeypatch.setattr(sys, "argv", ["bench.py", "--workload", "pubmed", "--seeds-per-gpu", "8", "--steps", "1", "--warmup", "0"])
     assert bench.run_rank(bench.parse_args()) == 3
+
+
+def _plain_run(tmp_path, monkeypatch, capsys, extra=()):
+    """One rank, no launcher, the CPU stand-in platform: returns the JSON line and the dump directory."""
+    sys.path.insert(0, ROOT)
+    import bench
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    out = tmp_path / "dump"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--prewarm", "0", "--workload", "pubmed",
+                                      "--seeds-per-gpu", "64", "--dump-outputs", str(out)] + list(extra))
+    assert bench.run_rank(bench.parse_args(), platform=_CpuPlatform) == 0
+    lines = [ln for ln in capsys.readouterr().out.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    return bench, json.loads(lines[0]), out
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_last_steps_rows(tmp_path, monkeypatch, capsys):
+    """A plain run prints the headline line without the --full blocks, and --dump-outputs writes exactly the rows the last
+    timed step computed, in the canonical form of bench.canonical_rows, as float64 .npy files."""
+    bench, line, out = _plain_run(tmp_path, monkeypatch, capsys)
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["full"] is False
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype"):
+        assert k in line
+    assert not {"host_api", "cold_call", "next_rows", "cpu_baseline"} & set(line)
+    from grand_plus_amd import RECIPES
+    from oracle import pyoracle
+    source, rkey, _ = bench.WORKLOADS["pubmed"]
+    recipe = RECIPES[rkey]
+    K = recipe.top_k
+    indptr, indices = bench.load_graph(source, 1)
+    seeds = bench.make_seeds(source, len(indptr) - 1, 64 * 4)[3 * 64:]          # step 4 of 4 (1 warm-up + 3 timed)
+    r, c, v, _ = pyoracle.gfpush(indptr, indices, seeds, recipe.coef(), recipe.rmax, K)
+    got = {n: np.load(out / f"{n}.npy") for n in ("row", "col", "val", "filled")}
+    assert sorted(os.listdir(out)) == ["col.npy", "filled.npy", "row.npy", "val.npy"]
+    assert all(a.dtype == np.float64 for a in got.values())
+    nf = (v.reshape(64, K) > 0).sum(1)
+    keep = np.arange(K)[None, :] < nf[:, None]
+    np.testing.assert_array_equal(got["filled"], nf)
+    for i in range(64):
+        n = nf[i]
+        exp_c, exp_v = c[i * K:i * K + n], v[i * K:i * K + n]
+        np.testing.assert_array_equal(got["val"][i, :n], np.sort(exp_v)[::-1])          # (this row set has no near-ties)
+        np.testing.assert_array_equal(got["row"][i, :n], r[i * K:i * K + n])
+        kth = exp_v.min()
+        tied = np.abs(exp_v - kth) <= bench.TIE_RTOL * kth
+        if n == K:                                                          # a full row: the K-th value's tie group has no column
+            assert (got["col"][i, :n] == -1).sum() == tied.sum()
+            np.testing.assert_array_equal(np.sort(got["col"][i, :n][got["col"][i, :n] >= 0]), np.sort(exp_c[~tied]))
+        else:
+            np.testing.assert_array_equal(np.sort(got["col"][i, :n]), np.sort(exp_c))
+        for name in ("row", "col", "val"):
+            assert not got[name][i, n:].any()
+    assert (np.diff(np.where(keep, got["val"], 0), axis=1) <= 0).all()
+
+
+def test_bench_dump_form_does_not_depend_on_slot_order_rounding_or_tie_choice():
+    """Two launches that return the same rows up to slot order, last-bit noise in the sums and which member of a K-th-value
+    tie group is kept dump the same arrays up to that noise; a real difference in a determined column still shows."""
+    sys.path.insert(0, ROOT)
+    import bench
+    K = 4
+    filled = np.array([4, 4, 2])
+    row = np.repeat([0, 1, 2], K)
+    a_col, a_val = np.array([5, 3, 7, 1, 10, 11, 12, 13, 8, 6, 99, 99]), np.array([.5, .3, .1, .2, .4, .3, .2, .1, .2, .3, 9, 9])
+    b_col = np.array([9, 1, 3, 5, 13, 12, 11, 10, 6, 8, 42, 42])           # row 0 keeps node 9 instead of the tied node 7
+    b_val = np.array([.1 * (1 + 1e-15), .2, .3 * (1 - 2e-15), .5, .1, .2, .3, .4, .3, .2, 7, 7])
+    got_a = bench.canonical_rows(row, a_col, a_val, filled, K)
+    got_b = bench.canonical_rows(row, b_col, b_val, filled, K)
+    for x, y in zip(got_a, got_b):
+        assert x.dtype == np.float64 and x.shape == (3, K)
+        np.testing.assert_allclose(x, y, rtol=1e-14, atol=0)
+    np.testing.assert_array_equal(got_a[1], [[5, 3, 1, -1], [10, 11, 12, -1], [6, 8, 0, 0]])
+    np.testing.assert_array_equal(got_a[2], [[.5, .3, .2, .1], [.4, .3, .2, .1], [.3, .2, 0, 0]])
+    b_col[1] = 2                                                            # a determined column that differs
+    assert not np.array_equal(bench.canonical_rows(row, b_col, b_val, filled, K)[1], got_a[1])
+
+
+def test_bench_dump_keeps_a_fixed_sample_under_the_byte_budget(tmp_path, monkeypatch, capsys):
+    """Above the budget the dump is a seeded sample of rows, the same from run to run, with the rows' positions beside it."""
+    import bench
+    K = 16                                                                  # the pubmed recipe's top-k
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 8 * (3 * K + 1) * 20)
+    _, _, out = _plain_run(tmp_path, monkeypatch, capsys)
+    full = tmp_path / "unsampled"
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 64 * 2**20)
+    _plain_run(tmp_path, monkeypatch, capsys, ["--dump-outputs", str(full)])
+    pick = np.load(out / "sample_rows.npy").astype(np.int64)
+    assert len(pick) == 20 and (np.diff(pick) > 0).all() and pick[-1] < 64
+    for n in ("row", "col", "val", "filled"):
+        np.testing.assert_array_equal(np.load(out / f"{n}.npy"), np.load(full / f"{n}.npy")[pick])
+    assert sum(os.path.getsize(out / f) for f in os.listdir(out)) < 64 * 2**20

@@ -27,7 +27,7 @@ python - <<PY
 import json, subprocess, sys
 out = {}
 for w, extra in (("mag", []), ("pubmed", []), ("reddit", []), ("cora", []), ("amazon2m", ["--seeds-per-gpu", "12350"])):
-    r = subprocess.run([sys.executable, "bench.py", "--workload", w] + extra, capture_output=True, text=True)
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--workload", w] + extra, capture_output=True, text=True)
     try:
         out[w] = json.loads(r.stdout.strip().splitlines()[-1])
     except Exception as e:
