@@ -29,6 +29,7 @@ EXPORTS = (
     "gp_propagate_features", "gp_internal_graph_csr", "gp_internal_diag_counters",
     "gp_graph_create_multi", "gp_graph_num_gpus", "gp_internal_multi_plan", "gp_internal_graph_acsr", "gp_graph_create_multi_on",
     "gp_seed_positions", "gp_batch_positions", "gp_internal_create_ms", "gp_internal_warm_device",
+    "gp_random_prop_coo_backward", "gp_random_prop_rows_backward", "gp_embedding_bag", "gp_embedding_bag_backward",
 )
 
 
@@ -134,6 +135,13 @@ def lib():
                                      ctypes.c_float, ctypes.c_int, ctypes.c_uint64, vp, vp, vp]
     _optional(L, "gp_seed_positions", [ctypes.c_int, vp, ctypes.c_int64, ctypes.c_int64, vp, vp, vp])
     _optional(L, "gp_batch_positions", [ctypes.c_int, vp, ctypes.c_int64, vp, ctypes.c_int64, vp, vp, vp])
+    i64, f32, u64 = ctypes.c_int64, ctypes.c_float, ctypes.c_uint64
+    _optional(L, "gp_random_prop_coo_backward", [ctypes.c_int, vp, i64, ctypes.c_int32, vp, vp, i64, f32, ctypes.c_int, u64, vp, vp, vp])
+    _optional(L, "gp_random_prop_rows_backward", [ctypes.c_int, vp, ctypes.c_int32, ctypes.c_int32, vp, vp, vp, ctypes.c_int32,
+                                                  vp, f32, ctypes.c_int, u64, vp, vp, i64, vp])
+    _bag = [ctypes.c_int, vp, i64, ctypes.c_int32, vp, i64, vp, vp, i64, vp, ctypes.c_int, vp, f32, ctypes.c_int, u64, vp, vp, vp, vp]
+    _optional(L, "gp_embedding_bag", _bag)
+    _optional(L, "gp_embedding_bag_backward", _bag)
     L.gp_propagate_features.restype = ctypes.c_int
     L.gp_propagate_features.argtypes = [vp, vp, ctypes.c_int32, vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, vp, vp]
     L.gp_internal_diag_counters.restype = ctypes.c_int

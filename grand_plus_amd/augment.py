@@ -11,6 +11,12 @@ Host-side mirror of `Grand_Plus.random_prop(feats, mat_scores, mat_idx, dropnode
 The reference's dropout draws from torch's global generator (`F.dropout`, `model.py:82`); here the
 keep decision of entry e is a counter-based RNG of (seed, e), or an explicit `keep` mask.  Both keep
 an entry with probability 1 - dropnode_rate and scale kept scores by 1/(1 - dropnode_rate).
+
+Both are differentiable with respect to the feature operand (`feats` / `features`) when grad mode is on
+and that tensor requires grad (MAG trains its embedding table through random_prop, model_mag.py:355-356).
+Scores, `val` and `keep` are constants, as in the reference, where they come from numpy
+(model_mag.py:342-343).  The backward kernels recompute the forward's mask from its seed.  Every other
+call takes the plain path: same launch, same output, no grad_fn.
 """
 from __future__ import annotations
 
@@ -34,12 +40,106 @@ def _check(t, dtype, name):
         raise TypeError(f"{name} must be a contiguous CUDA tensor of dtype {dtype}")
 
 
+def _new_seed():
+    return next(_seed_counter) * 0x9E3779B97F4A7C15 & (2**64 - 1)
+
+
+def _wants_grad(t):
+    import torch
+    return torch.is_grad_enabled() and t.requires_grad
+
+
+def _coo_forward(feats, mat_scores, mat_idx, n_out, dropnode_rate, training, seed, keep, stream):
+    import torch
+    M, F = feats.shape
+    out = torch.empty((n_out, F), dtype=torch.float32, device=feats.device)
+    rc = _native.lib().gp_random_prop_coo(
+        _dev_index(feats), feats.data_ptr(), M, F, mat_scores.data_ptr(), mat_idx.data_ptr(), n_out,
+        float(dropnode_rate), int(bool(training)), ctypes.c_uint64(seed), keep.data_ptr() if keep is not None else None,
+        out.data_ptr(), ctypes.c_void_p(stream))
+    _native.raise_for_status(rc)
+    return out
+
+
+def _rows_forward(features, col, val, filled, K, batch_rows, B, dropnode_rate, training, seed, keep, stream):
+    import torch
+    N, F = features.shape
+    out = torch.empty((B, F), dtype=torch.float32, device=features.device)
+    rc = _native.lib().gp_random_prop_rows(
+        _dev_index(features), features.data_ptr(), N, F, col.data_ptr(), val.data_ptr(),
+        filled.data_ptr() if filled is not None else None, int(K),
+        batch_rows.data_ptr() if batch_rows is not None else None, B,
+        float(dropnode_rate), int(bool(training)), ctypes.c_uint64(seed), keep.data_ptr() if keep is not None else None,
+        out.data_ptr(), ctypes.c_void_p(stream))
+    _native.raise_for_status(rc)
+    return out
+
+
+def _autograd_functions():
+    """The two torch.autograd.Function classes (built on first use: torch is imported lazily here)."""
+    global _CooFn, _RowsFn
+    if _CooFn is not None:
+        return _CooFn, _RowsFn
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    class CooFn(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, feats, mat_scores, mat_idx, n_out, dropnode_rate, training, seed, keep, stream):
+            ctx.save_for_backward(mat_scores, mat_idx, keep)
+            ctx.args = (feats.shape, n_out, dropnode_rate, training, seed)
+            return _coo_forward(feats, mat_scores, mat_idx, n_out, dropnode_rate, training, seed, keep, stream)
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, grad_out):
+            mat_scores, mat_idx, keep = ctx.saved_tensors
+            (M, F), n_out, p, training, seed = ctx.args
+            g = grad_out.contiguous()
+            grad = torch.empty((M, F), dtype=torch.float32, device=g.device)
+            rc = _native.lib().gp_random_prop_coo_backward(
+                _dev_index(g), g.data_ptr(), n_out, F, mat_scores.data_ptr(), mat_idx.data_ptr(), M,
+                float(p), int(bool(training)), ctypes.c_uint64(seed), keep.data_ptr() if keep is not None else None,
+                grad.data_ptr(), ctypes.c_void_p(torch.cuda.current_stream(g.device).cuda_stream))
+            _native.raise_for_status(rc)
+            return grad, None, None, None, None, None, None, None, None
+
+    class RowsFn(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, features, col, val, filled, K, batch_rows, B, dropnode_rate, training, seed, keep, stream):
+            ctx.save_for_backward(col, val, filled, batch_rows, keep)
+            ctx.args = (features.shape, K, B, dropnode_rate, training, seed)
+            return _rows_forward(features, col, val, filled, K, batch_rows, B, dropnode_rate, training, seed, keep, stream)
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, grad_out):
+            col, val, filled, batch_rows, keep = ctx.saved_tensors
+            (N, F), K, B, p, training, seed = ctx.args
+            g = grad_out.contiguous()
+            grad = torch.zeros((N, F), dtype=torch.float32, device=g.device)
+            rc = _native.lib().gp_random_prop_rows_backward(
+                _dev_index(g), g.data_ptr(), B, F, col.data_ptr(), val.data_ptr(),
+                filled.data_ptr() if filled is not None else None, int(K),
+                batch_rows.data_ptr() if batch_rows is not None else None,
+                float(p), int(bool(training)), ctypes.c_uint64(seed), keep.data_ptr() if keep is not None else None,
+                grad.data_ptr(), N, ctypes.c_void_p(torch.cuda.current_stream(g.device).cuda_stream))
+            _native.raise_for_status(rc)
+            return grad, None, None, None, None, None, None, None, None, None, None, None
+
+    _CooFn, _RowsFn = CooFn, RowsFn
+    return _CooFn, _RowsFn
+
+
+_CooFn = _RowsFn = None
+
+
 def random_prop(feats, mat_scores, mat_idx, dropnode_rate, training=True, seed=None, keep=None, stream=None):
     """Drop-in for `Grand_Plus.random_prop` (`model.py:80-87`) on CUDA tensors.
 
     feats [M, F] float32, mat_scores [M] float32, mat_idx [M] int64 sorted ascending (the order
     scipy's `.nonzero()` yields, `model.py:312`).  Returns [mat_idx[-1] + 1, F] float32.
-    `training` plays the role of `self.training`.
+    `training` plays the role of `self.training`.  Differentiable with respect to `feats`.
     """
     import torch
     _check(feats, torch.float32, "feats")
@@ -51,19 +151,15 @@ def random_prop(feats, mat_scores, mat_idx, dropnode_rate, training=True, seed=N
     if M == 0:
         return feats.new_zeros((0, F))
     n_out = int(mat_idx[-1].item()) + 1                                   # model.py:84 dim_size
-    out = torch.empty((n_out, F), dtype=torch.float32, device=feats.device)
     if keep is not None:
         _check(keep, torch.uint8, "keep")
     if seed is None:
-        seed = next(_seed_counter) * 0x9E3779B97F4A7C15 & (2**64 - 1)
+        seed = _new_seed()
     if stream is None:
         stream = torch.cuda.current_stream(feats.device).cuda_stream
-    rc = _native.lib().gp_random_prop_coo(
-        _dev_index(feats), feats.data_ptr(), M, F, mat_scores.data_ptr(), mat_idx.data_ptr(), n_out,
-        float(dropnode_rate), int(bool(training)), ctypes.c_uint64(seed), keep.data_ptr() if keep is not None else None,
-        out.data_ptr(), ctypes.c_void_p(stream))
-    _native.raise_for_status(rc)
-    return out
+    if _wants_grad(feats):                                                # gradient to feats only (model_mag.py:355)
+        return _autograd_functions()[0].apply(feats, mat_scores, mat_idx, n_out, dropnode_rate, training, seed, keep, stream)
+    return _coo_forward(feats, mat_scores, mat_idx, n_out, dropnode_rate, training, seed, keep, stream)
 
 
 def random_prop_rows(features, col, val, filled, K, batch_rows=None, dropnode_rate=0.5, training=True,
@@ -74,6 +170,8 @@ def random_prop_rows(features, col, val, filled, K, batch_rows=None, dropnode_ra
     filled int32 [S] as returned by `Graph.gfpush_device`; batch_rows int32 [B] = positions of the
     batch's seeds in the seed list (None = all S rows).  Returns [B, F] float32:
         out[b] = sum_k w_k X[col[r,k]] / (sum_k w_k + 1e-12),  r = batch_rows[b]
+    Differentiable with respect to `features` (the backward adds into a dense [N, F] gradient with fp32
+    atomics: not bitwise reproducible).
     """
     import torch
     _check(features, torch.float32, "features")
@@ -86,21 +184,15 @@ def random_prop_rows(features, col, val, filled, K, batch_rows=None, dropnode_ra
     if batch_rows is not None:
         _check(batch_rows, torch.int32, "batch_rows")
     B = S if batch_rows is None else batch_rows.numel()
-    out = torch.empty((B, F), dtype=torch.float32, device=features.device)
     if keep is not None:
         _check(keep, torch.uint8, "keep")
     if seed is None:
-        seed = next(_seed_counter) * 0x9E3779B97F4A7C15 & (2**64 - 1)
+        seed = _new_seed()
     if stream is None:
         stream = torch.cuda.current_stream(features.device).cuda_stream
-    rc = _native.lib().gp_random_prop_rows(
-        _dev_index(features), features.data_ptr(), N, F, col.data_ptr(), val.data_ptr(),
-        filled.data_ptr() if filled is not None else None, int(K),
-        batch_rows.data_ptr() if batch_rows is not None else None, B,
-        float(dropnode_rate), int(bool(training)), ctypes.c_uint64(seed), keep.data_ptr() if keep is not None else None,
-        out.data_ptr(), ctypes.c_void_p(stream))
-    _native.raise_for_status(rc)
-    return out
+    if _wants_grad(features):
+        return _autograd_functions()[1].apply(features, col, val, filled, K, batch_rows, B, dropnode_rate, training, seed, keep, stream)
+    return _rows_forward(features, col, val, filled, K, batch_rows, B, dropnode_rate, training, seed, keep, stream)
 
 
 def algorithmic_bytes(n_kept_entries: int, n_out: int, feat_dim: int) -> int:

@@ -179,6 +179,282 @@ random_prop_coo_kernel(const float* __restrict__ feats, int F, const float* __re
     }
 }
 
+// ---- Backward of random_prop.  Scores are constants (the reference builds them from numpy,
+// model_mag.py:342-343), so only the feature operand gets a gradient:
+//     d out[b,:] / d feats[e,:] = w'_e / (den_b + 1e-12),   b = idx[e]
+// w'_e and den_b are recomputed exactly as the forward computes them (same staging, same keep decision from
+// (seed, e) or d_keep, same sequential fp32 sum), so the backward applies the forward's mask without storing it.
+
+// COO form: a pure gather and stream.  Workgroup per output row b; every entry of the row's segment is
+// written (dropped entries get exact zeros), so every row of grad_feats is written.  No atomics.
+template <int VEC>
+__device__ __forceinline__ void scaled_rows_vec(const float* __restrict__ g_row, int F, const float* s_w, int n,
+                                                float inv, float* __restrict__ out_rows)
+{
+    typedef typename VecT<VEC>::type V;
+    const int FV = F / VEC;
+    for (int t = threadIdx.x; t < n * FV; t += kBlock) {
+        const int k = t / FV, f = (t - k * FV) * VEC;
+        const V g = *reinterpret_cast<const V*>(g_row + f);
+        const float* pg = reinterpret_cast<const float*>(&g);
+        const float w = s_w[k];
+        V o; float* po = reinterpret_cast<float*>(&o);
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) po[i] = (pg[i] * inv) * w;
+        *reinterpret_cast<V*>(out_rows + (size_t)k * F + f) = o;
+    }
+}
+
+__global__ void __launch_bounds__(kBlock)
+random_prop_coo_backward_kernel(const float* __restrict__ grad_out, int F, const float* __restrict__ scores,
+                                const long long* __restrict__ idx, long long n_entries, long long n_out,
+                                float p, int training, u64 seed, const unsigned char* __restrict__ keep,
+                                float* __restrict__ grad_feats)
+{
+    __shared__ float s_w[kStage];
+    __shared__ long long s_lo, s_hi;
+    const float scale = p < 1.0f ? 1.0f / (1.0f - p) : 0.0f;
+    for (long long b = blockIdx.x; b < n_out; b += gridDim.x) {
+        __syncthreads();
+        if (threadIdx.x < 2) {                        // the forward's segment search
+            const long long key = b + threadIdx.x;
+            long long lo = 0, hi = n_entries;
+            while (lo < hi) { const long long mid = (lo + hi) >> 1; if (idx[mid] < key) lo = mid + 1; else hi = mid; }
+            if (threadIdx.x == 0) s_lo = lo; else s_hi = lo;
+        }
+        __syncthreads();
+        const long long lo = s_lo, hi = s_hi;
+        const float* g_row = grad_out + (size_t)b * F;
+        if (hi - lo <= kStage) {
+            const int n = (int)(hi - lo);
+            for (int k = threadIdx.x; k < n; k += kBlock) {
+                const long long e = lo + k;
+                float w = scores[e];
+                if (training) w *= keep ? (keep[e] ? scale : 0.0f) : keep_scale(seed, (u64)e, p, scale);
+                s_w[k] = w;
+            }
+            __syncthreads();
+            float den = 0.0f;
+            for (int k = 0; k < n; ++k) den += s_w[k];                      // the forward's order
+            const float inv = 1.0f / (den + 1e-12f);
+            float* rows = grad_feats + (size_t)lo * F;
+            if ((F & 3) == 0)      scaled_rows_vec<4>(g_row, F, s_w, n, inv, rows);
+            else if ((F & 1) == 0) scaled_rows_vec<2>(g_row, F, s_w, n, inv, rows);
+            else                   scaled_rows_vec<1>(g_row, F, s_w, n, inv, rows);
+        } else {
+            float den = 0.0f;
+            for (long long e = lo; e < hi; ++e) {
+                float w = scores[e];
+                if (training) w *= keep ? (keep[e] ? scale : 0.0f) : keep_scale(seed, (u64)e, p, scale);
+                den += w;
+            }
+            const float inv = 1.0f / (den + 1e-12f);
+            for (long long e = lo; e < hi; ++e) {
+                float w = scores[e];
+                if (training) w *= keep ? (keep[e] ? scale : 0.0f) : keep_scale(seed, (u64)e, p, scale);
+                for (int f = threadIdx.x; f < F; f += kBlock) grad_feats[(size_t)e * F + f] = (g_row[f] * inv) * w;
+            }
+        }
+    }
+}
+
+// Fused form: grad_X[col[r,k], :] += w'_{r,k} / (den_b + 1e-12) * grad_out[b, :] into a caller-zeroed grad_X.
+// A node can occur in many rows (and twice in one row), so fp32 global atomics.  Each wave takes one staged
+// entry at a time and its 64 lanes add 64 consecutive floats of that entry's destination row: one 256-B
+// contiguous global_atomic_add_f32 wave-instruction per 64 columns (the full-rate shape).
+__global__ void __launch_bounds__(kBlock)
+random_prop_rows_backward_kernel(const float* __restrict__ grad_out, int F, const int* __restrict__ col,
+                                 const double* __restrict__ val, const int* __restrict__ filled, int K,
+                                 const int* __restrict__ batch_rows, int n_batch, long long n_nodes,
+                                 float p, int training, u64 seed, const unsigned char* __restrict__ keep,
+                                 float* __restrict__ grad_x)
+{
+    __shared__ int s_col[kStage];
+    __shared__ float s_w[kStage];
+    const float scale = p < 1.0f ? 1.0f / (1.0f - p) : 0.0f;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int b = blockIdx.x; b < n_batch; b += gridDim.x) {
+        const long long row = batch_rows ? batch_rows[b] : b;
+        const int n = filled ? min(filled[row], K) : K;
+        __syncthreads();
+        for (int k = threadIdx.x; k < n; k += kBlock) {                  // the forward's staging
+            const long long e = row * (long long)K + k;
+            float w = (float)val[e];
+            if (training) w *= keep ? (keep[e] ? scale : 0.0f) : keep_scale(seed, (u64)e, p, scale);
+            s_col[k] = col[e];
+            s_w[k] = w;
+        }
+        __syncthreads();
+        float den = 0.0f;
+        for (int k = 0; k < n; ++k) den += s_w[k];
+        const float inv = 1.0f / (den + 1e-12f);
+        const float* g_row = grad_out + (size_t)b * F;
+        for (int k = wave; k < n; k += kBlock / 64) {
+            const float w = s_w[k];
+            const int c = s_col[k];
+            if (w == 0.0f || c < 0 || c >= n_nodes) continue;           // wave-uniform; a dropped entry adds nothing
+            float* dst = grad_x + (size_t)c * F;
+            for (int f = lane; f < F; f += 64) atomicAdd(dst + f, (g_row[f] * inv) * w);
+        }
+    }
+}
+
+// ---- Embedding-bag (MAG's sparse first layer, MLP.emb, model_mag.py:48-55):
+//     out[m, :] = sum_j keep_{j,:} s d_j W[a_j, :] / (sum_j d_j + 1e-10)
+// Bag of output row m: storage entries [offsets[src], offsets[src + 1]) of (attr_idx, attr_data), src = nodes[m]
+// (nodes != NULL: rows of a device-resident node-attribute CSR) or m.  j = entry_base[m] + t (entry_base != NULL)
+// or the storage position itself: the entry's position in the batch's entry order, which keys the dropout of
+// element (j, h) as (seed, j*H + h).  Attribute ids outside [0, V) are never read or written; they add to *n_bad.
+struct BagLayout {
+    const long long* offsets; long long n_src;        // offsets[n_src + 1]
+    const long long* nodes;                             // [n_rows] or NULL
+    const long long* base;                              // [n_rows] or NULL
+    long long n_rows;
+    const void* idx; int idx64;                         // attr ids: int64 (idx64) or int32
+    const float* data;
+};
+
+__device__ __forceinline__ bool bag_of(const BagLayout& L, long long m, long long& s0, long long& s1, long long& jb)
+{
+    const long long src = L.nodes ? L.nodes[m] : m;
+    if (src < 0 || src >= L.n_src) { s0 = s1 = jb = 0; return false; }
+    s0 = L.offsets[src]; s1 = L.offsets[src + 1];
+    jb = L.base ? L.base[m] : s0;
+    return true;
+}
+
+__device__ __forceinline__ long long attr_id(const BagLayout& L, long long e)
+{
+    return L.idx64 ? reinterpret_cast<const long long*>(L.idx)[e] : (long long)reinterpret_cast<const int*>(L.idx)[e];
+}
+
+// Forward: propagate.hip's mapping -- a group of G = 2^log2g lanes owns one output row (G*VEC >= H when H
+// allows), fp32 sums.  The group's lanes first read G entries' (id, weight) at once, one per lane, and pass
+// them round with shuffles (a bag costs one dependent read round per G entries, not one per 8); then 8
+// gathered table rows are in flight per lane.  A dropped element is still loaded (its row is being read
+// anyway); an out-of-range id is not.
+template <int VEC>
+__global__ void __launch_bounds__(kBlock)
+embedding_bag_kernel(const float* __restrict__ W, long long V, int H, BagLayout L, float p, int training, u64 seed,
+                     const unsigned char* __restrict__ keep, float* __restrict__ out, int* __restrict__ n_bad, int log2g)
+{
+    typedef typename VecT<VEC>::type Vt;
+    const float scale = p < 1.0f ? 1.0f / (1.0f - p) : 0.0f;
+    const int lane = threadIdx.x & 63;
+    const int G = 1 << log2g, gl = lane & (G - 1), grp = lane >> log2g, rows_per_wave = 64 >> log2g;
+    const long long wave = ((long long)blockIdx.x * kBlock + threadIdx.x) >> 6;
+    const long long n_waves = ((long long)gridDim.x * kBlock) >> 6;
+    const long long n_iter = (L.n_rows + n_waves * rows_per_wave - 1) / (n_waves * rows_per_wave);
+    for (long long it = 0; it < n_iter; ++it) {                     // every lane runs every trip: shuffles need the whole wave
+        const long long m = (it * n_waves + wave) * rows_per_wave + grp;
+        const bool row_live = m < L.n_rows;
+        long long s0 = 0, s1 = 0, jb = 0;
+        if (row_live && !bag_of(L, m, s0, s1, jb) && gl == 0 && n_bad) atomicAdd(n_bad, 1);
+        long long len = s1 - s0, max_len = len;                     // the wave loops over its longest bag
+        for (int o = G; o < 64; o <<= 1) { const long long t = __shfl_xor(max_len, o); max_len = t > max_len ? t : max_len; }
+        const int n_f = (H + G * VEC - 1) / (G * VEC);
+        for (int fi = 0; fi < n_f; ++fi) {
+            const int f = (fi * G + gl) * VEC;
+            const bool f_live = f < H;
+            float acc[VEC], den = 0.0f;
+#pragma unroll
+            for (int i = 0; i < VEC; ++i) acc[i] = 0.0f;
+            for (long long c0 = 0; c0 < max_len; c0 += G) {
+                const bool cl = c0 + gl < len;                      // this lane reads entry c0 + gl of its group's bag
+                const long long my_a = cl ? attr_id(L, s0 + c0 + gl) : -1;
+                const float my_d = cl ? L.data[s0 + c0 + gl] : 0.0f;
+                if (cl && (my_a < 0 || my_a >= V) && fi == 0 && n_bad) atomicAdd(n_bad, 1);
+                for (int u0 = 0; u0 < G && c0 + u0 < max_len; u0 += 8) {
+                    Vt v[8]; float d[8]; bool ok[8];
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) {
+                        const int src = (grp << log2g) + ((u0 + u) & (G - 1));
+                        const long long a = __shfl(my_a, src);
+                        d[u] = __shfl(my_d, src);
+                        const bool live = u0 + u < G && c0 + u0 + u < len;
+                        ok[u] = live && f_live && a >= 0 && a < V;
+                        if (!live) d[u] = 0.0f;
+                        if (ok[u]) v[u] = *reinterpret_cast<const Vt*>(W + (size_t)a * H + f);
+                        else v[u] = Vt();
+                    }
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) {
+                        den += d[u];                                            // node_s_sum, model_mag.py:53 (raw attr_data)
+                        if (!ok[u]) continue;
+                        const float* pv = reinterpret_cast<const float*>(&v[u]);
+                        const u64 j = (u64)(jb + c0 + u0 + u);
+#pragma unroll
+                        for (int i = 0; i < VEC; ++i) {
+                            float x = pv[i];
+                            if (training) {                                     // F.dropout(feat_embeds), model_mag.py:50
+                                const u64 el = j * (u64)H + (u64)(f + i);
+                                x *= keep ? (keep[el] ? scale : 0.0f) : keep_scale(seed, el, p, scale);
+                            }
+                            acc[i] += x * d[u];                                 // model_mag.py:52
+                        }
+                    }
+                }
+            }
+            if (row_live && f_live) {
+                Vt o; float* po = reinterpret_cast<float*>(&o);
+#pragma unroll
+                for (int i = 0; i < VEC; ++i) po[i] = acc[i] / (den + 1e-10f); // model_mag.py:54
+                *reinterpret_cast<Vt*>(out + (size_t)m * H + f) = o;
+            }
+        }
+    }
+}
+
+// Backward into a dense, zeroed dW [V x H] (nn.Embedding(sparse=False)):
+//     dW[a_j, :] += keep_{j,:} s d_j / (den_m + 1e-10) * grad_out[m, :]
+// A wave owns an output row.  Its lanes read 64 entries' (id, weight) at once and reduce den with a butterfly
+// (every lane ends with the same sum); then per bag entry, broadcast by a shuffle, the 64 lanes add 64
+// consecutive floats of the entry's table row: at H = 64 one entry is exactly one 256-B global_atomic_add_f32
+// wave-instruction.  Not bitwise reproducible (fp32 atomic arrival order).
+__global__ void __launch_bounds__(kBlock)
+embedding_bag_backward_kernel(long long V, int H, BagLayout L, float p, int training, u64 seed,
+                              const unsigned char* __restrict__ keep, const float* __restrict__ grad_out,
+                              float* __restrict__ dW, int* __restrict__ n_bad)
+{
+    const float scale = p < 1.0f ? 1.0f / (1.0f - p) : 0.0f;
+    const int lane = threadIdx.x & 63;
+    const long long wave = ((long long)blockIdx.x * kBlock + threadIdx.x) >> 6;
+    const long long n_waves = ((long long)gridDim.x * kBlock) >> 6;
+    for (long long m = wave; m < L.n_rows; m += n_waves) {        // wave-uniform loop
+        long long s0, s1, jb;
+        if (!bag_of(L, m, s0, s1, jb)) { if (lane == 0 && n_bad) atomicAdd(n_bad, 1); continue; }
+        float den = 0.0f;
+        for (long long c0 = s0; c0 < s1; c0 += 64) {
+            float part = c0 + lane < s1 ? L.data[c0 + lane] : 0.0f;
+            for (int o = 1; o < 64; o <<= 1) part += __shfl_xor(part, o);
+            den += part;
+        }
+        const float inv = 1.0f / (den + 1e-10f);
+        for (int h0 = 0; h0 < H; h0 += 64) {
+            const int h = h0 + lane;
+            const bool live_h = h < H;
+            const float g = live_h ? grad_out[(size_t)m * H + h] * inv : 0.0f;
+            for (long long c0 = s0; c0 < s1; c0 += 64) {
+                const bool cl = c0 + lane < s1;
+                const long long my_a = cl ? attr_id(L, c0 + lane) : -1;
+                const float my_d = cl ? L.data[c0 + lane] : 0.0f;
+                if (cl && (my_a < 0 || my_a >= V) && h0 == 0 && n_bad) atomicAdd(n_bad, 1);
+                const int n = (int)(s1 - c0 < 64 ? s1 - c0 : 64);
+                for (int u = 0; u < n; ++u) {
+                    const long long a = __shfl(my_a, u);
+                    if (a < 0 || a >= V) continue;                              // wave-uniform
+                    float x = g * __shfl(my_d, u);
+                    if (training) {
+                        const u64 el = (u64)(jb + (c0 - s0) + u) * (u64)H + (u64)h;
+                        x *= keep ? (keep[el] ? scale : 0.0f) : keep_scale(seed, el, p, scale);
+                    }
+                    if (live_h && x != 0.0f) atomicAdd(dW + (size_t)a * H + h, x);
+                }
+            }
+        }
+    }
+}
+
 int launch_status(const char* what) {
     const hipError_t e = hipGetLastError();
     if (e == hipSuccess) return GP_OK;
@@ -310,6 +586,131 @@ int gp_random_prop_coo(int device, const float* d_feats, int64_t n_entries, int3
                        d_scores, (const long long*)d_idx, (long long)n_entries, (long long)n_out, dropnode_rate,
                        training, (u64)seed, d_keep, d_out);
     return launch_status("random_prop_coo_kernel");
+}
+
+}  // extern "C"
+
+// ---- Backward and embedding-bag entry points.  Arguments are checked before hipSetDevice.
+namespace {
+
+int set_device(int device, const char* where)
+{
+    const hipError_t e = hipSetDevice(device);
+    if (e == hipSuccess) return GP_OK;
+    gp_internal_set_error(GP_ERR_NO_DEVICE, where, hipGetErrorString(e));
+    return GP_ERR_NO_DEVICE;
+}
+
+int check_bag_args(const char* where, const float* d_table, int64_t n_vocab, int32_t dim, const int64_t* d_offsets,
+                   int64_t n_src, int64_t n_rows, const void* d_attr_idx, int idx_bytes, const float* d_attr_data,
+                   float rate, const void* d_dst)
+{
+    if (n_vocab < 0 || dim < 1 || n_src < 0 || n_rows < 0 || (idx_bytes != 4 && idx_bytes != 8) || !(rate >= 0.0f && rate <= 1.0f)) {
+        gp_internal_set_error(GP_ERR_INVALID_ARG, where, "negative size, dim < 1, idx_bytes not 4 or 8, or dropout rate outside [0, 1]");
+        return GP_ERR_INVALID_ARG;
+    }
+    if (n_rows > 0 && (!d_offsets || !d_attr_idx || !d_attr_data || !d_dst || (n_vocab > 0 && !d_table))) {
+        gp_internal_set_error(GP_ERR_NULL, where, "a device pointer is NULL");
+        return GP_ERR_NULL;
+    }
+    return GP_OK;
+}
+
+int bag_log2g(int H, int vec)
+{
+    int log2g = 0;                                   // smallest group with G * VEC >= H, at most a wave
+    while ((1 << log2g) * vec < H && log2g < 6) ++log2g;
+    return log2g;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gp_random_prop_coo_backward(int device, const float* d_grad_out, int64_t n_out, int32_t feat_dim,
+                                const float* d_scores, const int64_t* d_idx, int64_t n_entries,
+                                float dropnode_rate, int training, uint64_t seed, const uint8_t* d_keep,
+                                float* d_grad_feats, void* stream)
+{
+    const char* where = "gp_random_prop_coo_backward";
+    if (n_entries < 0 || n_entries > 2147483647ll || feat_dim < 1 || n_out < 0 || !(dropnode_rate >= 0.0f && dropnode_rate <= 1.0f)) {
+        gp_internal_set_error(GP_ERR_INVALID_ARG, where, "bad size or dropnode_rate outside [0, 1]");
+        return GP_ERR_INVALID_ARG;
+    }
+    if (n_out == 0) return GP_OK;
+    if (!d_grad_out || (n_entries > 0 && (!d_scores || !d_idx || !d_grad_feats))) { gp_internal_set_error(GP_ERR_NULL, where, "a device pointer is NULL"); return GP_ERR_NULL; }
+    if (const int rc = set_device(device, where)) return rc;
+    const int grid = n_out < 65535 ? (int)n_out : 65535;
+    hipLaunchKernelGGL(random_prop_coo_backward_kernel, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, d_grad_out, feat_dim,
+                       d_scores, (const long long*)d_idx, (long long)n_entries, (long long)n_out, dropnode_rate, training,
+                       (u64)seed, d_keep, d_grad_feats);
+    return launch_status("random_prop_coo_backward_kernel");
+}
+
+int gp_random_prop_rows_backward(int device, const float* d_grad_out, int32_t n_batch, int32_t feat_dim,
+                                 const int32_t* d_col, const double* d_val, const int32_t* d_filled, int32_t K,
+                                 const int32_t* d_batch_rows, float dropnode_rate, int training, uint64_t seed,
+                                 const uint8_t* d_keep, float* d_grad_x, int64_t n_nodes, void* stream)
+{
+    const char* where = "gp_random_prop_rows_backward";
+    if (n_batch < 0 || n_nodes < 1 || feat_dim < 1 || K < 1 || K > GP_MAX_K || !(dropnode_rate >= 0.0f && dropnode_rate <= 1.0f)) {
+        gp_internal_set_error(GP_ERR_INVALID_ARG, where, "bad size, K outside [1, 1024] or dropnode_rate outside [0, 1]");
+        return GP_ERR_INVALID_ARG;
+    }
+    if (n_batch == 0) return GP_OK;
+    if (!d_grad_out || !d_col || !d_val || !d_grad_x) { gp_internal_set_error(GP_ERR_NULL, where, "a device pointer is NULL"); return GP_ERR_NULL; }
+    if (const int rc = set_device(device, where)) return rc;
+    const int grid = n_batch < 65535 ? n_batch : 65535;
+    hipLaunchKernelGGL(random_prop_rows_backward_kernel, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, d_grad_out, feat_dim,
+                       d_col, d_val, d_filled, K, d_batch_rows, n_batch, (long long)n_nodes, dropnode_rate, training, (u64)seed,
+                       d_keep, d_grad_x);
+    return launch_status("random_prop_rows_backward_kernel");
+}
+
+int gp_embedding_bag(int device, const float* d_weight, int64_t n_vocab, int32_t dim,
+                     const int64_t* d_offsets, int64_t n_src, const int64_t* d_nodes, const int64_t* d_entry_base, int64_t n_rows,
+                     const void* d_attr_idx, int idx_bytes, const float* d_attr_data,
+                     float dropout_rate, int training, uint64_t seed, const uint8_t* d_keep,
+                     float* d_out, int32_t* d_n_bad, void* stream)
+{
+    const char* where = "gp_embedding_bag";
+    if (const int rc = check_bag_args(where, d_weight, n_vocab, dim, d_offsets, n_src, n_rows, d_attr_idx, idx_bytes, d_attr_data,
+                                      dropout_rate, d_out)) return rc;
+    if (n_rows == 0) return GP_OK;
+    if (const int rc = set_device(device, where)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (d_n_bad && hipMemsetAsync(d_n_bad, 0, sizeof(int32_t), s) != hipSuccess) { gp_internal_set_error(GP_ERR_HIP, where, "hipMemsetAsync failed"); return GP_ERR_HIP; }
+    const BagLayout L = {(const long long*)d_offsets, (long long)n_src, (const long long*)d_nodes, (const long long*)d_entry_base,
+                         (long long)n_rows, d_attr_idx, idx_bytes == 8, d_attr_data};
+    const int vec = (dim & 3) == 0 ? 4 : (dim & 1) == 0 ? 2 : 1;
+    const int log2g = bag_log2g(dim, vec);
+    const long long rows_per_block = (kBlock / 64) * (64 >> log2g);
+    const int grid = (int)std::min<long long>(65535ll * 16, (n_rows + rows_per_block - 1) / rows_per_block);
+    if (vec == 4)      hipLaunchKernelGGL(embedding_bag_kernel<4>, dim3(grid), dim3(kBlock), 0, s, d_weight, (long long)n_vocab, dim, L, dropout_rate, training, (u64)seed, d_keep, d_out, d_n_bad, log2g);
+    else if (vec == 2) hipLaunchKernelGGL(embedding_bag_kernel<2>, dim3(grid), dim3(kBlock), 0, s, d_weight, (long long)n_vocab, dim, L, dropout_rate, training, (u64)seed, d_keep, d_out, d_n_bad, log2g);
+    else               hipLaunchKernelGGL(embedding_bag_kernel<1>, dim3(grid), dim3(kBlock), 0, s, d_weight, (long long)n_vocab, dim, L, dropout_rate, training, (u64)seed, d_keep, d_out, d_n_bad, log2g);
+    return launch_status("embedding_bag_kernel");
+}
+
+int gp_embedding_bag_backward(int device, const float* d_grad_out, int64_t n_vocab, int32_t dim,
+                              const int64_t* d_offsets, int64_t n_src, const int64_t* d_nodes, const int64_t* d_entry_base, int64_t n_rows,
+                              const void* d_attr_idx, int idx_bytes, const float* d_attr_data,
+                              float dropout_rate, int training, uint64_t seed, const uint8_t* d_keep,
+                              float* d_grad_weight, int32_t* d_n_bad, void* stream)
+{
+    const char* where = "gp_embedding_bag_backward";
+    if (const int rc = check_bag_args(where, d_grad_weight, n_vocab, dim, d_offsets, n_src, n_rows, d_attr_idx, idx_bytes, d_attr_data,
+                                      dropout_rate, d_grad_out)) return rc;
+    if (n_rows == 0) return GP_OK;
+    if (const int rc = set_device(device, where)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (d_n_bad && hipMemsetAsync(d_n_bad, 0, sizeof(int32_t), s) != hipSuccess) { gp_internal_set_error(GP_ERR_HIP, where, "hipMemsetAsync failed"); return GP_ERR_HIP; }
+    const BagLayout L = {(const long long*)d_offsets, (long long)n_src, (const long long*)d_nodes, (const long long*)d_entry_base,
+                         (long long)n_rows, d_attr_idx, idx_bytes == 8, d_attr_data};
+    const int grid = (int)std::min<long long>(65535ll * 16, (n_rows + kBlock / 64 - 1) / (kBlock / 64));
+    hipLaunchKernelGGL(embedding_bag_backward_kernel, dim3(grid), dim3(kBlock), 0, s, (long long)n_vocab, dim, L, dropout_rate,
+                       training, (u64)seed, d_keep, d_grad_out, d_grad_weight, d_n_bad);
+    return launch_status("embedding_bag_backward_kernel");
 }
 
 }  // extern "C"

@@ -268,6 +268,56 @@ int gp_random_prop_coo(int device, const float* d_feats, int64_t n_entries, int3
                        float* d_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Backward of random_prop and MAG's embedding-bag layer.  All pointers are DEVICE
+ * pointers on `device`; launches are asynchronous on `stream`; arguments are checked before
+ * the device is touched.  (dropnode_rate / dropout_rate, training, seed, d_keep) mean what they
+ * mean for the forward entries above: pass the forward's values and the backward applies the
+ * forward's mask (recomputed from (seed, entry), never stored).
+ *
+ * Gradients flow to the feature operand only; scores and attr_data are constants.
+ * ------------------------------------------------------------------------------------------ */
+
+/* d_grad_feats[e,:] = w'_e / (den_b + 1e-12) * d_grad_out[b,:], b = d_idx[e]: every row of
+ * d_grad_feats[n_entries x feat_dim] is written (dropped entries get zeros).  No atomics. */
+int gp_random_prop_coo_backward(int device, const float* d_grad_out, int64_t n_out, int32_t feat_dim,
+                                const float* d_scores, const int64_t* d_idx, int64_t n_entries,
+                                float dropnode_rate, int training, uint64_t seed, const uint8_t* d_keep,
+                                float* d_grad_feats, void* stream);
+
+/* d_grad_x[col[r,k],:] += w'_{r,k} / (den_b + 1e-12) * d_grad_out[b,:], r = d_batch_rows[b], into a
+ * caller-zeroed d_grad_x[n_nodes x feat_dim].  fp32 global atomics: not bitwise reproducible.
+ * Column ids outside [0, n_nodes) are skipped. */
+int gp_random_prop_rows_backward(int device, const float* d_grad_out, int32_t n_batch, int32_t feat_dim,
+                                 const int32_t* d_col, const double* d_val, const int32_t* d_filled, int32_t K,
+                                 const int32_t* d_batch_rows, float dropnode_rate, int training, uint64_t seed,
+                                 const uint8_t* d_keep, float* d_grad_x, int64_t n_nodes, void* stream);
+
+/* Embedding-bag, reference MLP.emb (model_mag.py:48-55), table W[n_vocab x dim] fp32:
+ *   out[m,:] = sum_j keep_{j,:}/(1-rate) * d_j * W[a_j,:] / (sum_j d_j + 1e-10)
+ * The bag of row m is storage entries [d_offsets[src], d_offsets[src+1]) of d_attr_idx (int32 when
+ * idx_bytes = 4, int64 when 8) and d_attr_data, with src = d_nodes[m] when d_nodes is given (rows of a
+ * device-resident node-attribute CSR with n_src rows), else src = m.  The entry's position j in the
+ * batch's entry order is d_entry_base[m] + t when d_entry_base is given, else its storage position; the
+ * dropout of element (j, h) is d_keep[j*dim + h] or the RNG of (seed, j*dim + h).  The denominator
+ * uses the raw d_attr_data.  Attribute ids outside [0, n_vocab) and src outside [0, n_src) are never
+ * read; *d_n_bad (device int32, optional) is set to how many there were.  fp32 sums. */
+int gp_embedding_bag(int device, const float* d_weight, int64_t n_vocab, int32_t dim,
+                     const int64_t* d_offsets, int64_t n_src, const int64_t* d_nodes, const int64_t* d_entry_base, int64_t n_rows,
+                     const void* d_attr_idx, int idx_bytes, const float* d_attr_data,
+                     float dropout_rate, int training, uint64_t seed, const uint8_t* d_keep,
+                     float* d_out, int32_t* d_n_bad, void* stream);
+
+/* Its backward into a dense, caller-zeroed d_grad_weight[n_vocab x dim] (nn.Embedding(sparse=False)):
+ *   dW[a_j,:] += keep_{j,:}/(1-rate) * d_j / (den_m + 1e-10) * d_grad_out[m,:]
+ * Same bag layout and counter as gp_embedding_bag; out-of-range ids are never written.  fp32 global
+ * atomics (one 256-B wave-instruction per entry at dim = 64): not bitwise reproducible. */
+int gp_embedding_bag_backward(int device, const float* d_grad_out, int64_t n_vocab, int32_t dim,
+                              const int64_t* d_offsets, int64_t n_src, const int64_t* d_nodes, const int64_t* d_entry_base, int64_t n_rows,
+                              const void* d_attr_idx, int idx_bytes, const float* d_attr_data,
+                              float dropout_rate, int training, uint64_t seed, const uint8_t* d_keep,
+                              float* d_grad_weight, int32_t* d_n_bad, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * exact full-graph feature propagation of the inference path, reference
  * predict() (model.py:181-224), lines 186-210.  mode 0 = ppr, 1 = avg, 2 = single (args.prop_mode);
  * `order` = args.order propagation steps.  A is the CSR of `g` (adj + I as the caller built it,
