@@ -30,7 +30,16 @@ EXPORTS = (
     "gp_graph_create_multi", "gp_graph_num_gpus", "gp_internal_multi_plan", "gp_internal_graph_acsr", "gp_graph_create_multi_on",
     "gp_seed_positions", "gp_batch_positions", "gp_internal_create_ms", "gp_internal_warm_device",
     "gp_random_prop_coo_backward", "gp_random_prop_rows_backward", "gp_embedding_bag", "gp_embedding_bag_backward",
+    "gp_random_prop_coo_multi", "gp_random_prop_rows_multi", "gp_random_prop_coo_multi_backward",
+    "gp_random_prop_rows_multi_backward", "gp_grand_loss", "gp_grand_loss_backward",
 )
+GP_LOSS_KL, GP_LOSS_L2 = 0, 1
+GP_MAX_SAMPLES = 16
+
+
+def grand_loss_workspace_bytes(n_rows: int) -> int:
+    """GP_GRAND_LOSS_WORKSPACE_BYTES of grandplus.h."""
+    return 20 * n_rows
 
 
 class GpStats(ctypes.Structure):
@@ -142,6 +151,15 @@ def lib():
     _bag = [ctypes.c_int, vp, i64, ctypes.c_int32, vp, i64, vp, vp, i64, vp, ctypes.c_int, vp, f32, ctypes.c_int, u64, vp, vp, vp, vp]
     _optional(L, "gp_embedding_bag", _bag)
     _optional(L, "gp_embedding_bag_backward", _bag)
+    i32 = ctypes.c_int32
+    _optional(L, "gp_random_prop_rows_multi", [ctypes.c_int, vp, i64, i32, vp, vp, vp, i32, vp, i32, i32, f32, ctypes.c_int, u64, vp, i64, vp, vp])
+    _optional(L, "gp_random_prop_coo_multi", [ctypes.c_int, vp, i64, i32, vp, vp, i64, i32, f32, ctypes.c_int, u64, vp, vp, vp])
+    _optional(L, "gp_random_prop_coo_multi_backward", [ctypes.c_int, vp, i64, i32, vp, vp, i64, i32, f32, ctypes.c_int, u64, vp, vp, vp])
+    _optional(L, "gp_random_prop_rows_multi_backward", [ctypes.c_int, vp, i32, i32, vp, vp, vp, i32, vp, i32, f32, ctypes.c_int, u64, vp, i64,
+                                                        vp, i64, vp])
+    _loss = [ctypes.c_int, vp, i32, i64, i32, vp, i64, i64, f32, f32, f32, ctypes.c_int, ctypes.c_int]
+    _optional(L, "gp_grand_loss", _loss + [vp, vp, vp, vp])
+    _optional(L, "gp_grand_loss_backward", _loss + [vp, vp, vp, vp, vp, vp])
     L.gp_propagate_features.restype = ctypes.c_int
     L.gp_propagate_features.argtypes = [vp, vp, ctypes.c_int32, vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, vp, vp]
     L.gp_internal_diag_counters.restype = ctypes.c_int

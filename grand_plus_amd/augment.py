@@ -17,6 +17,10 @@ and that tensor requires grad (MAG trains its embedding table through random_pro
 Scores, `val` and `keep` are constants, as in the reference, where they come from numpy
 (model_mag.py:342-343).  The backward kernels recompute the forward's mask from its seed.  Every other
 call takes the plain path: same launch, same output, no grad_fn.
+
+`samples=S` (2 <= S <= 16) runs the S augmentations of one training step (`--sample S`, model.py:321-322) in one
+launch and returns [S, n_out, F]: out[s] equals, bit for bit, the single-sample call with
+`sample_seed(seed, s)` (or with `keep[s]`) -- DESIGN §7e.
 """
 from __future__ import annotations
 
@@ -42,6 +46,35 @@ def _check(t, dtype, name):
 
 def _new_seed():
     return next(_seed_counter) * 0x9E3779B97F4A7C15 & (2**64 - 1)
+
+
+_M64 = 2**64 - 1
+
+
+def sample_seed(seed: int, s: int) -> int:
+    """Seed of sample s of an S-sample call (the formula of grandplus.h): seed itself for s = 0."""
+    seed &= _M64
+    if s == 0:
+        return seed
+    x = (seed ^ (s * 0xD6E8FEB86659FD93)) & _M64
+    x = (x + 0x9E3779B97F4A7C15) & _M64
+    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & _M64
+    return x ^ (x >> 31)
+
+
+def _check_samples(samples):
+    if not isinstance(samples, int) or not 1 <= samples <= _native.GP_MAX_SAMPLES:
+        raise ValueError(f"samples must be an int in [1, {_native.GP_MAX_SAMPLES}], got {samples!r}")
+
+
+def _multi_keep(keep, S, L):
+    """An explicit mask of an S-sample call: uint8 [S, L] (or its flat form), row s = the single call's keep."""
+    import torch
+    _check(keep, torch.uint8, "keep")
+    if keep.numel() != S * L:
+        raise ValueError(f"keep must hold samples x {L} = {S * L} entries, got {keep.numel()}")
+    return keep
 
 
 def _wants_grad(t):
@@ -73,6 +106,91 @@ def _rows_forward(features, col, val, filled, K, batch_rows, B, dropnode_rate, t
         out.data_ptr(), ctypes.c_void_p(stream))
     _native.raise_for_status(rc)
     return out
+
+
+def _coo_multi_forward(feats, mat_scores, mat_idx, n_out, S, dropnode_rate, training, seed, keep, stream):
+    import torch
+    M, F = feats.shape
+    out = torch.empty((S, n_out, F), dtype=torch.float32, device=feats.device)
+    rc = _native.lib().gp_random_prop_coo_multi(
+        _dev_index(feats), feats.data_ptr(), M, F, mat_scores.data_ptr(), mat_idx.data_ptr(), n_out, S,
+        float(dropnode_rate), int(bool(training)), ctypes.c_uint64(seed), keep.data_ptr() if keep is not None else None,
+        out.data_ptr(), ctypes.c_void_p(stream))
+    _native.raise_for_status(rc)
+    return out
+
+
+def _rows_multi_forward(features, col, val, filled, K, batch_rows, B, S, dropnode_rate, training, seed, keep, stream):
+    import torch
+    N, F = features.shape
+    out = torch.empty((S, B, F), dtype=torch.float32, device=features.device)
+    rc = _native.lib().gp_random_prop_rows_multi(
+        _dev_index(features), features.data_ptr(), N, F, col.data_ptr(), val.data_ptr(),
+        filled.data_ptr() if filled is not None else None, int(K),
+        batch_rows.data_ptr() if batch_rows is not None else None, B, S,
+        float(dropnode_rate), int(bool(training)), ctypes.c_uint64(seed), keep.data_ptr() if keep is not None else None,
+        col.numel(), out.data_ptr(), ctypes.c_void_p(stream))
+    _native.raise_for_status(rc)
+    return out
+
+
+def _multi_autograd_functions():
+    """autograd Functions of the S-sample forms (gradient to the feature operand, summed over the samples)."""
+    global _CooMultiFn, _RowsMultiFn
+    if _CooMultiFn is not None:
+        return _CooMultiFn, _RowsMultiFn
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    class CooMultiFn(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, feats, mat_scores, mat_idx, n_out, S, dropnode_rate, training, seed, keep, stream):
+            ctx.save_for_backward(mat_scores, mat_idx, keep)
+            ctx.args = (feats.shape, n_out, S, dropnode_rate, training, seed)
+            return _coo_multi_forward(feats, mat_scores, mat_idx, n_out, S, dropnode_rate, training, seed, keep, stream)
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, grad_out):
+            mat_scores, mat_idx, keep = ctx.saved_tensors
+            (M, F), n_out, S, p, training, seed = ctx.args
+            g = grad_out.contiguous()
+            grad = torch.empty((M, F), dtype=torch.float32, device=g.device)
+            rc = _native.lib().gp_random_prop_coo_multi_backward(
+                _dev_index(g), g.data_ptr(), n_out, F, mat_scores.data_ptr(), mat_idx.data_ptr(), M, S,
+                float(p), int(bool(training)), ctypes.c_uint64(seed), keep.data_ptr() if keep is not None else None,
+                grad.data_ptr(), ctypes.c_void_p(torch.cuda.current_stream(g.device).cuda_stream))
+            _native.raise_for_status(rc)
+            return grad, None, None, None, None, None, None, None, None, None
+
+    class RowsMultiFn(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, features, col, val, filled, K, batch_rows, B, S, dropnode_rate, training, seed, keep, stream):
+            ctx.save_for_backward(col, val, filled, batch_rows, keep)
+            ctx.args = (features.shape, K, B, S, dropnode_rate, training, seed)
+            return _rows_multi_forward(features, col, val, filled, K, batch_rows, B, S, dropnode_rate, training, seed, keep, stream)
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, grad_out):
+            col, val, filled, batch_rows, keep = ctx.saved_tensors
+            (N, F), K, B, S, p, training, seed = ctx.args
+            g = grad_out.contiguous()
+            grad = torch.zeros((N, F), dtype=torch.float32, device=g.device)
+            rc = _native.lib().gp_random_prop_rows_multi_backward(
+                _dev_index(g), g.data_ptr(), B, F, col.data_ptr(), val.data_ptr(),
+                filled.data_ptr() if filled is not None else None, int(K),
+                batch_rows.data_ptr() if batch_rows is not None else None, S,
+                float(p), int(bool(training)), ctypes.c_uint64(seed), keep.data_ptr() if keep is not None else None,
+                col.numel(), grad.data_ptr(), N, ctypes.c_void_p(torch.cuda.current_stream(g.device).cuda_stream))
+            _native.raise_for_status(rc)
+            return grad, None, None, None, None, None, None, None, None, None, None, None, None
+
+    _CooMultiFn, _RowsMultiFn = CooMultiFn, RowsMultiFn
+    return _CooMultiFn, _RowsMultiFn
+
+
+_CooMultiFn = _RowsMultiFn = None
 
 
 def _autograd_functions():
@@ -134,36 +252,53 @@ def _autograd_functions():
 _CooFn = _RowsFn = None
 
 
-def random_prop(feats, mat_scores, mat_idx, dropnode_rate, training=True, seed=None, keep=None, stream=None):
+def random_prop(feats, mat_scores, mat_idx, dropnode_rate, training=True, seed=None, keep=None, stream=None,
+                samples=1, n_out=None):
     """Drop-in for `Grand_Plus.random_prop` (`model.py:80-87`) on CUDA tensors.
 
     feats [M, F] float32, mat_scores [M] float32, mat_idx [M] int64 sorted ascending (the order
     scipy's `.nonzero()` yields, `model.py:312`).  Returns [mat_idx[-1] + 1, F] float32.
     `training` plays the role of `self.training`.  Differentiable with respect to `feats`.
+    `n_out` (optional) is the number of output rows; given, it saves the host read of mat_idx[-1].
+    `samples` = S > 1 returns [S, n_out, F] from one launch (keep: uint8 [S, M]); see the module docstring.
     """
     import torch
+    _check_samples(samples)
     _check(feats, torch.float32, "feats")
     _check(mat_scores, torch.float32, "mat_scores")
     _check(mat_idx, torch.int64, "mat_idx")
     M, F = feats.shape
     if mat_scores.numel() != M or mat_idx.numel() != M:
         raise ValueError("feats, mat_scores and mat_idx must have the same number of entries")
-    if M == 0:
-        return feats.new_zeros((0, F))
-    n_out = int(mat_idx[-1].item()) + 1                                   # model.py:84 dim_size
-    if keep is not None:
-        _check(keep, torch.uint8, "keep")
+    if n_out is None:
+        if M == 0:
+            return feats.new_zeros((0, F)) if samples == 1 else feats.new_zeros((samples, 0, F))
+        n_out = int(mat_idx[-1].item()) + 1                               # model.py:84 dim_size
+    elif int(n_out) < 0:
+        raise ValueError("n_out must be >= 0")
+    n_out = int(n_out)
     if seed is None:
         seed = _new_seed()
     if stream is None:
         stream = torch.cuda.current_stream(feats.device).cuda_stream
+    if samples > 1:
+        if keep is not None:
+            keep = _multi_keep(keep, samples, M)
+        if _wants_grad(feats):
+            return _multi_autograd_functions()[0].apply(feats, mat_scores, mat_idx, n_out, samples, dropnode_rate, training, seed,
+                                                        keep, stream)
+        return _coo_multi_forward(feats, mat_scores, mat_idx, n_out, samples, dropnode_rate, training, seed, keep, stream)
+    if M == 0:
+        return feats.new_zeros((n_out, F))
+    if keep is not None:
+        _check(keep, torch.uint8, "keep")
     if _wants_grad(feats):                                                # gradient to feats only (model_mag.py:355)
         return _autograd_functions()[0].apply(feats, mat_scores, mat_idx, n_out, dropnode_rate, training, seed, keep, stream)
     return _coo_forward(feats, mat_scores, mat_idx, n_out, dropnode_rate, training, seed, keep, stream)
 
 
 def random_prop_rows(features, col, val, filled, K, batch_rows=None, dropnode_rate=0.5, training=True,
-                     seed=None, keep=None, stream=None):
+                     seed=None, keep=None, stream=None, samples=1):
     """Fused augmentation straight from the GFPush row matrix.
 
     features [N, F] float32 (node features resident on the GPU); col int32 [S*K], val float64 [S*K],
@@ -172,8 +307,10 @@ def random_prop_rows(features, col, val, filled, K, batch_rows=None, dropnode_ra
         out[b] = sum_k w_k X[col[r,k]] / (sum_k w_k + 1e-12),  r = batch_rows[b]
     Differentiable with respect to `features` (the backward adds into a dense [N, F] gradient with fp32
     atomics: not bitwise reproducible).
+    `samples` = S > 1 returns [S, B, F] from one launch (keep: uint8 [S, S_rows * K]); see the module docstring.
     """
     import torch
+    _check_samples(samples)
     _check(features, torch.float32, "features")
     _check(col, torch.int32, "col")
     _check(val, torch.float64, "val")
@@ -184,12 +321,19 @@ def random_prop_rows(features, col, val, filled, K, batch_rows=None, dropnode_ra
     if batch_rows is not None:
         _check(batch_rows, torch.int32, "batch_rows")
     B = S if batch_rows is None else batch_rows.numel()
-    if keep is not None:
-        _check(keep, torch.uint8, "keep")
     if seed is None:
         seed = _new_seed()
     if stream is None:
         stream = torch.cuda.current_stream(features.device).cuda_stream
+    if samples > 1:
+        if keep is not None:
+            keep = _multi_keep(keep, samples, col.numel())
+        if _wants_grad(features):
+            return _multi_autograd_functions()[1].apply(features, col, val, filled, K, batch_rows, B, samples, dropnode_rate,
+                                                        training, seed, keep, stream)
+        return _rows_multi_forward(features, col, val, filled, K, batch_rows, B, samples, dropnode_rate, training, seed, keep, stream)
+    if keep is not None:
+        _check(keep, torch.uint8, "keep")
     if _wants_grad(features):
         return _autograd_functions()[1].apply(features, col, val, filled, K, batch_rows, B, dropnode_rate, training, seed, keep, stream)
     return _rows_forward(features, col, val, filled, K, batch_rows, B, dropnode_rate, training, seed, keep, stream)

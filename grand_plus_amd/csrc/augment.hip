@@ -714,3 +714,445 @@ int gp_embedding_bag_backward(int device, const float* d_grad_out, int64_t n_voc
 }
 
 }  // extern "C"
+
+// ---- S-sample random_prop: the S augmentations of one training step (model.py:321-322) in one launch.
+// Sample s keeps entry e by keep_scale(gp_sample_seed(seed, s), e) or d_keep[s * keep_stride + e]; out is
+// [S x n_out x F], sample-major.  A workgroup stages its row's columns once and the weights of up to `nsc` samples
+// in dynamic LDS (nsc * stage floats, at most 64 KiB), loads every neighbour feature row once per sample chunk and
+// updates one accumulator per sample from that load.  Per sample and column the sums run in the single-sample
+// kernel's order (denominator over k, then the column sum over k), so out[s] equals gp_random_prop_* with
+// seed_s bit for bit; a dropped entry adds 0 * x, which leaves a finite sum unchanged.
+namespace {
+
+constexpr int kMaxSamples = 16;
+constexpr int kMultiLdsBytes = 65536;
+
+__device__ __forceinline__ u64 sample_seed(u64 seed, int s)
+{
+    if (s == 0) return seed;                          // the formula of grandplus.h (gp_sample_seed)
+    u64 x = seed ^ ((u64)s * 0xD6E8FEB86659FD93ull);
+    x += 0x9E3779B97F4A7C15ull;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+
+__device__ __forceinline__ float sample_weight(float w, long long e, int s, float p, float scale, int training, u64 seed,
+                                               const unsigned char* keep, long long keep_stride)
+{
+    if (!training) return w;
+    return w * (keep ? (keep[(long long)s * keep_stride + e] ? scale : 0.0f) : keep_scale(sample_seed(seed, s), (u64)e, p, scale));
+}
+
+// out[s0 + s][f] for s < ns from the staged columns (s_col, or col_base + k when s_col is NULL) and weights
+// s_w[s * stage + k].  NS >= ns is the unrolled accumulator count; samples ns..NS-1 see weight 0 and are not written.
+template <int VEC, int NS>
+__device__ __forceinline__ void weighted_rows_multi(const float* __restrict__ X, int F, const int* s_col, long long col_base,
+                                                    const float* s_w, int stage, int n, int ns,
+                                                    float* __restrict__ out_row, size_t out_stride)
+{
+    typedef typename VecT<VEC>::type V;
+    float inv[NS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        float den = 0.0f;
+        if (s < ns) for (int k = 0; k < n; ++k) den += s_w[s * stage + k];   // model.py:85-86, the single kernel's order
+        inv[s] = 1.0f / (den + 1e-12f);
+    }
+    for (int f = (blockIdx.y * kBlock + threadIdx.x) * VEC; f < F; f += gridDim.y * kBlock * VEC) {
+        float acc[NS][VEC];
+#pragma unroll
+        for (int s = 0; s < NS; ++s)
+#pragma unroll
+            for (int i = 0; i < VEC; ++i) acc[s][i] = 0.0f;
+        int k = 0;
+        for (; k + 8 <= n; k += 8) {
+            V v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const long long c = s_col ? (long long)s_col[k + u] : col_base + k + u;
+                v[u] = *reinterpret_cast<const V*>(X + (size_t)c * F + f);
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const float* pv = reinterpret_cast<const float*>(&v[u]);
+#pragma unroll
+                for (int s = 0; s < NS; ++s) {
+                    const float w = s < ns ? s_w[s * stage + k + u] : 0.0f;
+#pragma unroll
+                    for (int i = 0; i < VEC; ++i) acc[s][i] += w * pv[i];   // model.py:83-84
+                }
+            }
+        }
+        for (; k < n; ++k) {
+            const long long c = s_col ? (long long)s_col[k] : col_base + k;
+            const V v = *reinterpret_cast<const V*>(X + (size_t)c * F + f);
+            const float* pv = reinterpret_cast<const float*>(&v);
+#pragma unroll
+            for (int s = 0; s < NS; ++s) {
+                const float w = s < ns ? s_w[s * stage + k] : 0.0f;
+#pragma unroll
+                for (int i = 0; i < VEC; ++i) acc[s][i] += w * pv[i];
+            }
+        }
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            if (s >= ns) continue;
+            V o; float* po = reinterpret_cast<float*>(&o);
+#pragma unroll
+            for (int i = 0; i < VEC; ++i) po[i] = acc[s][i] * inv[s];
+            *reinterpret_cast<V*>(out_row + s * out_stride + f) = o;
+        }
+    }
+}
+
+// Fused form.  LDS: s_col[stage] then s_w[nsc][stage], stage = K; nsc <= NS (the kernel's accumulators per lane).
+template <int VEC, int NS>
+__global__ void __launch_bounds__(kBlock)
+random_prop_rows_multi_kernel(const float* __restrict__ X, int F, const int* __restrict__ col,
+                              const double* __restrict__ val, const int* __restrict__ filled, int K,
+                              const int* __restrict__ batch_rows, int n_batch, int S, int nsc, float p, int training, u64 seed,
+                              const unsigned char* __restrict__ keep, long long keep_stride, float* __restrict__ out)
+{
+    extern __shared__ float smem[];
+    int* s_col = reinterpret_cast<int*>(smem);
+    float* s_w = smem + K;
+    const float scale = p < 1.0f ? 1.0f / (1.0f - p) : 0.0f;
+    const size_t out_stride = (size_t)n_batch * F;
+    for (int b = blockIdx.x; b < n_batch; b += gridDim.x) {
+        const long long row = batch_rows ? batch_rows[b] : b;
+        const int n = filled ? min(filled[row], K) : K;
+        for (int s0 = 0; s0 < S; s0 += nsc) {
+            const int ns = min(nsc, S - s0);
+            __syncthreads();
+            for (int k = threadIdx.x; k < n; k += kBlock) {
+                const long long e = row * (long long)K + k;
+                const float w = (float)val[e];                      // model.py:314
+                if (s0 == 0) s_col[k] = col[e];
+                for (int s = 0; s < ns; ++s) s_w[s * K + k] = sample_weight(w, e, s0 + s, p, scale, training, seed, keep, keep_stride);
+            }
+            __syncthreads();
+            weighted_rows_multi<VEC, NS>(X, F, s_col, 0, s_w, K, n, ns, out + s0 * out_stride + (size_t)b * F, out_stride);
+        }
+    }
+}
+
+__device__ __forceinline__ void segment_of(const long long* __restrict__ idx, long long n_entries, long long b, long long& lo, long long& hi)
+{
+    // lower_bound(idx, b) and lower_bound(idx, b+1); every lane searches (same addresses: broadcast loads)
+    long long l = 0, h = n_entries;
+    while (l < h) { const long long mid = (l + h) >> 1; if (idx[mid] < b) l = mid + 1; else h = mid; }
+    lo = l; h = n_entries;
+    while (l < h) { const long long mid = (l + h) >> 1; if (idx[mid] < b + 1) l = mid + 1; else h = mid; }
+    hi = l;
+}
+
+// Reference-shaped form.  LDS: s_w[nsc][kStage].  A segment longer than kStage takes the single kernel's plain loop,
+// once per sample.
+template <int VEC, int NS>
+__global__ void __launch_bounds__(kBlock)
+random_prop_coo_multi_kernel(const float* __restrict__ feats, int F, const float* __restrict__ scores,
+                             const long long* __restrict__ idx, long long n_entries, long long n_out, int S, int nsc,
+                             float p, int training, u64 seed, const unsigned char* __restrict__ keep,
+                             float* __restrict__ out)
+{
+    extern __shared__ float s_w[];
+    const float scale = p < 1.0f ? 1.0f / (1.0f - p) : 0.0f;
+    const size_t out_stride = (size_t)n_out * F;
+    for (long long b = blockIdx.x; b < n_out; b += gridDim.x) {
+        long long lo, hi;
+        segment_of(idx, n_entries, b, lo, hi);
+        if (hi - lo <= kStage) {
+            const int n = (int)(hi - lo);
+            for (int s0 = 0; s0 < S; s0 += nsc) {
+                const int ns = min(nsc, S - s0);
+                __syncthreads();
+                for (int k = threadIdx.x; k < n; k += kBlock)
+                    for (int s = 0; s < ns; ++s) s_w[s * kStage + k] = sample_weight(scores[lo + k], lo + k, s0 + s, p, scale, training, seed, keep, n_entries);
+                __syncthreads();
+                weighted_rows_multi<VEC, NS>(feats, F, nullptr, lo, s_w, kStage, n, ns, out + s0 * out_stride + (size_t)b * F, out_stride);
+            }
+        } else {
+            for (int s = 0; s < S; ++s) {
+                float den = 0.0f;
+                for (long long e = lo; e < hi; ++e) den += sample_weight(scores[e], e, s, p, scale, training, seed, keep, n_entries);
+                const float inv = 1.0f / (den + 1e-12f);
+                float* out_row = out + s * out_stride + (size_t)b * F;
+                for (int f = blockIdx.y * kBlock + threadIdx.x; f < F; f += gridDim.y * kBlock) {
+                    float acc = 0.0f;
+                    for (long long e = lo; e < hi; ++e) {
+                        const float w = sample_weight(scores[e], e, s, p, scale, training, seed, keep, n_entries);
+                        if (w != 0.0f) acc += w * feats[(size_t)e * F + f];
+                    }
+                    out_row[f] = acc * inv;
+                }
+            }
+        }
+    }
+}
+
+// COO backward: grad_feats[e,:] = sum_s w'_{s,e} / (den_{s,b} + 1e-12) * g[s,b,:], summed over s in order, one pass,
+// no atomics.  Weights of a chunk of samples are staged as in the forward; with more than one chunk the chunk's
+// sum is added to what the same thread wrote for the previous chunk.
+template <int VEC>
+__device__ __forceinline__ void scaled_rows_multi(const float* __restrict__ g, size_t g_stride, int F, const float* s_w, int stage,
+                                                  int n, int ns, const float* inv, bool first, float* __restrict__ out_rows)
+{
+    typedef typename VecT<VEC>::type V;
+    const int FV = F / VEC;
+    for (int t = threadIdx.x; t < n * FV; t += kBlock) {
+        const int k = t / FV, f = (t - k * FV) * VEC;
+        V o = first ? V() : *reinterpret_cast<const V*>(out_rows + (size_t)k * F + f);
+        float* po = reinterpret_cast<float*>(&o);
+        for (int s = 0; s < ns; ++s) {
+            const V gv = *reinterpret_cast<const V*>(g + s * g_stride + f);
+            const float* pg = reinterpret_cast<const float*>(&gv);
+            const float w = s_w[s * stage + k];
+#pragma unroll
+            for (int i = 0; i < VEC; ++i) po[i] += (pg[i] * inv[s]) * w;
+        }
+        *reinterpret_cast<V*>(out_rows + (size_t)k * F + f) = o;
+    }
+}
+
+__global__ void __launch_bounds__(kBlock)
+random_prop_coo_multi_backward_kernel(const float* __restrict__ grad_out, int F, const float* __restrict__ scores,
+                                      const long long* __restrict__ idx, long long n_entries, long long n_out, int S, int nsc,
+                                      float p, int training, u64 seed, const unsigned char* __restrict__ keep,
+                                      float* __restrict__ grad_feats)
+{
+    extern __shared__ float s_w[];
+    const float scale = p < 1.0f ? 1.0f / (1.0f - p) : 0.0f;
+    const size_t g_stride = (size_t)n_out * F;
+    for (long long b = blockIdx.x; b < n_out; b += gridDim.x) {
+        long long lo, hi;
+        segment_of(idx, n_entries, b, lo, hi);
+        const float* g_row = grad_out + (size_t)b * F;
+        if (hi - lo <= kStage) {
+            const int n = (int)(hi - lo);
+            float* rows = grad_feats + (size_t)lo * F;
+            for (int s0 = 0; s0 < S; s0 += nsc) {
+                const int ns = min(nsc, S - s0);
+                __syncthreads();
+                for (int k = threadIdx.x; k < n; k += kBlock)
+                    for (int s = 0; s < ns; ++s) s_w[s * kStage + k] = sample_weight(scores[lo + k], lo + k, s0 + s, p, scale, training, seed, keep, n_entries);
+                __syncthreads();
+                float inv[kMaxSamples];
+                for (int s = 0; s < ns; ++s) {
+                    float den = 0.0f;
+                    for (int k = 0; k < n; ++k) den += s_w[s * kStage + k];          // the forward's order
+                    inv[s] = 1.0f / (den + 1e-12f);
+                }
+                const float* g = g_row + s0 * g_stride;
+                if ((F & 3) == 0)      scaled_rows_multi<4>(g, g_stride, F, s_w, kStage, n, ns, inv, s0 == 0, rows);
+                else if ((F & 1) == 0) scaled_rows_multi<2>(g, g_stride, F, s_w, kStage, n, ns, inv, s0 == 0, rows);
+                else                   scaled_rows_multi<1>(g, g_stride, F, s_w, kStage, n, ns, inv, s0 == 0, rows);
+            }
+        } else {
+            for (int s = 0; s < S; ++s) {
+                float den = 0.0f;
+                for (long long e = lo; e < hi; ++e) den += sample_weight(scores[e], e, s, p, scale, training, seed, keep, n_entries);
+                const float inv = 1.0f / (den + 1e-12f);
+                const float* g = g_row + s * g_stride;
+                for (long long e = lo; e < hi; ++e) {
+                    const float w = sample_weight(scores[e], e, s, p, scale, training, seed, keep, n_entries);
+                    for (int f = threadIdx.x; f < F; f += kBlock) {
+                        const float x = (g[f] * inv) * w;
+                        grad_feats[(size_t)e * F + f] = s == 0 ? x : grad_feats[(size_t)e * F + f] + x;
+                    }
+                }
+            }
+        }
+    }
+}
+
+// Fused backward: grad_X[col[r,k],:] += sum_s w'_{s,r,k} / (den_{s,b} + 1e-12) * g[s,b,:] -- the samples are summed in
+// registers and each element of an entry gets one fp32 atomic per sample chunk (one in all when S <= nsc).
+__global__ void __launch_bounds__(kBlock)
+random_prop_rows_multi_backward_kernel(const float* __restrict__ grad_out, int F, const int* __restrict__ col,
+                                       const double* __restrict__ val, const int* __restrict__ filled, int K,
+                                       const int* __restrict__ batch_rows, int n_batch, long long n_nodes, int S, int nsc,
+                                       float p, int training, u64 seed, const unsigned char* __restrict__ keep,
+                                       long long keep_stride, float* __restrict__ grad_x)
+{
+    extern __shared__ float smem[];
+    int* s_col = reinterpret_cast<int*>(smem);
+    float* s_inv = smem + K;                              // [nsc]
+    float* s_w = s_inv + kMaxSamples;                     // [nsc][K]
+    const float scale = p < 1.0f ? 1.0f / (1.0f - p) : 0.0f;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const size_t g_stride = (size_t)n_batch * F;
+    for (int b = blockIdx.x; b < n_batch; b += gridDim.x) {
+        const long long row = batch_rows ? batch_rows[b] : b;
+        const int n = filled ? min(filled[row], K) : K;
+        for (int s0 = 0; s0 < S; s0 += nsc) {
+            const int ns = min(nsc, S - s0);
+            __syncthreads();
+            for (int k = threadIdx.x; k < n; k += kBlock) {
+                const long long e = row * (long long)K + k;
+                const float w = (float)val[e];
+                if (s0 == 0) s_col[k] = col[e];
+                for (int s = 0; s < ns; ++s) s_w[s * K + k] = sample_weight(w, e, s0 + s, p, scale, training, seed, keep, keep_stride);
+            }
+            __syncthreads();
+            if (threadIdx.x < ns) {
+                float den = 0.0f;
+                for (int k = 0; k < n; ++k) den += s_w[threadIdx.x * K + k];
+                s_inv[threadIdx.x] = 1.0f / (den + 1e-12f);
+            }
+            __syncthreads();
+            const float* g = grad_out + s0 * g_stride + (size_t)b * F;
+            for (int k = wave; k < n; k += kBlock / 64) {
+                const int c = s_col[k];
+                bool any = false;
+                for (int s = 0; s < ns; ++s) any |= s_w[s * K + k] != 0.0f;
+                if (!any || c < 0 || c >= n_nodes) continue;               // wave-uniform
+                float* dst = grad_x + (size_t)c * F;
+                for (int f = lane; f < F; f += 64) {
+                    float x = 0.0f;
+                    for (int s = 0; s < ns; ++s) x += (g[s * g_stride + f] * s_inv[s]) * s_w[s * K + k];
+                    atomicAdd(dst + f, x);
+                }
+            }
+        }
+    }
+}
+
+int multi_check(const char* where, int32_t n_samples, float rate)
+{
+    if (n_samples < 1 || n_samples > kMaxSamples || !(rate >= 0.0f && rate <= 1.0f)) {
+        gp_internal_set_error(GP_ERR_INVALID_ARG, where, "n_samples outside [1, 16] or dropnode_rate outside [0, 1]");
+        return GP_ERR_INVALID_ARG;
+    }
+    return GP_OK;
+}
+
+int rows_nsc(int K, int S, int extra_floats)      // samples per chunk of the fused form's LDS
+{
+    const int fit = (kMultiLdsBytes / 4 - K - extra_floats) / K;
+    return std::min(S, std::min(fit, kMaxSamples));
+}
+
+// Accumulators per lane of the forward kernels: S rounded up to a power of two, at most 8 (a chunk of 8 samples at
+// VEC = 4 keeps 32 sums and 32 loaded floats per lane in registers); more samples take several chunks.
+int forward_ns(int S) { return S <= 1 ? 1 : S <= 2 ? 2 : S <= 4 ? 4 : 8; }
+
+#define GP_MULTI_DISPATCH(KERNEL, VEC, NS, ...)                                                                          \
+    do {                                                                                                                \
+        if (VEC == 4)      { if (NS == 1) KERNEL(4, 1, __VA_ARGS__); else if (NS == 2) KERNEL(4, 2, __VA_ARGS__);        \
+                             else if (NS == 4) KERNEL(4, 4, __VA_ARGS__); else KERNEL(4, 8, __VA_ARGS__); }             \
+        else if (VEC == 2) { if (NS == 1) KERNEL(2, 1, __VA_ARGS__); else if (NS == 2) KERNEL(2, 2, __VA_ARGS__);        \
+                             else if (NS == 4) KERNEL(2, 4, __VA_ARGS__); else KERNEL(2, 8, __VA_ARGS__); }             \
+        else               { if (NS == 1) KERNEL(1, 1, __VA_ARGS__); else if (NS == 2) KERNEL(1, 2, __VA_ARGS__);        \
+                             else if (NS == 4) KERNEL(1, 4, __VA_ARGS__); else KERNEL(1, 8, __VA_ARGS__); }             \
+    } while (0)
+
+}  // namespace
+
+extern "C" {
+
+int gp_random_prop_rows_multi(int device, const float* d_x, int64_t n_nodes, int32_t feat_dim,
+                              const int32_t* d_col, const double* d_val, const int32_t* d_filled, int32_t K,
+                              const int32_t* d_batch_rows, int32_t n_batch, int32_t n_samples,
+                              float dropnode_rate, int training, uint64_t seed, const uint8_t* d_keep, int64_t keep_stride,
+                              float* d_out, void* stream)
+{
+    const char* where = "gp_random_prop_rows_multi";
+    if (const int rc = multi_check(where, n_samples, dropnode_rate)) return rc;
+    if (n_nodes < 1 || feat_dim < 1 || K < 1 || K > GP_MAX_K || n_batch < 0 || (d_keep && keep_stride < 1)) {
+        gp_internal_set_error(GP_ERR_INVALID_ARG, where, "bad size, K outside [1, 1024] or keep_stride < 1 with a mask");
+        return GP_ERR_INVALID_ARG;
+    }
+    if (n_batch == 0) return GP_OK;
+    if (!d_x || !d_col || !d_val || !d_out) { gp_internal_set_error(GP_ERR_NULL, where, "a device pointer is NULL"); return GP_ERR_NULL; }
+    if (const int rc = set_device(device, where)) return rc;
+    const int ns = forward_ns(n_samples);
+    const int nsc = std::min(ns, rows_nsc(K, n_samples, 0));
+    const size_t lds = (size_t)(K + nsc * K) * 4;
+    const int grid = n_batch < 65535 ? n_batch : 65535;
+    const int vec = (feat_dim & 3) == 0 ? 4 : (feat_dim & 1) == 0 ? 2 : 1;
+    const int slabs = (feat_dim + kBlock * vec - 1) / (kBlock * vec);
+    hipStream_t s = (hipStream_t)stream;
+#define GP_ROWS_MULTI(V, N, _) hipLaunchKernelGGL((random_prop_rows_multi_kernel<V, N>), dim3(grid, slabs), dim3(kBlock), lds, s, d_x, \
+        feat_dim, d_col, d_val, d_filled, K, d_batch_rows, n_batch, n_samples, nsc, dropnode_rate, training, (u64)seed, d_keep,      \
+        (long long)keep_stride, d_out)
+    GP_MULTI_DISPATCH(GP_ROWS_MULTI, vec, ns, 0);
+#undef GP_ROWS_MULTI
+    return launch_status("random_prop_rows_multi_kernel");
+}
+
+int gp_random_prop_coo_multi(int device, const float* d_feats, int64_t n_entries, int32_t feat_dim,
+                             const float* d_scores, const int64_t* d_idx, int64_t n_out, int32_t n_samples,
+                             float dropnode_rate, int training, uint64_t seed, const uint8_t* d_keep,
+                             float* d_out, void* stream)
+{
+    const char* where = "gp_random_prop_coo_multi";
+    if (const int rc = multi_check(where, n_samples, dropnode_rate)) return rc;
+    if (n_entries < 0 || n_entries > 2147483647ll || feat_dim < 1 || n_out < 0) {
+        gp_internal_set_error(GP_ERR_INVALID_ARG, where, "bad size");
+        return GP_ERR_INVALID_ARG;
+    }
+    if (n_out == 0) return GP_OK;
+    if ((n_entries > 0 && (!d_feats || !d_scores || !d_idx)) || !d_out) { gp_internal_set_error(GP_ERR_NULL, where, "a device pointer is NULL"); return GP_ERR_NULL; }
+    if (const int rc = set_device(device, where)) return rc;
+    const int ns = forward_ns(n_samples);
+    const int nsc = std::min(ns, kMultiLdsBytes / (4 * kStage));
+    const size_t lds = (size_t)nsc * kStage * 4;
+    const int grid = n_out < 65535 ? (int)n_out : 65535;
+    const int vec = (feat_dim & 3) == 0 ? 4 : (feat_dim & 1) == 0 ? 2 : 1;
+    const int slabs = (feat_dim + kBlock * vec - 1) / (kBlock * vec);
+    hipStream_t s = (hipStream_t)stream;
+#define GP_COO_MULTI(V, N, _) hipLaunchKernelGGL((random_prop_coo_multi_kernel<V, N>), dim3(grid, slabs), dim3(kBlock), lds, s, d_feats, \
+        feat_dim, d_scores, (const long long*)d_idx, (long long)n_entries, (long long)n_out, n_samples, nsc, dropnode_rate, training,     \
+        (u64)seed, d_keep, d_out)
+    GP_MULTI_DISPATCH(GP_COO_MULTI, vec, ns, 0);
+#undef GP_COO_MULTI
+    return launch_status("random_prop_coo_multi_kernel");
+}
+
+int gp_random_prop_coo_multi_backward(int device, const float* d_grad_out, int64_t n_out, int32_t feat_dim,
+                                      const float* d_scores, const int64_t* d_idx, int64_t n_entries, int32_t n_samples,
+                                      float dropnode_rate, int training, uint64_t seed, const uint8_t* d_keep,
+                                      float* d_grad_feats, void* stream)
+{
+    const char* where = "gp_random_prop_coo_multi_backward";
+    if (const int rc = multi_check(where, n_samples, dropnode_rate)) return rc;
+    if (n_entries < 0 || n_entries > 2147483647ll || feat_dim < 1 || n_out < 0) {
+        gp_internal_set_error(GP_ERR_INVALID_ARG, where, "bad size");
+        return GP_ERR_INVALID_ARG;
+    }
+    if (n_out == 0) return GP_OK;
+    if (!d_grad_out || (n_entries > 0 && (!d_scores || !d_idx || !d_grad_feats))) { gp_internal_set_error(GP_ERR_NULL, where, "a device pointer is NULL"); return GP_ERR_NULL; }
+    if (const int rc = set_device(device, where)) return rc;
+    const int nsc = std::min<int>(n_samples, kMultiLdsBytes / (4 * kStage));
+    const int grid = n_out < 65535 ? (int)n_out : 65535;
+    hipLaunchKernelGGL(random_prop_coo_multi_backward_kernel, dim3(grid), dim3(kBlock), (size_t)nsc * kStage * 4, (hipStream_t)stream,
+                       d_grad_out, feat_dim, d_scores, (const long long*)d_idx, (long long)n_entries, (long long)n_out, n_samples, nsc,
+                       dropnode_rate, training, (u64)seed, d_keep, d_grad_feats);
+    return launch_status("random_prop_coo_multi_backward_kernel");
+}
+
+int gp_random_prop_rows_multi_backward(int device, const float* d_grad_out, int32_t n_batch, int32_t feat_dim,
+                                       const int32_t* d_col, const double* d_val, const int32_t* d_filled, int32_t K,
+                                       const int32_t* d_batch_rows, int32_t n_samples, float dropnode_rate, int training, uint64_t seed,
+                                       const uint8_t* d_keep, int64_t keep_stride, float* d_grad_x, int64_t n_nodes, void* stream)
+{
+    const char* where = "gp_random_prop_rows_multi_backward";
+    if (const int rc = multi_check(where, n_samples, dropnode_rate)) return rc;
+    if (n_batch < 0 || n_nodes < 1 || feat_dim < 1 || K < 1 || K > GP_MAX_K || (d_keep && keep_stride < 1)) {
+        gp_internal_set_error(GP_ERR_INVALID_ARG, where, "bad size, K outside [1, 1024] or keep_stride < 1 with a mask");
+        return GP_ERR_INVALID_ARG;
+    }
+    if (n_batch == 0) return GP_OK;
+    if (!d_grad_out || !d_col || !d_val || !d_grad_x) { gp_internal_set_error(GP_ERR_NULL, where, "a device pointer is NULL"); return GP_ERR_NULL; }
+    if (const int rc = set_device(device, where)) return rc;
+    const int nsc = rows_nsc(K, n_samples, kMaxSamples);
+    const size_t lds = (size_t)(K + kMaxSamples + nsc * K) * 4;
+    const int grid = n_batch < 65535 ? n_batch : 65535;
+    hipLaunchKernelGGL(random_prop_rows_multi_backward_kernel, dim3(grid), dim3(kBlock), lds, (hipStream_t)stream, d_grad_out, feat_dim,
+                       d_col, d_val, d_filled, K, d_batch_rows, n_batch, (long long)n_nodes, n_samples, nsc, dropnode_rate, training,
+                       (u64)seed, d_keep, (long long)keep_stride, d_grad_x);
+    return launch_status("random_prop_rows_multi_backward_kernel");
+}
+
+}  // extern "C"

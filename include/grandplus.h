@@ -318,6 +318,88 @@ int gp_embedding_bag_backward(int device, const float* d_grad_out, int64_t n_voc
                               float* d_grad_weight, int32_t* d_n_bad, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * S-sample random_prop: the `--sample S` augmentations of one training step
+ * (model.py:321-322) in one launch, 1 <= n_samples <= 16 (anything else: GP_ERR_INVALID_ARG).
+ * d_out is [S x n_out x feat_dim], sample-major: out[s] is the [n_out x feat_dim] block the
+ * single-sample entry above returns, bit for bit, when called with seed_s (or with mask row s):
+ *
+ *     seed_0 = seed
+ *     seed_s = mix(seed ^ (s * 0xD6E8FEB86659FD93)),  s >= 1,   all arithmetic mod 2^64, where
+ *     mix(x) : x += 0x9E3779B97F4A7C15;  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9;
+ *              x = (x ^ (x >> 27)) * 0x94D049BB133111EB;  return x ^ (x >> 31)
+ *
+ * (grand_plus_amd.augment.sample_seed mirrors it.)  An explicit mask d_keep is uint8 [S x L]: row s
+ * is the d_keep the single-sample call takes; L = keep_stride for the fused form (>= the largest
+ * r*K + K used, normally the length of d_col) and n_entries for the COO form.  Each neighbour
+ * feature row is read once per chunk of up to 8 samples: for S <= 8 the HBM bound is
+ * 4 F (entries + S n_out) + (4 + 4 S) entries bytes (a second feature pass for S > 8).
+ * ------------------------------------------------------------------------------------------ */
+int gp_random_prop_rows_multi(int device, const float* d_x, int64_t n_nodes, int32_t feat_dim,
+                              const int32_t* d_col, const double* d_val, const int32_t* d_filled, int32_t K,
+                              const int32_t* d_batch_rows, int32_t n_batch, int32_t n_samples,
+                              float dropnode_rate, int training, uint64_t seed, const uint8_t* d_keep, int64_t keep_stride,
+                              float* d_out, void* stream);
+
+/* n_out is the caller's (idx[-1] + 1 when it wants the reference's shape; passing it saves the host read). */
+int gp_random_prop_coo_multi(int device, const float* d_feats, int64_t n_entries, int32_t feat_dim,
+                             const float* d_scores, const int64_t* d_idx, int64_t n_out, int32_t n_samples,
+                             float dropnode_rate, int training, uint64_t seed, const uint8_t* d_keep,
+                             float* d_out, void* stream);
+
+/* d_grad_feats[e,:] = sum_s w'_{s,e} / (den_{s,b} + 1e-12) * d_grad_out[s,b,:], b = d_idx[e], summed over s in order:
+ * every row is written, no atomics, bitwise reproducible. */
+int gp_random_prop_coo_multi_backward(int device, const float* d_grad_out, int64_t n_out, int32_t feat_dim,
+                                      const float* d_scores, const int64_t* d_idx, int64_t n_entries, int32_t n_samples,
+                                      float dropnode_rate, int training, uint64_t seed, const uint8_t* d_keep,
+                                      float* d_grad_feats, void* stream);
+
+/* d_grad_x[col[r,k],:] += sum_s w'_{s,r,k} / (den_{s,b} + 1e-12) * d_grad_out[s,b,:] into a caller-zeroed d_grad_x: the
+ * samples are summed in registers, then one fp32 atomic per element and entry (per chunk of samples when K > 962).
+ * Not bitwise reproducible. */
+int gp_random_prop_rows_multi_backward(int device, const float* d_grad_out, int32_t n_batch, int32_t feat_dim,
+                                       const int32_t* d_col, const double* d_val, const int32_t* d_filled, int32_t K,
+                                       const int32_t* d_batch_rows, int32_t n_samples, float dropnode_rate, int training, uint64_t seed,
+                                       const uint8_t* d_keep, int64_t keep_stride, float* d_grad_x, int64_t n_nodes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The GRAND+ training objective after the MLP, fused (model.py:123-139, 321-331).
+ * d_z fp32 [S x B x C] (S = n_samples <= 16, B = n_rows, C = n_classes <= 4096): logits, or
+ * log-probabilities when inputs_are_log_probs != 0.  Rows b < n_labeled carry d_labels[b] (int64);
+ * the rest are the unlabelled batch.  With logp = log_softmax(z) and p = exp(logp):
+ *   L_sup  = (1/S) sum_s mean_{b < n_l, y_b != ignore_index} -logp[s,b,y_b]
+ *   avg_p  = (1/S) sum_s p[s];  mask_b = b >= n_l and max_c avg_p[b,c] > conf
+ *   q_b    = softmax(log(avg_p[b]) / tem)  (log(avg_p) formed in the log domain)
+ *   L_con  = (1/S) sum_s mean_{b in mask} (kind GP_LOSS_KL: sum_c -q logp;  GP_LOSS_L2: sum_c (p - q)^2)
+ *   loss   = L_sup + weight * L_con
+ * A mean over an empty set is NaN (as torch.mean of an empty tensor) and contributes no gradient.
+ * Labels outside [0, C) other than ignore_index are never read as an index: they are left out of
+ * L_sup and counted.
+ *
+ * gp_grand_loss writes d_out fp32[3] = {loss, L_sup, L_con} and d_counts int32[4] = {n_conf, n_valid,
+ * n_correct (argmax of the last sample == label), n_bad_labels}.  d_workspace: device memory of
+ * GP_GRAND_LOSS_WORKSPACE_BYTES(n_rows) bytes, 8-byte aligned, owned by the caller (nothing is
+ * allocated on the call path).  Two launches: a row kernel and a one-workgroup fp64 reduce.
+ *
+ * gp_grand_loss_backward writes d_grad_z [S x B x C] (the gradient with respect to d_z) from the same
+ * arguments, the forward's d_counts and the device scalars d_grad_loss (required), d_grad_sup and
+ * d_grad_con (the gradients of L_sup and L_con themselves; NULL = 0).  One launch.
+ *
+ * Both enqueue on `stream` and never synchronise; no atomics, so both are bitwise reproducible.
+ * Arguments (sizes, NULL pointers, tem <= 0, unknown kind) are checked before the device is touched.
+ * ------------------------------------------------------------------------------------------ */
+#define GP_LOSS_KL 0
+#define GP_LOSS_L2 1
+#define GP_GRAND_LOSS_WORKSPACE_BYTES(n_rows) ((int64_t)(n_rows) * 20)
+
+int gp_grand_loss(int device, const float* d_z, int32_t n_samples, int64_t n_rows, int32_t n_classes,
+                  const int64_t* d_labels, int64_t n_labeled, int64_t ignore_index, float weight, float tem, float conf,
+                  int kind, int inputs_are_log_probs, void* d_workspace, float* d_out, int32_t* d_counts, void* stream);
+int gp_grand_loss_backward(int device, const float* d_z, int32_t n_samples, int64_t n_rows, int32_t n_classes,
+                           const int64_t* d_labels, int64_t n_labeled, int64_t ignore_index, float weight, float tem, float conf,
+                           int kind, int inputs_are_log_probs, const float* d_grad_loss, const float* d_grad_sup,
+                           const float* d_grad_con, const int32_t* d_counts, float* d_grad_z, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * exact full-graph feature propagation of the inference path, reference
  * predict() (model.py:181-224), lines 186-210.  mode 0 = ppr, 1 = avg, 2 = single (args.prop_mode);
  * `order` = args.order propagation steps.  A is the CSR of `g` (adj + I as the caller built it,
