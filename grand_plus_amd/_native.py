@@ -32,9 +32,28 @@ EXPORTS = (
     "gp_random_prop_coo_backward", "gp_random_prop_rows_backward", "gp_embedding_bag", "gp_embedding_bag_backward",
     "gp_random_prop_coo_multi", "gp_random_prop_rows_multi", "gp_random_prop_coo_multi_backward",
     "gp_random_prop_rows_multi_backward", "gp_grand_loss", "gp_grand_loss_backward",
+    "gp_mlp_block_forward", "gp_mlp_block_backward",
 )
 GP_LOSS_KL, GP_LOSS_L2 = 0, 1
 GP_MAX_SAMPLES = 16
+
+
+GP_MLP_RELU, GP_MLP_NORM, GP_MLP_BN, GP_MLP_TRAINING = 1, 2, 4, 8
+
+
+def mlp_saved_floats(S: int, B: int, f_in: int) -> int:
+    """GP_MLP_SAVED_FLOATS of grandplus.h."""
+    return S * B + 4 * S * f_in
+
+
+def mlp_forward_workspace_bytes(S: int) -> int:
+    """GP_MLP_FORWARD_WORKSPACE_BYTES of grandplus.h."""
+    return S * 2097152
+
+
+def mlp_backward_workspace_bytes(S: int, B: int, f_in: int) -> int:
+    """GP_MLP_BACKWARD_WORKSPACE_BYTES of grandplus.h."""
+    return 4 * (S * B * f_in + 524288)
 
 
 def grand_loss_workspace_bytes(n_rows: int) -> int:
@@ -160,6 +179,10 @@ def lib():
     _loss = [ctypes.c_int, vp, i32, i64, i32, vp, i64, i64, f32, f32, f32, ctypes.c_int, ctypes.c_int]
     _optional(L, "gp_grand_loss", _loss + [vp, vp, vp, vp])
     _optional(L, "gp_grand_loss_backward", _loss + [vp, vp, vp, vp, vp, vp])
+    _optional(L, "gp_mlp_block_forward", [ctypes.c_int, vp, i32, i64, i32, i32, vp, vp, ctypes.c_int, vp, vp, vp, vp, vp, f32, f32,
+                                          f32, u64, i32, vp, vp, vp, vp, vp, vp])
+    _optional(L, "gp_mlp_block_backward", [ctypes.c_int, vp, i32, i64, i32, i32, vp, ctypes.c_int, vp, f32, u64, i32, vp,
+                                           vp, vp, vp, vp, vp, vp, vp, vp, vp, vp])
     L.gp_propagate_features.restype = ctypes.c_int
     L.gp_propagate_features.argtypes = [vp, vp, ctypes.c_int32, vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, vp, vp]
     L.gp_internal_diag_counters.restype = ctypes.c_int

@@ -1,0 +1,316 @@
+"""GRAND+'s MLP on MI355X: all S samples of a training step through each layer in one set of HIP launches.
+
+Reference `MLP.forward` (model.py:48-66, model_mag.py:57-67), called once per sample there.  Every layer is the block
+
+    block(x) = Linear( dropout_p( BN( node_norm( relu?(x) ) ) ) ),      node_norm(u) = u / (1e-12 + |u|_2)
+
+run by `gp_mlp_block_forward` / `gp_mlp_block_backward` of csrc/mlp.hip over x [S, B, F] (what
+`random_prop*(samples=S)` returns).  BatchNorm in training takes each sample's own batch statistics and updates the
+running statistics once per sample in sample order, exactly as S calls of `bn(x)`.
+
+  * `GrandPlusMLP` -- model.py's layout (layer 0: no ReLU, node_norm with `.detach()`, `bns[0]`, `input_droprate`);
+  * `MagMLP`       -- model_mag.py's layout (`embeds`, then "ReLU, node_norm, BN, hidden_droprate, fc" per layer).
+
+Both keep the reference's submodules (`fcs`, `bns`, `embeds`), so a `state_dict` loads in either direction.  Dropout of
+layer l, sample s, entry b * F + f uses the counter hash on `layer_seed(seed, l, s)` (grandplus.h), or an explicit uint8
+keep mask per layer.  Calls without grad (eval, `torch.no_grad`) run the forward kernels only.  There is no fallback:
+`reference_forward` is the torch formulation kept for comparison and benchmarks, never taken silently.
+"""
+from __future__ import annotations
+
+import ctypes
+
+import torch
+import torch.nn as nn
+from torch.autograd.function import once_differentiable
+
+from . import _native
+from .augment import _M64, _new_seed, sample_seed
+
+_LAYER_MUL = 0xA0761D6478BD642F
+
+
+def _mix(x: int) -> int:
+    x = (x + 0x9E3779B97F4A7C15) & _M64
+    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & _M64
+    return x ^ (x >> 31)
+
+
+def layer_seed(seed: int, layer: int, s: int = 0) -> int:
+    """Dropout seed of (layer, sample s) of a call with `seed`: GP_MLP_LAYER_SEED(gp_sample_seed(seed, s), layer)."""
+    return _mix(sample_seed(seed, s) ^ (((layer + 1) * _LAYER_MUL) & _M64))
+
+
+def _stream(t):
+    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+class _Cfg:
+    """The non-tensor arguments of one block call."""
+    __slots__ = ("flags", "bn", "p", "seed", "layer", "keep")
+
+    def __init__(self, flags, bn, p, seed, layer, keep):
+        self.flags, self.bn, self.p, self.seed, self.layer, self.keep = flags, bn, p, seed, layer, keep
+
+
+def _forward(x, weight, bias, gamma, beta, c, save_a):
+    S, B, F = x.shape
+    N = weight.shape[0]
+    out = torch.empty((S, B, N), dtype=torch.float32, device=x.device)
+    saved = None
+    if c.flags & (_native.GP_MLP_NORM | _native.GP_MLP_BN):
+        saved = torch.empty(_native.mlp_saved_floats(S, B, F), dtype=torch.float32, device=x.device)
+    a = torch.empty_like(x) if save_a else None
+    ws = torch.empty(_native.mlp_forward_workspace_bytes(S), dtype=torch.uint8, device=x.device)
+    bn = c.bn
+    rm = bn.running_mean if bn is not None else None
+    rv = bn.running_var if bn is not None else None
+    nbt = bn.num_batches_tracked if bn is not None and c.flags & _native.GP_MLP_TRAINING else None
+    rc = _native.lib().gp_mlp_block_forward(
+        x.device.index, x.data_ptr(), S, B, F, N, weight.data_ptr(), _ptr(bias), c.flags, _ptr(gamma), _ptr(beta),
+        _ptr(rm), _ptr(rv), _ptr(nbt), float(bn.eps) if bn is not None else 1e-5,
+        float(bn.momentum) if bn is not None else 0.1, float(c.p), ctypes.c_uint64(c.seed), c.layer, _ptr(c.keep),
+        out.data_ptr(), _ptr(saved), _ptr(a), ws.data_ptr(), _stream(x))
+    _native.raise_for_status(rc)
+    return out, saved, a
+
+
+class _BlockFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, gamma, beta, c):
+        out, saved, a = _forward(x, weight, bias, gamma, beta, c, save_a=ctx.needs_input_grad[1])
+        ctx.save_for_backward(x, weight, gamma, saved, a)
+        ctx.c = c
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        x, weight, gamma, saved, a = ctx.saved_tensors
+        c = ctx.c
+        S, B, F = x.shape
+        N = weight.shape[0]
+        gy = gy.contiguous()
+        nx, nw, nb, ng, nbe = ctx.needs_input_grad[:5]
+        new = lambda need, shape: torch.empty(shape, dtype=torch.float32, device=x.device) if need else None  # noqa: E731
+        gx, gw, gb = new(nx, x.shape), new(nw, weight.shape), new(nb, (N,))
+        gg = new(ng and gamma is not None, (F,))
+        gbe = new(nbe, (F,))
+        ws = torch.empty(_native.mlp_backward_workspace_bytes(S, B, F), dtype=torch.uint8, device=x.device)
+        rc = _native.lib().gp_mlp_block_backward(
+            x.device.index, x.data_ptr(), S, B, F, N, weight.data_ptr(), c.flags, _ptr(gamma), float(c.p),
+            ctypes.c_uint64(c.seed), c.layer, _ptr(c.keep), _ptr(saved), _ptr(a), gy.data_ptr(), _ptr(gx), _ptr(gw),
+            _ptr(gb), _ptr(gg), _ptr(gbe), ws.data_ptr(), _stream(x))
+        _native.raise_for_status(rc)
+        return gx, gw, gb, gg, gbe, None
+
+
+def _check_bn(bn):
+    if bn.momentum is None:
+        raise ValueError("BatchNorm1d with momentum=None (cumulative average) is not supported; the reference uses 0.1")
+    if not bn.track_running_stats or bn.running_mean is None:
+        raise ValueError("BatchNorm1d without running statistics is not supported (the reference tracks them)")
+
+
+def block(x, fc, bn, *, relu, node_norm, training, dropout, seed, layer, keep=None):
+    """One block on x [S, B, F] (contiguous float32 CUDA): Linear(dropout(BN(node_norm(relu?(x))))).  bn None = no
+    BatchNorm.  Differentiable with respect to x, fc's and bn's parameters; running statistics update in training."""
+    S, B, F = x.shape
+    flags = (_native.GP_MLP_RELU if relu else 0) | (_native.GP_MLP_NORM if node_norm else 0) | \
+            (_native.GP_MLP_BN if bn is not None else 0) | (_native.GP_MLP_TRAINING if training else 0)
+    if fc.weight.shape[1] != F:
+        raise ValueError(f"the layer takes {fc.weight.shape[1]} features, the input has {F}")
+    for name, t in (("weight", fc.weight), ("bias", fc.bias)) + ((("bn weight", bn.weight), ("bn bias", bn.bias),
+                                                                   ("running_mean", bn.running_mean),
+                                                                   ("running_var", bn.running_var)) if bn is not None else ()):
+        if t is not None and (t.dtype != torch.float32 or t.device != x.device or not t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous float32 tensor on {x.device}")
+    if bn is not None:
+        _check_bn(bn)
+        if bn.num_features != F:
+            raise ValueError(f"BatchNorm1d has {bn.num_features} features, the input has {F}")
+        if training and B < 2:
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size {[B, F]}")
+    if keep is not None:
+        if not isinstance(keep, torch.Tensor) or keep.dtype != torch.uint8 or keep.device != x.device or not keep.is_contiguous():
+            raise ValueError("keep must be a contiguous uint8 tensor on the input's device")
+        if keep.numel() != S * B * F:
+            raise ValueError(f"keep must hold S x B x F = {S * B * F} entries, got {keep.numel()}")
+    c = _Cfg(flags, bn, float(dropout), int(seed) & _M64, int(layer), keep if training and dropout > 0 else None)
+    gamma = bn.weight if bn is not None else None
+    beta = bn.bias if bn is not None else None
+    params = (x, fc.weight, fc.bias, gamma, beta)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in params):
+        return _BlockFn.apply(x, fc.weight, fc.bias, gamma, beta, c)
+    return _forward(x, fc.weight, fc.bias, gamma, beta, c, save_a=False)[0]
+
+
+def _check_input(X, layers, training):
+    """Every host check before the first launch: shape, dtype, layout, sample count, BatchNorm's batch size, device."""
+    if not isinstance(X, torch.Tensor):
+        raise ValueError("X must be a tensor")
+    if X.dtype != torch.float32:
+        raise ValueError(f"X must be float32, got {X.dtype}")
+    if X.dim() not in (2, 3):
+        raise ValueError(f"X must be [B, F] or [S, B, F], got {tuple(X.shape)}")
+    if not X.is_contiguous():
+        raise ValueError("X must be contiguous (what random_prop*(samples=S) returns)")
+    x = X[None] if X.dim() == 2 else X
+    S, B, _ = x.shape
+    if not 1 <= S <= _native.GP_MAX_SAMPLES:
+        raise ValueError(f"the number of samples must be in [1, {_native.GP_MAX_SAMPLES}], got {S}")
+    if B < 1:
+        raise ValueError("X has no rows")
+    for _fc, bn, *_ in layers:
+        if bn is not None:
+            _check_bn(bn)
+            if training and B < 2:
+                raise ValueError(f"Expected more than 1 value per channel when training, got input size {[B, bn.num_features]}")
+    if not X.is_cuda:
+        raise ValueError("the MLP runs on the GPU only: X must be a CUDA tensor (no CPU fallback)")
+    if layers and layers[0][0].weight.device != X.device:
+        raise ValueError(f"X is on {X.device}, the parameters on {layers[0][0].weight.device}")
+    return x
+
+
+def _keeps(keep, n):
+    if keep is None:
+        return [None] * n
+    keep = list(keep)
+    if len(keep) != n:
+        raise ValueError(f"keep needs one mask (or None) per layer: {n}, got {len(keep)}")
+    return keep
+
+
+def _run(module, X, seed, keep, layers):
+    """layers: (fc, bn or None, relu, node_norm, detach, dropout) per layer."""
+    x = _check_input(X, layers, module.training)
+    seed = _new_seed() if seed is None else int(seed)
+    keeps = _keeps(keep, len(layers))
+    for l, ((fc, bn, relu, norm, detach, p), k) in enumerate(zip(layers, keeps)):
+        if detach:
+            x = x.detach()
+        x = block(x, fc, bn, relu=relu, node_norm=norm, training=module.training, dropout=p, seed=seed, layer=l, keep=k)
+    return x[0] if X.dim() == 2 else x
+
+
+def _torch_block(x, fc, bn, relu, norm, detach, p, training):
+    import torch.nn.functional as F
+    if relu:
+        x = F.relu(x)
+    if norm:
+        x = x / (1e-12 + torch.norm(x, p=2, dim=-1, keepdim=True))
+        if detach:
+            x = x.detach()
+    if bn is not None:
+        x = bn(x)
+    x = F.dropout(x, p, training=training)
+    return fc(x)
+
+
+class _MLPBase:
+    def reset_param(self):
+        for lin in self.fcs:
+            lin.reset_parameters()
+
+    def normalize(self, embedding):
+        return embedding / (1e-12 + torch.norm(embedding, p=2, dim=-1, keepdim=True))
+
+    def forward(self, X, seed=None, keep=None):
+        """X [S, B, F] or [B, F] float32 CUDA, contiguous -> [S, B, C] or [B, C].  seed: the dropout seed of this call
+        (None = a fresh one); keep: one uint8 [S, B, F_l] mask (or None) per layer in place of the hash."""
+        return _run(self, X, seed, keep, self._layers())
+
+    def reference_forward(self, X):
+        """The reference's MLP.forward on one [B, F] sample with torch ops and this module's parameters (torch's own
+        dropout RNG): what the benchmark compares against, called once per sample as model.py:321-325 does."""
+        x = X
+        for fc, bn, relu, norm, detach, p in self._layers():
+            x = _torch_block(x, fc, bn, relu, norm, detach, p, self.training)
+        return x
+
+
+class GrandPlusMLP(_MLPBase, nn.Module):
+    """model.py's `MLP` (model.py:17-66) over the HIP block kernels; same constructor, submodules and state_dict."""
+
+    def __init__(self, num_features, num_classes, hidden_size, nlayers, use_bn, input_dropout, hidden_dropout, node_norm):
+        nn.Module.__init__(self)
+        if nlayers == 1:
+            fcs = [nn.Linear(num_features, num_classes, bias=True)]
+            bns = [nn.BatchNorm1d(num_features)]
+        else:
+            fcs = [nn.Linear(num_features, hidden_size, bias=True)]
+            bns = [nn.BatchNorm1d(num_features)]
+            for _ in range(nlayers - 2):
+                fcs.append(nn.Linear(hidden_size, hidden_size, bias=True))
+                bns.append(nn.BatchNorm1d(hidden_size))
+            bns.append(nn.BatchNorm1d(hidden_size))
+            fcs.append(nn.Linear(hidden_size, num_classes, bias=True))
+        self.fcs = nn.ModuleList(fcs)
+        self.bns = nn.ModuleList(bns)
+        self.input_droprate = input_dropout
+        self.hidden_droprate = hidden_dropout
+        self.use_bn = use_bn
+        self.node_norm = node_norm
+        self.reset_param()
+
+    def _layers(self):
+        out = []
+        for i, (fc, bn) in enumerate(zip(self.fcs, self.bns)):
+            out.append((fc, bn if self.use_bn else None, i > 0, bool(self.node_norm), i == 0 and bool(self.node_norm),
+                        self.input_droprate if i == 0 else self.hidden_droprate))
+        return out
+
+
+class MagMLP(_MLPBase, nn.Module):
+    """model_mag.py's `MLP` (model_mag.py:17-67): the embedding-bag layer `emb` over embedding.py's kernels, then
+    "ReLU, node_norm, BN, hidden_droprate, fc" per layer.  The gradient reaches X (and through `emb` the table)."""
+
+    def __init__(self, num_features, num_classes, hidden_size, nlayers, use_bn, input_dropout, hidden_dropout, node_norm):
+        nn.Module.__init__(self)
+        if nlayers == 1:
+            self.embeds = nn.Embedding(num_features, num_classes)
+            self.fcs = nn.ModuleList([])
+            self.bns = nn.ModuleList([])
+        else:
+            fcs, bns = [], []
+            self.embeds = nn.Embedding(num_features, hidden_size)
+            for _ in range(nlayers - 2):
+                fcs.append(nn.Linear(hidden_size, hidden_size, bias=True))
+                bns.append(nn.BatchNorm1d(hidden_size))
+            bns.append(nn.BatchNorm1d(hidden_size))
+            fcs.append(nn.Linear(hidden_size, num_classes, bias=True))
+            self.fcs = nn.ModuleList(fcs)
+            self.bns = nn.ModuleList(bns)
+        self.input_droprate = input_dropout
+        self.hidden_droprate = hidden_dropout
+        self.use_bn = use_bn
+        self.node_norm = node_norm
+        self.reset_param()
+
+    def emb(self, attr_idx, node_idx, attr_data, seed=None, keep=None):
+        """MLP.emb (model_mag.py:48-55) through embedding.embedding_bag (the reference's COO arguments)."""
+        from .embedding import embedding_bag
+        return embedding_bag(self.embeds.weight, attr_idx, node_idx, attr_data, self.input_droprate, self.training,
+                             seed, keep)
+
+    def emb_csr(self, attr_indptr, attr_indices, attr_data, nodes=None, seed=None, keep=None):
+        """MLP.emb over the bags of `nodes` in a GPU-resident node-attribute CSR (embedding.embedding_bag_csr)."""
+        from .embedding import embedding_bag_csr
+        return embedding_bag_csr(self.embeds.weight, attr_indptr, attr_indices, attr_data, nodes, self.input_droprate,
+                                 self.training, seed, keep)
+
+    def _layers(self):
+        return [(fc, bn if self.use_bn else None, True, bool(self.node_norm), False, self.hidden_droprate)
+                for fc, bn in zip(self.fcs, self.bns)]
+
+    def forward(self, X, seed=None, keep=None):
+        if not len(self.fcs):
+            _check_input(X, [], self.training)
+            return X
+        return _run(self, X, seed, keep, self._layers())

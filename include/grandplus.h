@@ -400,6 +400,66 @@ int gp_grand_loss_backward(int device, const float* d_z, int32_t n_samples, int6
                            const float* d_grad_con, const int32_t* d_counts, float* d_grad_z, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * GRAND+'s MLP, one block for all S samples of a step (model.py:48-66, model_mag.py:57-67):
+ *
+ *     block(x) = Linear( dropout_p( BN( node_norm( relu?(x) ) ) ) ),   node_norm(u) = u / (1e-12 + |u|_2)
+ *
+ * d_x fp32 [S x B x F_in] contiguous (S = n_samples in [1, 16], B = n_rows, F_in = f_in), d_out [S x B x F_out];
+ * d_weight [F_out x F_in] and d_bias [F_out] (NULL = no bias) as nn.Linear holds them.  flags: GP_MLP_RELU,
+ * GP_MLP_NORM (node_norm), GP_MLP_BN, GP_MLP_TRAINING.
+ *   BatchNorm in training uses sample s's own mean and biased variance over its B rows (B >= 2) and updates
+ *   d_running_mean / d_running_var (NULL = no running statistics) once per sample, in sample order:
+ *   r <- (1 - momentum) r + momentum stat_s with the unbiased variance, and *d_num_batches_tracked += S (NULL = none).
+ *   In eval the running statistics are folded into one per-column affine map.  d_bn_weight / d_bn_bias NULL = 1 / 0.
+ *   Dropout (training and dropout > 0): entry b * F_in + f of sample s is kept by d_keep[(s * B + b) * F_in + f] != 0
+ *   when d_keep (uint8 [S x B x F_in]) is given, else by augment.hip's counter hash on the seed
+ *       GP_MLP_LAYER_SEED(gp_sample_seed(seed, s), layer),   GP_MLP_LAYER_SEED(x, l) = mix(x ^ (l + 1) * 0xA0761D6478BD642F)
+ *   with gp_sample_seed and mix of the S-sample random_prop above (grand_plus_amd.mlp.layer_seed mirrors it).  Kept
+ *   entries are scaled by 1 / (1 - dropout); dropout = 1 gives zeros, dropout = 0 draws nothing.
+ *   The Linear is fp32-input MFMA; the steps before it are applied while its A tile is staged.
+ *
+ * Contracts:
+ *   - sample independence: out[s] equals the n_samples = 1 call on x[s] with gp_sample_seed(seed, s) (or keep row s),
+ *     bit for bit.  Every output element is one fixed k-ordered chain per reduction chunk, the chunks summed in order,
+ *     and the chunking depends on (B, F_in, F_out) only, never on S or on the row tiling;
+ *   - determinism: forward, every gradient and the running statistics are bitwise equal run to run (no atomics);
+ *   - no host synchronisation and no allocation on the call path: the caller passes the buffers below;
+ *   - the number of launches does not depend on S (forward at most 4, backward at most 7);
+ *   - any B: grid dimensions stay within their limits (eval over millions of rows).
+ *   Arguments are checked before the device is touched.
+ *
+ * gp_mlp_block_forward: d_saved (required with GP_MLP_NORM or GP_MLP_BN) receives GP_MLP_SAVED_FLOATS floats: the row
+ * scales [S*B], then per (s, f) the BN mean, 1/sqrt(var + eps), and the affine map's scale and shift.  d_saved_a
+ * (optional, [S x B x F_in]) receives the Linear's input a as it was used; the backward needs it for the weight gradient.
+ * d_workspace: GP_MLP_FORWARD_WORKSPACE_BYTES bytes.
+ *
+ * gp_mlp_block_backward takes the forward's arguments, d_saved, d_saved_a and d_grad_out [S x B x F_out], and writes
+ * those of d_grad_x [S x B x F_in], d_grad_weight, d_grad_bias, d_grad_bn_weight, d_grad_bn_bias that are not NULL
+ * (all are overwritten, summed over the S*B rows in a fixed order).  d_grad_x is the gradient at d_x through every
+ * step of the block.  d_workspace: GP_MLP_BACKWARD_WORKSPACE_BYTES bytes.
+ * ------------------------------------------------------------------------------------------ */
+#define GP_MLP_RELU 1
+#define GP_MLP_NORM 2
+#define GP_MLP_BN 4
+#define GP_MLP_TRAINING 8
+#define GP_MLP_SAVED_FLOATS(S, B, f_in) ((int64_t)(S) * (int64_t)(B) + 4 * (int64_t)(S) * (int64_t)(f_in))
+#define GP_MLP_FORWARD_WORKSPACE_BYTES(S) ((int64_t)(S) * 2097152)
+#define GP_MLP_BACKWARD_WORKSPACE_BYTES(S, B, f_in) (4 * ((int64_t)(S) * (int64_t)(B) * (int64_t)(f_in) + 524288))
+
+int gp_mlp_block_forward(int device, const float* d_x, int32_t n_samples, int64_t n_rows, int32_t f_in, int32_t f_out,
+                         const float* d_weight, const float* d_bias, int flags,
+                         const float* d_bn_weight, const float* d_bn_bias, float* d_running_mean, float* d_running_var,
+                         int64_t* d_num_batches_tracked, float bn_eps, float bn_momentum,
+                         float dropout, uint64_t seed, int32_t layer, const uint8_t* d_keep,
+                         float* d_out, float* d_saved, float* d_saved_a, void* d_workspace, void* stream);
+int gp_mlp_block_backward(int device, const float* d_x, int32_t n_samples, int64_t n_rows, int32_t f_in, int32_t f_out,
+                          const float* d_weight, int flags, const float* d_bn_weight,
+                          float dropout, uint64_t seed, int32_t layer, const uint8_t* d_keep,
+                          const float* d_saved, const float* d_saved_a, const float* d_grad_out,
+                          float* d_grad_x, float* d_grad_weight, float* d_grad_bias, float* d_grad_bn_weight, float* d_grad_bn_bias,
+                          void* d_workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * exact full-graph feature propagation of the inference path, reference
  * predict() (model.py:181-224), lines 186-210.  mode 0 = ppr, 1 = avg, 2 = single (args.prop_mode);
  * `order` = args.order propagation steps.  A is the CSR of `g` (adj + I as the caller built it,

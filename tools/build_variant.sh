@@ -5,4 +5,4 @@
 NAME=$1; shift
 SRC=${GP_SRC:-grand_plus_amd/csrc}
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -pthread -ffp-contract=off -munsafe-fp-atomics \
-  -Iinclude -I$SRC "$@" -o grand_plus_amd/libgrandplus_$NAME.so $SRC/gfpush.hip grand_plus_amd/csrc/augment.hip grand_plus_amd/csrc/propagate.hip grand_plus_amd/csrc/objective.hip
+  -Iinclude -I$SRC "$@" -o grand_plus_amd/libgrandplus_$NAME.so $SRC/gfpush.hip grand_plus_amd/csrc/augment.hip grand_plus_amd/csrc/propagate.hip grand_plus_amd/csrc/objective.hip grand_plus_amd/csrc/mlp.hip
