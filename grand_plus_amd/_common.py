@@ -1,0 +1,59 @@
+"""Seeds and tensor plumbing shared by augment.py, embedding.py, mlp.py and objective.py.
+
+The seed formulas mirror include/grandplus.h (and csrc/gp_common.hpp on the device) bit for bit; this is their only
+Python definition.  Seeds drawn for calls without an explicit one come from one counter for the whole process.
+"""
+from __future__ import annotations
+
+import ctypes
+import itertools
+
+_M64 = 2**64 - 1
+_GOLDEN = 0x9E3779B97F4A7C15
+_LAYER_MUL = 0xA0761D6478BD642F
+
+_seed_counter = itertools.count(0x5EED)
+
+
+def _new_seed():
+    return next(_seed_counter) * _GOLDEN & _M64
+
+
+def _mix(x: int) -> int:
+    x = (x + _GOLDEN) & _M64
+    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & _M64
+    return x ^ (x >> 31)
+
+
+def sample_seed(seed: int, s: int) -> int:
+    """Seed of sample s of an S-sample call (the formula of grandplus.h): seed itself for s = 0."""
+    seed &= _M64
+    return seed if s == 0 else _mix(seed ^ ((s * 0xD6E8FEB86659FD93) & _M64))
+
+
+def layer_seed(seed: int, layer: int, s: int = 0) -> int:
+    """Dropout seed of (layer, sample s) of a call with `seed`: GP_MLP_LAYER_SEED(gp_sample_seed(seed, s), layer)."""
+    return _mix(sample_seed(seed, s) ^ (((layer + 1) * _LAYER_MUL) & _M64))
+
+
+def _check(t, dtype, name):
+    import torch
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous() or not t.is_cuda:
+        raise TypeError(f"{name} must be a contiguous CUDA tensor of dtype {dtype}")
+
+
+def _dev_index(t):
+    if not t.is_cuda:
+        raise TypeError("random_prop runs on the GPU only: tensors must be CUDA tensors (no CPU fallback)")
+    return t.device.index
+
+
+def _stream(t, stream=None):
+    """The stream argument of a native call: the caller's raw stream handle, or the current stream of t's device."""
+    import torch
+    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream if stream is None else stream)
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None

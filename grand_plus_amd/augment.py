@@ -25,42 +25,9 @@ launch and returns [S, n_out, F]: out[s] equals, bit for bit, the single-sample 
 from __future__ import annotations
 
 import ctypes
-import itertools
 
 from . import _native
-
-_seed_counter = itertools.count(0x5EED)
-
-
-def _dev_index(t):
-    if not t.is_cuda:
-        raise TypeError("random_prop runs on the GPU only: tensors must be CUDA tensors (no CPU fallback)")
-    return t.device.index
-
-
-def _check(t, dtype, name):
-    import torch
-    if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous() or not t.is_cuda:
-        raise TypeError(f"{name} must be a contiguous CUDA tensor of dtype {dtype}")
-
-
-def _new_seed():
-    return next(_seed_counter) * 0x9E3779B97F4A7C15 & (2**64 - 1)
-
-
-_M64 = 2**64 - 1
-
-
-def sample_seed(seed: int, s: int) -> int:
-    """Seed of sample s of an S-sample call (the formula of grandplus.h): seed itself for s = 0."""
-    seed &= _M64
-    if s == 0:
-        return seed
-    x = (seed ^ (s * 0xD6E8FEB86659FD93)) & _M64
-    x = (x + 0x9E3779B97F4A7C15) & _M64
-    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & _M64
-    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & _M64
-    return x ^ (x >> 31)
+from ._common import _check, _dev_index, _new_seed, _ptr, _stream, sample_seed  # noqa: F401  (sample_seed: public here)
 
 
 def _check_samples(samples):
@@ -88,8 +55,7 @@ def _coo_forward(feats, mat_scores, mat_idx, n_out, dropnode_rate, training, see
     out = torch.empty((n_out, F), dtype=torch.float32, device=feats.device)
     rc = _native.lib().gp_random_prop_coo(
         _dev_index(feats), feats.data_ptr(), M, F, mat_scores.data_ptr(), mat_idx.data_ptr(), n_out,
-        float(dropnode_rate), int(bool(training)), ctypes.c_uint64(seed), keep.data_ptr() if keep is not None else None,
-        out.data_ptr(), ctypes.c_void_p(stream))
+        float(dropnode_rate), int(bool(training)), ctypes.c_uint64(seed), _ptr(keep), out.data_ptr(), _stream(feats, stream))
     _native.raise_for_status(rc)
     return out
 
@@ -100,10 +66,8 @@ def _rows_forward(features, col, val, filled, K, batch_rows, B, dropnode_rate, t
     out = torch.empty((B, F), dtype=torch.float32, device=features.device)
     rc = _native.lib().gp_random_prop_rows(
         _dev_index(features), features.data_ptr(), N, F, col.data_ptr(), val.data_ptr(),
-        filled.data_ptr() if filled is not None else None, int(K),
-        batch_rows.data_ptr() if batch_rows is not None else None, B,
-        float(dropnode_rate), int(bool(training)), ctypes.c_uint64(seed), keep.data_ptr() if keep is not None else None,
-        out.data_ptr(), ctypes.c_void_p(stream))
+        _ptr(filled), int(K), _ptr(batch_rows), B,
+        float(dropnode_rate), int(bool(training)), ctypes.c_uint64(seed), _ptr(keep), out.data_ptr(), _stream(features, stream))
     _native.raise_for_status(rc)
     return out
 
@@ -114,8 +78,7 @@ def _coo_multi_forward(feats, mat_scores, mat_idx, n_out, S, dropnode_rate, trai
     out = torch.empty((S, n_out, F), dtype=torch.float32, device=feats.device)
     rc = _native.lib().gp_random_prop_coo_multi(
         _dev_index(feats), feats.data_ptr(), M, F, mat_scores.data_ptr(), mat_idx.data_ptr(), n_out, S,
-        float(dropnode_rate), int(bool(training)), ctypes.c_uint64(seed), keep.data_ptr() if keep is not None else None,
-        out.data_ptr(), ctypes.c_void_p(stream))
+        float(dropnode_rate), int(bool(training)), ctypes.c_uint64(seed), _ptr(keep), out.data_ptr(), _stream(feats, stream))
     _native.raise_for_status(rc)
     return out
 
@@ -126,10 +89,8 @@ def _rows_multi_forward(features, col, val, filled, K, batch_rows, B, S, dropnod
     out = torch.empty((S, B, F), dtype=torch.float32, device=features.device)
     rc = _native.lib().gp_random_prop_rows_multi(
         _dev_index(features), features.data_ptr(), N, F, col.data_ptr(), val.data_ptr(),
-        filled.data_ptr() if filled is not None else None, int(K),
-        batch_rows.data_ptr() if batch_rows is not None else None, B, S,
-        float(dropnode_rate), int(bool(training)), ctypes.c_uint64(seed), keep.data_ptr() if keep is not None else None,
-        col.numel(), out.data_ptr(), ctypes.c_void_p(stream))
+        _ptr(filled), int(K), _ptr(batch_rows), B, S,
+        float(dropnode_rate), int(bool(training)), ctypes.c_uint64(seed), _ptr(keep), col.numel(), out.data_ptr(), _stream(features, stream))
     _native.raise_for_status(rc)
     return out
 
@@ -158,8 +119,7 @@ def _multi_autograd_functions():
             grad = torch.empty((M, F), dtype=torch.float32, device=g.device)
             rc = _native.lib().gp_random_prop_coo_multi_backward(
                 _dev_index(g), g.data_ptr(), n_out, F, mat_scores.data_ptr(), mat_idx.data_ptr(), M, S,
-                float(p), int(bool(training)), ctypes.c_uint64(seed), keep.data_ptr() if keep is not None else None,
-                grad.data_ptr(), ctypes.c_void_p(torch.cuda.current_stream(g.device).cuda_stream))
+                float(p), int(bool(training)), ctypes.c_uint64(seed), _ptr(keep), grad.data_ptr(), _stream(g))
             _native.raise_for_status(rc)
             return grad, None, None, None, None, None, None, None, None, None
 
@@ -179,10 +139,8 @@ def _multi_autograd_functions():
             grad = torch.zeros((N, F), dtype=torch.float32, device=g.device)
             rc = _native.lib().gp_random_prop_rows_multi_backward(
                 _dev_index(g), g.data_ptr(), B, F, col.data_ptr(), val.data_ptr(),
-                filled.data_ptr() if filled is not None else None, int(K),
-                batch_rows.data_ptr() if batch_rows is not None else None, S,
-                float(p), int(bool(training)), ctypes.c_uint64(seed), keep.data_ptr() if keep is not None else None,
-                col.numel(), grad.data_ptr(), N, ctypes.c_void_p(torch.cuda.current_stream(g.device).cuda_stream))
+                _ptr(filled), int(K), _ptr(batch_rows), S,
+                float(p), int(bool(training)), ctypes.c_uint64(seed), _ptr(keep), col.numel(), grad.data_ptr(), N, _stream(g))
             _native.raise_for_status(rc)
             return grad, None, None, None, None, None, None, None, None, None, None, None, None
 
@@ -217,8 +175,7 @@ def _autograd_functions():
             grad = torch.empty((M, F), dtype=torch.float32, device=g.device)
             rc = _native.lib().gp_random_prop_coo_backward(
                 _dev_index(g), g.data_ptr(), n_out, F, mat_scores.data_ptr(), mat_idx.data_ptr(), M,
-                float(p), int(bool(training)), ctypes.c_uint64(seed), keep.data_ptr() if keep is not None else None,
-                grad.data_ptr(), ctypes.c_void_p(torch.cuda.current_stream(g.device).cuda_stream))
+                float(p), int(bool(training)), ctypes.c_uint64(seed), _ptr(keep), grad.data_ptr(), _stream(g))
             _native.raise_for_status(rc)
             return grad, None, None, None, None, None, None, None, None
 
@@ -238,10 +195,8 @@ def _autograd_functions():
             grad = torch.zeros((N, F), dtype=torch.float32, device=g.device)
             rc = _native.lib().gp_random_prop_rows_backward(
                 _dev_index(g), g.data_ptr(), B, F, col.data_ptr(), val.data_ptr(),
-                filled.data_ptr() if filled is not None else None, int(K),
-                batch_rows.data_ptr() if batch_rows is not None else None,
-                float(p), int(bool(training)), ctypes.c_uint64(seed), keep.data_ptr() if keep is not None else None,
-                grad.data_ptr(), N, ctypes.c_void_p(torch.cuda.current_stream(g.device).cuda_stream))
+                _ptr(filled), int(K), _ptr(batch_rows),
+                float(p), int(bool(training)), ctypes.c_uint64(seed), _ptr(keep), grad.data_ptr(), N, _stream(g))
             _native.raise_for_status(rc)
             return grad, None, None, None, None, None, None, None, None, None, None, None
 
@@ -279,8 +234,6 @@ def random_prop(feats, mat_scores, mat_idx, dropnode_rate, training=True, seed=N
     n_out = int(n_out)
     if seed is None:
         seed = _new_seed()
-    if stream is None:
-        stream = torch.cuda.current_stream(feats.device).cuda_stream
     if samples > 1:
         if keep is not None:
             keep = _multi_keep(keep, samples, M)
@@ -323,8 +276,6 @@ def random_prop_rows(features, col, val, filled, K, batch_rows=None, dropnode_ra
     B = S if batch_rows is None else batch_rows.numel()
     if seed is None:
         seed = _new_seed()
-    if stream is None:
-        stream = torch.cuda.current_stream(features.device).cuda_stream
     if samples > 1:
         if keep is not None:
             keep = _multi_keep(keep, samples, col.numel())

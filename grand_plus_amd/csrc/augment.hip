@@ -16,39 +16,19 @@
 //                         per-step upload (the caller side of model.py:310-316).
 //   gp_random_prop_coo  : the reference's own argument shape (gathered feats [M x F],
 //                         scores [M], sorted segment ids [M]).
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "grandplus.h"
+#include "gp_common.hpp"
 
 #include <algorithm>
 
 namespace {
 
-typedef unsigned long long u64;
-typedef unsigned int u32;
 constexpr int kBlock = 256;
 constexpr int kStage = 1024;          // most neighbours of one output row staged per pass (= GP_MAX_K)
-
-__device__ __forceinline__ float keep_scale(u64 seed, u64 entry, float p, float scale) {
-    // counter-based RNG: one 24-bit uniform per (seed, entry); keep with probability 1-p
-    u64 x = seed + entry * 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    x ^= x >> 31;
-    const float u = (float)(u32)(x >> 40) * (1.0f / 16777216.0f);
-    return u >= p ? scale : 0.0f;
-}
 
 // Accumulates out[b, f0:f1] = sum_k w_k * X[c_k, f0:f1] / (sum_k w_k + 1e-12) for the staged (c_k, w_k).
 // VEC floats per lane per access (4 when F % 4 == 0, 2 when F % 2 == 0, else 1); blockIdx.y selects
 // the slab of kBlock*VEC feature columns, so small batches still spread over many workgroups; 8
 // feature rows are in flight per lane.
-template <int VEC> struct VecT;
-template <> struct VecT<4> { typedef float4 type; };
-template <> struct VecT<2> { typedef float2 type; };
-template <> struct VecT<1> { typedef float type; };
-
 template <int VEC>
 __device__ __forceinline__ void weighted_rows_vec(const float* __restrict__ X, int F, const int* s_col,
                                                   const float* s_w, int n, float* __restrict__ out_row)
@@ -455,13 +435,6 @@ embedding_bag_backward_kernel(long long V, int H, BagLayout L, float p, int trai
     }
 }
 
-int launch_status(const char* what) {
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return GP_OK;
-    gp_internal_set_error(GP_ERR_HIP, what, hipGetErrorString(e));
-    return GP_ERR_HIP;
-}
-
 // ---- where is the row of node v?  (`topk_adj[batch_index]`, model.py:310, without the host)
 // pos_of_node[v] = the first position of v in the seed list, -1 for a node that is no seed.
 __global__ void __launch_bounds__(256) seed_positions_init_kernel(int* pos_of_node, long long n_nodes)
@@ -507,39 +480,37 @@ int gp_internal_warm_device(int device)
 {
     if (hipSetDevice(device) != hipSuccess || hipFree(nullptr) != hipSuccess) {
         (void)hipGetLastError();
-        gp_internal_set_error(GP_ERR_NO_DEVICE, "gp_internal_warm_device", "no usable HIP device");
-        return GP_ERR_NO_DEVICE;
+        return fail(GP_ERR_NO_DEVICE, "gp_internal_warm_device", "no usable HIP device");
     }
     return GP_OK;
 }
 
 int gp_seed_positions(int device, const int32_t* d_seeds, int64_t n_seeds, int64_t n_nodes, int32_t* d_pos_of_node, int32_t* d_n_bad, void* stream)
 {
-    if (n_nodes < 0 || n_seeds < 0 || n_seeds > 0x7FFFFFFE) { gp_internal_set_error(GP_ERR_INVALID_ARG, "gp_seed_positions", "negative size or more than 2^31 - 2 seeds"); return GP_ERR_INVALID_ARG; }
-    if ((n_nodes > 0 && !d_pos_of_node) || (n_seeds > 0 && !d_seeds) || !d_n_bad) { gp_internal_set_error(GP_ERR_NULL, "gp_seed_positions", "null device pointer"); return GP_ERR_NULL; }
-    if (hipSetDevice(device) != hipSuccess) { gp_internal_set_error(GP_ERR_NO_DEVICE, "gp_seed_positions", "hipSetDevice failed"); return GP_ERR_NO_DEVICE; }
+    if (n_nodes < 0 || n_seeds < 0 || n_seeds > 0x7FFFFFFE) return fail(GP_ERR_INVALID_ARG, "gp_seed_positions", "negative size or more than 2^31 - 2 seeds");
+    if ((n_nodes > 0 && !d_pos_of_node) || (n_seeds > 0 && !d_seeds) || !d_n_bad) return fail(GP_ERR_NULL, "gp_seed_positions", "null device pointer");
+    if (const int rc = set_device(device, "gp_seed_positions")) return rc;
     hipStream_t s = (hipStream_t)stream;
     const int grid_n = (int)std::min<int64_t>(4096, (n_nodes + 255) / 256 + 1), grid_s = (int)std::min<int64_t>(4096, (n_seeds + 255) / 256 + 1);
-    if (hipMemsetAsync(d_n_bad, 0, sizeof(int), s) != hipSuccess) { gp_internal_set_error(GP_ERR_HIP, "gp_seed_positions", "hipMemsetAsync failed"); return GP_ERR_HIP; }
+    if (hipMemsetAsync(d_n_bad, 0, sizeof(int), s) != hipSuccess) return fail(GP_ERR_HIP, "gp_seed_positions", "hipMemsetAsync failed");
     hipLaunchKernelGGL(seed_positions_init_kernel, dim3(grid_n), dim3(256), 0, s, d_pos_of_node, (long long)n_nodes);
     hipLaunchKernelGGL(seed_positions_fill_kernel, dim3(grid_s), dim3(256), 0, s, d_seeds, (long long)n_seeds, d_pos_of_node, (long long)n_nodes, d_n_bad);
     hipLaunchKernelGGL(seed_positions_finish_kernel, dim3(grid_n), dim3(256), 0, s, d_pos_of_node, (long long)n_nodes);
-    if (hipGetLastError() != hipSuccess) { gp_internal_set_error(GP_ERR_HIP, "gp_seed_positions", "kernel launch failed"); return GP_ERR_HIP; }
-    return GP_OK;
+    return launch_status("gp_seed_positions");
 }
 
 int gp_batch_positions(int device, const int32_t* d_pos_of_node, int64_t n_nodes, const int64_t* d_node_ids, int64_t n,
                        int32_t* d_out, int32_t* d_n_missing, void* stream)
 {
-    if (n < 0 || n_nodes < 0) { gp_internal_set_error(GP_ERR_INVALID_ARG, "gp_batch_positions", "negative size"); return GP_ERR_INVALID_ARG; }
-    if (!d_n_missing || (n > 0 && (!d_pos_of_node || !d_node_ids || !d_out))) { gp_internal_set_error(GP_ERR_NULL, "gp_batch_positions", "null device pointer"); return GP_ERR_NULL; }
-    if (hipSetDevice(device) != hipSuccess) { gp_internal_set_error(GP_ERR_NO_DEVICE, "gp_batch_positions", "hipSetDevice failed"); return GP_ERR_NO_DEVICE; }
+    if (n < 0 || n_nodes < 0) return fail(GP_ERR_INVALID_ARG, "gp_batch_positions", "negative size");
+    if (!d_n_missing || (n > 0 && (!d_pos_of_node || !d_node_ids || !d_out))) return fail(GP_ERR_NULL, "gp_batch_positions", "null device pointer");
+    if (const int rc = set_device(device, "gp_batch_positions")) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if (hipMemsetAsync(d_n_missing, 0, sizeof(int), s) != hipSuccess) { gp_internal_set_error(GP_ERR_HIP, "gp_batch_positions", "hipMemsetAsync failed"); return GP_ERR_HIP; }
+    if (hipMemsetAsync(d_n_missing, 0, sizeof(int), s) != hipSuccess) return fail(GP_ERR_HIP, "gp_batch_positions", "hipMemsetAsync failed");
     if (n > 0) {
         hipLaunchKernelGGL(batch_positions_kernel, dim3((int)std::min<int64_t>(2048, (n + 255) / 256)), dim3(256), 0, s,
                            d_pos_of_node, (long long)n_nodes, (const long long*)d_node_ids, (long long)n, d_out, d_n_missing);
-        if (hipGetLastError() != hipSuccess) { gp_internal_set_error(GP_ERR_HIP, "gp_batch_positions", "kernel launch failed"); return GP_ERR_HIP; }
+        if (const int rc = launch_status("gp_batch_positions")) return rc;
     }
     return GP_OK;
 }
@@ -552,15 +523,12 @@ int gp_random_prop_rows(int device, const float* d_x, int64_t n_nodes, int32_t f
                         float* d_out, void* stream)
 {
     if (n_batch == 0) return GP_OK;
-    if (!d_x || !d_col || !d_val || !d_out) { gp_internal_set_error(GP_ERR_NULL, "gp_random_prop_rows", "a device pointer is NULL"); return GP_ERR_NULL; }
-    if (n_nodes < 1 || feat_dim < 1 || K < 1 || K > GP_MAX_K || n_batch < 0 || !(dropnode_rate >= 0.0f && dropnode_rate <= 1.0f)) {
-        gp_internal_set_error(GP_ERR_INVALID_ARG, "gp_random_prop_rows", "bad size, K outside [1, 1024] or dropnode_rate outside [0, 1]");
-        return GP_ERR_INVALID_ARG;
-    }
-    { const hipError_t e = hipSetDevice(device); if (e != hipSuccess) { gp_internal_set_error(GP_ERR_NO_DEVICE, "gp_random_prop_rows: hipSetDevice", hipGetErrorString(e)); return GP_ERR_NO_DEVICE; } }
+    if (!d_x || !d_col || !d_val || !d_out) return fail(GP_ERR_NULL, "gp_random_prop_rows", "a device pointer is NULL");
+    if (n_nodes < 1 || feat_dim < 1 || K < 1 || K > GP_MAX_K || n_batch < 0 || !(dropnode_rate >= 0.0f && dropnode_rate <= 1.0f))
+        return fail(GP_ERR_INVALID_ARG, "gp_random_prop_rows", "bad size, K outside [1, 1024] or dropnode_rate outside [0, 1]");
+    if (const int rc = set_device(device, "gp_random_prop_rows")) return rc;
     const int grid = n_batch < 65535 ? n_batch : 65535;
-    const int vec = (feat_dim & 3) == 0 ? 4 : (feat_dim & 1) == 0 ? 2 : 1;
-    const int slabs = (feat_dim + kBlock * vec - 1) / (kBlock * vec);
+    const int vec = vec_width(feat_dim), slabs = feature_slabs(feat_dim, vec, kBlock);
     hipLaunchKernelGGL(random_prop_rows_kernel, dim3(grid, slabs), dim3(kBlock), 0, (hipStream_t)stream, d_x, feat_dim, d_col,
                        d_val, d_filled, K, d_batch_rows, n_batch, dropnode_rate, training, (u64)seed, d_keep, d_out);
     return launch_status("random_prop_rows_kernel");
@@ -572,16 +540,13 @@ int gp_random_prop_coo(int device, const float* d_feats, int64_t n_entries, int3
                        float* d_out, void* stream)
 {
     if (n_out == 0) return GP_OK;
-    if (n_entries > 0 && (!d_feats || !d_scores || !d_idx)) { gp_internal_set_error(GP_ERR_NULL, "gp_random_prop_coo", "a device pointer is NULL"); return GP_ERR_NULL; }
-    if (!d_out) { gp_internal_set_error(GP_ERR_NULL, "gp_random_prop_coo", "d_out is NULL"); return GP_ERR_NULL; }
-    if (n_entries < 0 || n_entries > 2147483647ll || feat_dim < 1 || n_out < 0 || !(dropnode_rate >= 0.0f && dropnode_rate <= 1.0f)) {
-        gp_internal_set_error(GP_ERR_INVALID_ARG, "gp_random_prop_coo", "bad size or dropnode_rate outside [0, 1]");
-        return GP_ERR_INVALID_ARG;
-    }
-    { const hipError_t e = hipSetDevice(device); if (e != hipSuccess) { gp_internal_set_error(GP_ERR_NO_DEVICE, "gp_random_prop_coo: hipSetDevice", hipGetErrorString(e)); return GP_ERR_NO_DEVICE; } }
+    if (n_entries > 0 && (!d_feats || !d_scores || !d_idx)) return fail(GP_ERR_NULL, "gp_random_prop_coo", "a device pointer is NULL");
+    if (!d_out) return fail(GP_ERR_NULL, "gp_random_prop_coo", "d_out is NULL");
+    if (n_entries < 0 || n_entries > 2147483647ll || feat_dim < 1 || n_out < 0 || !(dropnode_rate >= 0.0f && dropnode_rate <= 1.0f))
+        return fail(GP_ERR_INVALID_ARG, "gp_random_prop_coo", "bad size or dropnode_rate outside [0, 1]");
+    if (const int rc = set_device(device, "gp_random_prop_coo")) return rc;
     const int grid = n_out < 65535 ? (int)n_out : 65535;
-    const int vec = (feat_dim & 3) == 0 ? 4 : (feat_dim & 1) == 0 ? 2 : 1;
-    const int slabs = (feat_dim + kBlock * vec - 1) / (kBlock * vec);
+    const int vec = vec_width(feat_dim), slabs = feature_slabs(feat_dim, vec, kBlock);
     hipLaunchKernelGGL(random_prop_coo_kernel, dim3(grid, slabs), dim3(kBlock), 0, (hipStream_t)stream, d_feats, feat_dim,
                        d_scores, (const long long*)d_idx, (long long)n_entries, (long long)n_out, dropnode_rate,
                        training, (u64)seed, d_keep, d_out);
@@ -593,34 +558,15 @@ int gp_random_prop_coo(int device, const float* d_feats, int64_t n_entries, int3
 // ---- Backward and embedding-bag entry points.  Arguments are checked before hipSetDevice.
 namespace {
 
-int set_device(int device, const char* where)
-{
-    const hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess) return GP_OK;
-    gp_internal_set_error(GP_ERR_NO_DEVICE, where, hipGetErrorString(e));
-    return GP_ERR_NO_DEVICE;
-}
-
 int check_bag_args(const char* where, const float* d_table, int64_t n_vocab, int32_t dim, const int64_t* d_offsets,
                    int64_t n_src, int64_t n_rows, const void* d_attr_idx, int idx_bytes, const float* d_attr_data,
                    float rate, const void* d_dst)
 {
-    if (n_vocab < 0 || dim < 1 || n_src < 0 || n_rows < 0 || (idx_bytes != 4 && idx_bytes != 8) || !(rate >= 0.0f && rate <= 1.0f)) {
-        gp_internal_set_error(GP_ERR_INVALID_ARG, where, "negative size, dim < 1, idx_bytes not 4 or 8, or dropout rate outside [0, 1]");
-        return GP_ERR_INVALID_ARG;
-    }
-    if (n_rows > 0 && (!d_offsets || !d_attr_idx || !d_attr_data || !d_dst || (n_vocab > 0 && !d_table))) {
-        gp_internal_set_error(GP_ERR_NULL, where, "a device pointer is NULL");
-        return GP_ERR_NULL;
-    }
+    if (n_vocab < 0 || dim < 1 || n_src < 0 || n_rows < 0 || (idx_bytes != 4 && idx_bytes != 8) || !(rate >= 0.0f && rate <= 1.0f))
+        return fail(GP_ERR_INVALID_ARG, where, "negative size, dim < 1, idx_bytes not 4 or 8, or dropout rate outside [0, 1]");
+    if (n_rows > 0 && (!d_offsets || !d_attr_idx || !d_attr_data || !d_dst || (n_vocab > 0 && !d_table)))
+        return fail(GP_ERR_NULL, where, "a device pointer is NULL");
     return GP_OK;
-}
-
-int bag_log2g(int H, int vec)
-{
-    int log2g = 0;                                   // smallest group with G * VEC >= H, at most a wave
-    while ((1 << log2g) * vec < H && log2g < 6) ++log2g;
-    return log2g;
 }
 
 }  // namespace
@@ -633,12 +579,10 @@ int gp_random_prop_coo_backward(int device, const float* d_grad_out, int64_t n_o
                                 float* d_grad_feats, void* stream)
 {
     const char* where = "gp_random_prop_coo_backward";
-    if (n_entries < 0 || n_entries > 2147483647ll || feat_dim < 1 || n_out < 0 || !(dropnode_rate >= 0.0f && dropnode_rate <= 1.0f)) {
-        gp_internal_set_error(GP_ERR_INVALID_ARG, where, "bad size or dropnode_rate outside [0, 1]");
-        return GP_ERR_INVALID_ARG;
-    }
+    if (n_entries < 0 || n_entries > 2147483647ll || feat_dim < 1 || n_out < 0 || !(dropnode_rate >= 0.0f && dropnode_rate <= 1.0f))
+        return fail(GP_ERR_INVALID_ARG, where, "bad size or dropnode_rate outside [0, 1]");
     if (n_out == 0) return GP_OK;
-    if (!d_grad_out || (n_entries > 0 && (!d_scores || !d_idx || !d_grad_feats))) { gp_internal_set_error(GP_ERR_NULL, where, "a device pointer is NULL"); return GP_ERR_NULL; }
+    if (!d_grad_out || (n_entries > 0 && (!d_scores || !d_idx || !d_grad_feats))) return fail(GP_ERR_NULL, where, "a device pointer is NULL");
     if (const int rc = set_device(device, where)) return rc;
     const int grid = n_out < 65535 ? (int)n_out : 65535;
     hipLaunchKernelGGL(random_prop_coo_backward_kernel, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, d_grad_out, feat_dim,
@@ -653,12 +597,10 @@ int gp_random_prop_rows_backward(int device, const float* d_grad_out, int32_t n_
                                  const uint8_t* d_keep, float* d_grad_x, int64_t n_nodes, void* stream)
 {
     const char* where = "gp_random_prop_rows_backward";
-    if (n_batch < 0 || n_nodes < 1 || feat_dim < 1 || K < 1 || K > GP_MAX_K || !(dropnode_rate >= 0.0f && dropnode_rate <= 1.0f)) {
-        gp_internal_set_error(GP_ERR_INVALID_ARG, where, "bad size, K outside [1, 1024] or dropnode_rate outside [0, 1]");
-        return GP_ERR_INVALID_ARG;
-    }
+    if (n_batch < 0 || n_nodes < 1 || feat_dim < 1 || K < 1 || K > GP_MAX_K || !(dropnode_rate >= 0.0f && dropnode_rate <= 1.0f))
+        return fail(GP_ERR_INVALID_ARG, where, "bad size, K outside [1, 1024] or dropnode_rate outside [0, 1]");
     if (n_batch == 0) return GP_OK;
-    if (!d_grad_out || !d_col || !d_val || !d_grad_x) { gp_internal_set_error(GP_ERR_NULL, where, "a device pointer is NULL"); return GP_ERR_NULL; }
+    if (!d_grad_out || !d_col || !d_val || !d_grad_x) return fail(GP_ERR_NULL, where, "a device pointer is NULL");
     if (const int rc = set_device(device, where)) return rc;
     const int grid = n_batch < 65535 ? n_batch : 65535;
     hipLaunchKernelGGL(random_prop_rows_backward_kernel, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, d_grad_out, feat_dim,
@@ -679,11 +621,11 @@ int gp_embedding_bag(int device, const float* d_weight, int64_t n_vocab, int32_t
     if (n_rows == 0) return GP_OK;
     if (const int rc = set_device(device, where)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if (d_n_bad && hipMemsetAsync(d_n_bad, 0, sizeof(int32_t), s) != hipSuccess) { gp_internal_set_error(GP_ERR_HIP, where, "hipMemsetAsync failed"); return GP_ERR_HIP; }
+    if (d_n_bad && hipMemsetAsync(d_n_bad, 0, sizeof(int32_t), s) != hipSuccess) return fail(GP_ERR_HIP, where, "hipMemsetAsync failed");
     const BagLayout L = {(const long long*)d_offsets, (long long)n_src, (const long long*)d_nodes, (const long long*)d_entry_base,
                          (long long)n_rows, d_attr_idx, idx_bytes == 8, d_attr_data};
-    const int vec = (dim & 3) == 0 ? 4 : (dim & 1) == 0 ? 2 : 1;
-    const int log2g = bag_log2g(dim, vec);
+    const int vec = vec_width(dim);
+    const int log2g = lane_group_log2(dim, vec);
     const long long rows_per_block = (kBlock / 64) * (64 >> log2g);
     const int grid = (int)std::min<long long>(65535ll * 16, (n_rows + rows_per_block - 1) / rows_per_block);
     if (vec == 4)      hipLaunchKernelGGL(embedding_bag_kernel<4>, dim3(grid), dim3(kBlock), 0, s, d_weight, (long long)n_vocab, dim, L, dropout_rate, training, (u64)seed, d_keep, d_out, d_n_bad, log2g);
@@ -704,7 +646,7 @@ int gp_embedding_bag_backward(int device, const float* d_grad_out, int64_t n_voc
     if (n_rows == 0) return GP_OK;
     if (const int rc = set_device(device, where)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if (d_n_bad && hipMemsetAsync(d_n_bad, 0, sizeof(int32_t), s) != hipSuccess) { gp_internal_set_error(GP_ERR_HIP, where, "hipMemsetAsync failed"); return GP_ERR_HIP; }
+    if (d_n_bad && hipMemsetAsync(d_n_bad, 0, sizeof(int32_t), s) != hipSuccess) return fail(GP_ERR_HIP, where, "hipMemsetAsync failed");
     const BagLayout L = {(const long long*)d_offsets, (long long)n_src, (const long long*)d_nodes, (const long long*)d_entry_base,
                          (long long)n_rows, d_attr_idx, idx_bytes == 8, d_attr_data};
     const int grid = (int)std::min<long long>(65535ll * 16, (n_rows + kBlock / 64 - 1) / (kBlock / 64));
@@ -726,16 +668,6 @@ namespace {
 
 constexpr int kMaxSamples = 16;
 constexpr int kMultiLdsBytes = 65536;
-
-__device__ __forceinline__ u64 sample_seed(u64 seed, int s)
-{
-    if (s == 0) return seed;                          // the formula of grandplus.h (gp_sample_seed)
-    u64 x = seed ^ ((u64)s * 0xD6E8FEB86659FD93ull);
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
 
 __device__ __forceinline__ float sample_weight(float w, long long e, int s, float p, float scale, int training, u64 seed,
                                                const unsigned char* keep, long long keep_stride)
@@ -1020,10 +952,8 @@ random_prop_rows_multi_backward_kernel(const float* __restrict__ grad_out, int F
 
 int multi_check(const char* where, int32_t n_samples, float rate)
 {
-    if (n_samples < 1 || n_samples > kMaxSamples || !(rate >= 0.0f && rate <= 1.0f)) {
-        gp_internal_set_error(GP_ERR_INVALID_ARG, where, "n_samples outside [1, 16] or dropnode_rate outside [0, 1]");
-        return GP_ERR_INVALID_ARG;
-    }
+    if (n_samples < 1 || n_samples > kMaxSamples || !(rate >= 0.0f && rate <= 1.0f))
+        return fail(GP_ERR_INVALID_ARG, where, "n_samples outside [1, 16] or dropnode_rate outside [0, 1]");
     return GP_OK;
 }
 
@@ -1059,19 +989,16 @@ int gp_random_prop_rows_multi(int device, const float* d_x, int64_t n_nodes, int
 {
     const char* where = "gp_random_prop_rows_multi";
     if (const int rc = multi_check(where, n_samples, dropnode_rate)) return rc;
-    if (n_nodes < 1 || feat_dim < 1 || K < 1 || K > GP_MAX_K || n_batch < 0 || (d_keep && keep_stride < 1)) {
-        gp_internal_set_error(GP_ERR_INVALID_ARG, where, "bad size, K outside [1, 1024] or keep_stride < 1 with a mask");
-        return GP_ERR_INVALID_ARG;
-    }
+    if (n_nodes < 1 || feat_dim < 1 || K < 1 || K > GP_MAX_K || n_batch < 0 || (d_keep && keep_stride < 1))
+        return fail(GP_ERR_INVALID_ARG, where, "bad size, K outside [1, 1024] or keep_stride < 1 with a mask");
     if (n_batch == 0) return GP_OK;
-    if (!d_x || !d_col || !d_val || !d_out) { gp_internal_set_error(GP_ERR_NULL, where, "a device pointer is NULL"); return GP_ERR_NULL; }
+    if (!d_x || !d_col || !d_val || !d_out) return fail(GP_ERR_NULL, where, "a device pointer is NULL");
     if (const int rc = set_device(device, where)) return rc;
     const int ns = forward_ns(n_samples);
     const int nsc = std::min(ns, rows_nsc(K, n_samples, 0));
     const size_t lds = (size_t)(K + nsc * K) * 4;
     const int grid = n_batch < 65535 ? n_batch : 65535;
-    const int vec = (feat_dim & 3) == 0 ? 4 : (feat_dim & 1) == 0 ? 2 : 1;
-    const int slabs = (feat_dim + kBlock * vec - 1) / (kBlock * vec);
+    const int vec = vec_width(feat_dim), slabs = feature_slabs(feat_dim, vec, kBlock);
     hipStream_t s = (hipStream_t)stream;
 #define GP_ROWS_MULTI(V, N, _) hipLaunchKernelGGL((random_prop_rows_multi_kernel<V, N>), dim3(grid, slabs), dim3(kBlock), lds, s, d_x, \
         feat_dim, d_col, d_val, d_filled, K, d_batch_rows, n_batch, n_samples, nsc, dropnode_rate, training, (u64)seed, d_keep,      \
@@ -1088,19 +1015,16 @@ int gp_random_prop_coo_multi(int device, const float* d_feats, int64_t n_entries
 {
     const char* where = "gp_random_prop_coo_multi";
     if (const int rc = multi_check(where, n_samples, dropnode_rate)) return rc;
-    if (n_entries < 0 || n_entries > 2147483647ll || feat_dim < 1 || n_out < 0) {
-        gp_internal_set_error(GP_ERR_INVALID_ARG, where, "bad size");
-        return GP_ERR_INVALID_ARG;
-    }
+    if (n_entries < 0 || n_entries > 2147483647ll || feat_dim < 1 || n_out < 0)
+        return fail(GP_ERR_INVALID_ARG, where, "bad size");
     if (n_out == 0) return GP_OK;
-    if ((n_entries > 0 && (!d_feats || !d_scores || !d_idx)) || !d_out) { gp_internal_set_error(GP_ERR_NULL, where, "a device pointer is NULL"); return GP_ERR_NULL; }
+    if ((n_entries > 0 && (!d_feats || !d_scores || !d_idx)) || !d_out) return fail(GP_ERR_NULL, where, "a device pointer is NULL");
     if (const int rc = set_device(device, where)) return rc;
     const int ns = forward_ns(n_samples);
     const int nsc = std::min(ns, kMultiLdsBytes / (4 * kStage));
     const size_t lds = (size_t)nsc * kStage * 4;
     const int grid = n_out < 65535 ? (int)n_out : 65535;
-    const int vec = (feat_dim & 3) == 0 ? 4 : (feat_dim & 1) == 0 ? 2 : 1;
-    const int slabs = (feat_dim + kBlock * vec - 1) / (kBlock * vec);
+    const int vec = vec_width(feat_dim), slabs = feature_slabs(feat_dim, vec, kBlock);
     hipStream_t s = (hipStream_t)stream;
 #define GP_COO_MULTI(V, N, _) hipLaunchKernelGGL((random_prop_coo_multi_kernel<V, N>), dim3(grid, slabs), dim3(kBlock), lds, s, d_feats, \
         feat_dim, d_scores, (const long long*)d_idx, (long long)n_entries, (long long)n_out, n_samples, nsc, dropnode_rate, training,     \
@@ -1117,12 +1041,10 @@ int gp_random_prop_coo_multi_backward(int device, const float* d_grad_out, int64
 {
     const char* where = "gp_random_prop_coo_multi_backward";
     if (const int rc = multi_check(where, n_samples, dropnode_rate)) return rc;
-    if (n_entries < 0 || n_entries > 2147483647ll || feat_dim < 1 || n_out < 0) {
-        gp_internal_set_error(GP_ERR_INVALID_ARG, where, "bad size");
-        return GP_ERR_INVALID_ARG;
-    }
+    if (n_entries < 0 || n_entries > 2147483647ll || feat_dim < 1 || n_out < 0)
+        return fail(GP_ERR_INVALID_ARG, where, "bad size");
     if (n_out == 0) return GP_OK;
-    if (!d_grad_out || (n_entries > 0 && (!d_scores || !d_idx || !d_grad_feats))) { gp_internal_set_error(GP_ERR_NULL, where, "a device pointer is NULL"); return GP_ERR_NULL; }
+    if (!d_grad_out || (n_entries > 0 && (!d_scores || !d_idx || !d_grad_feats))) return fail(GP_ERR_NULL, where, "a device pointer is NULL");
     if (const int rc = set_device(device, where)) return rc;
     const int nsc = std::min<int>(n_samples, kMultiLdsBytes / (4 * kStage));
     const int grid = n_out < 65535 ? (int)n_out : 65535;
@@ -1139,12 +1061,10 @@ int gp_random_prop_rows_multi_backward(int device, const float* d_grad_out, int3
 {
     const char* where = "gp_random_prop_rows_multi_backward";
     if (const int rc = multi_check(where, n_samples, dropnode_rate)) return rc;
-    if (n_batch < 0 || n_nodes < 1 || feat_dim < 1 || K < 1 || K > GP_MAX_K || (d_keep && keep_stride < 1)) {
-        gp_internal_set_error(GP_ERR_INVALID_ARG, where, "bad size, K outside [1, 1024] or keep_stride < 1 with a mask");
-        return GP_ERR_INVALID_ARG;
-    }
+    if (n_batch < 0 || n_nodes < 1 || feat_dim < 1 || K < 1 || K > GP_MAX_K || (d_keep && keep_stride < 1))
+        return fail(GP_ERR_INVALID_ARG, where, "bad size, K outside [1, 1024] or keep_stride < 1 with a mask");
     if (n_batch == 0) return GP_OK;
-    if (!d_grad_out || !d_col || !d_val || !d_grad_x) { gp_internal_set_error(GP_ERR_NULL, where, "a device pointer is NULL"); return GP_ERR_NULL; }
+    if (!d_grad_out || !d_col || !d_val || !d_grad_x) return fail(GP_ERR_NULL, where, "a device pointer is NULL");
     if (const int rc = set_device(device, where)) return rc;
     const int nsc = rows_nsc(K, n_samples, kMaxSamples);
     const size_t lds = (size_t)(K + kMaxSamples + nsc * K) * 4;

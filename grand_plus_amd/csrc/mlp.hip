@@ -15,15 +15,10 @@
 // Backward: dA = dY W (GEMM), BN's column sums and dn (mlp_bn_backward_kernel), the row norm and ReLU
 // (mlp_row_backward_kernel, only when dX is wanted), dW = dY^T a over the saved a (GEMM, split-M partials summed in a
 // fixed order), db (mlp_colsum_kernel).  No atomics anywhere: every result is bitwise reproducible.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "grandplus.h"
+#include "gp_common.hpp"
 
 namespace {
 
-typedef unsigned long long u64;
-typedef unsigned int u32;
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kBlock = 256;
@@ -33,31 +28,6 @@ constexpr int kLdsStride = kTile + 16;
 constexpr int kMaxS = 16;
 constexpr long long kTargetTiles = 128;   // split the reduction until about this many tiles per sample exist
 constexpr long long kMaxSplits = 32;
-
-// ---- dropout: the counter hash of augment.hip (keep_scale) on the seed of (sample s, layer l), entry b * F_in + f
-__device__ __forceinline__ u64 mix64(u64 x)
-{
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-
-__device__ __forceinline__ u64 layer_sample_seed(u64 seed, int s, int layer)
-{
-    const u64 ss = s == 0 ? seed : mix64(seed ^ ((u64)s * 0xD6E8FEB86659FD93ull));      // gp_sample_seed
-    return mix64(ss ^ ((u64)(layer + 1) * 0xA0761D6478BD642Full));                      // GP_MLP_LAYER_SEED
-}
-
-__device__ __forceinline__ float keep_scale(u64 seed, u64 entry, float p, float scale)
-{
-    u64 x = seed + entry * 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    x ^= x >> 31;
-    const float u = (float)(u32)(x >> 40) * (1.0f / 16777216.0f);
-    return u >= p ? scale : 0.0f;
-}
 
 // Everything the A-operand prologue (and the backward, which applies the same maps) needs.
 struct Block {
@@ -73,7 +43,7 @@ struct Block {
 __device__ __forceinline__ float drop_scale(const Block& P, long long s, long long b, int k)
 {
     if (!P.drop) return 1.0f;
-    const long long e = b * P.K + k;
+    const long long e = b * P.K + k;                // the counter hash on the seed of (sample s, layer), or the mask
     if (P.keep) return P.keep[s * P.B * P.K + e] ? P.scale : 0.0f;
     return keep_scale(layer_sample_seed(P.seed, (int)s, P.layer), (u64)e, P.p, P.scale);
 }
@@ -92,12 +62,6 @@ __device__ __forceinline__ float prologue(const Block& P, float v, long long m, 
     const long long s = m / P.B, b = m - s * P.B;
     if (P.mul) v = v * P.mul[s * P.sstride + k] + P.add[s * P.sstride + k];
     if (P.drop) v = v * drop_scale(P, s, b, k);
-    return v;
-}
-
-__device__ __forceinline__ float wave_sum(float v)
-{
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
 }
 
@@ -419,19 +383,6 @@ int grid1(long long n, long long per)
     return (int)(g < 65535 ? (g > 0 ? g : 1) : 65535);
 }
 
-int fail(int status, const char* where, const char* detail)
-{
-    gp_internal_set_error(status, where, detail);
-    return status;
-}
-
-int launch_status(const char* where)
-{
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return GP_OK;
-    return fail(GP_ERR_HIP, where, hipGetErrorString(e));
-}
-
 template <bool A_KC, bool B_KC, bool PRO>
 int run_gemm(Gemm g, const Block& P, void* ws, hipStream_t st, const char* name)
 {
@@ -463,12 +414,6 @@ int check_common(const char* where, const float* d_x, int32_t S, int64_t B, int3
         return fail(GP_ERR_INVALID_ARG, where, "BatchNorm in training needs more than 1 row per sample");
     if (!d_x || !d_w) return fail(GP_ERR_NULL, where, "a device pointer is NULL");
     return GP_OK;
-}
-
-int set_device(int device, const char* where)
-{
-    const hipError_t e = hipSetDevice(device);
-    return e == hipSuccess ? GP_OK : fail(GP_ERR_NO_DEVICE, where, hipGetErrorString(e));
 }
 
 Block make_block(const float* d_x, int32_t S, int64_t B, int32_t f_in, int flags, float dropout, uint64_t seed, int32_t layer,

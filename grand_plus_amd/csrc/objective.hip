@@ -15,10 +15,7 @@
 //   grand_loss_backward_kernel one wave per row: p and q recomputed, dz written from the device scalars.
 // Sums over c and over s run in a fixed order (wave butterflies, then s ascending), so value and gradient are
 // bitwise the same run to run.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "grandplus.h"
+#include "gp_common.hpp"
 
 namespace {
 
@@ -38,18 +35,6 @@ struct LossArgs {
     int kind;                       // GP_LOSS_KL / GP_LOSS_L2
     int logp_in;                    // z already holds log-probabilities
 };
-
-__device__ __forceinline__ float wave_max(float v)
-{
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-
-__device__ __forceinline__ float wave_sum(float v)
-{
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 // Per-row state every pass needs: logp[s,c] = (z[s,c] - mx[s]) - ls[s] (torch's log_softmax order; 0 and 0 when z holds
 // log-probabilities), the largest avg_p and q's normaliser: q_c = exp(t_c - tmax) / tsum, t_c = log(avg_p_c) / tem.
@@ -303,30 +288,12 @@ int check_loss_args(const char* where, const float* d_z, int32_t S, int64_t B, i
                     float tem, int kind)
 {
     if (S < 1 || S > kMaxS || B < 0 || C < 1 || C > kMaxC || n_l < 0 || n_l > B || !(tem > 0.0f) ||
-        (kind != GP_LOSS_KL && kind != GP_LOSS_L2)) {
-        gp_internal_set_error(GP_ERR_INVALID_ARG, where,
+        (kind != GP_LOSS_KL && kind != GP_LOSS_L2))
+        return fail(GP_ERR_INVALID_ARG, where,
                               "n_samples outside [1, 16], n_classes outside [1, 4096], n_rows < 0, n_labeled outside [0, n_rows], "
                               "tem <= 0 or unknown kind");
-        return GP_ERR_INVALID_ARG;
-    }
-    if ((B > 0 && !d_z) || (n_l > 0 && !d_labels)) { gp_internal_set_error(GP_ERR_NULL, where, "a device pointer is NULL"); return GP_ERR_NULL; }
+    if ((B > 0 && !d_z) || (n_l > 0 && !d_labels)) return fail(GP_ERR_NULL, where, "a device pointer is NULL");
     return GP_OK;
-}
-
-int set_device(int device, const char* where)
-{
-    const hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess) return GP_OK;
-    gp_internal_set_error(GP_ERR_NO_DEVICE, where, hipGetErrorString(e));
-    return GP_ERR_NO_DEVICE;
-}
-
-int launch_status(const char* where)
-{
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return GP_OK;
-    gp_internal_set_error(GP_ERR_HIP, where, hipGetErrorString(e));
-    return GP_ERR_HIP;
 }
 
 int row_grid(long long B)
@@ -345,7 +312,7 @@ int gp_grand_loss(int device, const float* d_z, int32_t n_samples, int64_t n_row
 {
     const char* where = "gp_grand_loss";
     if (const int rc = check_loss_args(where, d_z, n_samples, n_rows, n_classes, d_labels, n_labeled, tem, kind)) return rc;
-    if (!d_out || !d_counts || (n_rows > 0 && !d_workspace)) { gp_internal_set_error(GP_ERR_NULL, where, "a device pointer is NULL"); return GP_ERR_NULL; }
+    if (!d_out || !d_counts || (n_rows > 0 && !d_workspace)) return fail(GP_ERR_NULL, where, "a device pointer is NULL");
     if (const int rc = set_device(device, where)) return rc;
     hipStream_t s = (hipStream_t)stream;
     double* part = static_cast<double*>(d_workspace);
@@ -368,7 +335,7 @@ int gp_grand_loss_backward(int device, const float* d_z, int32_t n_samples, int6
 {
     const char* where = "gp_grand_loss_backward";
     if (const int rc = check_loss_args(where, d_z, n_samples, n_rows, n_classes, d_labels, n_labeled, tem, kind)) return rc;
-    if (!d_grad_loss || !d_counts || (n_rows > 0 && !d_grad_z)) { gp_internal_set_error(GP_ERR_NULL, where, "a device pointer is NULL"); return GP_ERR_NULL; }
+    if (!d_grad_loss || !d_counts || (n_rows > 0 && !d_grad_z)) return fail(GP_ERR_NULL, where, "a device pointer is NULL");
     if (n_rows == 0) return GP_OK;
     if (const int rc = set_device(device, where)) return rc;
     const LossArgs a = {d_z, n_samples, (long long)n_rows, n_classes, (const long long*)d_labels, (long long)n_labeled,

@@ -12,16 +12,12 @@
 // every neighbour contributes one coalesced read of its feature row; sums are kept in fp64 registers
 // and rounded to fp32 once per step (storage is fp32: the consumer is an fp32 MLP).  Rows longer than
 // kLongRow neighbours are taken by whole workgroups with an ordered LDS reduction (deterministic).
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "gp_common.hpp"
 
 #include <algorithm>
 
-#include "grandplus.h"
-
 namespace {
 
-typedef unsigned int u32;
 constexpr int kBlock = 256;                  // 4 waves: 4 rows per workgroup
 constexpr int kLongRow = 4096;               // neighbours above which a row is handled by spmm_long_kernel
 constexpr int kLongBlock = 1024;
@@ -30,18 +26,13 @@ constexpr int kLongBlock = 1024;
 // of G = 2^log2g lanes (G*VEC >= F when possible) owns one row, so a wave handles 64/G rows at once and
 // every neighbour costs one 16-byte (VEC = 4) load per lane; 8 neighbour rows are in flight per lane.
 // `accumulate`: y is also added into `sum` (ppr / avg); y is always written to x_next.
-template <int VEC> struct PV;
-template <> struct PV<4> { typedef float4 type; };
-template <> struct PV<2> { typedef float2 type; };
-template <> struct PV<1> { typedef float type; };
-
 template <int VEC>
 __global__ void __launch_bounds__(kBlock)
 spmm_kernel(const int* __restrict__ indptr, const int* __restrict__ indices, const float* __restrict__ wts,
             u32 node_mask, const double* __restrict__ scale, long long n_rows, const float* __restrict__ x, int F,
             float* __restrict__ x_next, float* __restrict__ sum, int accumulate, int log2g)
 {
-    typedef typename PV<VEC>::type V;
+    typedef typename VecT<VEC>::type V;
     const int lane = threadIdx.x & 63;
     const int G = 1 << log2g, gl = lane & (G - 1), grp = lane >> log2g, rows_per_wave = 64 >> log2g;
     const long long wave = ((long long)blockIdx.x * kBlock + threadIdx.x) >> 6;
@@ -99,7 +90,7 @@ spmm_long_kernel(const int* __restrict__ indptr, const int* __restrict__ indices
                  u32 node_mask, const double* __restrict__ scale, const int* __restrict__ long_rows, int n_long,
                  const float* __restrict__ x, int F, float* __restrict__ x_next, float* __restrict__ sum, int accumulate)
 {
-    typedef typename PV<VEC>::type V;
+    typedef typename VecT<VEC>::type V;
     __shared__ double part[kLongBlock / 64][64 * VEC];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n_w = kLongBlock / 64;
     const int slabs = (F + 64 * VEC - 1) / (64 * VEC);
@@ -206,17 +197,15 @@ extern "C" {
 int gp_propagate_features(gp_graph* g, const float* d_features, int32_t feat_dim, const float* d_edge_weight,
                           int mode, int order, double alpha, float* d_out, void* stream)
 {
-    if (!g || !d_features || !d_out) { gp_internal_set_error(GP_ERR_NULL, "gp_propagate_features", "null argument"); return GP_ERR_NULL; }
-    if (feat_dim < 1 || order < 0 || mode < 0 || mode > 2 || !(alpha >= 0.0 && alpha <= 1.0)) {
-        gp_internal_set_error(GP_ERR_INVALID_ARG, "gp_propagate_features", "feat_dim < 1, order < 0, mode not in {0 ppr,1 avg,2 single} or alpha outside [0,1]");
-        return GP_ERR_INVALID_ARG;
-    }
+    if (!g || !d_features || !d_out) return fail(GP_ERR_NULL, "gp_propagate_features", "null argument");
+    if (feat_dim < 1 || order < 0 || mode < 0 || mode > 2 || !(alpha >= 0.0 && alpha <= 1.0))
+        return fail(GP_ERR_INVALID_ARG, "gp_propagate_features", "feat_dim < 1, order < 0, mode not in {0 ppr,1 avg,2 single} or alpha outside [0,1]");
     const int device = gp_graph_device(g);
     const int64_t n = gp_graph_num_nodes(g);
     const int* indptr = nullptr; const int* indices = nullptr; uint32_t node_mask = 0;
     int rc = gp_internal_graph_csr(g, &indptr, &indices, &node_mask, stream);
     if (rc) return rc;
-    if (!hip_ok(hipSetDevice(device), "hipSetDevice")) return GP_ERR_NO_DEVICE;
+    if ((rc = set_device(device, "gp_propagate_features"))) return rc;
     hipStream_t s = (hipStream_t)stream;
     const size_t nf = (size_t)n * (size_t)feat_dim;
     if (n == 0) return GP_OK;
@@ -234,8 +223,7 @@ int gp_propagate_features(gp_graph* g, const float* d_features, int32_t feat_dim
         const hipError_t e = hipMallocAsync(ptr, bytes, s);
         if (e == hipSuccess) return GP_OK;
         (void)hipGetLastError();
-        gp_internal_set_error(e == hipErrorOutOfMemory ? GP_ERR_NOMEM : GP_ERR_HIP, "hipMallocAsync", hipGetErrorString(e));
-        return e == hipErrorOutOfMemory ? GP_ERR_NOMEM : GP_ERR_HIP;
+        return fail(e == hipErrorOutOfMemory ? GP_ERR_NOMEM : GP_ERR_HIP, "hipMallocAsync", hipGetErrorString(e));
     };
     if ((rc = alloc((void**)&xa, nf * sizeof(float))) || (rc = alloc((void**)&xb, nf * sizeof(float))) ||
         (rc = alloc((void**)&scale, (size_t)n * sizeof(double))) || (rc = alloc((void**)&long_rows, (size_t)cap_long * sizeof(int))) ||
@@ -250,16 +238,14 @@ int gp_propagate_features(gp_graph* g, const float* d_features, int32_t feat_dim
     if (!hip_ok(hipMemcpyAsync(&n_long, n_long_d, sizeof(int), hipMemcpyDeviceToHost, s), "hipMemcpyAsync") ||
         !hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize"))
         return GP_ERR_HIP;
-    if (n_long > cap_long) { gp_internal_set_error(GP_ERR_OVERFLOW, "gp_propagate_features", "more than 2^20 rows longer than 4096"); return GP_ERR_OVERFLOW; }
+    if (n_long > cap_long) return fail(GP_ERR_OVERFLOW, "gp_propagate_features", "more than 2^20 rows longer than 4096");
 
     // X0 (model.py:186-187 / :195 / :203) and the running sum
     const int accumulate = mode != 2;
     hipLaunchKernelGGL(axpby_kernel, dim3(4096), dim3(256), 0, s, d_features, mode == 0 ? (float)alpha : 1.0f, xa,
                        accumulate ? d_out : (float*)nullptr, (long long)nf);
     float* cur = xa; float* nxt = xb;
-    const int vec = (feat_dim & 3) == 0 ? 4 : (feat_dim & 1) == 0 ? 2 : 1;
-    int log2g = 0;
-    while (log2g < 6 && (1 << log2g) * vec < feat_dim) ++log2g;               // G*VEC >= F, G <= 64
+    const int vec = vec_width(feat_dim), log2g = lane_group_log2(feat_dim, vec);         // G*VEC >= F, G <= 64
     const long long rows_per_block = (long long)(kBlock / 64) * (64 >> log2g);
     const int grid = (int)std::min<long long>((n + rows_per_block - 1) / rows_per_block, 256 * 32);
     for (int it = 0; it < order; ++it) {
@@ -272,7 +258,7 @@ int gp_propagate_features(gp_graph* g, const float* d_features, int32_t feat_dim
                                         (long long)n, cur, feat_dim, nxt, d_out, accumulate, log2g); break;
         }
         if (n_long > 0) {
-            const int slabs = (feat_dim + 64 * vec - 1) / (64 * vec);
+            const int slabs = feature_slabs(feat_dim, vec, 64);
             const int lgrid = (int)std::min<long long>((long long)n_long * slabs, 4096);
             switch (vec) {
                 case 4: hipLaunchKernelGGL(spmm_long_kernel<4>, dim3(lgrid), dim3(kLongBlock), 0, s, indptr, indices, d_edge_weight, node_mask,
@@ -287,8 +273,7 @@ int gp_propagate_features(gp_graph* g, const float* d_features, int32_t feat_dim
     }
     if (mode == 1) hipLaunchKernelGGL(scale_kernel, dim3(4096), dim3(256), 0, s, d_out, 1.0f / (float)(order + 1), (long long)nf);   // model.py:201
     if (mode == 2) { if (!hip_ok(hipMemcpyAsync(d_out, cur, nf * sizeof(float), hipMemcpyDeviceToDevice, s), "hipMemcpyAsync")) return GP_ERR_HIP; }
-    if (!hip_ok(hipGetLastError(), "propagate kernels")) return GP_ERR_HIP;
-    return GP_OK;                                          // ~Scratch frees
+    return launch_status("propagate kernels");             // ~Scratch frees
 }
 
 }  // extern "C"

@@ -24,12 +24,7 @@ from __future__ import annotations
 import ctypes
 
 from . import _native
-from .augment import _check, _dev_index, _new_seed
-
-
-def _stream(t):
-    import torch
-    return torch.cuda.current_stream(t.device).cuda_stream
+from ._common import _check, _dev_index, _new_seed, _ptr, _stream
 
 
 class _Layout:
@@ -43,8 +38,7 @@ class _Layout:
         return (self.offsets, self.nodes, self.base, self.attr_idx, self.attr_data)
 
     def args(self):
-        ptr = lambda t: t.data_ptr() if t is not None else None        # noqa: E731
-        return (ptr(self.offsets), self.n_src, ptr(self.nodes), ptr(self.base), self.n_rows,
+        return (_ptr(self.offsets), self.n_src, _ptr(self.nodes), _ptr(self.base), self.n_rows,
                 self.attr_idx.data_ptr(), self.attr_idx.element_size(), self.attr_data.data_ptr())
 
 
@@ -54,7 +48,7 @@ def _forward(weight, L, p, training, seed, keep, n_bad):
     out = torch.empty((L.n_rows, H), dtype=torch.float32, device=weight.device)
     rc = _native.lib().gp_embedding_bag(
         _dev_index(weight), weight.data_ptr(), V, H, *L.args(), float(p), int(bool(training)), ctypes.c_uint64(seed),
-        keep.data_ptr() if keep is not None else None, out.data_ptr(), n_bad.data_ptr(), ctypes.c_void_p(_stream(weight)))
+        _ptr(keep), out.data_ptr(), n_bad.data_ptr(), _stream(weight))
     _native.raise_for_status(rc)
     return out
 
@@ -66,7 +60,7 @@ def _backward(weight_shape, grad_out, L, p, training, seed, keep):
     dW = torch.zeros((V, H), dtype=torch.float32, device=g.device)
     rc = _native.lib().gp_embedding_bag_backward(
         _dev_index(g), g.data_ptr(), V, H, *L.args(), float(p), int(bool(training)), ctypes.c_uint64(seed),
-        keep.data_ptr() if keep is not None else None, dW.data_ptr(), None, ctypes.c_void_p(_stream(g)))
+        _ptr(keep), dW.data_ptr(), None, _stream(g))
     _native.raise_for_status(rc)
     return dW
 

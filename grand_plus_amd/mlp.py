@@ -25,29 +25,7 @@ import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
 from . import _native
-from .augment import _M64, _new_seed, sample_seed
-
-_LAYER_MUL = 0xA0761D6478BD642F
-
-
-def _mix(x: int) -> int:
-    x = (x + 0x9E3779B97F4A7C15) & _M64
-    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & _M64
-    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & _M64
-    return x ^ (x >> 31)
-
-
-def layer_seed(seed: int, layer: int, s: int = 0) -> int:
-    """Dropout seed of (layer, sample s) of a call with `seed`: GP_MLP_LAYER_SEED(gp_sample_seed(seed, s), layer)."""
-    return _mix(sample_seed(seed, s) ^ (((layer + 1) * _LAYER_MUL) & _M64))
-
-
-def _stream(t):
-    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
-
-
-def _ptr(t):
-    return t.data_ptr() if t is not None else None
+from ._common import _M64, _new_seed, _ptr, _stream, layer_seed  # noqa: F401  (layer_seed: public here)
 
 
 class _Cfg:

@@ -16,23 +16,21 @@ outside [0, C) are never used as an index: they are left out and counted in part
 """
 from __future__ import annotations
 
-import ctypes
-
 from . import _native
+from ._common import _ptr, _stream
 
 _KINDS = {"kl": _native.GP_LOSS_KL, "l2": _native.GP_LOSS_L2}
 
 
-def _loss_call(z, labels, n_labeled, weight, tem, conf, kind, ignore_index, logp_in, stream):
+def _loss_call(z, labels, n_labeled, weight, tem, conf, kind, ignore_index, logp_in):
     import torch
     S, B, C = z.shape
     out = torch.empty(3, dtype=torch.float32, device=z.device)
     counts = torch.empty(4, dtype=torch.int32, device=z.device)
     ws = torch.empty(max(_native.grand_loss_workspace_bytes(B), 8), dtype=torch.uint8, device=z.device)
     rc = _native.lib().gp_grand_loss(
-        z.device.index, z.data_ptr(), S, B, C, labels.data_ptr() if labels is not None else None, n_labeled, ignore_index,
-        float(weight), float(tem), float(conf), kind, int(logp_in), ws.data_ptr(), out.data_ptr(), counts.data_ptr(),
-        ctypes.c_void_p(stream))
+        z.device.index, z.data_ptr(), S, B, C, _ptr(labels), n_labeled, ignore_index,
+        float(weight), float(tem), float(conf), kind, int(logp_in), ws.data_ptr(), out.data_ptr(), counts.data_ptr(), _stream(z))
     _native.raise_for_status(rc)
     return out, counts
 
@@ -47,8 +45,7 @@ def _loss_function():
     class LossFn(torch.autograd.Function):
         @staticmethod
         def forward(ctx, z, labels, n_labeled, weight, tem, conf, kind, ignore_index, logp_in):
-            stream = torch.cuda.current_stream(z.device).cuda_stream
-            out, counts = _loss_call(z, labels, n_labeled, weight, tem, conf, kind, ignore_index, logp_in, stream)
+            out, counts = _loss_call(z, labels, n_labeled, weight, tem, conf, kind, ignore_index, logp_in)
             ctx.save_for_backward(z, labels, counts)
             ctx.args = (n_labeled, weight, tem, conf, kind, ignore_index, logp_in)
             ctx.set_materialize_grads(False)
@@ -66,10 +63,9 @@ def _loss_function():
             g_loss, g_sup, g_con = (g.float().contiguous() if g is not None else None for g in (g_loss, g_sup, g_con))
             dz = torch.empty_like(z)
             rc = _native.lib().gp_grand_loss_backward(
-                z.device.index, z.data_ptr(), S, B, C, labels.data_ptr() if labels is not None else None, n_labeled,
+                z.device.index, z.data_ptr(), S, B, C, _ptr(labels), n_labeled,
                 ignore_index, float(weight), float(tem), float(conf), kind, int(logp_in), g_loss.data_ptr(),
-                g_sup.data_ptr() if g_sup is not None else None, g_con.data_ptr() if g_con is not None else None,
-                counts.data_ptr(), dz.data_ptr(), ctypes.c_void_p(torch.cuda.current_stream(z.device).cuda_stream))
+                _ptr(g_sup), _ptr(g_con), counts.data_ptr(), dz.data_ptr(), _stream(z))
             _native.raise_for_status(rc)
             return dz, None, None, None, None, None, None, None, None
 
@@ -125,7 +121,7 @@ def grand_plus_loss(logits, labels, n_labeled, weight, *, tem=0.1, conf=None, ki
     if torch.is_grad_enabled() and z.requires_grad:
         loss, l_sup, l_con, counts = _loss_function().apply(z, labels, *args)
     else:
-        out, counts = _loss_call(z, labels, *args, torch.cuda.current_stream(z.device).cuda_stream)
+        out, counts = _loss_call(z, labels, *args)
         loss, l_sup, l_con = out[0], out[1], out[2]
     parts = {"sup": l_sup, "con": l_con, "n_conf": counts[0], "n_valid": counts[1], "n_correct": counts[2],
              "n_bad_labels": counts[3]}

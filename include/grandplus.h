@@ -412,7 +412,7 @@ int gp_grand_loss_backward(int device, const float* d_z, int32_t n_samples, int6
  *   r <- (1 - momentum) r + momentum stat_s with the unbiased variance, and *d_num_batches_tracked += S (NULL = none).
  *   In eval the running statistics are folded into one per-column affine map.  d_bn_weight / d_bn_bias NULL = 1 / 0.
  *   Dropout (training and dropout > 0): entry b * F_in + f of sample s is kept by d_keep[(s * B + b) * F_in + f] != 0
- *   when d_keep (uint8 [S x B x F_in]) is given, else by augment.hip's counter hash on the seed
+ *   when d_keep (uint8 [S x B x F_in]) is given, else by random_prop's counter hash (keep_scale, csrc/gp_common.hpp) on the seed
  *       GP_MLP_LAYER_SEED(gp_sample_seed(seed, s), layer),   GP_MLP_LAYER_SEED(x, l) = mix(x ^ (l + 1) * 0xA0761D6478BD642F)
  *   with gp_sample_seed and mix of the S-sample random_prop above (grand_plus_amd.mlp.layer_seed mirrors it).  Kept
  *   entries are scaled by 1 / (1 - dropout); dropout = 1 gives zeros, dropout = 0 draws nothing.
