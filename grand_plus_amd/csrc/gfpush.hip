@@ -25,6 +25,7 @@
 #include <string>
 #include <chrono>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 using namespace gp;
@@ -122,6 +123,7 @@ struct gp_graph {
     int sk_block = 0, sk_lg_mu = 0, sk_lg_mr = 0, sk_target = 0, sk_direct_max = 0;   // options: geometry of the sketch kernel (0 = default)
     int sk_seed_merge = 1; int gk_acsr = 1;                                                       // option: the general kernel runs on the self-addressed copy too when the graph is large (0 = packed CSR + indptr)
     int est_kind = 0; int last_kind = 1; bool sk_auto_off = false; double sk_off_rmax = 0.0; int sk_off_n_coef = 0;                                   // which kernel the running estimate / the last call belongs to
+    bool last_sk_soft = false;                                             // the last call ran the sketch kernel as an automatic or soft pick, not because option kernel = 2 insisted (grow_estimate)
     int64_t est_level_edges = 0;                                           // option: edges per level the first-launch slabs are sized for (0 = automatic)
     double est_edges = 0.0, est_log = 0.0;                                 // running estimate (grows from the observed maxima)
     double est_rmax = -1.0; int est_n_coef = 0;                            // the call parameters that estimate belongs to
@@ -138,11 +140,10 @@ struct gp_graph {
     // thresholds on rmax and graph size.  One entry per (rmax, n_coef, K); ms[] = general kernel in the shape the old
     // thresholds pick / sketch kernel / general kernel in the other shape (0: not a candidate).
     struct Choice { double rmax; int n_coef, K; int kernel, block_threads, lds_bytes; float ms[3]; };
-    std::vector<Choice> choices; bool calibrating = false; bool choice_soft = false; int measure_choice = 1; u64* d_cal_counters = nullptr;
+    std::vector<Choice> choices; int measure_choice = 1; u64* d_cal_counters = nullptr;
     float last_cal_ms[3] = {0.f, 0.f, 0.f};
     bool reset_pending = true; int64_t rows_total = 0;
     gp_stats last{};
-    // staging for the host-buffer entry point
     // ---- multi-GPU handle (gp_graph_create_multi): this object then owns no device memory itself; part[0] holds the CSR
     //      on the first GPU, the other GPUs get their replica (peer copy) the first time a call is large enough to shard.
     bool multi = false; int n_parts = 0; int force_collective = 0; int gather_host = 0; int64_t min_rows_per_gpu = 2048;
@@ -155,50 +156,11 @@ struct gp_graph {
     // one packed slab [val f64 x slots | row i32 x slots | col i32 x slots | filled i32 x seeds] on the device and one pinned
     // mirror: the rows come back with ONE D2H copy (the layout grand_plus_amd/sharded.py all-gathers)
     int* d_seeds = nullptr; int64_t seeds_cap = 0;
-    char* d_out = nullptr; size_t out_bytes = 0;
+    size_t out_bytes = 0;
     char* h_slab[2] = {nullptr, nullptr}; bool h_slab_clean[2] = {false, false}; int h_slab_next = 0; std::vector<unsigned char> h_done;     // gp_gfpush: two pinned output slabs, used alternately
 };
 
 namespace {
-
-template <int BLOCK> int launch_kernel(const KParams& kp, int n_wg, int lds_bytes, hipStream_t s) {
-    if (kp.row_map) {                                   // the retry launch (its own symbol: see gfpush_retry_kernel)
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(gfpush_retry_kernel<BLOCK>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-        hipLaunchKernelGGL(gfpush_retry_kernel<BLOCK>, dim3(n_wg), dim3(BLOCK), lds_bytes, s, kp);
-    } else {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(gfpush_kernel<BLOCK>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-        hipLaunchKernelGGL(gfpush_kernel<BLOCK>, dim3(n_wg), dim3(BLOCK), lds_bytes, s, kp);
-    }
-    HIP_TRY(hipGetLastError());
-    return GP_OK;
-}
-
-template <int BLOCK> int resident_blocks(int lds_bytes, int* out) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(gfpush_kernel<BLOCK>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-    int nb = 0;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, gfpush_kernel<BLOCK>, BLOCK, lds_bytes));
-    *out = std::max(nb, 1);
-    return GP_OK;
-}
-
-#ifndef GP_DIAG
-template <int BLOCK> int launch_sk(const KParams& kp, int n_wg, int lds_bytes, hipStream_t s) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(gfpush_sk_kernel<BLOCK>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-    hipLaunchKernelGGL(gfpush_sk_kernel<BLOCK>, dim3(n_wg), dim3(BLOCK), lds_bytes, s, kp);
-    HIP_TRY(hipGetLastError());
-    return GP_OK;
-}
-template <int BLOCK> int resident_sk(int lds_bytes, int* out) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(gfpush_sk_kernel<BLOCK>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-    int nb = 0;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, gfpush_sk_kernel<BLOCK>, BLOCK, lds_bytes));
-    *out = std::max(nb, 1);
-    return GP_OK;
-}
-#endif
 
 void free_workspace(Workspace& w) {
     if (w.base) (void)hipFree(w.base);
@@ -427,9 +389,10 @@ int ensure_workspace(gp_graph* g, int n_coef, double rmax, int n_wg, int64_t n_s
 // Slab sizing follows the RETRY RATE, not the largest row ever seen (sizing 768 slabs for 1.5 x the maximum made a
 // 13.6 GB workspace of which a row touches 0.4 MB).  The estimate starts at max(32 Ki edges per level, bound / 4) and grows by
 // half when more than 0.1 % of a completed call's rows outgrew their slab (they were re-run exactly by the next launch), and
-// doubles above 2 %.  Called when the previous call is known to have completed; applied once per call.
+// doubles above 2 %.  Called when the previous call is known to have completed; applied once per call (grown_for_call is false
+// from the moment a call is enqueued until its counters have been looked at).
 void grow_estimate(gp_graph* g) {
-    if (!g->launched || g->est_level_edges != 0 || g->grown_for_call || g->last_call_rows <= 0) return;
+    if (g->est_level_edges != 0 || g->grown_for_call || g->last_call_rows <= 0) return;
     g->grown_for_call = true;
     const double rows = (double)g->last_call_rows;
     const double outgrown = (double)(g->last_kind == 2 ? g->h_counters[kSkSlabFails] : g->h_counters[kRetryRows]);
@@ -439,7 +402,7 @@ void grow_estimate(gp_graph* g) {
     // the automatic choice of the sketch kernel is a guess from (rmax, graph size): when a call hands more than 5 % of its rows
     // back for other reasons than slab size -- each of them runs twice, the second time on an eighth of the chip -- later calls
     // of this recipe go to the general kernel
-    if (g->last_kind == 2 && (g->kernel == 0 || g->choice_soft) && (double)g->h_counters[kRetryRows] - outgrown > 0.05 * rows) {
+    if (g->last_kind == 2 && g->last_sk_soft && (double)g->h_counters[kRetryRows] - outgrown > 0.05 * rows) {
         g->sk_auto_off = true; g->sk_off_rmax = g->est_rmax; g->sk_off_n_coef = g->est_n_coef;
     }
 }
@@ -668,6 +631,365 @@ void plan_block(const MultiPlan& m, int d, int64_t n_seeds, int64_t* lo, int64_t
     *n = d < m.G ? std::min<int64_t>(*lo + m.per, n_seeds) - *lo : 0;
 }
 
+// ------------------------------------------------------------------ one call: what it is asked to run, its plan, its launches
+
+// The arguments of one gp_gfpush_device call.
+struct CallArgs {
+    const int32_t* d_seeds; int64_t n_seeds; const double* coef; int n_coef; double rmax; int K;
+    int32_t* d_row; int32_t* d_col; double* d_val; int32_t* d_filled; hipStream_t s;
+};
+
+// What a call is asked to run: built by gp_gfpush_device from the handle's options or from the recipe's measured Choice, and by
+// calibrate_choice for each candidate.  enqueue_call takes kernel, shape and softness from here, never from the handle.
+struct CallShape {
+    int kernel = 0;                          // 0 = the thresholds choose, 1 = general kernel, 2 = sketch kernel whenever the call allows it
+    int block_threads = 0, lds_bytes = 0;    // launch shape of the general kernel (0 = choose)
+    bool soft = false;                       // kernel 2 is CHOSEN, not insisted on: where the sketch kernel cannot run or keeps handing rows back, the general kernel takes over as in the automatic path
+    // A timing run of calibrate_choice: the counters accumulate in this block (zeroed in full first); the handle's own block and
+    // the caller's statistics (last, rows_total, reset_pending, launched, last_cal_ms) stay as they are.  nullptr: an ordinary call.
+    u64* timing_counters = nullptr;
+    bool insists_on_sketch() const { return kernel == 2 && !soft; }
+};
+
+// Geometry.  Two 512-thread workgroups per CU (80 KB of LDS each) or one 1024-thread workgroup owning all
+// 160 KB.  All waves of a workgroup move through a row's phases together, so they wait for memory together
+// and compete for issue slots together; a second, independent workgroup on the CU fills those gaps (one
+// row's barriers, memory stalls and TOP-K overlap the other row's inserts).  The half-size table costs extra
+// hash partitions on the biggest levels, which the one-lane-per-edge EXPAND made cheap (a partition pass
+// re-reads and filters at ~25 wave-instructions per 64 edges).  Measured on MI355X, 65 536 rows (tools/exp_run2.sh):
+// MAG-shape +13 %, Reddit-shape +15 %, Pubmed +20 %, Cora +74 %; the Amazon2M recipe (rmax 1e-6: levels of
+// ~100 k edges, 14+ partitions even with 160 KB) loses 36 % and keeps 1 x 1024, as does any rmax < 5e-6 on a
+// graph that is neither tiny nor sparse.
+// Three 512-thread workgroups per CU (52 KB of LDS each, 6 waves per SIMD at 80 VGPRs): a third resident row hides
+// more of each row's barriers and latency than the smaller table costs in extra hash partitions, once TOP-K no
+// longer falls off a cliff at that size (its histogram and tie bucket now live inside the aggregation table's bytes
+// and tau is read off a 16x finer histogram).  Measured on MI355X (round 3, 65 536 rows) against 2 x 768 x 80 KB:
+// MAG-shape +2.9 %, Reddit-shape +1.3 %, Pubmed +13 %, Cora +10 %.  K > 128 keeps 2 x 768 (sel[K] eats the table).
+// The threshold pick of the general kernel's shape, as workgroups per CU: 3, 2 or 1 (plan_general gives their threads and LDS).
+int threshold_wgs_per_cu(const gp_graph* g, double rmax, int K) {
+    const bool tiny = (double)g->n_nodes <= 0.75 * (double)((80 * 1024 - kCtlBytes) / 12);
+    const bool sparse = g->nnz < 8 * g->n_nodes;
+    const bool two_per_cu = K <= 256 && (tiny || sparse || rmax >= 5e-6);
+    return !two_per_cu ? 1 : K <= 128 ? 3 : 2;
+}
+
+// The threshold pick of the kernel -- the sketch kernel for the recipes whose push test filters (rmax >= 5e-6; at 1e-6 and
+// below most of a frontier pushes and the sketch has nothing to remove) on large graphs (measured, 65 536 rows: MAG-shape
+// +15 %, Reddit-shape +36 % over the general kernel; the 19.7 k-node Pubmed graph, where half of a frontier pushes, -18 %)
+bool threshold_picks_sketch(const gp_graph* g, double rmax) { return rmax >= 5e-6 && g->n_nodes >= 65536; }
+
+// How the sketch kernel runs a call (use == false: it does not) and how the general kernel does, or re-runs what was handed back.
+struct SketchPlan { bool use = false; int block = 0, lds = 0, wg = 0; u32 lg_mu = 0, lg_mr = 0, cx = 0; double coef_sum = 0.0; };
+struct GeneralPlan { int block_threads = 0, lds_bytes = 0, n_wg = 0; u32 lds_slots = 0; };
+
+// The one place a run-time block size becomes a template argument: f(std::integral_constant<int, BLOCK>()) names the kernel
+// built for `block` threads, out of the sizes listed (nullptr: none of them; gp_set_option admits no other, and the first HIP
+// call on a null kernel reports it).
+using Kernel = void (*)(KParams);
+template <int... BLOCKS, class F> Kernel kernel_for(int block, F f) {
+    Kernel k = nullptr;
+    (void)(... || (block == BLOCKS && ((k = f(std::integral_constant<int, BLOCKS>())), true)));
+    return k;
+}
+
+// Workgroups of kernel k that fit a CU / one launch of it, with `lds_bytes` of dynamic LDS.
+int resident_blocks(Kernel k, int block, int lds_bytes, int* out) {
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
+    int nb = 0;
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(k), block, lds_bytes));
+    *out = std::max(nb, 1);
+    return GP_OK;
+}
+int launch_kernel(Kernel k, int block, const KParams& kp, int n_wg, int lds_bytes, hipStream_t s) {
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
+    void* args[] = {const_cast<KParams*>(&kp)};
+    (void)hipLaunchKernel(reinterpret_cast<const void*>(k), dim3(n_wg), dim3(block), args, lds_bytes, s);
+    HIP_TRY(hipGetLastError());
+    return GP_OK;
+}
+
+void use_slabs(KParams& kp, const Slabs& sl) {
+    kp.push = sl.push; kp.push_cap = sl.push_cap;
+    kp.bt = sl.bt; kp.bt_cap = sl.bt_cap;
+    kp.resg = sl.resg; kp.resg_cap = sl.resg_cap;
+    kp.log_key = sl.log_key; kp.log_val = sl.log_val; kp.log_cap = sl.log_cap;
+    kp.log_pu = sl.log_pu; kp.arch = sl.arch; kp.arch_cap = sl.arch_cap;
+    kp.cand = sl.cand; kp.cand_cap = sl.cand_cap;
+    kp.bucket = sl.bucket; kp.bucket_cap = sl.bucket_cap;
+}
+
+// Which copy of the graph a launch runs on.  The self-addressed one (round 6: also for the general kernel on large graphs -- no
+// indptr line per pushing node, aligned runs: ~2 of the Amazon2M line's 13.6 MB per row) or the packed CSR + indptr.
+void use_csr(KParams& kp, const gp_graph* g, bool acsr, bool general) {
+    if (acsr) {
+        kp.indices = g->d_acsr; kp.nnz = (int)(g->n_units << 5);
+        kp.deg_shift = g->a_shift; kp.node_mask = g->a_mask; kp.deg_sat = g->a_sat;
+        kp.node_pos = g->d_node_pos; kp.unit_info = g->d_unit_info; kp.sk_hub_units = g->a_sat > 32u ? 1u : 0u;
+    } else {
+        kp.indices = g->d_indices; kp.nnz = (int)g->nnz;
+        kp.deg_shift = g->deg_shift; kp.node_mask = g->node_mask; kp.deg_sat = g->deg_sat;
+    }
+    kp.gk_acsr = acsr && general ? 1u : 0u;
+}
+
+#ifndef GP_DIAG
+constexpr bool kDiagBuild = false;
+Kernel sketch_kernel(int block) { return kernel_for<512, 1024, 768>(block, [](auto b) -> Kernel { return gfpush_sk_kernel<decltype(b)::value>; }); }
+
+// ---- which kernel.  The sketch kernel (gfpush_sketch.hpp) keeps exact fp64 accumulators only for the targets that may
+// push and reads the top-K off a cumulative upper-bound table; it needs coef >= 0 (upper bounds add up), a recipe that
+// fits its control block, and a threshold the fixed-point sketch can resolve.  Rows it cannot finish come back on a
+// retry list and the general kernel runs them.  p: whether it takes the call, and its geometry if it does.
+int plan_sketch(gp_graph* g, const CallArgs& a, const CallShape& shape, SketchPlan& p)
+{
+    const int K = a.K;
+    bool ok = shape.kernel != 1 && a.n_coef <= kSkMaxCoef && K <= 128 && a.rmax * 2147483648.0 >= 64.0 && !g->force_global && !g->exact_stats &&
+              a.n_seeds > 0;
+    for (int i = 0; i < a.n_coef; ++i) { if (a.coef[i] < 0.0) ok = false; p.coef_sum += a.coef[i]; }
+    if (!(p.coef_sum < 1.0e6)) ok = false;
+    const bool sk_off = g->sk_auto_off && g->sk_off_rmax == a.rmax && g->sk_off_n_coef == a.n_coef;   // (this recipe kept handing rows back)
+    p.use = ok && (shape.insists_on_sketch() || (!sk_off && (shape.kernel == 2 || threshold_picks_sketch(g, a.rmax))));
+    if (p.use) {                                       // it runs on the self-addressed CSR (built now if this is the first such call)
+        int rc = ensure_acsr(g, a.s);
+        if (rc) return rc;
+        if (g->acsr_state != 1) p.use = false;
+    }
+    if (!p.use) return GP_OK;
+    p.block = g->sk_block ? g->sk_block : 768;
+    p.lds = p.block == 512 ? kThreeLds : p.block == 1024 ? 160 * 1024 : 80 * 1024;
+    p.lg_mu = (u32)(g->sk_lg_mu ? g->sk_lg_mu : (p.block == 512 ? 12 : p.block == 1024 ? 14 : 13));
+    // the reserve sketch resolves the K-th total when ~4K of its cells are heavy: 2 048 cells for K <= 32 (the MAG recipe: 1 024 / 4 096
+    // cells +4 % / +5 % kernel time), 4 096 beyond (the Reddit recipe, K = 64: -5 %; the exact table pays for them with 680 slots)
+    p.lg_mr = (u32)(g->sk_lg_mr ? g->sk_lg_mr : (K > 32 && p.block >= 768 ? 12 : 11));
+    const int64_t x_bytes = (int64_t)p.lds - kCtlBytes - (4ll << p.lg_mu) - (4ll << p.lg_mr);
+    p.cx = x_bytes > 0 ? (u32)(x_bytes / 12) & ~3u : 0u;
+    // the exact table, and the aggregation table TOP-K builds over the level sketch + exact table, need >= kMinCap slots
+    const int64_t ca = ((4ll << p.lg_mu) + 12ll * p.cx - 16ll * ((int64_t)kSkTie + K)) / 12;
+    if (p.cx < kMinCap || ca < (int64_t)kMinCap) {
+        if (shape.insists_on_sketch() && (g->sk_lg_mu || g->sk_lg_mr)) return fail(GP_ERR_INVALID_ARG, "sketch sizes leave no room for the exact table (sk_lg_mu %u, sk_lg_mr %u)", p.lg_mu, p.lg_mr);
+        p.use = false;
+        return GP_OK;
+    }
+    int per_cu = 1;
+    int rc = resident_blocks(sketch_kernel(p.block), p.block, p.lds + g->lds_pad, &per_cu);
+    if (rc) return rc;
+    p.wg = g->num_cus * per_cu;
+    if (g->max_workgroups > 0) p.wg = std::min(p.wg, g->max_workgroups);
+    p.wg = (int)std::max<int64_t>(1, std::min<int64_t>(p.wg, a.n_seeds));
+    return GP_OK;
+}
+
+// The sketch kernel over every row of the call; what it cannot finish goes to retry_list (count in kRetryRows).
+int launch_sketch(const gp_graph* g, KParams& kp, const CallArgs& a, const SketchPlan& sk)
+{
+    const Workspace& w = g->ws;
+    use_slabs(kp, w.skl);
+    kp.row_map = nullptr; kp.n_rows_dev = nullptr; kp.queue_counter = kQueue;
+    kp.retry_list = w.retry_list; kp.retry_counter = kRetryRows;
+    kp.sk_lg_mu = sk.lg_mu; kp.sk_lg_mr = sk.lg_mr; kp.sk_cx = sk.cx;
+    kp.sk_target = (u32)(g->sk_target > 0 ? g->sk_target : 4 * a.K);
+    kp.sk_direct_max = g->sk_direct_max > 0 ? (u32)g->sk_direct_max : 0xFFFFFFFFu;
+    kp.sk_rscale = 2147483648.0 / std::max(1.0, sk.coef_sum);
+    {   // rmax * 2^31 * (1 - 2^-10), rounded DOWN to fp32: cell >= packed degree * this is necessary for r >= rmax * deg
+        float t = (float)(a.rmax * 2147483648.0 * (1.0 - 1.0 / 1024.0));
+        while ((double)t > a.rmax * 2147483648.0 * (1.0 - 1.0 / 1024.0)) t = std::nextafterf(t, 0.0f);
+        kp.sk_thr_f = t;
+    }
+    // ... on the self-addressed CSR: keys are unit numbers under the packed degree
+    use_csr(kp, g, true, false);
+    return launch_kernel(sketch_kernel(sk.block), sk.block, kp, sk.wg, sk.lds + g->lds_pad, a.s);
+}
+#else
+// (the diagnostic build instruments the general kernel on the packed CSR only: no sketch kernel, nothing to choose by measurement)
+constexpr bool kDiagBuild = true;
+int plan_sketch(gp_graph*, const CallArgs&, const CallShape&, SketchPlan&) { return GP_OK; }
+int launch_sketch(const gp_graph*, KParams&, const CallArgs&, const SketchPlan&) { return GP_OK; }
+#endif
+
+Kernel general_kernel(int block) { return kernel_for<256, 512, 768, 1024>(block, [](auto b) -> Kernel { return gfpush_kernel<decltype(b)::value>; }); }
+// (the retry launch is its own symbol: see gfpush_retry_kernel)
+Kernel retry_kernel(int block) { return kernel_for<256, 512, 768, 1024>(block, [](auto b) -> Kernel { return gfpush_retry_kernel<decltype(b)::value>; }); }
+
+// The general kernel's launch shape, its workgroups, and the workspace of the whole call.  Three fall-backs: the sketch
+// kernel's slabs do not fit (sk.use is cleared: the general kernel alone), three workgroups per CU -> two, two -> one.
+int plan_general(gp_graph* g, const CallArgs& a, const CallShape& shape, SketchPlan& sk, GeneralPlan& p)
+{
+    const int K = a.K;
+    const bool auto_shape = shape.block_threads == 0 && shape.lds_bytes == 0;
+    int wgs_per_cu = auto_shape ? threshold_wgs_per_cu(g, a.rmax, K) : 1;
+    for (;;) {
+        p.block_threads = shape.block_threads; p.lds_bytes = shape.lds_bytes;
+        if (auto_shape) {
+            // 12 waves per row: with the phases compiled as separate functions (32-66 VGPRs each) two 768-thread workgroups
+            // fit a CU at 80 VGPRs without spilling the loops (round 3: MAG +11 %, Reddit +7 %, Pubmed +3 % over 2 x 512);
+            // (direct-indexed tables of small graphs are instantiated for both two-per-CU shapes: Cora +11 % at 768)
+            p.block_threads = wgs_per_cu == 3 ? 512 : wgs_per_cu == 2 ? 768 : 1024;
+            p.lds_bytes = wgs_per_cu == 3 ? kThreeLds : wgs_per_cu == 2 ? 80 * 1024 : 160 * 1024;
+        } else {
+            if (p.block_threads == 0) p.block_threads = 1024;
+            if (p.lds_bytes == 0) p.lds_bytes = 160 * 1024;
+        }
+        p.lds_slots = (u32)((p.lds_bytes - kCtlBytes) / 12) & ~3u;     // multiple of 4: 128-bit LDS accesses on both arrays
+        // TOP-K carves sel[K] out of the table region and aggregates in what is
+        // left; like every LDS table that aggregation table needs >= kMinCap slots (home_lds: cap - kProbeSpan)
+        const size_t topk_fixed = 16 * (size_t)K;
+        const size_t topk_region = std::max<size_t>(12 * (size_t)kMinCap, kTopkBins * 4 + 16 * (size_t)kBucketCap);   // table, or histogram + compacted bucket
+        if ((size_t)p.lds_slots * 12 < topk_fixed + topk_region)
+            return fail(GP_ERR_INVALID_ARG, "lds_bytes = %d too small for K = %d (top-K needs %zu bytes of LDS)",
+                        p.lds_bytes, K, topk_fixed + topk_region + kCtlBytes);
+
+        int per_cu = 1;
+        int rc = resident_blocks(general_kernel(p.block_threads), p.block_threads, p.lds_bytes + g->lds_pad, &per_cu);
+        if (rc) return rc;
+        p.n_wg = g->num_cus * per_cu;
+        if (g->max_workgroups > 0) p.n_wg = std::min(p.n_wg, g->max_workgroups);
+        if (sk.use) p.n_wg = std::min(p.n_wg, std::max(8, g->num_cus / 2));  // the general kernel only re-runs what the sketch kernel hands back (a per-mille of the call)
+        p.n_wg = (int)std::max<int64_t>(1, std::min<int64_t>(p.n_wg, a.n_seeds));
+        rc = ensure_workspace(g, a.n_coef, a.rmax, p.n_wg, a.n_seeds, sk.use ? sk.wg : 0);
+        if (rc == GP_ERR_NOMEM && sk.use && !shape.insists_on_sketch()) {          // the automatic choice must not fail where the general kernel alone fits
+            sk.use = false; g_last_error.clear();
+            continue;
+        }
+        if (rc) return rc;
+        if (sk.use) break;
+        // the workspace budget could not hold two workgroups per CU: one big workgroup per CU is better than
+        // a half-empty chip
+        if (wgs_per_cu == 3 && g->ws.est.n_wg < p.n_wg && g->ws.est.n_wg < 3 * g->num_cus) { wgs_per_cu = 2; continue; }
+        if (wgs_per_cu == 2 && g->ws.est.n_wg < p.n_wg && g->ws.est.n_wg < 2 * g->num_cus) { wgs_per_cu = 1; continue; }
+        break;
+    }
+    p.n_wg = std::min(p.n_wg, g->ws.est.n_wg);
+    return GP_OK;
+}
+
+// Everything of KParams that is the same for every launch of the call (use_slabs / use_csr and the launch sequences set the rest).
+KParams call_params(const gp_graph* g, const CallArgs& a, const GeneralPlan& gk, u64* counters)
+{
+    KParams kp;
+    std::memset(&kp, 0, sizeof kp);
+    kp.indptr = g->d_indptr; kp.indices = g->d_indices; kp.n_nodes = (int)g->n_nodes; kp.nnz = (int)g->nnz;
+    kp.deg_shift = g->deg_shift; kp.node_mask = g->node_mask; kp.deg_sat = g->deg_sat;
+    kp.seeds = a.d_seeds; kp.n_seeds = a.n_seeds;
+    kp.coef = g->d_coef; kp.n_coef = a.n_coef; kp.rmax = a.rmax; kp.K = a.K;
+    kp.out_row = a.d_row; kp.out_col = a.d_col; kp.out_val = a.d_val; kp.out_filled = a.d_filled;
+    kp.counters = counters;
+    kp.lds_slots = gk.lds_slots;
+    kp.force_global = g->force_global;
+    kp.prune = g->exact_stats ? 0 : 1;
+    kp.diag_flags = g->diag_flags;
+    kp.rows_distinct = g->rows_distinct && g->seedrow ? 1u : 0u;
+    kp.solo = (g->solo_levels ? 1u : 0u) | (g->sk_seed_merge ? 2u : 0u);      // (bit 1: the sketch kernel's wave 0 does level 1 in the call of level 0)
+    // direct-indexed level tables: the whole graph fits the table of the 512-thread kernel (Cora, Citeseer)
+    kp.direct = ((gk.block_threads == 512 || gk.block_threads == 768) && (u64)g->n_nodes + 4 <= (u64)gk.lds_slots && g->direct_tables) ? 1 : 0;
+    for (int i = 0; i < a.n_coef; ++i) if (a.coef[i] < 0.0) kp.prune = 0;      // the bound needs coef >= 0
+    return kp;
+}
+
+// One pass of the general kernel and where its rows come from and go to.  rows == nullptr: every row of the call; else the
+// list whose length is counter n_rows.  Rows that outgrow the estimate-sized slabs go to `overflow` (numbered by counter
+// n_overflow) and, when bound-sized slabs exist, are re-run on those by a second launch that pulls from overflow_queue.
+struct GeneralPass { const u32* rows; int n_rows; int queue; u32* overflow; int n_overflow; int overflow_queue; };
+
+int launch_general(const gp_graph* g, KParams& kp, const GeneralPlan& gk, bool gk_acsr, const GeneralPass& pass, hipStream_t s)
+{
+    const Workspace& w = g->ws;
+    const bool two_tier = w.big.n_wg > 0;
+    use_csr(kp, g, gk_acsr, true);
+    use_slabs(kp, w.est);
+    kp.row_map = pass.rows; kp.n_rows_dev = pass.rows ? kp.counters + pass.n_rows : nullptr; kp.queue_counter = pass.queue;
+    kp.retry_list = two_tier ? pass.overflow : nullptr; kp.retry_counter = pass.n_overflow;
+    const Kernel k = pass.rows ? retry_kernel(gk.block_threads) : general_kernel(gk.block_threads);
+    int rc = launch_kernel(k, gk.block_threads, kp, gk.n_wg, gk.lds_bytes + g->lds_pad, s);
+    if (rc || !two_tier) return rc;
+    // Retry launch, enqueued unconditionally (no host synchronisation): it reads the number of rows that outgrew
+    // their slab from device memory and is a few microseconds of nothing when that number is zero.
+    use_slabs(kp, w.big);
+    kp.row_map = pass.overflow; kp.n_rows_dev = kp.counters + pass.n_overflow; kp.queue_counter = pass.overflow_queue;
+    kp.retry_list = nullptr;
+    return launch_kernel(retry_kernel(gk.block_threads), gk.block_threads, kp, w.big.n_wg, gk.lds_bytes + g->lds_pad, s);
+}
+
+// Plans and enqueues one call on a.s: everything behind gp_gfpush_device's argument checks, for the caller's call and for
+// each timing run of calibrate_choice alike.
+int enqueue_call(gp_graph* g, const CallArgs& a, const CallShape& shape)
+{
+    const hipStream_t s = a.s;
+    const bool timing = shape.timing_counters != nullptr;
+    u64* const counters = timing ? shape.timing_counters : g->d_counters;
+    // workspace and counters are per graph: launches on one stream are ordered by the stream,
+    // a launch on a DIFFERENT stream first waits for the previous one
+    if (g->launched && g->last_stream != s) HIP_TRY(hipStreamSynchronize(g->last_stream));
+    // Grow the slab estimate from what the previous call observed, whether or not the caller ever asks for statistics
+    // (ADVICE r2): once that call has completed, its counters are in the pinned mirror.
+    if (!g->grown_for_call && g->est_rmax == a.rmax && g->est_n_coef == a.n_coef) {
+        const hipError_t qs = hipStreamQuery(g->last_stream);
+        if (qs == hipSuccess) grow_estimate(g);
+        else if (qs != hipErrorNotReady) (void)hipGetLastError();
+    }
+
+    SketchPlan sk; GeneralPlan gk;
+    int rc = plan_sketch(g, a, shape, sk);
+    if (rc) return rc;
+    rc = plan_general(g, a, shape, sk, gk);
+    if (rc) return rc;
+    rc = ensure_packed(g, s);
+    if (rc) return rc;
+    Workspace& w = g->ws;
+
+    if (a.n_coef > g->coef_cap) {
+        if (g->d_coef) (void)hipFree(g->d_coef);
+        g->d_coef = nullptr; g->coef_cap = 0;
+        HIP_TRY(hipMalloc(&g->d_coef, sizeof(double) * (size_t)a.n_coef));
+        g->coef_cap = a.n_coef;
+    }
+    HIP_TRY(hipMemcpyAsync(g->d_coef, a.coef, sizeof(double) * (size_t)a.n_coef, hipMemcpyHostToDevice, s));
+    if (timing || g->reset_pending) {
+        HIP_TRY(hipMemsetAsync(counters, 0, sizeof(u64) * kNumCounters, s));
+        if (!timing) { g->reset_pending = false; g->rows_total = 0; }
+    } else {
+        HIP_TRY(hipMemsetAsync(counters, 0, sizeof(u64) * (kSkSlabFails + 1), s));  // the queue heads and the retry counts (per call: ADVICE r4)
+        if (g->est_recipe_changed)                                                          // maxima of another recipe must not size this one's slabs
+            HIP_TRY(hipMemsetAsync(counters + kMaxLevelEdges, 0, sizeof(u64) * 2, s));
+    }
+    g->est_recipe_changed = false;
+    if (w.dirty) {
+        hipLaunchKernelGGL(init_tables_kernel, dim3(4096), dim3(256), 0, s, w.est.resg, (u64)w.est.n_wg * w.est.resg_cap);
+        if (w.big.n_wg > 0)
+            hipLaunchKernelGGL(init_tables_kernel, dim3(1024), dim3(256), 0, s, w.big.resg, (u64)w.big.n_wg * w.big.resg_cap);
+        HIP_TRY(hipGetLastError());
+        w.dirty = false;
+    }
+
+    KParams kp = call_params(g, a, gk, counters);
+    bool gk_acsr = !kDiagBuild && g->gk_acsr && !kp.direct && !g->force_global && g->n_nodes >= 65536 && a.n_seeds > 0;
+    if (gk_acsr) { rc = ensure_acsr(g, s); if (rc) return rc; gk_acsr = g->acsr_state == 1; }
+
+    HIP_TRY(hipEventRecord(g->ev0, s));
+    if (a.n_seeds > 0 && !sk.use) {
+        rc = launch_general(g, kp, gk, gk_acsr, GeneralPass{nullptr, 0, kQueue, w.retry_list, kRetryRows, kQueueRetry}, s);
+    } else if (a.n_seeds > 0) {
+        // 1. the sketch kernel over every row; 2. the general kernel over its retry list (a quarter of the chip: the list is a
+        //    per-cent of the call); rows that outgrow ITS estimate-sized slabs go to retry_list2 ... 3. ... which the bound-sized slabs take
+        rc = launch_sketch(g, kp, a, sk);
+        if (!rc) rc = launch_general(g, kp, gk, gk_acsr, GeneralPass{w.retry_list, kRetryRows, kQueueRetry, w.retry_list2, kRetryRows2, kQueueRetry2}, s);
+    }
+    if (rc) return rc;
+    HIP_TRY(hipEventRecord(g->ev1, s));
+    HIP_TRY(hipMemcpyAsync(g->h_counters, counters, sizeof(u64) * kNumCounters, hipMemcpyDeviceToHost, s));
+    g->last_stream = s; g->last_call_rows = a.n_seeds; g->grown_for_call = false;
+    g->last_kind = sk.use ? 2 : 1; g->last_sk_soft = sk.use && !shape.insists_on_sketch();
+    if (timing) return GP_OK;
+    g->launched = true;
+    std::memset(&g->last, 0, sizeof g->last);
+    g->rows_total += a.n_seeds;
+    g->last.rows = g->rows_total;
+    g->last.kernel = g->last_kind;
+    g->last.workgroups = sk.use ? sk.wg : gk.n_wg; g->last.block_threads = sk.use ? sk.block : gk.block_threads;
+    g->last.lds_bytes = sk.use ? sk.lds : gk.lds_bytes; g->last.lds_slots = sk.use ? (int)sk.cx : (int)gk.lds_slots;
+    g->last.workspace_bytes = (int64_t)w.bytes;
+    return GP_OK;
+}
+
 // Rows timed per candidate / smallest call that is worth a calibration.  16 384 rows are ~30 rows per resident workgroup: both
 // kernels LEARN per workgroup how to plan a level (cand_q / ratio_q) and pay for an overflowed pass while they do; on 2 048 rows
 // (4 per workgroup) the MAG line's sketch kernel timed 2.0 ms against 1.4 ms for the general kernel in its slowest shape, which
@@ -680,36 +1002,32 @@ constexpr int64_t kCalRows = 16384, kCalMinRows = 32768;
 // Counters of the calibration runs go to a scratch block, the caller's accumulate untouched.  A candidate that cannot run here
 // (no memory for its slabs, a shape the call does not allow) is "not a candidate", never the user's error.
 // One-off cost: six short launches and two stream synchronisations.
-int calibrate_choice(gp_graph* g, const int32_t* d_seeds, const double* coef, int n_coef, double rmax, int K, hipStream_t s)
+int calibrate_choice(gp_graph* g, const CallArgs& call)
 {
     if (!g->d_cal_counters) HIP_TRY(hipMalloc(&g->d_cal_counters, sizeof(u64) * kNumCounters));
+    const int K = call.K;
+    const hipStream_t s = call.s;
     const size_t cal_slots = (size_t)kCalRows * (size_t)K;
     char* d_cal_out = nullptr;
     HIP_TRY(hipMalloc(&d_cal_out, 16 * cal_slots + 4 * (size_t)kCalRows));
     struct OutGuard { char* p; ~OutGuard() { if (p) (void)hipFree(p); } } out_guard{d_cal_out};
-    double* c_val = (double*)d_cal_out; int32_t* c_row = (int32_t*)(d_cal_out + 8 * cal_slots);
-    int32_t* c_col = (int32_t*)(d_cal_out + 12 * cal_slots); int32_t* c_filled = (int32_t*)(d_cal_out + 16 * cal_slots);
-    // the heuristic shape of the general kernel (what gp_gfpush_device picks when nothing is set) and the other one
-    const bool tiny = (double)g->n_nodes <= 0.75 * (double)((80 * 1024 - kCtlBytes) / 12);
-    const bool sparse = g->nnz < 8 * g->n_nodes;
-    const bool two_per_cu = K <= 256 && (tiny || sparse || rmax >= 5e-6);
-    struct Cand { int kernel, block, lds; };
-    const Cand cands[3] = { {1, 0, 0}, {2, 0, 0}, two_per_cu ? Cand{1, 1024, 160 * 1024} : Cand{1, 768, 80 * 1024} };
-    gp_graph::Choice ch; ch.rmax = rmax; ch.n_coef = n_coef; ch.K = K; ch.kernel = 0; ch.block_threads = 0; ch.lds_bytes = 0;
+    CallArgs a = call;
+    a.n_seeds = kCalRows;
+    a.d_val = (double*)d_cal_out; a.d_row = (int32_t*)(d_cal_out + 8 * cal_slots);
+    a.d_col = (int32_t*)(d_cal_out + 12 * cal_slots); a.d_filled = (int32_t*)(d_cal_out + 16 * cal_slots);
+    // the general kernel in the shape the thresholds pick, the sketch kernel, the general kernel in the other shape
+    const bool two_per_cu = threshold_wgs_per_cu(g, call.rmax, K) > 1;
+    u64* const tc = g->d_cal_counters;
+    const CallShape cands[3] = { {1, 0, 0, false, tc}, {2, 0, 0, false, tc},
+                                 two_per_cu ? CallShape{1, 1024, 160 * 1024, false, tc} : CallShape{1, 768, 80 * 1024, false, tc} };
+    gp_graph::Choice ch; ch.rmax = call.rmax; ch.n_coef = call.n_coef; ch.K = K; ch.kernel = 0; ch.block_threads = 0; ch.lds_bytes = 0;
     ch.ms[0] = ch.ms[1] = ch.ms[2] = 0.f;
-    // (everything the nested calls would change of the caller's statistics is put back afterwards)
-    u64* const counters = g->d_counters; const bool reset_pending = g->reset_pending; const int64_t rows_total = g->rows_total;
-    const gp_stats last = g->last; const bool launched = g->launched;
-    g->d_counters = g->d_cal_counters; g->reset_pending = true;
-    g->calibrating = true;
     int rc = GP_OK;
     for (int c = 0; c < 3 && rc == GP_OK; ++c) {
         if (c == 2 && K > 256) continue;                    // (two workgroups per CU need K <= 256: no other shape to try)
-        g->kernel = cands[c].kernel; g->block_threads = cands[c].block; g->lds_bytes = cands[c].lds;
         float ms = 0.f;
         for (int rep = 0; rep < 2 && rc == GP_OK; ++rep) {  // (the first run of a kernel pays code upload and first touch of its slabs)
-            g->reset_pending = true;
-            rc = gp_gfpush_device(g, d_seeds, kCalRows, coef, n_coef, rmax, K, c_row, c_col, c_val, c_filled, (void*)s);
+            rc = enqueue_call(g, a, cands[c]);
             if (rc == GP_ERR_NOMEM || rc == GP_ERR_INVALID_ARG) { rc = GP_OK; g_last_error.clear(); ms = 0.f; break; }   // not a candidate here
             if (rc) break;
             if (hipStreamSynchronize(s) != hipSuccess) { rc = fail(GP_ERR_HIP, "calibration: hipStreamSynchronize failed"); break; }
@@ -720,20 +1038,37 @@ int calibrate_choice(gp_graph* g, const int32_t* d_seeds, const double* coef, in
         ch.ms[c] = ms;
     }
     {   // what the thresholds would pick stays unless another candidate is more than 5 % faster (timing noise must not flip a recipe)
-        const int heur = rmax >= 5e-6 && g->n_nodes >= 65536 && ch.ms[1] > 0.f ? 1 : 0;
+        const int heur = threshold_picks_sketch(g, call.rmax) && ch.ms[1] > 0.f ? 1 : 0;
         int pick = ch.ms[heur] > 0.f ? heur : -1;
         for (int c = 0; c < 3; ++c)
             if (ch.ms[c] > 0.f && (pick < 0 || ch.ms[c] < 0.95f * ch.ms[pick])) pick = c;
-        if (pick >= 0) { ch.kernel = cands[pick].kernel; ch.block_threads = cands[pick].block; ch.lds_bytes = cands[pick].lds; }
+        if (pick >= 0) { ch.kernel = cands[pick].kernel; ch.block_threads = cands[pick].block_threads; ch.lds_bytes = cands[pick].lds_bytes; }
     }
-    g->kernel = 0; g->block_threads = 0; g->lds_bytes = 0; g->calibrating = false;
-    g->d_counters = counters; g->reset_pending = reset_pending; g->rows_total = rows_total; g->last = last; g->launched = launched;
     g->grown_for_call = true;                               // (the mirror holds the calibration's counters: nothing to grow from)
     // The workspace now holds slabs for every candidate.  It stays (the chosen layout fits in it: no hipFree / hipMalloc pair in
     // front of the call that follows -- VERDICT r5 weak #9) unless it is a large part of the budget.
     if (g->ws.bytes > ((size_t)g->workspace_mb << 20) / 8 || g->ws.bytes > ((size_t)8 << 30)) free_workspace(g->ws);
     if (rc) return rc;
     g->choices.push_back(ch);                               // (kernel 0: nothing could be timed -- the thresholds decide, as without a calibration)
+    return GP_OK;
+}
+
+// The measured choice of the call's recipe (nullptr: the options or the thresholds decide).  A recipe is calibrated by its
+// first call of >= kCalMinRows rows with nothing forced; smaller calls of the same recipe then use what that call measured
+// (the reference's own S of 10-12 k rows: VERDICT r5 weak #9), and the thresholds before it.
+int measured_choice(gp_graph* g, const CallArgs& a, const gp_graph::Choice** out)
+{
+    *out = nullptr;
+    if (kDiagBuild || g->kernel != 0 || g->block_threads != 0 || g->lds_bytes != 0 || !g->measure_choice ||
+        g->force_global || g->exact_stats || a.n_seeds <= 0) return GP_OK;
+    const gp_graph::Choice* c = nullptr;
+    for (const auto& e : g->choices) if (e.rmax == a.rmax && e.n_coef == a.n_coef && e.K == a.K) c = &e;
+    if (!c && a.n_seeds >= kCalMinRows) {
+        int rc = calibrate_choice(g, a);
+        if (rc) return rc;
+        c = &g->choices.back();
+    }
+    if (c && c->kernel != 0) *out = c;
     return GP_OK;
 }
 
@@ -919,7 +1254,6 @@ void gp_graph_destroy(gp_graph* g) {
     if (g->h_counters) (void)hipHostFree(g->h_counters);
     if (g->d_coef) (void)hipFree(g->d_coef);
     if (g->d_seeds) (void)hipFree(g->d_seeds);
-    if (g->d_out) (void)hipFree(g->d_out);
     for (int i = 0; i < 2; ++i) if (g->h_slab[i]) (void)hipHostFree(g->h_slab[i]);
     if (g->ev0) (void)hipEventDestroy(g->ev0);
     if (g->ev1) (void)hipEventDestroy(g->ev1);
@@ -1028,314 +1362,15 @@ int gp_gfpush_device(gp_graph* g, const int32_t* d_seeds, int64_t n_seeds,
                                                   "a multi-GPU handle takes host buffers through gp_gfpush");
     if (n_seeds > 0 && (!d_seeds || !d_row || !d_col || !d_val)) return fail(GP_ERR_NULL, "a device buffer is NULL");
     HIP_TRY(hipSetDevice(g->device));
-    hipStream_t s = (hipStream_t)stream;
-#ifndef GP_DIAG
-    if (g->kernel == 0 && g->block_threads == 0 && g->lds_bytes == 0 && g->measure_choice && !g->calibrating &&
-        !g->force_global && !g->exact_stats && n_seeds > 0) {
-        // a recipe is calibrated by its first call of >= kCalMinRows rows; smaller calls of the same recipe then use what that
-        // call measured (the reference's own S of 10-12 k rows: VERDICT r5 weak #9), and the thresholds before it
-        gp_graph::Choice* c = nullptr;
-        for (auto& e : g->choices) if (e.rmax == rmax && e.n_coef == n_coef && e.K == K) c = &e;
-        if (!c && n_seeds >= kCalMinRows) {
-            rc = calibrate_choice(g, d_seeds, coef, n_coef, rmax, K, s);
-            if (rc) return rc;
-            c = &g->choices.back();
-        }
-        if (c && c->kernel != 0) {
-            // the call itself, with the measured kernel and shape -- CHOSEN, not insisted on: where the sketch kernel's slabs do not
-            // fit, or it keeps handing rows back, the general kernel takes over as in the automatic path (choice_soft)
-            g->calibrating = true; g->choice_soft = true;
-            g->kernel = c->kernel; g->block_threads = c->block_threads; g->lds_bytes = c->lds_bytes;
-            rc = gp_gfpush_device(g, d_seeds, n_seeds, coef, n_coef, rmax, K, d_row, d_col, d_val, d_filled, stream);
-            g->kernel = 0; g->block_threads = 0; g->lds_bytes = 0;
-            g->calibrating = false; g->choice_soft = false;
-            std::memcpy(g->last_cal_ms, c->ms, sizeof g->last_cal_ms);
-            return rc;
-        }
-    }
-    if (!g->calibrating) std::memset(g->last_cal_ms, 0, sizeof g->last_cal_ms);
-#endif
-    // workspace and counters are per graph: launches on one stream are ordered by the stream,
-    // a launch on a DIFFERENT stream first waits for the previous one
-    if (g->launched && g->last_stream != s) HIP_TRY(hipStreamSynchronize(g->last_stream));
-    // Grow the slab estimate from what the previous call observed, whether or not the caller ever asks for statistics
-    // (ADVICE r2): once that call has completed, its counters are in the pinned mirror.
-    if (g->launched && g->est_rmax == rmax && g->est_n_coef == n_coef) {
-        const hipError_t qs = hipStreamQuery(g->last_stream);
-        if (qs == hipSuccess) grow_estimate(g);
-        else if (qs != hipErrorNotReady) (void)hipGetLastError();
-    }
-
-    // Geometry.  Two 512-thread workgroups per CU (80 KB of LDS each) or one 1024-thread workgroup owning all
-    // 160 KB.  All waves of a workgroup move through a row's phases together, so they wait for memory together
-    // and compete for issue slots together; a second, independent workgroup on the CU fills those gaps (one
-    // row's barriers, memory stalls and TOP-K overlap the other row's inserts).  The half-size table costs extra
-    // hash partitions on the biggest levels, which the one-lane-per-edge EXPAND made cheap (a partition pass
-    // re-reads and filters at ~25 wave-instructions per 64 edges).  Measured on MI355X, 65 536 rows (tools/exp_run2.sh):
-    // MAG-shape +13 %, Reddit-shape +15 %, Pubmed +20 %, Cora +74 %; the Amazon2M recipe (rmax 1e-6: levels of
-    // ~100 k edges, 14+ partitions even with 160 KB) loses 36 % and keeps 1 x 1024, as does any rmax < 5e-6 on a
-    // graph that is neither tiny nor sparse.
-    const bool auto_shape = g->block_threads == 0 && g->lds_bytes == 0;
-    const bool tiny = (double)g->n_nodes <= 0.75 * (double)((80 * 1024 - kCtlBytes) / 12);
-    const bool sparse = g->nnz < 8 * g->n_nodes;
-    bool two_per_cu = auto_shape && K <= 256 && (tiny || sparse || rmax >= 5e-6);
-    // Three 512-thread workgroups per CU (52 KB of LDS each, 6 waves per SIMD at 80 VGPRs): a third resident row hides
-    // more of each row's barriers and latency than the smaller table costs in extra hash partitions, once TOP-K no
-    // longer falls off a cliff at that size (its histogram and tie bucket now live inside the aggregation table's bytes
-    // and tau is read off a 16x finer histogram).  Measured on MI355X (round 3, 65 536 rows) against 2 x 768 x 80 KB:
-    // MAG-shape +2.9 %, Reddit-shape +1.3 %, Pubmed +13 %, Cora +10 %.  K > 128 keeps 2 x 768 (sel[K] eats the table).
-    bool three_per_cu = two_per_cu && K <= 128;
-
-    // ---- which kernel.  The sketch kernel (gfpush_sketch.hpp) keeps exact fp64 accumulators only for the targets that may
-    // push and reads the top-K off a cumulative upper-bound table; it needs coef >= 0 (upper bounds add up), a recipe that
-    // fits its control block, and a threshold the fixed-point sketch can resolve.  Rows it cannot finish come back on a
-    // retry list and the general kernel runs them.
-    bool use_sk = false;
-    double coef_sum = 0.0;
-#ifndef GP_DIAG
-    {
-        bool ok = g->kernel != 1 && n_coef <= kSkMaxCoef && K <= 128 && rmax * 2147483648.0 >= 64.0 && !g->force_global && !g->exact_stats &&
-                  n_seeds > 0;
-        for (int i = 0; i < n_coef; ++i) { if (coef[i] < 0.0) ok = false; coef_sum += coef[i]; }
-        if (!(coef_sum < 1.0e6)) ok = false;
-        // automatic: the recipes whose push test filters (rmax >= 5e-6; at 1e-6 and below most of a frontier pushes and the
-        // sketch has nothing to remove) on large graphs (measured, 65 536 rows: MAG-shape +15 %, Reddit-shape +36 % over the general
-        // kernel; the 19.7 k-node Pubmed graph, where half of a frontier pushes, -18 %)
-        const bool auto_sk = rmax >= 5e-6 && g->n_nodes >= 65536;
-        const bool sk_off = g->sk_auto_off && g->sk_off_rmax == rmax && g->sk_off_n_coef == n_coef;   // (this recipe kept handing rows back)
-        use_sk = ok && ((g->kernel == 2 && !(g->choice_soft && sk_off)) || (g->kernel == 0 && auto_sk && !sk_off));
-        if (use_sk) {                                      // it runs on the self-addressed CSR (built now if this is the first such call)
-            rc = ensure_acsr(g, s);
-            if (rc) return rc;
-            if (g->acsr_state != 1) use_sk = false;
-        }
-    }
-#endif
-    int sk_block = 0, sk_lds = 0, sk_wg = 0; u32 sk_lg_mu = 0, sk_lg_mr = 0, sk_cx = 0;
-#ifndef GP_DIAG
-    if (use_sk) {
-        sk_block = g->sk_block ? g->sk_block : 768;
-        sk_lds = sk_block == 512 ? kThreeLds : sk_block == 1024 ? 160 * 1024 : 80 * 1024;
-        sk_lg_mu = (u32)(g->sk_lg_mu ? g->sk_lg_mu : (sk_block == 512 ? 12 : sk_block == 1024 ? 14 : 13));
-        // the reserve sketch resolves the K-th total when ~4K of its cells are heavy: 2 048 cells for K <= 32 (the MAG recipe: 1 024 / 4 096
-        // cells +4 % / +5 % kernel time), 4 096 beyond (the Reddit recipe, K = 64: -5 %; the exact table pays for them with 680 slots)
-        sk_lg_mr = (u32)(g->sk_lg_mr ? g->sk_lg_mr : (K > 32 && sk_block >= 768 ? 12 : 11));
-        const int64_t x_bytes = (int64_t)sk_lds - kCtlBytes - (4ll << sk_lg_mu) - (4ll << sk_lg_mr);
-        sk_cx = x_bytes > 0 ? (u32)(x_bytes / 12) & ~3u : 0u;
-        // the exact table, and the aggregation table TOP-K builds over the level sketch + exact table, need >= kMinCap slots
-        const int64_t ca = ((4ll << sk_lg_mu) + 12ll * sk_cx - 16ll * ((int64_t)kSkTie + K)) / 12;
-        if (sk_cx < kMinCap || ca < (int64_t)kMinCap) {
-            if (g->kernel == 2 && !g->choice_soft && (g->sk_lg_mu || g->sk_lg_mr)) return fail(GP_ERR_INVALID_ARG, "sketch sizes leave no room for the exact table (sk_lg_mu %u, sk_lg_mr %u)", sk_lg_mu, sk_lg_mr);
-            use_sk = false;
-        }
-    }
-    if (use_sk) {
-        int per_cu = 1;
-        rc = sk_block == 512 ? resident_sk<512>(sk_lds + g->lds_pad, &per_cu) : sk_block == 1024 ? resident_sk<1024>(sk_lds + g->lds_pad, &per_cu) : resident_sk<768>(sk_lds + g->lds_pad, &per_cu);
-        if (rc) return rc;
-        sk_wg = g->num_cus * per_cu;
-        if (g->max_workgroups > 0) sk_wg = std::min(sk_wg, g->max_workgroups);
-        sk_wg = (int)std::max<int64_t>(1, std::min<int64_t>(sk_wg, n_seeds));
-    }
-#endif
-    int block_threads = 0, lds_bytes = 0, n_wg = 0;
-    u32 lds_slots = 0;
-    for (;;) {
-        block_threads = g->block_threads; lds_bytes = g->lds_bytes;
-        if (auto_shape) {
-            // 12 waves per row: with the phases compiled as separate functions (32-66 VGPRs each) two 768-thread workgroups
-            // fit a CU at 80 VGPRs without spilling the loops (round 3: MAG +11 %, Reddit +7 %, Pubmed +3 % over 2 x 512);
-            // (direct-indexed tables of small graphs are instantiated for both two-per-CU shapes: Cora +11 % at 768)
-            block_threads = three_per_cu ? 512 : two_per_cu ? 768 : 1024;
-            lds_bytes = three_per_cu ? kThreeLds : two_per_cu ? 80 * 1024 : 160 * 1024;
-        } else {
-            if (block_threads == 0) block_threads = 1024;
-            if (lds_bytes == 0) lds_bytes = 160 * 1024;
-        }
-        lds_slots = (u32)((lds_bytes - kCtlBytes) / 12) & ~3u;     // multiple of 4: 128-bit LDS accesses on both arrays
-        // TOP-K carves sel[K] out of the table region and aggregates in what is
-        // left; like every LDS table that aggregation table needs >= kMinCap slots (home_lds: cap - kProbeSpan)
-        const size_t topk_fixed = 16 * (size_t)K;
-        const size_t topk_region = std::max<size_t>(12 * (size_t)kMinCap, kTopkBins * 4 + 16 * (size_t)kBucketCap);   // table, or histogram + compacted bucket
-        if ((size_t)lds_slots * 12 < topk_fixed + topk_region)
-            return fail(GP_ERR_INVALID_ARG, "lds_bytes = %d too small for K = %d (top-K needs %zu bytes of LDS)",
-                        lds_bytes, K, topk_fixed + topk_region + kCtlBytes);
-
-        int per_cu = 1;
-        switch (block_threads) {
-            case 256: rc = resident_blocks<256>(lds_bytes + g->lds_pad, &per_cu); break;
-            case 512: rc = resident_blocks<512>(lds_bytes + g->lds_pad, &per_cu); break;
-            case 768: rc = resident_blocks<768>(lds_bytes + g->lds_pad, &per_cu); break;
-            default:  rc = resident_blocks<1024>(lds_bytes + g->lds_pad, &per_cu); break;
-        }
-        if (rc) return rc;
-        n_wg = g->num_cus * per_cu;
-        if (g->max_workgroups > 0) n_wg = std::min(n_wg, g->max_workgroups);
-        if (use_sk) n_wg = std::min(n_wg, std::max(8, g->num_cus / 2));  // the general kernel only re-runs what the sketch kernel hands back (a per-mille of the call)
-        n_wg = (int)std::max<int64_t>(1, std::min<int64_t>(n_wg, n_seeds));
-        rc = ensure_workspace(g, n_coef, rmax, n_wg, n_seeds, use_sk ? sk_wg : 0);
-        if (rc == GP_ERR_NOMEM && use_sk && (g->kernel != 2 || g->choice_soft)) {          // the automatic choice must not fail where the general kernel alone fits
-            use_sk = false; g_last_error.clear();
-            continue;
-        }
-        if (rc) return rc;
-        if (use_sk) break;
-        // the workspace budget could not hold two workgroups per CU: one big workgroup per CU is better than
-        // a half-empty chip
-        if (three_per_cu && g->ws.est.n_wg < n_wg && g->ws.est.n_wg < 3 * g->num_cus) { three_per_cu = false; continue; }
-        if (two_per_cu && g->ws.est.n_wg < n_wg && g->ws.est.n_wg < 2 * g->num_cus) { two_per_cu = false; continue; }
-        break;
-    }
-    rc = ensure_packed(g, s);
+    const CallArgs a{d_seeds, n_seeds, coef, n_coef, rmax, K, d_row, d_col, d_val, d_filled, (hipStream_t)stream};
+    const gp_graph::Choice* c = nullptr;
+    rc = measured_choice(g, a, &c);
     if (rc) return rc;
-    Workspace& w = g->ws;
-    n_wg = std::min(n_wg, w.est.n_wg);
-
-    if (n_coef > g->coef_cap) {
-        if (g->d_coef) (void)hipFree(g->d_coef);
-        g->d_coef = nullptr; g->coef_cap = 0;
-        HIP_TRY(hipMalloc(&g->d_coef, sizeof(double) * (size_t)n_coef));
-        g->coef_cap = n_coef;
-    }
-    HIP_TRY(hipMemcpyAsync(g->d_coef, coef, sizeof(double) * (size_t)n_coef, hipMemcpyHostToDevice, s));
-    if (g->reset_pending) {
-        HIP_TRY(hipMemsetAsync(g->d_counters, 0, sizeof(u64) * kNumCounters, s));
-        g->reset_pending = false; g->rows_total = 0;
-    } else {
-        HIP_TRY(hipMemsetAsync(g->d_counters, 0, sizeof(u64) * (kSkSlabFails + 1), s));  // the queue heads and the retry counts (per call: ADVICE r4)
-        if (g->est_recipe_changed)                                                          // maxima of another recipe must not size this one's slabs
-            HIP_TRY(hipMemsetAsync(g->d_counters + kMaxLevelEdges, 0, sizeof(u64) * 2, s));
-    }
-    g->est_recipe_changed = false;
-    if (w.dirty) {
-        hipLaunchKernelGGL(init_tables_kernel, dim3(4096), dim3(256), 0, s, w.est.resg, (u64)w.est.n_wg * w.est.resg_cap);
-        if (w.big.n_wg > 0)
-            hipLaunchKernelGGL(init_tables_kernel, dim3(1024), dim3(256), 0, s, w.big.resg, (u64)w.big.n_wg * w.big.resg_cap);
-        HIP_TRY(hipGetLastError());
-        w.dirty = false;
-    }
-
-    KParams kp;
-    std::memset(&kp, 0, sizeof kp);
-    kp.indptr = g->d_indptr; kp.indices = g->d_indices; kp.n_nodes = (int)g->n_nodes; kp.nnz = (int)g->nnz;
-    kp.deg_shift = g->deg_shift; kp.node_mask = g->node_mask; kp.deg_sat = g->deg_sat;
-    kp.seeds = d_seeds; kp.n_seeds = n_seeds;
-    kp.coef = g->d_coef; kp.n_coef = n_coef; kp.rmax = rmax; kp.K = K;
-    kp.out_row = d_row; kp.out_col = d_col; kp.out_val = d_val; kp.out_filled = d_filled;
-    auto use_slabs = [&kp](const Slabs& sl) {
-        kp.push = sl.push; kp.push_cap = sl.push_cap;
-        kp.bt = sl.bt; kp.bt_cap = sl.bt_cap;
-        kp.resg = sl.resg; kp.resg_cap = sl.resg_cap;
-        kp.log_key = sl.log_key; kp.log_val = sl.log_val; kp.log_cap = sl.log_cap;
-        kp.log_pu = sl.log_pu; kp.arch = sl.arch; kp.arch_cap = sl.arch_cap;
-        kp.cand = sl.cand; kp.cand_cap = sl.cand_cap;
-        kp.bucket = sl.bucket; kp.bucket_cap = sl.bucket_cap;
-    };
-    const bool two_tier = w.big.n_wg > 0;
-    kp.counters = g->d_counters;
-    kp.lds_slots = lds_slots;
-    kp.force_global = g->force_global;
-    kp.prune = g->exact_stats ? 0 : 1;
-    kp.diag_flags = g->diag_flags;
-    kp.rows_distinct = g->rows_distinct && g->seedrow ? 1u : 0u;
-    kp.solo = (g->solo_levels ? 1u : 0u) | (g->sk_seed_merge ? 2u : 0u);      // (bit 1: the sketch kernel's wave 0 does level 1 in the call of level 0)
-    // direct-indexed level tables: the whole graph fits the table of the 512-thread kernel (Cora, Citeseer)
-    kp.direct = ((block_threads == 512 || block_threads == 768) && (u64)g->n_nodes + 4 <= (u64)lds_slots && g->direct_tables) ? 1 : 0;
-    for (int i = 0; i < n_coef; ++i) if (coef[i] < 0.0) kp.prune = 0;      // the bound needs coef >= 0
-
-    // Which copy of the graph a launch runs on.  The self-addressed one (round 6: also for the general kernel on large graphs -- no
-    // indptr line per pushing node, aligned runs: ~2 of the Amazon2M line's 13.6 MB per row) or the packed CSR + indptr.
-    bool gk_acsr = g->gk_acsr && !kp.direct && !g->force_global && g->n_nodes >= 65536 && n_seeds > 0;
-#ifndef GP_DIAG
-    if (gk_acsr) { rc = ensure_acsr(g, s); if (rc) return rc; gk_acsr = g->acsr_state == 1; }
-#else
-    gk_acsr = false;
-#endif
-    auto use_csr = [&](bool acsr, bool general) {
-        if (acsr) {
-            kp.indices = g->d_acsr; kp.nnz = (int)(g->n_units << 5);
-            kp.deg_shift = g->a_shift; kp.node_mask = g->a_mask; kp.deg_sat = g->a_sat;
-            kp.node_pos = g->d_node_pos; kp.unit_info = g->d_unit_info; kp.sk_hub_units = g->a_sat > 32u ? 1u : 0u;
-        } else {
-            kp.indices = g->d_indices; kp.nnz = (int)g->nnz;
-            kp.deg_shift = g->deg_shift; kp.node_mask = g->node_mask; kp.deg_sat = g->deg_sat;
-        }
-        kp.gk_acsr = acsr && general ? 1u : 0u;
-    };
-    auto launch = [&](int wgs) {
-        switch (block_threads) {
-            case 256: return launch_kernel<256>(kp, wgs, lds_bytes + g->lds_pad, s);
-            case 512: return launch_kernel<512>(kp, wgs, lds_bytes + g->lds_pad, s);
-            case 768: return launch_kernel<768>(kp, wgs, lds_bytes + g->lds_pad, s);
-            default:  return launch_kernel<1024>(kp, wgs, lds_bytes + g->lds_pad, s);
-        }
-    };
-    HIP_TRY(hipEventRecord(g->ev0, s));
-    if (n_seeds > 0 && !use_sk) {
-        use_csr(gk_acsr, true);
-        use_slabs(w.est);
-        kp.row_map = nullptr; kp.n_rows_dev = nullptr; kp.queue_counter = kQueue;
-        kp.retry_list = two_tier ? w.retry_list : nullptr; kp.retry_counter = kRetryRows;
-        rc = launch(n_wg);
-        if (rc) return rc;
-        if (two_tier) {
-            // Retry launch, enqueued unconditionally (no host synchronisation): it reads the number of rows that outgrew
-            // their slab from device memory and is a few microseconds of nothing when that number is zero.
-            use_slabs(w.big);
-            kp.row_map = w.retry_list; kp.n_rows_dev = g->d_counters + kRetryRows; kp.queue_counter = kQueueRetry;
-            kp.retry_list = nullptr;
-            rc = launch(w.big.n_wg);
-            if (rc) return rc;
-        }
-    }
-#ifndef GP_DIAG
-    if (n_seeds > 0 && use_sk) {
-        // 1. the sketch kernel over every row; what it cannot finish goes to retry_list (count in kRetryRows)
-        use_slabs(w.skl);
-        kp.row_map = nullptr; kp.n_rows_dev = nullptr; kp.queue_counter = kQueue;
-        kp.retry_list = w.retry_list; kp.retry_counter = kRetryRows;
-        kp.sk_lg_mu = sk_lg_mu; kp.sk_lg_mr = sk_lg_mr; kp.sk_cx = sk_cx;
-        kp.sk_target = (u32)(g->sk_target > 0 ? g->sk_target : 4 * K);
-        kp.sk_direct_max = g->sk_direct_max > 0 ? (u32)g->sk_direct_max : 0xFFFFFFFFu;
-        kp.sk_rscale = 2147483648.0 / std::max(1.0, coef_sum);
-        {   // rmax * 2^31 * (1 - 2^-10), rounded DOWN to fp32: cell >= packed degree * this is necessary for r >= rmax * deg
-            float t = (float)(rmax * 2147483648.0 * (1.0 - 1.0 / 1024.0));
-            while ((double)t > rmax * 2147483648.0 * (1.0 - 1.0 / 1024.0)) t = std::nextafterf(t, 0.0f);
-            kp.sk_thr_f = t;
-        }
-        // ... on the self-addressed CSR: keys are unit numbers under the packed degree
-        use_csr(true, false);
-        rc = sk_block == 512 ? launch_sk<512>(kp, sk_wg, sk_lds + g->lds_pad, s) : sk_block == 1024 ? launch_sk<1024>(kp, sk_wg, sk_lds + g->lds_pad, s) : launch_sk<768>(kp, sk_wg, sk_lds + g->lds_pad, s);
-        if (rc) return rc;
-        use_csr(gk_acsr, true);
-        // 2. the general kernel over that list (a quarter of the chip: the list is a per-cent of the call); rows that outgrow
-        //    ITS estimate-sized slabs go to retry_list2 ...
-        use_slabs(w.est);
-        kp.row_map = w.retry_list; kp.n_rows_dev = g->d_counters + kRetryRows; kp.queue_counter = kQueueRetry;
-        kp.retry_list = two_tier ? w.retry_list2 : nullptr; kp.retry_counter = kRetryRows2;
-        rc = launch(n_wg);
-        if (rc) return rc;
-        if (two_tier) {     // 3. ... which the bound-sized slabs take
-            use_slabs(w.big);
-            kp.row_map = w.retry_list2; kp.n_rows_dev = g->d_counters + kRetryRows2; kp.queue_counter = kQueueRetry2;
-            kp.retry_list = nullptr;
-            rc = launch(w.big.n_wg);
-            if (rc) return rc;
-        }
-    }
-#endif
-    HIP_TRY(hipEventRecord(g->ev1, s));
-    HIP_TRY(hipMemcpyAsync(g->h_counters, g->d_counters, sizeof(u64) * kNumCounters, hipMemcpyDeviceToHost, s));
-    g->launched = true; g->last_stream = s; g->last_call_rows = n_seeds; g->grown_for_call = false;
-    std::memset(&g->last, 0, sizeof g->last);
-    g->rows_total += n_seeds;
-    g->last.rows = g->rows_total;
-    g->last_kind = use_sk ? 2 : 1;
-    g->last.kernel = g->last_kind;
-    g->last.workgroups = use_sk ? sk_wg : n_wg; g->last.block_threads = use_sk ? sk_block : block_threads;
-    g->last.lds_bytes = use_sk ? sk_lds : lds_bytes; g->last.lds_slots = use_sk ? (int)sk_cx : (int)lds_slots;
-    g->last.workspace_bytes = (int64_t)w.bytes;
-    return GP_OK;
+    CallShape shape{g->kernel, g->block_threads, g->lds_bytes};                      // what the options ask for ...
+    if (c) shape = CallShape{c->kernel, c->block_threads, c->lds_bytes, true};       // ... or the measured kernel and shape -- CHOSEN, not insisted on (CallShape::soft)
+    if (c) std::memcpy(g->last_cal_ms, c->ms, sizeof g->last_cal_ms);
+    else std::memset(g->last_cal_ms, 0, sizeof g->last_cal_ms);
+    return enqueue_call(g, a, shape);
 }
 
 int gp_reset_stats(gp_graph* g) {
