@@ -16,7 +16,6 @@ The MAG vocabulary size and bag lengths are not known here: --vocab, --bag and -
 (defaults: 500 000 attribute ids, 20 attributes per node, 2 000 000 nodes), as are the synthetic [S x K] rows.
 """
 import argparse
-import json
 import os
 import sys
 import time
@@ -28,23 +27,11 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import torch.nn.functional as Fn  # noqa: E402
 
+from _bench_steps import emit, synthetic_rows, timed, torch_prop  # noqa: E402
 from grand_plus_amd.augment import algorithmic_bytes, random_prop  # noqa: E402
 from grand_plus_amd.embedding import embedding_bag_csr, flatten_rows  # noqa: E402
 
 HBM, ATOMIC = 8.0e12, 1.3e12
-
-
-def timed(fn, iters):
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(iters):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) / iters * 1e3                                      # microseconds
 
 
 def torch_emb(W, attr_idx, node_idx, attr_data, p, training, n_out):
@@ -52,13 +39,6 @@ def torch_emb(W, attr_idx, node_idx, attr_data, p, training, n_out):
     num = torch.zeros((n_out, W.shape[1]), device=W.device).index_add_(0, node_idx, fe * attr_data[:, None])
     den = torch.zeros((n_out, 1), device=W.device).index_add_(0, node_idx, attr_data[:, None])
     return num / (den + 1e-10)
-
-
-def torch_prop(feats, scores, idx, p, training, n_out):
-    s = Fn.dropout(scores, p, training=training)
-    num = torch.zeros((n_out, feats.shape[1]), device=feats.device).index_add_(0, idx, feats * s[:, None])
-    den = torch.zeros((n_out, 1), device=feats.device).index_add_(0, idx, s[:, None])
-    return num / (den + 1e-12)
 
 
 def main():
@@ -81,9 +61,7 @@ def main():
     ip, ix, dt = (torch.from_numpy(x).to(dev) for x in (indptr, indices, data))
     W = (torch.randn((V, H), device=dev) * 0.1).requires_grad_(True)
     S = 20_000                                                                   # resident [S x K] rows (synthetic)
-    col = torch.from_numpy(rng.integers(0, N, S * K).astype(np.int32)).to(dev)
-    val = torch.from_numpy(np.sort(rng.random((S, K)) ** 4, axis=1)[:, ::-1].copy().reshape(-1)).to(dev)
-    filled = torch.full((S,), K, dtype=torch.int32, device=dev)
+    col, val, filled = synthetic_rows(rng, dev, S, K, N)
     host = None
     if not a.no_host:
         import scipy.sparse as sp
@@ -149,8 +127,8 @@ def main():
                     if rows is not None:
                         torch_prop(emb, scores, mat_idx, 0.5, False, B)
             passes = 1
-        us = timed(ours, a.iters)
-        us_plain = timed(plain, a.iters)
+        us = timed(ours, a.iters, 1, warmup=3)[0]
+        us_plain = timed(plain, a.iters, 1, warmup=3)[0]
         W.grad = None
         emb_bytes = nnz * (4 * H + 8) + M * 4 * H                                # table rows + (id, weight) + output rows
         prop_bytes = algorithmic_bytes(M, B, H) if rows is not None else 0
@@ -178,7 +156,7 @@ def main():
                 torch.tensor(bf.data, dtype=torch.float32).to(dev); torch.tensor(n_i, dtype=torch.long).to(dev)
                 torch.cuda.synchronize()
                 rec["reference_host_prep_us"] = round((time.perf_counter() - t0) * 1e6, 1)
-        print(json.dumps(rec), flush=True)
+        emit(rec)
 
 
 if __name__ == "__main__":

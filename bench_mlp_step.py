@@ -18,7 +18,6 @@ Times are CUDA events around the whole call (launches included), median of --rep
 Features, graphs and rows are synthetic (uniform random neighbours and scores).
 """
 import argparse
-import json
 import os
 import sys
 
@@ -27,11 +26,12 @@ sys.path.insert(0, ROOT)
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
-import torch.nn.functional as Fn  # noqa: E402
 
+from _bench_steps import batch_of, emit, synthetic_rows, timed, torch_prop  # noqa: E402
 from grand_plus_amd.augment import random_prop, random_prop_rows  # noqa: E402
 from grand_plus_amd.mlp import GrandPlusMLP, MagMLP  # noqa: E402
 from grand_plus_amd.objective import grand_plus_loss  # noqa: E402
+from oracle.objective_ref import grand_loss_ref  # noqa: E402
 
 # name: layout, F, H, C, nlayers, use_bn/node_norm, input/hidden dropout, labelled + unlabelled rows, step (nodes, K, loss)
 CASES = {
@@ -45,39 +45,6 @@ CASES = {
 }
 S, TEM, P_NODE = 2, 0.1, 0.5
 AMAZON2M_NODES = 2_449_029
-
-
-def consis_loss_ref(logps, tem, conf, kind):
-    """consis_loss of model.py:123-139."""
-    ps = [torch.exp(p) for p in logps]
-    sum_p = 0.
-    for p in ps:
-        sum_p = sum_p + p
-    avg_p = sum_p / len(ps)
-    sharp_p = (torch.pow(avg_p, 1. / tem) / torch.sum(torch.pow(avg_p, 1. / tem), dim=1, keepdim=True)).detach()
-    loss = 0.
-    for p in ps:
-        if kind == "kl":
-            loss += torch.mean((-sharp_p * torch.log(p)).sum(1)[avg_p.max(1)[0] > conf])
-        else:
-            loss += torch.mean((p - sharp_p).pow(2).sum(1)[avg_p.max(1)[0] > conf])
-    return loss / len(ps)
-
-
-def ref_objective(logits, labels, n_l, kind, C):
-    outs, loss = [], 0.
-    for z in logits:
-        lp = torch.log_softmax(z, dim=-1)
-        outs.append(lp[n_l:])
-        loss = loss + Fn.nll_loss(lp[:n_l], labels)
-    return loss / len(logits) + consis_loss_ref(outs, TEM, 2.0 / C, kind)
-
-
-def torch_prop(feats, scores, idx, p, n_out):
-    s = Fn.dropout(scores, p, training=True)
-    num = torch.zeros((n_out, feats.shape[1]), device=feats.device).index_add_(0, idx, feats * s[:, None])
-    den = torch.zeros((n_out, 1), device=feats.device).index_add_(0, idx, s[:, None])
-    return num / (den + 1e-12)
 
 
 def build(name, dev, rng):
@@ -94,13 +61,9 @@ def build(name, dev, rng):
         N, K, kind = step
         S_rows = 20_000
         n_nodes = N if N is not None else S_rows * K
-        col = torch.from_numpy(rng.integers(0, n_nodes, S_rows * K).astype(np.int32)).to(dev)
-        val = torch.from_numpy(np.sort(rng.random((S_rows, K)) ** 4, axis=1)[:, ::-1].copy().reshape(-1)).to(dev)
-        rows = torch.from_numpy(rng.choice(S_rows, B, replace=False).astype(np.int32)).to(dev)
-        r = rows.long()
-        c.update(K=K, kind=kind, col=col, val=val, rows=rows, filled=torch.full((S_rows,), K, dtype=torch.int32, device=dev),
-                 nbr=col.view(S_rows, K)[r].reshape(-1).long(), scores=val.view(S_rows, K)[r].reshape(-1).float(),
-                 idx=torch.arange(B, device=dev).repeat_interleave(K))
+        col, val, filled = synthetic_rows(rng, dev, S_rows, K, n_nodes)
+        rows, nbr, scores, idx = batch_of(rng, dev, col, val, S_rows, K, B)
+        c.update(K=K, kind=kind, col=col, val=val, rows=rows, filled=filled, nbr=nbr, scores=scores, idx=idx)
         if N is None:                                               # MAG: the embedding output of the batch, trained
             c["X"] = None
             c["feats"] = (torch.randn((B * K, Fin), device=dev) * 0.1).requires_grad_(True)
@@ -141,8 +104,8 @@ def variants(c):
         loss.backward()
 
     def step_ref():
-        logits = [m.reference_forward(torch_prop(c["feats"], c["scores"], c["idx"], P_NODE, B)) for _ in range(S)]
-        ref_objective(logits, c["labels"], n_l, kind, C).backward()
+        logits = [m.reference_forward(torch_prop(c["feats"], c["scores"], c["idx"], P_NODE, True, B)) for _ in range(S)]
+        grand_loss_ref(logits, c["labels"], n_l, 1.0, TEM, 2.0 / C, kind)[0].backward()
 
     v.update(step_ours=step_ours, step_s7e=step_s7e, step_ref=step_ref)
     return v
@@ -163,30 +126,6 @@ def eval_variants(dev, batch):
         return go
 
     return {"eval_ours": run(m), "eval_torch": run(m.reference_forward)}
-
-
-def timed(fn, iters, reps):
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(iters):
-            fn()
-        b.record()
-        torch.cuda.synchronize()
-        out.append(a.elapsed_time(b) / iters * 1e3)                  # microseconds
-    return float(np.median(out)), float(min(out)), float(max(out))
-
-
-def emit(rec, path):
-    line = json.dumps(rec)
-    print(line, flush=True)
-    if path:
-        with open(path, "a") as f:
-            f.write(line + "\n")
 
 
 def main():
@@ -214,7 +153,7 @@ def main():
         rec = {"case": name, "layout": layout, "S": S, "B": c["B"], "F": F, "H": H, "C": C, "nlayers": nl, "bn_norm": bn,
                "dropout": [pin, phid], "iters": a.iters, "reps": a.reps}
         for key, fn in variants(c).items():
-            med, lo, hi = timed(fn, a.iters, a.reps)
+            med, lo, hi = timed(fn, a.iters, a.reps, warmup=3)
             rec[key + "_us"] = round(med, 1)
             rec[key + "_us_range"] = [round(lo, 1), round(hi, 1)]
         rec["mlp_speedup"] = round(rec["mlp_torch_us"] / rec["mlp_ours_us"], 2)
@@ -226,7 +165,7 @@ def main():
     if a.eval:
         rec = {"case": "amazon2m_get_local_logits", "rows": AMAZON2M_NODES, "batch": a.eval_batch, "iters": 1, "reps": 3}
         for key, fn in eval_variants(dev, a.eval_batch).items():
-            med, lo, hi = timed(fn, 1, 3)
+            med, lo, hi = timed(fn, 1, 3, warmup=3)
             rec[key + "_us"] = round(med, 1)
             rec[key + "_us_range"] = [round(lo, 1), round(hi, 1)]
         rec["eval_speedup"] = round(rec["eval_torch_us"] / rec["eval_ours_us"], 2)

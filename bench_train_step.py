@@ -18,7 +18,6 @@ Times are CUDA events around the whole step (launches included), median of --rep
 Graphs, features and rows are synthetic (node counts of the datasets, uniform random neighbours and scores).
 """
 import argparse
-import json
 import os
 import sys
 
@@ -27,10 +26,11 @@ sys.path.insert(0, ROOT)
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
-import torch.nn.functional as Fn  # noqa: E402
 
+from _bench_steps import batch_of, emit, synthetic_rows, timed, torch_prop  # noqa: E402
 from grand_plus_amd.augment import random_prop, random_prop_rows  # noqa: E402
 from grand_plus_amd.objective import grand_plus_loss  # noqa: E402
+from oracle.objective_ref import grand_loss_ref  # noqa: E402
 
 # name: nodes, F (MAG: H), C, labelled, unlabelled, K, loss kind  (run_*.sh; tem 0.1 everywhere, --sample 2)
 CASES = {
@@ -42,55 +42,15 @@ CASES = {
 S, TEM, P_NODE = 2, 0.1, 0.5
 
 
-def consis_loss_ref(logps, tem, conf, kind):
-    """consis_loss of model.py:123-139."""
-    ps = [torch.exp(p) for p in logps]
-    sum_p = 0.
-    for p in ps:
-        sum_p = sum_p + p
-    avg_p = sum_p / len(ps)
-    sharp_p = (torch.pow(avg_p, 1. / tem) / torch.sum(torch.pow(avg_p, 1. / tem), dim=1, keepdim=True)).detach()
-    loss = 0.
-    for p in ps:
-        if kind == "kl":
-            loss += torch.mean((-sharp_p * torch.log(p)).sum(1)[avg_p.max(1)[0] > conf])
-        else:
-            loss += torch.mean((p - sharp_p).pow(2).sum(1)[avg_p.max(1)[0] > conf])
-    return loss / len(ps)
-
-
-def ref_objective(logits, labels, n_l, w, kind, C):
-    outs, loss = [], 0.
-    for z in logits:
-        lp = torch.log_softmax(z, dim=-1)
-        outs.append(lp[n_l:])
-        loss = loss + Fn.nll_loss(lp[:n_l], labels)
-    return loss / len(logits) + w * consis_loss_ref(outs, TEM, 2.0 / C, kind)
-
-
-def torch_prop(feats, scores, idx, p, n_out):
-    s = Fn.dropout(scores, p, training=True)
-    num = torch.zeros((n_out, feats.shape[1]), device=feats.device).index_add_(0, idx, feats * s[:, None])
-    den = torch.zeros((n_out, 1), device=feats.device).index_add_(0, idx, s[:, None])
-    return num / (den + 1e-12)
-
-
 def build(name, dev, rng):
     N, F, C, n_l, n_u, K, kind = CASES[name]
     B = n_l + n_u
     S_rows = 20_000
     n_nodes = N if N is not None else S_rows * K
-    col = torch.from_numpy(rng.integers(0, n_nodes, S_rows * K).astype(np.int32)).to(dev)
-    val = torch.from_numpy(np.sort(rng.random((S_rows, K)) ** 4, axis=1)[:, ::-1].copy().reshape(-1)).to(dev)
-    filled = torch.full((S_rows,), K, dtype=torch.int32, device=dev)
-    rows = torch.from_numpy(rng.choice(S_rows, B, replace=False).astype(np.int32)).to(dev)
+    col, val, filled = synthetic_rows(rng, dev, S_rows, K, n_nodes)
+    rows, nbr, scores, idx = batch_of(rng, dev, col, val, S_rows, K, B)
     labels = torch.from_numpy(rng.integers(0, C, n_l)).to(dev)
     head = (torch.randn((F, C), device=dev) * 0.05).requires_grad_(True)
-    # the reference's tensors after its host preparation and upload (model.py:310-316): gathered rows, scores, ids
-    r = rows.long()
-    nbr = col.view(S_rows, K)[r].reshape(-1).long()
-    scores = val.view(S_rows, K)[r].reshape(-1).float()
-    idx = torch.arange(B, device=dev).repeat_interleave(K)
     if N is None:                                                   # MAG: the embedding output of the batch, trained
         X = None
         feats = (torch.randn((B * K, F), device=dev) * 0.1).requires_grad_(True)
@@ -111,7 +71,7 @@ def variants(c):
         loss.backward()
 
     def ref_objective_only():
-        ref_objective(z_ref, c["labels"], n_l, 1.0, kind, C).backward()
+        grand_loss_ref(z_ref, c["labels"], n_l, 1.0, TEM, 2.0 / C, kind)[0].backward()
 
     def ours_step():
         if c["X"] is not None:
@@ -123,26 +83,10 @@ def variants(c):
         loss.backward()
 
     def ref_step():
-        logits = [torch_prop(c["feats"], c["scores"], c["idx"], P_NODE, B) @ head for _ in range(S)]
-        ref_objective(logits, c["labels"], n_l, 1.0, kind, C).backward()
+        logits = [torch_prop(c["feats"], c["scores"], c["idx"], P_NODE, True, B) @ head for _ in range(S)]
+        grand_loss_ref(logits, c["labels"], n_l, 1.0, TEM, 2.0 / C, kind)[0].backward()
 
     return {"ours_objective": ours_objective, "ref_objective": ref_objective_only, "ours_step": ours_step, "ref_step": ref_step}
-
-
-def timed(fn, iters, reps):
-    for _ in range(5):
-        fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(iters):
-            fn()
-        b.record()
-        torch.cuda.synchronize()
-        out.append(a.elapsed_time(b) / iters * 1e3)                  # microseconds
-    return float(np.median(out)), float(min(out)), float(max(out))
 
 
 def main():
@@ -168,16 +112,12 @@ def main():
         rec = {"case": name, "S": S, "B": c["B"], "labelled": c["n_l"], "K": c["K"], "F": c["F"], "C": c["C"], "loss": c["kind"],
                "tem": TEM, "iters": a.iters, "reps": a.reps}
         for key in ("ours_objective", "ref_objective", "ours_step", "ref_step"):
-            med, lo, hi = timed(v[key], a.iters, a.reps)
+            med, lo, hi = timed(v[key], a.iters, a.reps, warmup=5)
             rec[key + "_us"] = round(med, 1)
             rec[key + "_us_range"] = [round(lo, 1), round(hi, 1)]
         rec["objective_speedup"] = round(rec["ref_objective_us"] / rec["ours_objective_us"], 2)
         rec["step_speedup"] = round(rec["ref_step_us"] / rec["ours_step_us"], 2)
-        line = json.dumps(rec)
-        print(line, flush=True)
-        if a.out:
-            with open(a.out, "a") as f:
-                f.write(line + "\n")
+        emit(rec, a.out)
 
 
 if __name__ == "__main__":

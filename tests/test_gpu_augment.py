@@ -4,6 +4,8 @@ different order -> |d| <= 2e-5 * (|ref| + 1e-6)."""
 import numpy as np
 import pytest
 
+from augment_cases import rows_to_coo
+
 pytestmark = pytest.mark.gpu
 
 RTOL, ATOL = 2e-5, 2e-7
@@ -20,19 +22,6 @@ def _case(S=300, K=32, N=5000, F=128, seed=0, ragged=True):
     return col, val, filled, X
 
 
-def _flatten(col, val, filled, X, rows):
-    """What the reference's caller builds on the host (model.py:310-316)."""
-    import torch
-    idx, cols, sc = [], [], []
-    for b, r in enumerate(rows.tolist()):
-        n = int(filled[r])
-        idx += [b] * n; cols += col[r, :n].tolist(); sc += val[r, :n].tolist()
-    mat_idx = torch.tensor(idx, dtype=torch.int64)
-    scores = torch.tensor(sc, dtype=torch.float64).to(torch.float32)        # model.py:314
-    feats = X[torch.tensor(cols, dtype=torch.int64)]                        # model.py:313
-    return feats, scores, mat_idx
-
-
 @pytest.mark.parametrize("F", [128, 602, 1433, 7])          # vector path, Reddit, Cora (odd), tiny
 @pytest.mark.parametrize("training", [False, True])
 def test_rows_and_coo_match_reference(F, training):
@@ -43,7 +32,8 @@ def test_rows_and_coo_match_reference(F, training):
     S, K = col.shape
     rows = torch.randperm(S)[:150].to(torch.int32)
     p = 0.5
-    feats, scores, mat_idx = _flatten(col, val, filled, X, rows)
+    mat_idx, cols, scores, _ = rows_to_coo(col, val, filled, K, rows)
+    feats = X[cols]                                                         # model.py:313
     keep_flat = (torch.rand(scores.shape) >= p).to(torch.uint8)
     ref = random_prop_ref(feats, scores, mat_idx, p, training, keep_flat)
     # reference-shaped entry point

@@ -8,6 +8,9 @@ import ctypes
 import numpy as np
 import pytest
 
+from augment_cases import close
+from oracle.objective_ref import consis_loss_ref
+
 pytestmark = pytest.mark.gpu
 
 
@@ -22,12 +25,6 @@ def emb_ref(W, attr_idx, node_idx, attr_data, p, training, keep):
     num = torch.zeros((n_out, W.shape[1]), dtype=fe.dtype).index_add_(0, node_idx, fe * d[:, None])
     den = torch.zeros((n_out, 1), dtype=fe.dtype).index_add_(0, node_idx, d[:, None])
     return num / (den + 1e-10)
-
-
-def _close(got, ref, terms):
-    got, ref, terms = got.double().cpu(), ref.double().cpu(), terms.double().cpu()
-    bad = (got - ref).abs() > 1e-5 * terms + 1e-7
-    assert not bool(bad.any()), f"{int(bad.sum())} elements off; max |d| {float((got - ref).abs().max()):.3e}"
 
 
 def _bags(V, n_out, seed, max_len=12):
@@ -63,9 +60,9 @@ def _check_layer(W, attr_idx, node_idx, attr_data, p, training, keep, G):
     out = embedding_bag(Wc, attr_idx.cuda(), node_idx.cuda(), attr_data.cuda(), input_droprate=p, training=training,
                         keep=keep.reshape(-1).cuda() if keep is not None else None)
     assert out.shape == ref.shape and out.grad_fn is not None
-    _close(out, ref.detach(), terms.detach())
+    close(out, ref.detach(), terms.detach())
     out.backward(G.cuda())
-    _close(Wc.grad[uniq.cuda()], ws.grad, wa.grad)
+    close(Wc.grad[uniq.cuda()], ws.grad, wa.grad)
     rest = torch.ones(W.shape[0], dtype=torch.bool, device="cuda"); rest[uniq.cuda()] = False
     assert torch.count_nonzero(Wc.grad[rest]) == 0                              # rows no bag names are untouched
     return out
@@ -144,7 +141,7 @@ def test_csr_form_equals_coo_form_bitwise():
                   torch.from_numpy(A.data), 0.0, False, None)
     terms = emb_ref(W.double().abs().cpu(), torch.from_numpy(attr_idx.astype(np.int64)), torch.from_numpy(node_idx.astype(np.int64)),
                     torch.from_numpy(A.data), 0.0, False, None)
-    _close(ev[:ref.shape[0]], ref, terms)
+    close(ev[:ref.shape[0]], ref, terms)
 
 
 def test_out_of_range_ids():
@@ -189,18 +186,6 @@ def test_out_of_range_ids():
     assert torch.count_nonzero(Wr.grad.sum(1)) == 3
 
 
-def _consis_l2(logps, tem, conf):
-    """consis_loss(args.loss == 'l2') of model_mag.py:125-142."""
-    import torch
-    ps = [torch.exp(p) for p in logps]
-    avg_p = sum(ps) / len(ps)
-    sharp_p = (torch.pow(avg_p, 1. / tem) / torch.sum(torch.pow(avg_p, 1. / tem), dim=1, keepdim=True)).detach()
-    loss = 0.
-    for p in ps:
-        loss = loss + torch.mean((p - sharp_p).pow(2).sum(1)[avg_p.max(1)[0] > conf])
-    return loss / len(ps)
-
-
 def test_mag_shaped_training_step_end_to_end():
     import torch
     import torch.nn.functional as Fn
@@ -239,7 +224,7 @@ def test_mag_shaped_training_step_end_to_end():
         logp = torch.log_softmax(fc(Fn.relu(aug)), dim=-1)
         outs.append(logp[n_train:])
         loss = loss + Fn.nll_loss(logp[:n_train], labels.cuda())
-    loss = loss / 2 + 1.0 * _consis_l2(outs, 0.5, 0.0)
+    loss = loss / 2 + 1.0 * consis_loss_ref(outs, 0.5, 0.0, "l2")
     loss.backward()
 
     # the restated pure-torch pipeline in float64 under the same masks (reference order: csr rows, nonzero)
@@ -257,7 +242,7 @@ def test_mag_shaped_training_step_end_to_end():
         logp = torch.log_softmax(Fn.relu(aug) @ fw.t() + fb, dim=-1)
         outs_r.append(logp[n_train:])
         loss_r = loss_r + Fn.nll_loss(logp[:n_train], labels)
-    loss_r = loss_r / 2 + 1.0 * _consis_l2(outs_r, 0.5, 0.0)
+    loss_r = loss_r / 2 + 1.0 * consis_loss_ref(outs_r, 0.5, 0.0, "l2")
     loss_r.backward()
 
     assert abs(loss.item() - loss_r.item()) <= 1e-5 * abs(loss_r.item()) + 1e-7

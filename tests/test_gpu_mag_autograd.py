@@ -5,41 +5,9 @@ import ctypes
 
 import pytest
 
+from augment_cases import close, ragged_coo, ref_grad, rows_case, rows_to_coo
+
 pytestmark = pytest.mark.gpu
-
-
-def _close(got, ref, terms):
-    import torch
-    got, ref, terms = got.double().cpu(), ref.double().cpu(), terms.double().cpu()
-    bad = (got - ref).abs() > 1e-5 * terms + 1e-7
-    assert not bool(bad.any()), f"{int(bad.sum())} elements off; max |d| {float((got - ref).abs().max()):.3e}"
-
-
-def _ragged_coo(F, seed, n_out=60, long_row=True):
-    """Sorted segment ids with empty output rows in the middle and (optionally) one segment longer than the
-    kernels' 1 024-entry LDS stage."""
-    import torch
-    g = torch.Generator().manual_seed(seed)
-    lens = torch.randint(0, 40, (n_out,), generator=g)
-    lens[3] = 0; lens[4] = 0; lens[17] = 0; lens[-1] = 5
-    if long_row:
-        lens[10] = 1100
-    idx = torch.repeat_interleave(torch.arange(n_out), lens)
-    M = idx.numel()
-    feats = torch.randn((M, F), generator=g, dtype=torch.float64)
-    scores = (torch.rand((M,), generator=g, dtype=torch.float64) ** 2 + 1e-6).float()
-    return feats, scores, idx, g
-
-
-def _ref_grad(feats64, scores, idx, p, training, keep, G64):
-    from oracle.random_prop_ref import random_prop_ref
-    x = feats64.clone().requires_grad_(True)
-    out = random_prop_ref(x, scores.double(), idx, p, training, keep)
-    (out * G64).sum().backward()
-    xa = feats64.abs().clone().requires_grad_(True)
-    outa = random_prop_ref(xa, scores.double().abs(), idx, p, training, keep)
-    (outa * G64.abs()).sum().backward()
-    return out.detach(), x.grad, xa.grad
 
 
 @pytest.mark.parametrize("F", [7, 64, 602])
@@ -48,17 +16,17 @@ def _ref_grad(feats64, scores, idx, p, training, keep, G64):
 def test_coo_backward_matches_reference_gradient(F, training, p):
     import torch
     from grand_plus_amd.augment import random_prop
-    feats64, scores, idx, g = _ragged_coo(F, seed=F * 7 + int(p * 10) + training)
+    feats64, scores, idx, g = ragged_coo(F, seed=F * 7 + int(p * 10) + training, n_out=60, dtype=torch.float64)
     keep = (torch.rand(scores.shape, generator=g) >= p).to(torch.uint8)
     n_out = int(idx[-1]) + 1
     G = torch.randn((n_out, F), generator=g, dtype=torch.float32)
-    ref_out, ref_grad, terms = _ref_grad(feats64, scores, idx, p, training, keep, G.double())
+    ref, terms = ref_grad(feats64, scores, idx, p, training, keep, G)
     x = feats64.float().cuda().requires_grad_(True)
     out = random_prop(x, scores.cuda(), idx.cuda(), p, training=training, keep=keep.cuda())
     assert out.grad_fn is not None
     out.backward(G.cuda())
     assert x.grad.shape == (idx.numel(), F)
-    _close(x.grad, ref_grad, terms)
+    close(x.grad, ref, terms)
     if training and p == 1.0:
         assert torch.count_nonzero(x.grad) == 0
     # dropped entries get exact zeros
@@ -66,50 +34,26 @@ def test_coo_backward_matches_reference_gradient(F, training, p):
         assert torch.count_nonzero(x.grad.cpu()[keep == 0]) == 0
 
 
-def _rows_case(seed=0, S=120, K=32, N=3000, F=64):
-    import torch
-    g = torch.Generator().manual_seed(seed)
-    col = torch.randint(0, N, (S, K), generator=g, dtype=torch.int32)
-    col[:, 0] = 7                                   # node 7 in every row ...
-    col[5, 9] = 7                                   # ... and twice in row 5
-    col[11, 3] = col[11, 20] = 42                   # another node twice in one row
-    val = torch.rand((S, K), generator=g, dtype=torch.float64) ** 3 + 1e-9
-    filled = torch.randint(1, K + 1, (S,), generator=g, dtype=torch.int32)
-    filled[5] = K; filled[11] = K
-    X = torch.randn((N, F), generator=g, dtype=torch.float32)
-    return col, val, filled, X, g
-
-
 @pytest.mark.parametrize("F", [7, 64, 602])
 @pytest.mark.parametrize("training", [False, True])
 def test_rows_backward_matches_reference_gradient(F, training):
     import torch
     from grand_plus_amd.augment import random_prop_rows
-    from oracle.random_prop_ref import random_prop_ref
-    col, val, filled, X, g = _rows_case(seed=F, F=F)
+    col, val, filled, X, g = rows_case(seed=F, F=F, second_duplicate=True)
     S, K = col.shape
     rows = torch.randperm(S, generator=g)[:90].to(torch.int32)
     rows[:2] = torch.tensor([5, 11], dtype=torch.int32)
     p = 0.5
     keep_rows = (torch.rand((S, K), generator=g) >= p).to(torch.uint8)
     keep_rows[5, 0] = keep_rows[5, 9] = 1
-    # the flattened (reference) form of the same batch and mask
-    idx, cols, sc, kp = [], [], [], []
-    for b, r in enumerate(rows.tolist()):
-        n = int(filled[r])
-        idx += [b] * n; cols += col[r, :n].tolist(); sc += val[r, :n].tolist(); kp += keep_rows[r, :n].tolist()
-    idx = torch.tensor(idx); cols = torch.tensor(cols, dtype=torch.int64)
-    scores = torch.tensor(sc, dtype=torch.float64).float(); kp = torch.tensor(kp, dtype=torch.uint8)
+    idx, cols, scores, kp = rows_to_coo(col, val, filled, K, rows, keep_rows)   # the reference's form of the same batch and mask
     G = torch.randn((rows.numel(), F), generator=g)
-    X64 = X.double().requires_grad_(True)
-    (random_prop_ref(X64[cols], scores.double(), idx, p, training, kp) * G.double()).sum().backward()
-    Xa = X.double().abs().requires_grad_(True)
-    (random_prop_ref(Xa[cols], scores.double(), idx, p, training, kp) * G.double().abs()).sum().backward()
+    ref, terms = ref_grad(X, scores, idx, p, training, kp[0], G, cols=cols)
     x = X.cuda().requires_grad_(True)
     out = random_prop_rows(x, col.reshape(-1).cuda(), val.reshape(-1).cuda(), filled.cuda(), K, batch_rows=rows.cuda(),
                            dropnode_rate=p, training=training, keep=keep_rows.reshape(-1).cuda())
     out.backward(G.cuda())
-    _close(x.grad, X64.grad, Xa.grad)
+    close(x.grad, ref, terms)
     assert float(x.grad[7].abs().sum()) > 0
 
 
@@ -118,7 +62,7 @@ def test_internal_rng_mask_is_the_forwards_mask():
     the internal-RNG forward bitwise.  The same for the fused form, whose rows here hold distinct nodes."""
     import torch
     from grand_plus_amd.augment import random_prop, random_prop_rows
-    feats64, scores, idx, g = _ragged_coo(64, seed=3)
+    feats64, scores, idx, g = ragged_coo(64, seed=3, n_out=60, dtype=torch.float64)
     x = feats64.float().cuda().requires_grad_(True)
     sc, ic = scores.cuda(), idx.cuda()
     out = random_prop(x, sc, ic, 0.5, training=True, seed=1234)
@@ -148,7 +92,7 @@ def test_nothing_changes_without_grad():
     import torch
     from grand_plus_amd import _native
     from grand_plus_amd.augment import random_prop, random_prop_rows
-    feats64, scores, idx, g = _ragged_coo(96, seed=5, long_row=False)
+    feats64, scores, idx, g = ragged_coo(96, seed=5, n_out=60, dtype=torch.float64, long_row=False)
     f, sc, ic = feats64.float().cuda(), scores.cuda(), idx.cuda()
     n_out = int(idx[-1]) + 1
     direct = torch.empty((n_out, 96), device="cuda")
@@ -165,7 +109,7 @@ def test_nothing_changes_without_grad():
     assert torch.equal(a, direct) and torch.equal(b, direct) and torch.equal(c.detach(), direct)
     assert c.grad_fn is not None
     # fused form
-    col, val, filled, X, g = _rows_case(seed=9)
+    col, val, filled, X, g = rows_case(seed=9, second_duplicate=True)
     S, K = col.shape
     Xc, cc, vc, fc = X.cuda(), col.reshape(-1).cuda(), val.reshape(-1).cuda(), filled.cuda()
     rows = torch.arange(0, S, 3, dtype=torch.int32).cuda()

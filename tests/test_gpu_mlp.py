@@ -1,9 +1,13 @@
-"""The S-sample MLP block against a float64 restatement, kept in this file, of the reference's MLP.forward
+"""The S-sample MLP block against the float64 restatement in oracle/mlp_ref.py of the reference's MLP.forward
 (model.py:48-66 and model_mag.py:57-67) through torch autograd with F.batch_norm and the same keep masks, one call per
 sample as the reference makes.  Tolerances in the style of §7e: outputs within 2e-5 * sum|a*w| (+1e-6) of the
 last layer, gradients within 1e-4 of the largest reference entry."""
 import numpy as np
 import pytest
+
+from augment_cases import rows_to_coo
+from oracle.mlp_ref import RefMagMLP, RefMLP
+from oracle.objective_ref import grand_loss_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -22,101 +26,11 @@ CASES = [
 ]
 
 
-def _ref_classes():
-    import torch
-    import torch.nn as nn
-    import torch.nn.functional as Fn
-
-    def normalize(x):
-        return x / (1e-12 + torch.norm(x, p=2, dim=-1, keepdim=True))
-
-    def drop(x, p, keep):
-        if keep is None or p == 0:
-            return x
-        return x * keep.to(x.dtype) / (1.0 - p) if p < 1 else x * 0.0
-
-    def bn_f(bn, x, training):
-        return Fn.batch_norm(x, bn.running_mean, bn.running_var, bn.weight, bn.bias, training, bn.momentum, bn.eps)
-
-    class RefMLP(nn.Module):
-        """model.py's MLP (constructor and forward), dropout by explicit masks."""
-
-        def __init__(self, num_features, num_classes, hidden_size, nlayers, use_bn, input_dropout, hidden_dropout, node_norm):
-            super().__init__()
-            if nlayers == 1:
-                fcs, bns = [nn.Linear(num_features, num_classes)], [nn.BatchNorm1d(num_features)]
-            else:
-                fcs, bns = [nn.Linear(num_features, hidden_size)], [nn.BatchNorm1d(num_features)]
-                for _ in range(nlayers - 2):
-                    fcs.append(nn.Linear(hidden_size, hidden_size))
-                    bns.append(nn.BatchNorm1d(hidden_size))
-                bns.append(nn.BatchNorm1d(hidden_size))
-                fcs.append(nn.Linear(hidden_size, num_classes))
-            self.fcs, self.bns = nn.ModuleList(fcs), nn.ModuleList(bns)
-            self.input_droprate, self.hidden_droprate = input_dropout, hidden_dropout
-            self.use_bn, self.node_norm = use_bn, node_norm
-
-        def forward(self, X, keeps):
-            if self.node_norm:
-                X = normalize(X).detach()
-            if self.use_bn:
-                X = bn_f(self.bns[0], X, self.training)
-            embs = drop(X, self.input_droprate, keeps[0] if self.training else None)
-            self.last_a = embs
-            embs = self.fcs[0](embs)
-            for i, (fc, bn) in enumerate(zip(self.fcs[1:], self.bns[1:])):
-                embs = Fn.relu(embs)
-                if self.node_norm:
-                    embs = normalize(embs)
-                if self.use_bn:
-                    embs = bn_f(bn, embs, self.training)
-                embs = drop(embs, self.hidden_droprate, keeps[i + 1] if self.training else None)
-                self.last_a = embs
-                embs = fc(embs)
-            return embs
-
-    class RefMagMLP(nn.Module):
-        """model_mag.py's MLP (constructor and forward)."""
-
-        def __init__(self, num_features, num_classes, hidden_size, nlayers, use_bn, input_dropout, hidden_dropout, node_norm):
-            super().__init__()
-            if nlayers == 1:
-                self.embeds = nn.Embedding(num_features, num_classes)
-                self.fcs, self.bns = nn.ModuleList([]), nn.ModuleList([])
-            else:
-                self.embeds = nn.Embedding(num_features, hidden_size)
-                fcs, bns = [], []
-                for _ in range(nlayers - 2):
-                    fcs.append(nn.Linear(hidden_size, hidden_size))
-                    bns.append(nn.BatchNorm1d(hidden_size))
-                bns.append(nn.BatchNorm1d(hidden_size))
-                fcs.append(nn.Linear(hidden_size, num_classes))
-                self.fcs, self.bns = nn.ModuleList(fcs), nn.ModuleList(bns)
-            self.input_droprate, self.hidden_droprate = input_dropout, hidden_dropout
-            self.use_bn, self.node_norm = use_bn, node_norm
-
-        def forward(self, X, keeps):
-            embs = X
-            for i, (fc, bn) in enumerate(zip(self.fcs, self.bns)):
-                embs = Fn.relu(embs)
-                if self.node_norm:
-                    embs = normalize(embs)
-                if self.use_bn:
-                    embs = bn_f(bn, embs, self.training)
-                embs = drop(embs, self.hidden_droprate, keeps[i] if self.training else None)
-                self.last_a = embs
-                embs = fc(embs)
-            return embs
-
-    return RefMLP, RefMagMLP
-
-
 def _pair(case, seed=0):
     """(ours on cuda, the restatement in float64 on cuda), same parameters and running statistics."""
     import torch
     from grand_plus_amd.mlp import GrandPlusMLP, MagMLP
     _, layout, F, H, C, nl, bn, norm, pin, phid, _B = case
-    RefMLP, RefMagMLP = _ref_classes()
     torch.manual_seed(seed)
     ours = (GrandPlusMLP if layout == "model" else MagMLP)(F, C, H, nl, bn, pin, phid, norm)
     g = torch.Generator().manual_seed(seed + 1)
@@ -321,7 +235,6 @@ def test_dropout_edges_p0_p1_and_no_bn():
 
 def test_state_dict_round_trips_with_the_restatement():
     import torch
-    RefMLP, RefMagMLP = _ref_classes()
     from grand_plus_amd.mlp import GrandPlusMLP, MagMLP
     for ours_cls, ref_cls in ((GrandPlusMLP, RefMLP), (MagMLP, RefMagMLP)):
         for nl in (1, 2, 3):
@@ -362,21 +275,6 @@ def test_forward_and_backward_do_not_synchronise():
 
 
 # ---- steps end to end
-def _grand_loss_ref(z, labels, n_l, w, tem, conf):
-    """model.py:321-331 with args.loss = l2 on the S logit tensors z[s]."""
-    import torch
-    import torch.nn.functional as Fn
-    S = z.shape[0]
-    lps = [torch.log_softmax(z[s], -1) for s in range(S)]
-    sup = sum(Fn.nll_loss(lp[:n_l], labels) for lp in lps) / S
-    ps = [lp[n_l:].exp() for lp in lps]
-    avg = sum(ps) / S
-    sharp = (avg.pow(1 / tem) / avg.pow(1 / tem).sum(1, keepdim=True)).detach()
-    mask = avg.max(1)[0] > conf
-    con = sum(torch.mean((p - sharp).pow(2).sum(1)[mask]) for p in ps) / S
-    return sup + w * con
-
-
 def _check_params(ours, ref):
     for (name, p), (_, q) in zip(ours.named_parameters(), ref.named_parameters()):
         if q.grad is None:
@@ -421,20 +319,10 @@ def test_training_step_end_to_end(shape):
     loss, _ = grand_plus_loss(ours(aug, keep=keeps), labels.cuda(), n_l, w, tem=tem, conf=0.0, kind="l2")
     loss.backward()
 
-    col, val, filled = rm.col.cpu().reshape(len(seeds), K), rm.val.cpu().reshape(len(seeds), K), rm.filled.cpu()
-    idx, cols, sc = [], [], []
-    kp = [[] for _ in range(S)]
-    for b, r in enumerate(rows.cpu().tolist()):
-        m = int(filled[r])
-        idx += [b] * m; cols += col[r, :m].tolist(); sc += val[r, :m].tolist()
-        for s in range(S):
-            kp[s] += keep[s, r * K:r * K + m].tolist()
-    idx = torch.tensor(idx); cols = torch.tensor(cols, dtype=torch.int64)
-    scores = torch.tensor(sc, dtype=torch.float64).float().double()
-    aug_r = torch.stack([random_prop_ref(X.double()[cols], scores, idx, p_node, True, torch.tensor(kp[s], dtype=torch.uint8))
-                         for s in range(S)]).cuda()
+    idx, cols, scores, kp = rows_to_coo(rm.col.cpu(), rm.val.cpu(), rm.filled.cpu(), K, rows.cpu(), keep)
+    aug_r = torch.stack([random_prop_ref(X.double()[cols], scores.double(), idx, p_node, True, kp[s]) for s in range(S)]).cuda()
     z_ref, _ = _run_ref(ref, aug_r, keeps)
-    loss_r = _grand_loss_ref(z_ref, labels.cuda(), n_l, w, tem, 0.0)          # every unlabelled row in the consistency term
+    loss_r, _, _ = grand_loss_ref(z_ref, labels.cuda(), n_l, w, tem, 0.0, "l2")   # every unlabelled row in the consistency term
     loss_r.backward()
     assert abs(float(loss) - float(loss_r)) <= 1e-4 * abs(float(loss_r)) + 1e-6, (float(loss), float(loss_r))
     _check_params(ours, ref)
@@ -466,7 +354,6 @@ def test_mag_shaped_step_through_magmlp_reaches_the_embedding_table():
     dt = torch.from_numpy(A.data).cuda()
     torch.manual_seed(0)
     ours = MagMLP(V, C, H, 2, False, 0.0, 0.2, False)
-    _, RefMagMLP = _ref_classes()
     ref = RefMagMLP(V, C, H, 2, False, 0.0, 0.2, False)
     ref.load_state_dict(ours.state_dict())
     ours.cuda().train(); ref.double().cuda().train()
@@ -495,7 +382,7 @@ def test_mag_shaped_step_through_magmlp_reaches_the_embedding_table():
     emb_r = num / (den + 1e-10)                                                  # MLP.emb, model_mag.py:48-55 (no dropout)
     aug_r = torch.stack([random_prop_ref(emb_r, scores.double(), mat_idx, p_node, True, keep[s].cuda()) for s in range(S)])
     z_ref, _ = _run_ref(ref, aug_r, keeps)
-    loss_r = _grand_loss_ref(z_ref, labels.cuda(), n_train, 1.0, 0.5, 0.0)
+    loss_r, _, _ = grand_loss_ref(z_ref, labels.cuda(), n_train, 1.0, 0.5, 0.0, "l2")
     loss_r.backward()
     assert abs(float(loss) - float(loss_r)) <= 1e-4 * abs(float(loss_r)) + 1e-6
     assert float(ours.embeds.weight.grad.abs().max()) > 0

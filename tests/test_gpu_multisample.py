@@ -4,28 +4,9 @@ oracle.random_prop_ref summed over the samples under the same masks.  Tolerance 
 |d| <= 1e-5 * sum|terms| + 1e-7, sum|terms| = the same gradient with every operand replaced by its magnitude."""
 import pytest
 
+from augment_cases import close, ragged_coo, ref_grad, rows_case, rows_to_coo
+
 pytestmark = pytest.mark.gpu
-
-
-def _close(got, ref, terms):
-    got, ref, terms = got.double().cpu(), ref.double().cpu(), terms.double().cpu()
-    bad = (got - ref).abs() > 1e-5 * terms + 1e-7
-    assert not bool(bad.any()), f"{int(bad.sum())} elements off; max |d| {float((got - ref).abs().max()):.3e}"
-
-
-def _ragged_coo(F, seed, n_out=50, long_row=True):
-    """Sorted segment ids with empty rows in the middle and (optionally) one segment above the 1 024-entry stage."""
-    import torch
-    g = torch.Generator().manual_seed(seed)
-    lens = torch.randint(0, 40, (n_out,), generator=g)
-    lens[3] = 0; lens[4] = 0; lens[17] = 0; lens[-1] = 5
-    if long_row:
-        lens[10] = 1100
-    idx = torch.repeat_interleave(torch.arange(n_out), lens)
-    M = idx.numel()
-    feats = torch.randn((M, F), generator=g, dtype=torch.float32)
-    scores = torch.rand((M,), generator=g) ** 2 + 1e-6
-    return feats, scores, idx, g
 
 
 def _coo_multi(feats, scores, idx, n_out, S, p, training, seed=None, keep=None):
@@ -45,7 +26,7 @@ def _coo_multi(feats, scores, idx, n_out, S, p, training, seed=None, keep=None):
 def test_coo_multi_equals_single_calls_bitwise(F, S, p):
     import torch
     from grand_plus_amd.augment import random_prop, sample_seed
-    feats, scores, idx, g = _ragged_coo(F, seed=F + 100 * S + int(10 * p))
+    feats, scores, idx, g = ragged_coo(F, seed=F + 100 * S + int(10 * p), n_out=50)
     f, sc, ix = feats.cuda(), scores.cuda(), idx.cuda()
     n_out = int(idx[-1]) + 1
     seed = 0x1234567 + F * S
@@ -65,26 +46,13 @@ def test_coo_multi_equals_single_calls_bitwise(F, S, p):
             assert torch.equal(out[s], one)
 
 
-def _rows_case(seed=0, S_rows=120, K=32, N=3000, F=64):
-    import torch
-    g = torch.Generator().manual_seed(seed)
-    col = torch.randint(0, N, (S_rows, K), generator=g, dtype=torch.int32)
-    col[:, 0] = 7
-    col[5, 9] = 7
-    val = torch.rand((S_rows, K), generator=g, dtype=torch.float64) ** 3 + 1e-9
-    filled = torch.randint(1, K + 1, (S_rows,), generator=g, dtype=torch.int32)
-    filled[5] = K; filled[8] = 0                                                   # a full row and an empty one
-    X = torch.randn((N, F), generator=g, dtype=torch.float32)
-    return col, val, filled, X, g
-
-
 @pytest.mark.parametrize("F", [7, 128, 602])
 @pytest.mark.parametrize("S", [1, 2, 3, 16])
 @pytest.mark.parametrize("p", [0.0, 0.5, 1.0])
 def test_rows_multi_equals_single_calls_bitwise(F, S, p):
     import torch
     from grand_plus_amd import augment
-    col, val, filled, X, g = _rows_case(seed=F + S, F=F)
+    col, val, filled, X, g = rows_case(seed=F + S, F=F, empty_row=8)
     S_rows, K = col.shape
     rows = torch.randperm(S_rows, generator=g)[:90].to(torch.int32)
     rows[:2] = torch.tensor([5, 8], dtype=torch.int32)
@@ -117,17 +85,6 @@ def test_rows_multi_equals_single_calls_bitwise(F, S, p):
             assert torch.equal(out[s], one)
 
 
-def _ref_multi_grad(feats64, scores, idx, p, training, keeps, G64):
-    """sum_s <random_prop_ref(feats, mask s), G[s]> through autograd, and the same with magnitudes."""
-    from oracle.random_prop_ref import random_prop_ref
-    x = feats64.clone().requires_grad_(True)
-    xa = feats64.abs().clone().requires_grad_(True)
-    for s in range(G64.shape[0]):
-        (random_prop_ref(x, scores.double(), idx, p, training, keeps[s]) * G64[s]).sum().backward()
-        (random_prop_ref(xa, scores.double().abs(), idx, p, training, keeps[s]) * G64[s].abs()).sum().backward()
-    return x.grad, xa.grad
-
-
 @pytest.mark.parametrize("F", [7, 128, 602])
 @pytest.mark.parametrize("S", [2, 3, 16])
 @pytest.mark.parametrize("training", [False, True])
@@ -135,16 +92,16 @@ def test_coo_multi_backward_matches_reference_gradient(F, S, training):
     import torch
     from grand_plus_amd.augment import random_prop
     p = 0.5
-    feats, scores, idx, g = _ragged_coo(F, seed=3 * F + S + training)
+    feats, scores, idx, g = ragged_coo(F, seed=3 * F + S + training, n_out=50)
     keep = (torch.rand((S, idx.numel()), generator=g) >= p).to(torch.uint8)
     n_out = int(idx[-1]) + 1
     G = torch.randn((S, n_out, F), generator=g)
-    ref, terms = _ref_multi_grad(feats.double(), scores, idx, p, training, keep, G.double())
+    ref, terms = ref_grad(feats, scores, idx, p, training, keep, G)
     x = feats.cuda().requires_grad_(True)
     out = random_prop(x, scores.cuda(), idx.cuda(), p, training=training, keep=keep.cuda(), samples=S)
     assert out.grad_fn is not None
     out.backward(G.cuda())
-    _close(x.grad, ref, terms)
+    close(x.grad, ref, terms)
     if training:                                                                  # dropped in every sample: exact zeros
         assert torch.count_nonzero(x.grad.cpu()[(keep == 0).all(0)]) == 0
 
@@ -155,41 +112,27 @@ def test_coo_multi_backward_matches_reference_gradient(F, S, training):
 def test_rows_multi_backward_matches_reference_gradient(F, S, training):
     import torch
     from grand_plus_amd.augment import random_prop_rows
-    col, val, filled, X, g = _rows_case(seed=5 * F + S, F=F)
+    col, val, filled, X, g = rows_case(seed=5 * F + S, F=F, empty_row=8)
     S_rows, K = col.shape
     rows = torch.randperm(S_rows, generator=g)[:90].to(torch.int32)
     rows[:2] = torch.tensor([5, 8], dtype=torch.int32)
     p = 0.5
     keep = (torch.rand((S, S_rows, K), generator=g) >= p).to(torch.uint8)
-    idx, cols, sc, kp = [], [], [], [[] for _ in range(S)]
-    for b, r in enumerate(rows.tolist()):
-        n = int(filled[r])
-        idx += [b] * n; cols += col[r, :n].tolist(); sc += val[r, :n].tolist()
-        for s in range(S):
-            kp[s] += keep[s, r, :n].tolist()
-    idx = torch.tensor(idx); cols = torch.tensor(cols, dtype=torch.int64)
-    scores = torch.tensor(sc, dtype=torch.float64).float()
-    kp = torch.tensor(kp, dtype=torch.uint8)
-    n_out = int(idx[-1]) + 1
+    idx, cols, scores, kp = rows_to_coo(col, val, filled, K, rows, keep)
     G = torch.randn((S, rows.numel(), F), generator=g)
-    X64 = X.double().requires_grad_(True)
-    Xa = X.double().abs().requires_grad_(True)
-    from oracle.random_prop_ref import random_prop_ref
-    for s in range(S):
-        (random_prop_ref(X64[cols], scores.double(), idx, p, training, kp[s]) * G[s, :n_out].double()).sum().backward()
-        (random_prop_ref(Xa[cols], scores.double(), idx, p, training, kp[s]) * G[s, :n_out].double().abs()).sum().backward()
+    ref, terms = ref_grad(X, scores, idx, p, training, kp, G, cols=cols)
     x = X.cuda().requires_grad_(True)
     out = random_prop_rows(x, col.reshape(-1).cuda(), val.reshape(-1).cuda(), filled.cuda(), K, batch_rows=rows.cuda(),
                            dropnode_rate=p, training=training, keep=keep.reshape(S, -1).cuda(), samples=S)
     out.backward(G.cuda())
-    _close(x.grad, X64.grad, Xa.grad)
+    close(x.grad, ref, terms)
     assert float(x.grad[7].abs().sum()) > 0
 
 
 def test_coo_multi_with_n_out_needs_no_host_synchronisation():
     import torch
     from grand_plus_amd.augment import random_prop
-    feats, scores, idx, g = _ragged_coo(64, seed=11, long_row=False)
+    feats, scores, idx, g = ragged_coo(64, seed=11, n_out=50, long_row=False)
     n_out = int(idx[-1]) + 1
     x = feats.cuda().requires_grad_(True)
     sc, ix = scores.cuda(), idx.cuda()

@@ -1,4 +1,4 @@
-"""The fused GRAND+ objective against a float64 restatement of the reference kept in this file:
+"""The fused GRAND+ objective against the float64 restatement of the reference in oracle/objective_ref.py:
 log_softmax + F.nll_loss per sample (model.py:323-327) and consis_loss (model.py:123-139), through autograd.
 Tolerances: the loss within 1e-5 |ref| + 1e-7; dz per element within 1e-5 max|ref row| + 1e-7.  Ends with two
 training steps end to end: a Cora-shaped one with BatchNorm and the MAG-shaped one of test_gpu_embedding.py, both
@@ -8,40 +8,10 @@ import math
 import numpy as np
 import pytest
 
+from augment_cases import rows_to_coo
+from oracle.objective_ref import consis_loss_ref, grand_loss_ref
+
 pytestmark = pytest.mark.gpu
-
-
-def consis_loss_ref(logps, tem, conf, kind):
-    """consis_loss of model.py:123-139, args.loss = kind."""
-    import torch
-    ps = [torch.exp(p) for p in logps]
-    sum_p = 0.
-    for p in ps:
-        sum_p = sum_p + p
-    avg_p = sum_p / len(ps)
-    sharp_p = (torch.pow(avg_p, 1. / tem) / torch.sum(torch.pow(avg_p, 1. / tem), dim=1, keepdim=True)).detach()
-    loss = 0.
-    for p in ps:
-        if kind == "kl":
-            loss += torch.mean((-sharp_p * torch.log(p)).sum(1)[avg_p.max(1)[0] > conf])
-        else:
-            loss += torch.mean((p - sharp_p).pow(2).sum(1)[avg_p.max(1)[0] > conf])
-    return loss / len(ps)
-
-
-def grand_loss_ref(z, labels, n_l, w, tem, conf, kind, ignore_index=-100):
-    """model.py:321-329 on the S logit tensors z[s] (any dtype): (loss, L_sup, L_con)."""
-    import torch
-    import torch.nn.functional as Fn
-    S = z.shape[0]
-    outs, sup = [], 0.
-    for s in range(S):
-        lp = torch.log_softmax(z[s], dim=-1)
-        outs.append(lp[n_l:])
-        sup = sup + Fn.nll_loss(lp[:n_l], labels[:n_l], ignore_index=ignore_index)
-    sup = sup / S
-    con = consis_loss_ref(outs, tem, conf, kind)
-    return sup + w * con, sup, con
 
 
 def _logits(S, B, C, seed, scale=3.0):
@@ -261,20 +231,9 @@ def test_cora_shaped_training_step_end_to_end():
     loss.backward()
 
     # float64 reference under the same masks: the flattened rows of the batch (model.py:310-316)
-    col, val, filled = rm.col.cpu().reshape(S_rows, K), rm.val.cpu().reshape(S_rows, K), rm.filled.cpu()
-    rws = rows.cpu().tolist()
-    idx, cols, sc = [], [], []
-    kp = [[] for _ in range(S)]
-    for b, r in enumerate(rws):
-        m = int(filled[r])
-        idx += [b] * m; cols += col[r, :m].tolist(); sc += val[r, :m].tolist()
-        for s in range(S):
-            kp[s] += keep[s, r * K:r * K + m].tolist()
-    idx = torch.tensor(idx); cols = torch.tensor(cols, dtype=torch.int64)
-    scores = torch.tensor(sc, dtype=torch.float64).float().double()
+    idx, cols, scores, kp = rows_to_coo(rm.col.cpu(), rm.val.cpu(), rm.filled.cpu(), K, rows.cpu(), keep)
     R = {k: v.double().clone().requires_grad_(True) for k, v in init.items()}
-    z_ref = torch.stack([mlp(random_prop_ref(X.double()[cols], scores, idx, p_node, True, torch.tensor(kp[s], dtype=torch.uint8)), R)
-                         for s in range(S)])
+    z_ref = torch.stack([mlp(random_prop_ref(X.double()[cols], scores.double(), idx, p_node, True, kp[s]), R) for s in range(S)])
     loss_r, _, _ = grand_loss_ref(z_ref, labels, n_l, w, tem, 2.0 / C, "l2")
     loss_r.backward()
     assert abs(float(loss) - float(loss_r)) <= 1e-5 * abs(float(loss_r)) + 1e-7
