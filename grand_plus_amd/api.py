@@ -162,6 +162,8 @@ class Graph:
             raise TypeError(f"features must be a contiguous float32 [N, F] tensor on {dev}")
         if features.shape[0] != self.num_nodes:
             raise ValueError("features must have one row per node")
+        if features.shape[1] < 1:
+            raise ValueError("features must have at least one column")
         modes = {"ppr": 0, "avg": 1, "single": 2}
         if prop_mode not in modes:
             raise ValueError(f"Unknown propagation mode: {prop_mode}")            # model.py:210
@@ -170,6 +172,9 @@ class Graph:
             raise TypeError("edge_weight must be a contiguous float32 [nnz] tensor on the graph's device")
         if out is None:
             out = torch.empty_like(features)
+        elif (not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != torch.float32
+              or not out.is_contiguous() or out.shape != features.shape):
+            raise TypeError(f"out must be a contiguous float32 tensor of features' shape {tuple(features.shape)} on {dev}")
         if stream is None:
             stream = torch.cuda.current_stream(dev).cuda_stream
         _native.raise_for_status(_native.lib().gp_propagate_features(
