@@ -32,13 +32,28 @@ EXPORTS = (
     "gp_random_prop_coo_backward", "gp_random_prop_rows_backward", "gp_embedding_bag", "gp_embedding_bag_backward",
     "gp_random_prop_coo_multi", "gp_random_prop_rows_multi", "gp_random_prop_coo_multi_backward",
     "gp_random_prop_rows_multi_backward", "gp_grand_loss", "gp_grand_loss_backward",
-    "gp_mlp_block_forward", "gp_mlp_block_backward",
+    "gp_mlp_block_forward", "gp_mlp_block_backward", "gp_clip_adam_step",
 )
 GP_LOSS_KL, GP_LOSS_L2 = 0, 1
 GP_MAX_SAMPLES = 16
 
 
 GP_MLP_RELU, GP_MLP_NORM, GP_MLP_BN, GP_MLP_TRAINING = 1, 2, 4, 8
+
+
+GP_OPTIM_MAX_TENSORS = 32
+GP_OPTIM_CLIP_ONLY, GP_OPTIM_NORM_ONLY, GP_OPTIM_NORM_READY = 1, 2, 4
+
+
+def optim_workspace_bytes() -> int:
+    """GP_OPTIM_WORKSPACE_BYTES of grandplus.h."""
+    return 8192
+
+
+class GpOptimTensor(ctypes.Structure):
+    """gp_optim_tensor of grandplus.h: device pointers as integers."""
+    _fields_ = [("param", ctypes.c_void_p), ("grad", ctypes.c_void_p), ("exp_avg", ctypes.c_void_p),
+                ("exp_avg_sq", ctypes.c_void_p), ("numel", ctypes.c_int64)]
 
 
 def mlp_saved_floats(S: int, B: int, f_in: int) -> int:
@@ -183,6 +198,8 @@ def lib():
                                           f32, u64, i32, vp, vp, vp, vp, vp, vp])
     _optional(L, "gp_mlp_block_backward", [ctypes.c_int, vp, i32, i64, i32, i32, vp, ctypes.c_int, vp, f32, u64, i32, vp,
                                            vp, vp, vp, vp, vp, vp, vp, vp, vp, vp])
+    _optional(L, "gp_clip_adam_step", [ctypes.c_int, ctypes.POINTER(GpOptimTensor), i32, ctypes.c_int, f32, f32, ctypes.c_double,
+                                       ctypes.c_double, f32, f32, f32, f32, vp, vp, vp])
     L.gp_propagate_features.restype = ctypes.c_int
     L.gp_propagate_features.argtypes = [vp, vp, ctypes.c_int32, vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, vp, vp]
     L.gp_internal_diag_counters.restype = ctypes.c_int

@@ -1,0 +1,175 @@
+"""Gradient clipping and Adam on MI355X, over the fused HIP kernels of csrc/optim.hip.
+
+Reference, at the end of every training step (`model.py:116-120, 333-334`, same in `model_mag.py`):
+
+    grad_norm = clip_grad_norm(model.parameters(), args.clip_norm);  optimizer.step()        # torch.optim.Adam
+
+Here that is two launches for the whole model -- one float64 sum of squares over every gradient, one kernel that forms
+the clip coefficient and applies Adam -- with no host synchronisation: `ClipAdam.step()` returns the norm as a 0-dim
+device tensor and reads nothing back.
+
+Documented difference from the reference: `ClipAdam.step()` leaves `p.grad` unscaled (the coefficient is applied while
+the update reads the gradient; the reference never looks at the gradients after the step).  `clip_grad_norm` is the
+standalone form and does scale them in place.  float32 CUDA parameters only: there is no CPU fallback.
+"""
+from __future__ import annotations
+
+import math
+
+import torch
+
+from . import _native
+from ._common import _stream
+
+__all__ = ["ClipAdam", "clip_grad_norm"]
+
+
+def _check_tensor(t, what):
+    if not isinstance(t, torch.Tensor) or t.is_sparse:
+        raise TypeError(f"{what} must be a dense tensor (sparse gradients are not supported)")
+    # the kernels read every pointer as a dense float*: dtype and layout come first, so that they are refused on any device
+    if t.dtype != torch.float32:
+        raise TypeError(f"{what} must be float32, got {t.dtype} (no CPU fallback, no other precision)")
+    if not t.is_contiguous():
+        raise TypeError(f"{what} must be contiguous, got strides {tuple(t.stride())} for shape {tuple(t.shape)} "
+                        f"(no CPU fallback, no strided path)")
+    if not t.is_cuda:
+        raise TypeError(f"{what} must be a CUDA tensor: the optimiser runs on the GPU only (no CPU fallback)")
+
+
+def _no_gradients(params):
+    """The norm of no gradients: 0 as a 0-dim float32 tensor on the device of the first parameter, if there is one."""
+    dev = params[0].device if params else None
+    return torch.zeros((), dtype=torch.float32, device=dev)
+
+
+def _table(entries):
+    """The host array of gp_optim_tensor for (param, grad, exp_avg, exp_avg_sq) tuples (None = NULL)."""
+    tab = (_native.GpOptimTensor * max(len(entries), 1))()
+    for e, (p, g, m, v) in zip(tab, entries):
+        e.param = p.data_ptr() if p is not None else None
+        e.grad = g.data_ptr()
+        e.exp_avg = m.data_ptr() if m is not None else None
+        e.exp_avg_sq = v.data_ptr() if v is not None else None
+        e.numel = g.numel()
+    return tab
+
+
+def _buffers(dev):
+    """(workspace, norm scalar) from torch's caching allocator."""
+    return (torch.empty(_native.optim_workspace_bytes(), dtype=torch.uint8, device=dev),
+            torch.empty((), dtype=torch.float32, device=dev))
+
+
+def _call(dev, like, entries, flags, ws, norm, max_norm=0.0, lr=0.0, betas=(0.0, 0.0), eps=0.0, weight_decay=0.0,
+          step_size=0.0, rsqrt_bc2=0.0):
+    rc = _native.lib().gp_clip_adam_step(dev.index, _table(entries), len(entries), flags, max_norm, lr, betas[0], betas[1],
+                                         eps, weight_decay, step_size, rsqrt_bc2, ws.data_ptr(), norm.data_ptr(), _stream(like))
+    _native.raise_for_status(rc)
+
+
+def clip_grad_norm(params, max_norm):
+    """Drop-in for the reference's `clip_grad_norm(params, max_norm)` (model.py:116-120): the 2-norm of all gradients as a
+    0-dim float32 device tensor; with max_norm > 0 the gradients are scaled in place by min(max_norm / (norm + 1e-6), 1)
+    (torch's `clip_grad_norm_`), otherwise they are left alone.  Parameters without a gradient are skipped; with no
+    gradient at all the result is 0 on the first parameter's device and nothing is launched."""
+    params = [params] if isinstance(params, torch.Tensor) else list(params)
+    grads = [p.grad for p in params if p.grad is not None]
+    if not grads:
+        return _no_gradients(params)
+    for g in grads:
+        _check_tensor(g, "a gradient")
+        if g.device != grads[0].device:
+            raise TypeError("all gradients must be on one device")
+    dev = grads[0].device
+    ws, norm = _buffers(dev)
+    _call(dev, grads[0], [(None, g, None, None) for g in grads], _native.GP_OPTIM_CLIP_ONLY, ws, norm, max_norm=float(max_norm))
+    return norm
+
+
+class ClipAdam(torch.optim.Optimizer):
+    """`clip_grad_norm_(all parameters, clip_norm)` followed by `torch.optim.Adam.step()`, as one pair of launches.
+
+    Arguments, their range checks and the state (`step`, `exp_avg`, `exp_avg_sq`) are torch.optim.Adam's, so a checkpoint
+    of either loads into the other; `step` is kept as a Python number here.  clip_norm <= 0 means no clipping
+    (model.py:119-120).  One norm is taken over the gradients of ALL parameter groups; the hyper-parameters are per group.
+    `step()` returns that norm, before clipping, as a 0-dim float32 device tensor (a closure is called for its gradients;
+    its loss is not returned).  `p.grad` is left unscaled.  Parameters whose `.grad` is None are skipped and get no state;
+    if none has a gradient, `step()` returns 0 on the first parameter's device and launches nothing.
+    Every parameter that has a gradient must be a contiguous float32 CUDA tensor, all on one device: `step()` raises
+    TypeError otherwise, before anything is launched or any state changes (the constructor accepts a model that is still
+    on the CPU).  The same holds for `exp_avg` and `exp_avg_sq` of a loaded checkpoint.
+    """
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, clip_norm=0.0, *,
+                 amsgrad=False, maximize=False):
+        if amsgrad or maximize:
+            raise ValueError("ClipAdam does not implement amsgrad or maximize")
+        if isinstance(lr, torch.Tensor) or any(isinstance(b, torch.Tensor) for b in betas):
+            raise ValueError("ClipAdam takes lr and betas as Python numbers, not Tensors")
+        if not math.isfinite(float(clip_norm)):
+            raise ValueError(f"Invalid clip_norm value: {clip_norm}")
+        # torch.optim.Adam's own constructor checks the ranges (its messages) and names the keys of a parameter group
+        probe = torch.optim.Adam([torch.nn.Parameter(torch.empty(0))], lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        self.clip_norm = float(clip_norm)
+        super().__init__(params, dict(probe.defaults))
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        for s in self.state.values():                                # torch.optim.Adam keeps `step` as a tensor
+            if "step" in s:
+                s["step"] = self._number(s["step"])
+
+    @staticmethod
+    def _number(step):
+        return int(step.item() if isinstance(step, torch.Tensor) else step)
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        if closure is not None:
+            with torch.enable_grad():
+                closure()
+        todo, calls, dev = [], {}, None                              # calls: (group index, step count) -> entries
+        for gi, group in enumerate(self.param_groups):
+            if group.get("amsgrad") or group.get("maximize") or group.get("decoupled_weight_decay"):
+                raise ValueError("ClipAdam does not implement amsgrad, maximize or decoupled_weight_decay")
+            for p in group["params"]:
+                g = p.grad
+                if g is None:
+                    continue
+                _check_tensor(g, "a gradient")
+                _check_tensor(p, "a parameter")
+                if dev is None:
+                    dev = p.device
+                if p.device != dev or g.device != dev:
+                    raise TypeError("all parameters and gradients must be on one device")
+                loaded = self.state.get(p) or {}                     # state of an earlier step or of a checkpoint
+                for key in ("exp_avg", "exp_avg_sq") if loaded else ():
+                    s = loaded[key]
+                    _check_tensor(s, key)
+                    if s.device != dev or s.shape != p.shape:
+                        raise TypeError(f"{key} must have its parameter's device and shape, got {tuple(s.shape)} on {s.device}")
+                todo.append((gi, p, g))
+        for gi, p, g in todo:                                        # every check has passed: now the state may change
+            state = self.state[p]
+            if len(state) == 0:
+                state["step"] = 0
+                state["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+                state["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+            t = state["step"] = self._number(state["step"]) + 1
+            calls.setdefault((gi, t), []).append((p, g, state["exp_avg"], state["exp_avg_sq"]))
+        if dev is None:
+            return _no_gradients([p for group in self.param_groups for p in group["params"]])
+        ws, norm = _buffers(dev)
+        like = next(iter(calls.values()))[0][0]
+        flags = 0
+        if len(calls) > 1:                                           # one norm over everything, then an update per group
+            _call(dev, like, [e for entries in calls.values() for e in entries], _native.GP_OPTIM_NORM_ONLY, ws, norm)
+            flags = _native.GP_OPTIM_NORM_READY
+        for (gi, t), entries in calls.items():
+            group = self.param_groups[gi]
+            lr, (beta1, beta2) = float(group["lr"]), group["betas"]
+            _call(dev, like, entries, flags, ws, norm, max_norm=self.clip_norm, lr=lr, betas=(float(beta1), float(beta2)),
+                  eps=float(group["eps"]), weight_decay=float(group["weight_decay"]),
+                  step_size=lr / (1.0 - beta1 ** t), rsqrt_bc2=1.0 / math.sqrt(1.0 - beta2 ** t))
+        return norm

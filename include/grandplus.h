@@ -460,6 +460,55 @@ int gp_mlp_block_backward(int device, const float* d_x, int32_t n_samples, int64
                           void* d_workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The end of a training step, fused (model.py:116-120, 333-334, same in model_mag.py):
+ *
+ *     norm = || all gradients ||_2;   coef = max_norm > 0 ? min(max_norm / (norm + 1e-6), 1) : 1     (clip_grad_norm_)
+ *     g = grad * coef + weight_decay * p;   m = beta1 m + (1 - beta1) g;   v = beta2 v + (1 - beta2) g g
+ *     p -= step_size * (m / (sqrt(v) * rsqrt_bc2 + eps))                                              (torch.optim.Adam)
+ *
+ * for fp32 tensors on `device`.  `tensors` is a HOST array of n_tensors entries of DEVICE pointers (numel = 0 is legal
+ * and contributes nothing); it is copied into the kernel arguments, GP_OPTIM_MAX_TENSORS entries per launch, so nothing
+ * is uploaded.  step_size = lr / (1 - beta1^t) and rsqrt_bc2 = 1 / sqrt(1 - beta2^t) are the caller's, formed in double
+ * from its step count t.  beta1 and beta2 are doubles because the kernel needs (float)(1 - beta), which a beta already
+ * rounded to float no longer gives (1 - (float)0.999 is off by 1.3e-5 of itself); lr only takes part through step_size.
+ * The squares are summed in float64 (exact products); the update is fp32 without fused multiply-adds.  A NaN norm gives
+ * a NaN coef, as torch.clamp does.  *d_norm_out (device float) receives the norm before clipping.
+ * d_workspace: GP_OPTIM_WORKSPACE_BYTES bytes of device memory, 8-byte aligned, the caller's.
+ *
+ * flags:
+ *   GP_OPTIM_CLIP_ONLY   the standalone clip_grad_norm: grad * coef is written back into grad (the const of the struct
+ *                        member is cast away in this mode only) and nothing else is touched; param / exp_avg / exp_avg_sq may
+ *                        be NULL.  With max_norm <= 0 nothing is written but the norm.
+ *   GP_OPTIM_NORM_ONLY   only the squared-norm partials are left in d_workspace (d_norm_out may be NULL);
+ *   GP_OPTIM_NORM_READY  d_workspace holds the partials of an earlier GP_OPTIM_NORM_ONLY call on this stream: one norm
+ *                        over several calls with different hyper-parameters (an optimiser's parameter groups).
+ *
+ * Contracts:
+ *   - launches: at most 2 when n_tensors <= GP_OPTIM_MAX_TENSORS (one with NORM_ONLY or NORM_READY); more tensors are
+ *     cut into groups of GP_OPTIM_MAX_TENSORS: one norm launch per group, then one update launch per group;
+ *   - no atomics: the partials are summed in index order with one fixed tree, bitwise the same run to run and in
+ *     every workgroup;
+ *   - element independence: an element's update depends only on its own param, grad, exp_avg, exp_avg_sq and on coef,
+ *     not on its position, its tensor's alignment or the other tensors of the call;
+ *   - grad is read-only (without GP_OPTIM_CLIP_ONLY);
+ *   - nothing on the call path synchronises, copies or allocates; arguments are checked before the device is touched:
+ *     GP_ERR_INVALID_ARG for n_tensors < 0, numel < 0, an unknown flag or a non-finite hyper-parameter, GP_ERR_NULL for
+ *     a missing pointer.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct gp_optim_tensor {
+    float* param; const float* grad; float* exp_avg; float* exp_avg_sq; int64_t numel;
+} gp_optim_tensor;
+#define GP_OPTIM_MAX_TENSORS 32
+#define GP_OPTIM_WORKSPACE_BYTES 8192   /* 1024 float64 partials, however many elements there are */
+#define GP_OPTIM_CLIP_ONLY 1
+#define GP_OPTIM_NORM_ONLY 2
+#define GP_OPTIM_NORM_READY 4
+
+int gp_clip_adam_step(int device, const gp_optim_tensor* tensors, int32_t n_tensors, int flags,
+                      float max_norm, float lr, double beta1, double beta2, float eps, float weight_decay,
+                      float step_size, float rsqrt_bc2, void* d_workspace, float* d_norm_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * exact full-graph feature propagation of the inference path, reference
  * predict() (model.py:181-224), lines 186-210.  mode 0 = ppr, 1 = avg, 2 = single (args.prop_mode);
  * `order` = args.order propagation steps.  A is the CSR of `g` (adj + I as the caller built it,
