@@ -8,6 +8,8 @@ from __future__ import annotations
 import ctypes
 import itertools
 
+import torch
+
 _M64 = 2**64 - 1
 _GOLDEN = 0x9E3779B97F4A7C15
 _LAYER_MUL = 0xA0761D6478BD642F
@@ -38,7 +40,6 @@ def layer_seed(seed: int, layer: int, s: int = 0) -> int:
 
 
 def _check(t, dtype, name):
-    import torch
     if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous() or not t.is_cuda:
         raise TypeError(f"{name} must be a contiguous CUDA tensor of dtype {dtype}")
 
@@ -51,7 +52,6 @@ def _dev_index(t):
 
 def _stream(t, stream=None):
     """The stream argument of a native call: the caller's raw stream handle, or the current stream of t's device."""
-    import torch
     return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream if stream is None else stream)
 
 

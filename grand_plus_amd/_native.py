@@ -20,20 +20,6 @@ GP_ERR_NULL, GP_ERR_INVALID_CSR, GP_ERR_INVALID_SEED, GP_ERR_INVALID_ARG = 1, 2,
 GP_ERR_NO_DEVICE, GP_ERR_HIP, GP_ERR_NOMEM, GP_ERR_OVERFLOW = 5, 6, 7, 8
 GP_MAX_K = 1024
 
-# every symbol include/grandplus.h declares (tests check the library exports all of them)
-EXPORTS = (
-    "gp_abi_version", "gp_strerror", "gp_last_error", "gp_device_count",
-    "gp_graph_create", "gp_graph_destroy", "gp_graph_num_nodes", "gp_graph_nnz",
-    "gp_graph_device", "gp_gfpush", "gp_gfpush_device", "gp_get_stats", "gp_reset_stats",
-    "gp_set_option", "gp_random_prop_rows", "gp_random_prop_coo", "gp_internal_set_error",
-    "gp_propagate_features", "gp_internal_graph_csr", "gp_internal_diag_counters",
-    "gp_graph_create_multi", "gp_graph_num_gpus", "gp_internal_multi_plan", "gp_internal_graph_acsr", "gp_graph_create_multi_on",
-    "gp_seed_positions", "gp_batch_positions", "gp_internal_create_ms", "gp_internal_warm_device",
-    "gp_random_prop_coo_backward", "gp_random_prop_rows_backward", "gp_embedding_bag", "gp_embedding_bag_backward",
-    "gp_random_prop_coo_multi", "gp_random_prop_rows_multi", "gp_random_prop_coo_multi_backward",
-    "gp_random_prop_rows_multi_backward", "gp_grand_loss", "gp_grand_loss_backward",
-    "gp_mlp_block_forward", "gp_mlp_block_backward", "gp_clip_adam_step",
-)
 GP_LOSS_KL, GP_LOSS_L2 = 0, 1
 GP_MAX_SAMPLES = 16
 
@@ -102,20 +88,81 @@ class GpStats(ctypes.Structure):
         return d
 
 
+# The C ABI of include/grandplus.h, declared once: name -> (restype, argtypes, required).  tests/test_host_logic.py holds every
+# entry against the header's prototype, type by type.  The pointer convention:
+#   * device pointers (and streams) travel as c_void_p integers, from tensor.data_ptr();
+#   * host arrays travel as typed POINTER(...);
+#   * gp_graph* is c_void_p, gp_graph** (and any other T**) is POINTER(c_void_p);
+#   * const char* is c_char_p.
+# A name that is not required may be missing from an older build selected with GRANDPLUS_LIB (an A/B run): calling it there
+# raises a clear error.  A missing required name fails at load.  (gp_internal_graph_csr, gp_internal_multi_plan and
+# gp_internal_set_error were never needed at load, so they are not required either.)
+_int, _i32, _i64, _u32, _u64, _f32, _f64 = (ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32, ctypes.c_uint64,
+                                            ctypes.c_float, ctypes.c_double)
+_vp, _str = ctypes.c_void_p, ctypes.c_char_p
+_intp, _i32p, _i64p, _u32p, _f64p, _vpp = (ctypes.POINTER(t) for t in (_int, _i32, _i64, _u32, _f64, _vp))
+_bag = [_int, _vp, _i64, _i32, _vp, _i64, _vp, _vp, _i64, _vp, _int, _vp, _f32, _int, _u64, _vp, _vp, _vp, _vp]
+_loss = [_int, _vp, _i32, _i64, _i32, _vp, _i64, _i64, _f32, _f32, _f32, _int, _int]
+_SIGNATURES = {
+    "gp_abi_version": (_int, [], True),
+    "gp_strerror": (_str, [_int], True),
+    "gp_last_error": (_str, [], True),
+    "gp_device_count": (_int, [], True),
+    "gp_graph_create": (_int, [_i32p, _i64, _i32p, _i64, _int, _vpp], True),
+    "gp_graph_create_multi": (_int, [_i32p, _i64, _i32p, _i64, _int, _vpp], True),
+    "gp_graph_create_multi_on": (_int, [_i32p, _i64, _i32p, _i64, _intp, _int, _vpp], False),
+    "gp_graph_num_gpus": (_int, [_vp], True),
+    "gp_graph_destroy": (None, [_vp], True),
+    "gp_graph_num_nodes": (_i64, [_vp], True),
+    "gp_graph_nnz": (_i64, [_vp], True),
+    "gp_graph_device": (_int, [_vp], True),
+    "gp_gfpush": (_int, [_vp, _i32p, _i64, _f64p, _int, _f64, _int, _i32p, _i32p, _f64p], True),
+    "gp_gfpush_device": (_int, [_vp, _vp, _i64, _f64p, _int, _f64, _int, _vp, _vp, _vp, _vp, _vp], True),
+    "gp_get_stats": (_int, [_vp, ctypes.POINTER(GpStats)], True),
+    "gp_reset_stats": (_int, [_vp], True),
+    "gp_set_option": (_int, [_vp, _str, _i64], True),
+    "gp_random_prop_rows": (_int, [_int, _vp, _i64, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _f32, _int, _u64, _vp, _vp, _vp], True),
+    "gp_seed_positions": (_int, [_int, _vp, _i64, _i64, _vp, _vp, _vp], False),
+    "gp_batch_positions": (_int, [_int, _vp, _i64, _vp, _i64, _vp, _vp, _vp], False),
+    "gp_random_prop_coo": (_int, [_int, _vp, _i64, _i32, _vp, _vp, _i64, _f32, _int, _u64, _vp, _vp, _vp], True),
+    "gp_random_prop_coo_backward": (_int, [_int, _vp, _i64, _i32, _vp, _vp, _i64, _f32, _int, _u64, _vp, _vp, _vp], False),
+    "gp_random_prop_rows_backward": (_int, [_int, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _f32, _int, _u64, _vp, _vp, _i64, _vp],
+                                     False),
+    "gp_embedding_bag": (_int, _bag, False),
+    "gp_embedding_bag_backward": (_int, _bag, False),
+    "gp_random_prop_rows_multi": (_int, [_int, _vp, _i64, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _f32, _int, _u64, _vp, _i64,
+                                         _vp, _vp], False),
+    "gp_random_prop_coo_multi": (_int, [_int, _vp, _i64, _i32, _vp, _vp, _i64, _i32, _f32, _int, _u64, _vp, _vp, _vp], False),
+    "gp_random_prop_coo_multi_backward": (_int, [_int, _vp, _i64, _i32, _vp, _vp, _i64, _i32, _f32, _int, _u64, _vp, _vp, _vp], False),
+    "gp_random_prop_rows_multi_backward": (_int, [_int, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _f32, _int, _u64, _vp, _i64,
+                                                  _vp, _i64, _vp], False),
+    "gp_grand_loss": (_int, _loss + [_vp, _vp, _vp, _vp], False),
+    "gp_grand_loss_backward": (_int, _loss + [_vp, _vp, _vp, _vp, _vp, _vp], False),
+    "gp_mlp_block_forward": (_int, [_int, _vp, _i32, _i64, _i32, _i32, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _f32, _f32,
+                                    _f32, _u64, _i32, _vp, _vp, _vp, _vp, _vp, _vp], False),
+    "gp_mlp_block_backward": (_int, [_int, _vp, _i32, _i64, _i32, _i32, _vp, _int, _vp, _f32, _u64, _i32, _vp,
+                                     _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], False),
+    "gp_clip_adam_step": (_int, [_int, ctypes.POINTER(GpOptimTensor), _i32, _int, _f32, _f32, _f64, _f64, _f32, _f32, _f32, _f32,
+                                 _vp, _vp, _vp], False),
+    "gp_propagate_features": (_int, [_vp, _vp, _i32, _vp, _int, _int, _f64, _vp, _vp], True),
+    "gp_internal_graph_csr": (_int, [_vp, _vpp, _vpp, _u32p, _vp], False),
+    "gp_internal_graph_acsr": (_int, [_vp, _vp, _vp, _vp, _i64p, _intp, _u32p], False),
+    "gp_internal_diag_counters": (_int, [_vp, _i64p, _int], True),
+    "gp_internal_multi_plan": (_int, [_i64, _int, _int, _i64, _int, _int, _i64p, _int], False),
+    "gp_internal_set_error": (None, [_int, _str, _str], False),
+    "gp_internal_create_ms": (None, [_f64p], False),
+    "gp_internal_warm_device": (_int, [_int], False),
+}
+EXPORTS = tuple(_SIGNATURES)          # every symbol include/grandplus.h declares (tests check the library exports all of them)
+
 _LIB = None
 
 
-def _optional(L, name, argtypes):
-    """Declare an entry point an older build (GRANDPLUS_LIB=... for an A/B run) may lack: calling it there raises a clear error."""
-    try:
-        f = getattr(L, name)
-    except AttributeError:
-        def missing(*_a, **_k):
-            raise RuntimeError(f"{LIB_PATH} does not export {name} (an older build?): rebuild the library")
-        setattr(L, name, missing)
-        return
-    f.restype = ctypes.c_int
-    f.argtypes = argtypes
+def _missing(name):
+    """Stands in for an entry point an older build (GRANDPLUS_LIB=... for an A/B run) lacks: calling it raises a clear error."""
+    def missing(*_a, **_k):
+        raise RuntimeError(f"{LIB_PATH} does not export {name} (an older build?): rebuild the library")
+    return missing
 
 
 def lib():
@@ -136,85 +183,14 @@ def lib():
     except ImportError:
         pass
     L = ctypes.CDLL(LIB_PATH)
-    i32p, f64p = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double)
-    vp = ctypes.c_void_p
-    L.gp_abi_version.restype = ctypes.c_int
-    L.gp_strerror.restype = ctypes.c_char_p
-    L.gp_strerror.argtypes = [ctypes.c_int]
-    L.gp_last_error.restype = ctypes.c_char_p
-    L.gp_device_count.restype = ctypes.c_int
-    L.gp_graph_create.restype = ctypes.c_int
-    L.gp_graph_create.argtypes = [i32p, ctypes.c_int64, i32p, ctypes.c_int64, ctypes.c_int,
-                                  ctypes.POINTER(vp)]
-    L.gp_graph_create_multi.restype = ctypes.c_int
-    L.gp_graph_create_multi.argtypes = [i32p, ctypes.c_int64, i32p, ctypes.c_int64, ctypes.c_int, ctypes.POINTER(vp)]
-    _optional(L, "gp_graph_create_multi_on", [i32p, ctypes.c_int64, i32p, ctypes.c_int64, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.POINTER(vp)])
-    L.gp_graph_num_gpus.restype = ctypes.c_int
-    L.gp_graph_num_gpus.argtypes = [vp]
-    L.gp_graph_destroy.restype = None
-    L.gp_graph_destroy.argtypes = [vp]
-    L.gp_graph_num_nodes.restype = ctypes.c_int64
-    L.gp_graph_num_nodes.argtypes = [vp]
-    L.gp_graph_nnz.restype = ctypes.c_int64
-    L.gp_graph_nnz.argtypes = [vp]
-    L.gp_graph_device.restype = ctypes.c_int
-    L.gp_graph_device.argtypes = [vp]
-    L.gp_gfpush.restype = ctypes.c_int
-    L.gp_gfpush.argtypes = [vp, i32p, ctypes.c_int64, f64p, ctypes.c_int, ctypes.c_double,
-                            ctypes.c_int, i32p, i32p, f64p]
-    # device pointers travel as integers (tensor.data_ptr())
-    L.gp_gfpush_device.restype = ctypes.c_int
-    L.gp_gfpush_device.argtypes = [vp, vp, ctypes.c_int64, f64p, ctypes.c_int, ctypes.c_double,
-                                   ctypes.c_int, vp, vp, vp, vp, vp]
-    L.gp_get_stats.restype = ctypes.c_int
-    L.gp_get_stats.argtypes = [vp, ctypes.POINTER(GpStats)]
-    L.gp_reset_stats.restype = ctypes.c_int
-    L.gp_reset_stats.argtypes = [vp]
-    L.gp_random_prop_rows.restype = ctypes.c_int
-    L.gp_random_prop_rows.argtypes = [ctypes.c_int, vp, ctypes.c_int64, ctypes.c_int32, vp, vp, vp, ctypes.c_int32,
-                                      vp, ctypes.c_int32, ctypes.c_float, ctypes.c_int, ctypes.c_uint64, vp, vp, vp]
-    L.gp_random_prop_coo.restype = ctypes.c_int
-    L.gp_random_prop_coo.argtypes = [ctypes.c_int, vp, ctypes.c_int64, ctypes.c_int32, vp, vp, ctypes.c_int64,
-                                     ctypes.c_float, ctypes.c_int, ctypes.c_uint64, vp, vp, vp]
-    _optional(L, "gp_seed_positions", [ctypes.c_int, vp, ctypes.c_int64, ctypes.c_int64, vp, vp, vp])
-    _optional(L, "gp_batch_positions", [ctypes.c_int, vp, ctypes.c_int64, vp, ctypes.c_int64, vp, vp, vp])
-    i64, f32, u64 = ctypes.c_int64, ctypes.c_float, ctypes.c_uint64
-    _optional(L, "gp_random_prop_coo_backward", [ctypes.c_int, vp, i64, ctypes.c_int32, vp, vp, i64, f32, ctypes.c_int, u64, vp, vp, vp])
-    _optional(L, "gp_random_prop_rows_backward", [ctypes.c_int, vp, ctypes.c_int32, ctypes.c_int32, vp, vp, vp, ctypes.c_int32,
-                                                  vp, f32, ctypes.c_int, u64, vp, vp, i64, vp])
-    _bag = [ctypes.c_int, vp, i64, ctypes.c_int32, vp, i64, vp, vp, i64, vp, ctypes.c_int, vp, f32, ctypes.c_int, u64, vp, vp, vp, vp]
-    _optional(L, "gp_embedding_bag", _bag)
-    _optional(L, "gp_embedding_bag_backward", _bag)
-    i32 = ctypes.c_int32
-    _optional(L, "gp_random_prop_rows_multi", [ctypes.c_int, vp, i64, i32, vp, vp, vp, i32, vp, i32, i32, f32, ctypes.c_int, u64, vp, i64, vp, vp])
-    _optional(L, "gp_random_prop_coo_multi", [ctypes.c_int, vp, i64, i32, vp, vp, i64, i32, f32, ctypes.c_int, u64, vp, vp, vp])
-    _optional(L, "gp_random_prop_coo_multi_backward", [ctypes.c_int, vp, i64, i32, vp, vp, i64, i32, f32, ctypes.c_int, u64, vp, vp, vp])
-    _optional(L, "gp_random_prop_rows_multi_backward", [ctypes.c_int, vp, i32, i32, vp, vp, vp, i32, vp, i32, f32, ctypes.c_int, u64, vp, i64,
-                                                        vp, i64, vp])
-    _loss = [ctypes.c_int, vp, i32, i64, i32, vp, i64, i64, f32, f32, f32, ctypes.c_int, ctypes.c_int]
-    _optional(L, "gp_grand_loss", _loss + [vp, vp, vp, vp])
-    _optional(L, "gp_grand_loss_backward", _loss + [vp, vp, vp, vp, vp, vp])
-    _optional(L, "gp_mlp_block_forward", [ctypes.c_int, vp, i32, i64, i32, i32, vp, vp, ctypes.c_int, vp, vp, vp, vp, vp, f32, f32,
-                                          f32, u64, i32, vp, vp, vp, vp, vp, vp])
-    _optional(L, "gp_mlp_block_backward", [ctypes.c_int, vp, i32, i64, i32, i32, vp, ctypes.c_int, vp, f32, u64, i32, vp,
-                                           vp, vp, vp, vp, vp, vp, vp, vp, vp, vp])
-    _optional(L, "gp_clip_adam_step", [ctypes.c_int, ctypes.POINTER(GpOptimTensor), i32, ctypes.c_int, f32, f32, ctypes.c_double,
-                                       ctypes.c_double, f32, f32, f32, f32, vp, vp, vp])
-    L.gp_propagate_features.restype = ctypes.c_int
-    L.gp_propagate_features.argtypes = [vp, vp, ctypes.c_int32, vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, vp, vp]
-    L.gp_internal_diag_counters.restype = ctypes.c_int
-    L.gp_internal_diag_counters.argtypes = [vp, ctypes.POINTER(ctypes.c_int64), ctypes.c_int]
-    _optional(L, "gp_internal_graph_acsr", [vp, vp, vp, vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_uint32)])
-    _optional(L, "gp_internal_warm_device", [ctypes.c_int])
-    try:
-        L.gp_internal_create_ms.restype = None
-        L.gp_internal_create_ms.argtypes = [ctypes.POINTER(ctypes.c_double)]
-    except AttributeError:
-        pass
-    L.gp_set_option.restype = ctypes.c_int
-    L.gp_set_option.argtypes = [vp, ctypes.c_char_p, ctypes.c_int64]
+    for name, (restype, argtypes, required) in _SIGNATURES.items():
+        if not required and not hasattr(L, name):
+            setattr(L, name, _missing(name))
+            continue
+        f = getattr(L, name)
+        f.restype, f.argtypes = restype, argtypes
     # (ABI 3 is accepted only for an older build named explicitly through GRANDPLUS_LIB for an A/B run: its gp_stats is a prefix of
-    #  this one, and the entry points it lacks raise a clear error where they are called -- _optional)
+    #  this one, and the entry points it lacks raise a clear error where they are called -- _missing)
     abi = L.gp_abi_version()
     if abi != 4 and not (abi == 3 and os.environ.get("GRANDPLUS_LIB")):
         raise RuntimeError(f"libgrandplus.so ABI version {abi}, this package needs 4: rebuild (python -c 'import __graft_entry__ as g; g.build()')")

@@ -26,8 +26,14 @@ from __future__ import annotations
 
 import ctypes
 
+import torch
+from torch.autograd.function import once_differentiable
+
 from . import _native
 from ._common import _check, _dev_index, _new_seed, _ptr, _stream, sample_seed  # noqa: F401  (sample_seed: public here)
+
+# In the helpers and Functions below `samples` is None for the single-sample C entry point (output [n_out, F]) or an int S for
+# the S-sample one (output [S, n_out, F], S = 1 included).  The public functions pass None for samples=1.
 
 
 def _check_samples(samples):
@@ -35,176 +41,103 @@ def _check_samples(samples):
         raise ValueError(f"samples must be an int in [1, {_native.GP_MAX_SAMPLES}], got {samples!r}")
 
 
-def _multi_keep(keep, S, L):
-    """An explicit mask of an S-sample call: uint8 [S, L] (or its flat form), row s = the single call's keep."""
-    import torch
+def _check_keep(keep, samples, L):
+    """An explicit mask: uint8, L entries of the single call; [S, L] (or its flat form) for S samples, row s = the single call's keep."""
     _check(keep, torch.uint8, "keep")
-    if keep.numel() != S * L:
-        raise ValueError(f"keep must hold samples x {L} = {S * L} entries, got {keep.numel()}")
-    return keep
+    if samples is not None and keep.numel() != samples * L:
+        raise ValueError(f"keep must hold samples x {L} = {samples * L} entries, got {keep.numel()}")
 
 
 def _wants_grad(t):
-    import torch
     return torch.is_grad_enabled() and t.requires_grad
 
 
-def _coo_forward(feats, mat_scores, mat_idx, n_out, dropnode_rate, training, seed, keep, stream):
-    import torch
+def _coo_forward(feats, mat_scores, mat_idx, n_out, samples, dropnode_rate, training, seed, keep, stream):
     M, F = feats.shape
-    out = torch.empty((n_out, F), dtype=torch.float32, device=feats.device)
-    rc = _native.lib().gp_random_prop_coo(
-        _dev_index(feats), feats.data_ptr(), M, F, mat_scores.data_ptr(), mat_idx.data_ptr(), n_out,
-        float(dropnode_rate), int(bool(training)), ctypes.c_uint64(seed), _ptr(keep), out.data_ptr(), _stream(feats, stream))
+    L = _native.lib()
+    fn, shape, S = (L.gp_random_prop_coo, (n_out, F), ()) if samples is None else \
+                   (L.gp_random_prop_coo_multi, (samples, n_out, F), (samples,))
+    out = torch.empty(shape, dtype=torch.float32, device=feats.device)
+    rc = fn(_dev_index(feats), feats.data_ptr(), M, F, mat_scores.data_ptr(), mat_idx.data_ptr(), n_out, *S,
+            float(dropnode_rate), int(bool(training)), ctypes.c_uint64(seed), _ptr(keep), out.data_ptr(), _stream(feats, stream))
     _native.raise_for_status(rc)
     return out
 
 
-def _rows_forward(features, col, val, filled, K, batch_rows, B, dropnode_rate, training, seed, keep, stream):
-    import torch
+def _coo_backward(grad_out, mat_scores, mat_idx, M, n_out, samples, dropnode_rate, training, seed, keep):
+    g = grad_out.contiguous()
+    F = g.shape[-1]
+    L = _native.lib()
+    fn, S = (L.gp_random_prop_coo_backward, ()) if samples is None else (L.gp_random_prop_coo_multi_backward, (samples,))
+    grad = torch.empty((M, F), dtype=torch.float32, device=g.device)
+    rc = fn(_dev_index(g), g.data_ptr(), n_out, F, mat_scores.data_ptr(), mat_idx.data_ptr(), M, *S,
+            float(dropnode_rate), int(bool(training)), ctypes.c_uint64(seed), _ptr(keep), grad.data_ptr(), _stream(g))
+    _native.raise_for_status(rc)
+    return grad
+
+
+def _rows_forward(features, col, val, filled, K, batch_rows, B, samples, dropnode_rate, training, seed, keep, stream):
     N, F = features.shape
-    out = torch.empty((B, F), dtype=torch.float32, device=features.device)
-    rc = _native.lib().gp_random_prop_rows(
-        _dev_index(features), features.data_ptr(), N, F, col.data_ptr(), val.data_ptr(),
-        _ptr(filled), int(K), _ptr(batch_rows), B,
-        float(dropnode_rate), int(bool(training)), ctypes.c_uint64(seed), _ptr(keep), out.data_ptr(), _stream(features, stream))
+    L = _native.lib()
+    fn, shape, S, stride = (L.gp_random_prop_rows, (B, F), (), ()) if samples is None else \
+                           (L.gp_random_prop_rows_multi, (samples, B, F), (samples,), (col.numel(),))
+    out = torch.empty(shape, dtype=torch.float32, device=features.device)
+    rc = fn(_dev_index(features), features.data_ptr(), N, F, col.data_ptr(), val.data_ptr(), _ptr(filled), int(K),
+            _ptr(batch_rows), B, *S, float(dropnode_rate), int(bool(training)), ctypes.c_uint64(seed), _ptr(keep), *stride,
+            out.data_ptr(), _stream(features, stream))
     _native.raise_for_status(rc)
     return out
 
 
-def _coo_multi_forward(feats, mat_scores, mat_idx, n_out, S, dropnode_rate, training, seed, keep, stream):
-    import torch
-    M, F = feats.shape
-    out = torch.empty((S, n_out, F), dtype=torch.float32, device=feats.device)
-    rc = _native.lib().gp_random_prop_coo_multi(
-        _dev_index(feats), feats.data_ptr(), M, F, mat_scores.data_ptr(), mat_idx.data_ptr(), n_out, S,
-        float(dropnode_rate), int(bool(training)), ctypes.c_uint64(seed), _ptr(keep), out.data_ptr(), _stream(feats, stream))
+def _rows_backward(grad_out, col, val, filled, K, batch_rows, B, N, samples, dropnode_rate, training, seed, keep):
+    g = grad_out.contiguous()
+    F = g.shape[-1]
+    L = _native.lib()
+    fn, S, stride = (L.gp_random_prop_rows_backward, (), ()) if samples is None else \
+                    (L.gp_random_prop_rows_multi_backward, (samples,), (col.numel(),))
+    grad = torch.zeros((N, F), dtype=torch.float32, device=g.device)
+    rc = fn(_dev_index(g), g.data_ptr(), B, F, col.data_ptr(), val.data_ptr(), _ptr(filled), int(K), _ptr(batch_rows), *S,
+            float(dropnode_rate), int(bool(training)), ctypes.c_uint64(seed), _ptr(keep), *stride, grad.data_ptr(), N, _stream(g))
     _native.raise_for_status(rc)
-    return out
+    return grad
 
 
-def _rows_multi_forward(features, col, val, filled, K, batch_rows, B, S, dropnode_rate, training, seed, keep, stream):
-    import torch
-    N, F = features.shape
-    out = torch.empty((S, B, F), dtype=torch.float32, device=features.device)
-    rc = _native.lib().gp_random_prop_rows_multi(
-        _dev_index(features), features.data_ptr(), N, F, col.data_ptr(), val.data_ptr(),
-        _ptr(filled), int(K), _ptr(batch_rows), B, S,
-        float(dropnode_rate), int(bool(training)), ctypes.c_uint64(seed), _ptr(keep), col.numel(), out.data_ptr(), _stream(features, stream))
-    _native.raise_for_status(rc)
-    return out
+# Both forward helpers under the names the S-sample ones had before the single and S-sample forms were merged (same arguments):
+# tests/test_gpu_multisample.py reaches the S-sample entry points with S = 1 through them.
+_coo_multi_forward, _rows_multi_forward = _coo_forward, _rows_forward
 
 
-def _multi_autograd_functions():
-    """autograd Functions of the S-sample forms (gradient to the feature operand, summed over the samples)."""
-    global _CooMultiFn, _RowsMultiFn
-    if _CooMultiFn is not None:
-        return _CooMultiFn, _RowsMultiFn
-    import torch
-    from torch.autograd.function import once_differentiable
+class _CooFn(torch.autograd.Function):
+    """random_prop with the gradient to feats (summed over the samples of an S-sample call)."""
 
-    class CooMultiFn(torch.autograd.Function):
-        @staticmethod
-        def forward(ctx, feats, mat_scores, mat_idx, n_out, S, dropnode_rate, training, seed, keep, stream):
-            ctx.save_for_backward(mat_scores, mat_idx, keep)
-            ctx.args = (feats.shape, n_out, S, dropnode_rate, training, seed)
-            return _coo_multi_forward(feats, mat_scores, mat_idx, n_out, S, dropnode_rate, training, seed, keep, stream)
+    @staticmethod
+    def forward(ctx, feats, mat_scores, mat_idx, n_out, samples, dropnode_rate, training, seed, keep, stream):
+        ctx.save_for_backward(mat_scores, mat_idx, keep)
+        ctx.args = (feats.shape[0], n_out, samples, dropnode_rate, training, seed)
+        return _coo_forward(feats, mat_scores, mat_idx, n_out, samples, dropnode_rate, training, seed, keep, stream)
 
-        @staticmethod
-        @once_differentiable
-        def backward(ctx, grad_out):
-            mat_scores, mat_idx, keep = ctx.saved_tensors
-            (M, F), n_out, S, p, training, seed = ctx.args
-            g = grad_out.contiguous()
-            grad = torch.empty((M, F), dtype=torch.float32, device=g.device)
-            rc = _native.lib().gp_random_prop_coo_multi_backward(
-                _dev_index(g), g.data_ptr(), n_out, F, mat_scores.data_ptr(), mat_idx.data_ptr(), M, S,
-                float(p), int(bool(training)), ctypes.c_uint64(seed), _ptr(keep), grad.data_ptr(), _stream(g))
-            _native.raise_for_status(rc)
-            return grad, None, None, None, None, None, None, None, None, None
-
-    class RowsMultiFn(torch.autograd.Function):
-        @staticmethod
-        def forward(ctx, features, col, val, filled, K, batch_rows, B, S, dropnode_rate, training, seed, keep, stream):
-            ctx.save_for_backward(col, val, filled, batch_rows, keep)
-            ctx.args = (features.shape, K, B, S, dropnode_rate, training, seed)
-            return _rows_multi_forward(features, col, val, filled, K, batch_rows, B, S, dropnode_rate, training, seed, keep, stream)
-
-        @staticmethod
-        @once_differentiable
-        def backward(ctx, grad_out):
-            col, val, filled, batch_rows, keep = ctx.saved_tensors
-            (N, F), K, B, S, p, training, seed = ctx.args
-            g = grad_out.contiguous()
-            grad = torch.zeros((N, F), dtype=torch.float32, device=g.device)
-            rc = _native.lib().gp_random_prop_rows_multi_backward(
-                _dev_index(g), g.data_ptr(), B, F, col.data_ptr(), val.data_ptr(),
-                _ptr(filled), int(K), _ptr(batch_rows), S,
-                float(p), int(bool(training)), ctypes.c_uint64(seed), _ptr(keep), col.numel(), grad.data_ptr(), N, _stream(g))
-            _native.raise_for_status(rc)
-            return grad, None, None, None, None, None, None, None, None, None, None, None, None
-
-    _CooMultiFn, _RowsMultiFn = CooMultiFn, RowsMultiFn
-    return _CooMultiFn, _RowsMultiFn
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        mat_scores, mat_idx, keep = ctx.saved_tensors
+        return (_coo_backward(grad_out, mat_scores, mat_idx, *ctx.args, keep),) + (None,) * 9
 
 
-_CooMultiFn = _RowsMultiFn = None
+class _RowsFn(torch.autograd.Function):
+    """random_prop_rows with the gradient to features (summed over the samples of an S-sample call)."""
 
+    @staticmethod
+    def forward(ctx, features, col, val, filled, K, batch_rows, B, samples, dropnode_rate, training, seed, keep, stream):
+        ctx.save_for_backward(col, val, filled, batch_rows, keep)
+        ctx.args = (K, B, features.shape[0], samples, dropnode_rate, training, seed)
+        return _rows_forward(features, col, val, filled, K, batch_rows, B, samples, dropnode_rate, training, seed, keep, stream)
 
-def _autograd_functions():
-    """The two torch.autograd.Function classes (built on first use: torch is imported lazily here)."""
-    global _CooFn, _RowsFn
-    if _CooFn is not None:
-        return _CooFn, _RowsFn
-    import torch
-    from torch.autograd.function import once_differentiable
-
-    class CooFn(torch.autograd.Function):
-        @staticmethod
-        def forward(ctx, feats, mat_scores, mat_idx, n_out, dropnode_rate, training, seed, keep, stream):
-            ctx.save_for_backward(mat_scores, mat_idx, keep)
-            ctx.args = (feats.shape, n_out, dropnode_rate, training, seed)
-            return _coo_forward(feats, mat_scores, mat_idx, n_out, dropnode_rate, training, seed, keep, stream)
-
-        @staticmethod
-        @once_differentiable
-        def backward(ctx, grad_out):
-            mat_scores, mat_idx, keep = ctx.saved_tensors
-            (M, F), n_out, p, training, seed = ctx.args
-            g = grad_out.contiguous()
-            grad = torch.empty((M, F), dtype=torch.float32, device=g.device)
-            rc = _native.lib().gp_random_prop_coo_backward(
-                _dev_index(g), g.data_ptr(), n_out, F, mat_scores.data_ptr(), mat_idx.data_ptr(), M,
-                float(p), int(bool(training)), ctypes.c_uint64(seed), _ptr(keep), grad.data_ptr(), _stream(g))
-            _native.raise_for_status(rc)
-            return grad, None, None, None, None, None, None, None, None
-
-    class RowsFn(torch.autograd.Function):
-        @staticmethod
-        def forward(ctx, features, col, val, filled, K, batch_rows, B, dropnode_rate, training, seed, keep, stream):
-            ctx.save_for_backward(col, val, filled, batch_rows, keep)
-            ctx.args = (features.shape, K, B, dropnode_rate, training, seed)
-            return _rows_forward(features, col, val, filled, K, batch_rows, B, dropnode_rate, training, seed, keep, stream)
-
-        @staticmethod
-        @once_differentiable
-        def backward(ctx, grad_out):
-            col, val, filled, batch_rows, keep = ctx.saved_tensors
-            (N, F), K, B, p, training, seed = ctx.args
-            g = grad_out.contiguous()
-            grad = torch.zeros((N, F), dtype=torch.float32, device=g.device)
-            rc = _native.lib().gp_random_prop_rows_backward(
-                _dev_index(g), g.data_ptr(), B, F, col.data_ptr(), val.data_ptr(),
-                _ptr(filled), int(K), _ptr(batch_rows),
-                float(p), int(bool(training)), ctypes.c_uint64(seed), _ptr(keep), grad.data_ptr(), N, _stream(g))
-            _native.raise_for_status(rc)
-            return grad, None, None, None, None, None, None, None, None, None, None, None
-
-    _CooFn, _RowsFn = CooFn, RowsFn
-    return _CooFn, _RowsFn
-
-
-_CooFn = _RowsFn = None
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        col, val, filled, batch_rows, keep = ctx.saved_tensors
+        K, B, *rest = ctx.args
+        return (_rows_backward(grad_out, col, val, filled, K, batch_rows, B, *rest, keep),) + (None,) * 12
 
 
 def random_prop(feats, mat_scores, mat_idx, dropnode_rate, training=True, seed=None, keep=None, stream=None,
@@ -217,7 +150,6 @@ def random_prop(feats, mat_scores, mat_idx, dropnode_rate, training=True, seed=N
     `n_out` (optional) is the number of output rows; given, it saves the host read of mat_idx[-1].
     `samples` = S > 1 returns [S, n_out, F] from one launch (keep: uint8 [S, M]); see the module docstring.
     """
-    import torch
     _check_samples(samples)
     _check(feats, torch.float32, "feats")
     _check(mat_scores, torch.float32, "mat_scores")
@@ -234,20 +166,13 @@ def random_prop(feats, mat_scores, mat_idx, dropnode_rate, training=True, seed=N
     n_out = int(n_out)
     if seed is None:
         seed = _new_seed()
-    if samples > 1:
-        if keep is not None:
-            keep = _multi_keep(keep, samples, M)
-        if _wants_grad(feats):
-            return _multi_autograd_functions()[0].apply(feats, mat_scores, mat_idx, n_out, samples, dropnode_rate, training, seed,
-                                                        keep, stream)
-        return _coo_multi_forward(feats, mat_scores, mat_idx, n_out, samples, dropnode_rate, training, seed, keep, stream)
-    if M == 0:
+    samples = None if samples == 1 else samples
+    if samples is None and M == 0:
         return feats.new_zeros((n_out, F))
     if keep is not None:
-        _check(keep, torch.uint8, "keep")
-    if _wants_grad(feats):                                                # gradient to feats only (model_mag.py:355)
-        return _autograd_functions()[0].apply(feats, mat_scores, mat_idx, n_out, dropnode_rate, training, seed, keep, stream)
-    return _coo_forward(feats, mat_scores, mat_idx, n_out, dropnode_rate, training, seed, keep, stream)
+        _check_keep(keep, samples, M)
+    args = (feats, mat_scores, mat_idx, n_out, samples, dropnode_rate, training, seed, keep, stream)
+    return _CooFn.apply(*args) if _wants_grad(feats) else _coo_forward(*args)   # gradient to feats only (model_mag.py:355)
 
 
 def random_prop_rows(features, col, val, filled, K, batch_rows=None, dropnode_rate=0.5, training=True,
@@ -262,7 +187,6 @@ def random_prop_rows(features, col, val, filled, K, batch_rows=None, dropnode_ra
     atomics: not bitwise reproducible).
     `samples` = S > 1 returns [S, B, F] from one launch (keep: uint8 [S, S_rows * K]); see the module docstring.
     """
-    import torch
     _check_samples(samples)
     _check(features, torch.float32, "features")
     _check(col, torch.int32, "col")
@@ -276,18 +200,11 @@ def random_prop_rows(features, col, val, filled, K, batch_rows=None, dropnode_ra
     B = S if batch_rows is None else batch_rows.numel()
     if seed is None:
         seed = _new_seed()
-    if samples > 1:
-        if keep is not None:
-            keep = _multi_keep(keep, samples, col.numel())
-        if _wants_grad(features):
-            return _multi_autograd_functions()[1].apply(features, col, val, filled, K, batch_rows, B, samples, dropnode_rate,
-                                                        training, seed, keep, stream)
-        return _rows_multi_forward(features, col, val, filled, K, batch_rows, B, samples, dropnode_rate, training, seed, keep, stream)
+    samples = None if samples == 1 else samples
     if keep is not None:
-        _check(keep, torch.uint8, "keep")
-    if _wants_grad(features):
-        return _autograd_functions()[1].apply(features, col, val, filled, K, batch_rows, B, dropnode_rate, training, seed, keep, stream)
-    return _rows_forward(features, col, val, filled, K, batch_rows, B, dropnode_rate, training, seed, keep, stream)
+        _check_keep(keep, samples, col.numel())
+    args = (features, col, val, filled, K, batch_rows, B, samples, dropnode_rate, training, seed, keep, stream)
+    return _RowsFn.apply(*args) if _wants_grad(features) else _rows_forward(*args)
 
 
 def algorithmic_bytes(n_kept_entries: int, n_out: int, feat_dim: int) -> int:

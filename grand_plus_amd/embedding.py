@@ -23,6 +23,9 @@ from __future__ import annotations
 
 import ctypes
 
+import torch
+from torch.autograd.function import once_differentiable
+
 from . import _native
 from ._common import _check, _dev_index, _new_seed, _ptr, _stream
 
@@ -43,7 +46,6 @@ class _Layout:
 
 
 def _forward(weight, L, p, training, seed, keep, n_bad):
-    import torch
     V, H = weight.shape
     out = torch.empty((L.n_rows, H), dtype=torch.float32, device=weight.device)
     rc = _native.lib().gp_embedding_bag(
@@ -54,7 +56,6 @@ def _forward(weight, L, p, training, seed, keep, n_bad):
 
 
 def _backward(weight_shape, grad_out, L, p, training, seed, keep):
-    import torch
     V, H = weight_shape
     g = grad_out.contiguous()
     dW = torch.zeros((V, H), dtype=torch.float32, device=g.device)
@@ -65,37 +66,23 @@ def _backward(weight_shape, grad_out, L, p, training, seed, keep):
     return dW
 
 
-_BagFn = None
+class _BagFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, weight, L, p, training, seed, keep, n_bad):
+        ctx.save_for_backward(*L.tensors(), keep)
+        ctx.args = (weight.shape, L.n_src, L.n_rows, p, training, seed)
+        return _forward(weight, L, p, training, seed, keep, n_bad)
 
-
-def _bag_fn():
-    global _BagFn
-    if _BagFn is not None:
-        return _BagFn
-    import torch
-    from torch.autograd.function import once_differentiable
-
-    class BagFn(torch.autograd.Function):
-        @staticmethod
-        def forward(ctx, weight, L, p, training, seed, keep, n_bad):
-            ctx.save_for_backward(*L.tensors(), keep)
-            ctx.args = (weight.shape, L.n_src, L.n_rows, p, training, seed)
-            return _forward(weight, L, p, training, seed, keep, n_bad)
-
-        @staticmethod
-        @once_differentiable
-        def backward(ctx, grad_out):
-            offsets, nodes, base, attr_idx, attr_data, keep = ctx.saved_tensors
-            shape, n_src, n_rows, p, training, seed = ctx.args
-            L = _Layout(offsets, n_src, nodes, base, n_rows, attr_idx, attr_data)
-            return _backward(shape, grad_out, L, p, training, seed, keep), None, None, None, None, None, None
-
-    _BagFn = BagFn
-    return BagFn
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        offsets, nodes, base, attr_idx, attr_data, keep = ctx.saved_tensors
+        shape, n_src, n_rows, p, training, seed = ctx.args
+        L = _Layout(offsets, n_src, nodes, base, n_rows, attr_idx, attr_data)
+        return _backward(shape, grad_out, L, p, training, seed, keep), None, None, None, None, None, None
 
 
 def _run(weight, L, n_entries, input_droprate, training, seed, keep, validate):
-    import torch
     _check(weight, torch.float32, "weight")
     if weight.dim() != 2:
         raise TypeError("weight must be a 2-D [V, H] table")
@@ -109,7 +96,7 @@ def _run(weight, L, n_entries, input_droprate, training, seed, keep, validate):
         seed = _new_seed()
     n_bad = torch.zeros(1, dtype=torch.int32, device=weight.device)
     if torch.is_grad_enabled() and weight.requires_grad:
-        out = _bag_fn().apply(weight, L, float(input_droprate), bool(training), seed, keep, n_bad)
+        out = _BagFn.apply(weight, L, float(input_droprate), bool(training), seed, keep, n_bad)
     else:
         out = _forward(weight, L, input_droprate, training, seed, keep, n_bad)
     if validate:
@@ -129,7 +116,6 @@ def embedding_bag(weight, attr_idx, node_idx, attr_data, input_droprate=0.0, tra
     internal dropout RNG (parity tests).  validate=True raises IndexError when an id lies outside [0, V)
     (one host synchronisation); with validate=False such ids are skipped, never read or written.
     """
-    import torch
     _check(attr_idx, torch.int64, "attr_idx")
     _check(node_idx, torch.int64, "node_idx")
     _check(attr_data, torch.float32, "attr_data")
@@ -155,7 +141,6 @@ def embedding_bag_csr(weight, attr_indptr, attr_indices, attr_data, nodes=None, 
     bitwise for the same seed (same entry order, same dropout keys).  Replaces the slicing, `.nonzero()`,
     upload and host-side lookup of model_mag.py:339-347.
     """
-    import torch
     _check(attr_indptr, torch.int64, "attr_indptr")
     _check(attr_indices, torch.int32, "attr_indices")
     _check(attr_data, torch.float32, "attr_data")
@@ -185,7 +170,6 @@ def flatten_rows(col, val, filled, K, batch_rows):
     reference's `topk_adj.tocsr()` sorts columns ascending -- only the fp32 summation order and which mask
     element lands on which entry differ.  The output length is data-dependent: one count is read back.
     """
-    import torch
     _check(col, torch.int32, "col")
     _check(val, torch.float64, "val")
     _check(filled, torch.int32, "filled")

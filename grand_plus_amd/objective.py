@@ -16,6 +16,9 @@ outside [0, C) are never used as an index: they are left out and counted in part
 """
 from __future__ import annotations
 
+import torch
+from torch.autograd.function import once_differentiable
+
 from . import _native
 from ._common import _ptr, _stream
 
@@ -23,7 +26,6 @@ _KINDS = {"kl": _native.GP_LOSS_KL, "l2": _native.GP_LOSS_L2}
 
 
 def _loss_call(z, labels, n_labeled, weight, tem, conf, kind, ignore_index, logp_in):
-    import torch
     S, B, C = z.shape
     out = torch.empty(3, dtype=torch.float32, device=z.device)
     counts = torch.empty(4, dtype=torch.int32, device=z.device)
@@ -35,45 +37,32 @@ def _loss_call(z, labels, n_labeled, weight, tem, conf, kind, ignore_index, logp
     return out, counts
 
 
-def _loss_function():
-    global _LossFn
-    if _LossFn is not None:
-        return _LossFn
-    import torch
-    from torch.autograd.function import once_differentiable
+class _LossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z, labels, n_labeled, weight, tem, conf, kind, ignore_index, logp_in):
+        out, counts = _loss_call(z, labels, n_labeled, weight, tem, conf, kind, ignore_index, logp_in)
+        ctx.save_for_backward(z, labels, counts)
+        ctx.args = (n_labeled, weight, tem, conf, kind, ignore_index, logp_in)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(counts)
+        return out[0], out[1], out[2], counts
 
-    class LossFn(torch.autograd.Function):
-        @staticmethod
-        def forward(ctx, z, labels, n_labeled, weight, tem, conf, kind, ignore_index, logp_in):
-            out, counts = _loss_call(z, labels, n_labeled, weight, tem, conf, kind, ignore_index, logp_in)
-            ctx.save_for_backward(z, labels, counts)
-            ctx.args = (n_labeled, weight, tem, conf, kind, ignore_index, logp_in)
-            ctx.set_materialize_grads(False)
-            ctx.mark_non_differentiable(counts)
-            return out[0], out[1], out[2], counts
-
-        @staticmethod
-        @once_differentiable
-        def backward(ctx, g_loss, g_sup, g_con, _g_counts):
-            z, labels, counts = ctx.saved_tensors
-            n_labeled, weight, tem, conf, kind, ignore_index, logp_in = ctx.args
-            S, B, C = z.shape
-            if g_loss is None:
-                g_loss = torch.zeros((), dtype=torch.float32, device=z.device)
-            g_loss, g_sup, g_con = (g.float().contiguous() if g is not None else None for g in (g_loss, g_sup, g_con))
-            dz = torch.empty_like(z)
-            rc = _native.lib().gp_grand_loss_backward(
-                z.device.index, z.data_ptr(), S, B, C, _ptr(labels), n_labeled,
-                ignore_index, float(weight), float(tem), float(conf), kind, int(logp_in), g_loss.data_ptr(),
-                _ptr(g_sup), _ptr(g_con), counts.data_ptr(), dz.data_ptr(), _stream(z))
-            _native.raise_for_status(rc)
-            return dz, None, None, None, None, None, None, None, None
-
-    _LossFn = LossFn
-    return _LossFn
-
-
-_LossFn = None
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_loss, g_sup, g_con, _g_counts):
+        z, labels, counts = ctx.saved_tensors
+        n_labeled, weight, tem, conf, kind, ignore_index, logp_in = ctx.args
+        S, B, C = z.shape
+        if g_loss is None:
+            g_loss = torch.zeros((), dtype=torch.float32, device=z.device)
+        g_loss, g_sup, g_con = (g.float().contiguous() if g is not None else None for g in (g_loss, g_sup, g_con))
+        dz = torch.empty_like(z)
+        rc = _native.lib().gp_grand_loss_backward(
+            z.device.index, z.data_ptr(), S, B, C, _ptr(labels), n_labeled,
+            ignore_index, float(weight), float(tem), float(conf), kind, int(logp_in), g_loss.data_ptr(),
+            _ptr(g_sup), _ptr(g_con), counts.data_ptr(), dz.data_ptr(), _stream(z))
+        _native.raise_for_status(rc)
+        return dz, None, None, None, None, None, None, None, None
 
 
 def grand_plus_loss(logits, labels, n_labeled, weight, *, tem=0.1, conf=None, kind="l2", ignore_index=-100,
@@ -91,7 +80,6 @@ def grand_plus_loss(logits, labels, n_labeled, weight, *, tem=0.1, conf=None, ki
     sample's correct labelled rows, what model.py:333's accuracy counts) and "n_bad_labels".  validate=True reads
     n_bad_labels back (one host synchronisation) and raises IndexError when a label is outside [0, C).
     """
-    import torch
     if kind not in _KINDS:
         raise ValueError(f"kind must be 'kl' or 'l2', got {kind!r}")
     z = logits if isinstance(logits, torch.Tensor) else torch.stack(list(logits))
@@ -119,7 +107,7 @@ def grand_plus_loss(logits, labels, n_labeled, weight, *, tem=0.1, conf=None, ki
     conf = 2.0 / C if conf is None else float(conf)
     args = (n_labeled, float(weight), float(tem), conf, _KINDS[kind], int(ignore_index), bool(inputs_are_log_probs))
     if torch.is_grad_enabled() and z.requires_grad:
-        loss, l_sup, l_con, counts = _loss_function().apply(z, labels, *args)
+        loss, l_sup, l_con, counts = _LossFn.apply(z, labels, *args)
     else:
         out, counts = _loss_call(z, labels, *args)
         loss, l_sup, l_con = out[0], out[1], out[2]

@@ -27,6 +27,73 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, name), f"libgrandplus.so does not export {name}"
     assert _native.lib().gp_abi_version() == 4
     assert _native.lib().gp_strerror(2) == b"invalid CSR"
+    for name in _native.EXPORTS:                      # declared on the loaded library, or the stub of a name an older build lacks
+        f = getattr(_native.lib(), name)
+        assert f.argtypes is not None if isinstance(f, ctypes._CFuncPtr) else f.__name__ == "missing", name
+
+
+_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint32_t": ctypes.c_uint32,
+            "uint64_t": ctypes.c_uint64, "float": ctypes.c_float, "double": ctypes.c_double}
+
+
+def _declared_prototypes():
+    """name -> (return type, [parameter types]) of every gp_* prototype, each type as (base type without const, number of *)."""
+    text = open(os.path.join(ROOT, "include", "grandplus.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+
+    def ctype(decl):
+        m = re.fullmatch(r"(?:const\s+)?(\w+)\s*(\**)", decl.strip())
+        assert m, decl
+        return m.group(1), len(m.group(2))
+
+    protos = {}
+    for ret, name, params in re.findall(r"\b((?:const\s+)?\w+\s*\**)\s*\b(gp_[a-z_0-9]+)\s*\(([^)]*)\)\s*;", text):
+        params = [] if params.strip() == "void" else [re.sub(r"\w+$", "", p.strip()) for p in params.split(",")]
+        assert name not in protos
+        protos[name] = (ctype(ret), [ctype(p) for p in params])
+    return protos
+
+
+def _allowed_ctypes(base, stars):
+    """The ctypes types the binding may declare for a C type (the pointer convention stated above _native._SIGNATURES)."""
+    from grand_plus_amd import _native
+    if stars == 0:
+        return (None,) if base == "void" else (_SCALARS[base],)
+    if (base, stars) == ("char", 1):
+        return (ctypes.c_char_p,)
+    if stars == 2:                                    # gp_graph**, const int**: an array of pointers held as integers
+        return (ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p))
+    assert stars == 1, (base, stars)
+    if base in ("void", "gp_graph"):                  # untyped device memory, a stream, the opaque handle
+        return (ctypes.c_void_p,)
+    pointee = {"gp_stats": _native.GpStats, "gp_optim_tensor": _native.GpOptimTensor, "uint8_t": ctypes.c_uint8}.get(base) or _SCALARS[base]
+    return (ctypes.c_void_p, ctypes.POINTER(pointee))
+
+
+def test_binding_signatures_match_header():
+    """Every entry of the binding's table against the header's prototype: the count, and each type in its position."""
+    from grand_plus_amd import _native
+    protos = _declared_prototypes()
+    assert len(protos) == 42 and sorted(protos) == _declared_symbols()
+    assert sorted(_native._SIGNATURES) == sorted(protos)
+    for name, (ret, params) in protos.items():
+        restype, argtypes, required = _native._SIGNATURES[name]
+        assert isinstance(required, bool)
+        assert restype in _allowed_ctypes(*ret), f"{name}: restype {restype} for {ret}"
+        assert len(argtypes) == len(params), f"{name}: {len(argtypes)} argtypes for {len(params)} parameters"
+        for i, (got, want) in enumerate(zip(argtypes, params)):
+            assert got in _allowed_ctypes(*want), f"{name}: argument {i} is {got} for {want}"
+
+
+def test_importing_the_package_loads_neither_torch_nor_the_library():
+    import subprocess
+    import sys
+    code = ("import sys, grand_plus_amd\n"
+            "from grand_plus_amd import *\n"
+            "print('torch' in sys.modules, grand_plus_amd._native._LIB)")
+    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    assert r.stdout.split() == ["False", "None"]
 
 
 def test_stats_struct_matches_header():
@@ -178,9 +245,6 @@ def test_multi_gpu_partition_arithmetic_through_the_host_seam():
     from grand_plus_amd import _native
     from grand_plus_amd.sharded import packed_stride, shard_range
     L = _native.lib()
-    L.gp_internal_multi_plan.restype = ctypes.c_int
-    L.gp_internal_multi_plan.argtypes = [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
-                                         ctypes.POINTER(ctypes.c_int64), ctypes.c_int]
 
     def plan(S, K, parts, min_rows=2048, force=0, host=0):
         out = (ctypes.c_int64 * (5 + 2 * parts))()
