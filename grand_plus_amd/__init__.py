@@ -5,8 +5,8 @@ include/grandplus.h), the ctypes binding (`_native`), the host-side mirror of th
 reference's `propagation.Graph` (`api.Graph`), the caller-side recipe helpers (`recipes`),
 the multi-GPU seed-sharding driver (`sharded`), the tie-aware parity comparator (`parity`)
 and the synthetic workload generator (`synth`).  The training-step pieces (`augment`, `mlp`, `objective`, `optim`) need
-torch and are imported on demand; `ClipAdam` and `clip_grad_norm` of `optim` are reachable from here by name, and stay
-out of `__all__` so that `from grand_plus_amd import *` loads neither torch nor the native library.
+torch and are imported on demand; `ClipAdam` and `clip_grad_norm` of `optim` and `valid`, `predict`, `eval_head` and
+`eval_reduce` of `evaluate` are reachable from here by name, and stay out of `__all__` so that `from grand_plus_amd import *` loads neither torch nor the native library.
 """
 from .api import Graph, algorithmic_bytes          # noqa: F401
 from .recipes import RECIPES, Recipe, make_coef    # noqa: F401
@@ -14,8 +14,11 @@ from .recipes import RECIPES, Recipe, make_coef    # noqa: F401
 __all__ = ["Graph", "algorithmic_bytes", "RECIPES", "Recipe", "make_coef"]
 
 
-def __getattr__(name):                              # the optimiser needs torch: loaded when first asked for
+def __getattr__(name):                              # these need torch: loaded when first asked for
     if name in ("ClipAdam", "clip_grad_norm"):
         from . import optim
         return getattr(optim, name)
+    if name in ("valid", "predict", "eval_head", "eval_reduce"):
+        from . import evaluate
+        return getattr(evaluate, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

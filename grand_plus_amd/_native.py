@@ -36,6 +36,15 @@ def optim_workspace_bytes() -> int:
     return 8192
 
 
+GP_EVAL_WRONG, GP_EVAL_CORRECT, GP_EVAL_IGNORED, GP_EVAL_BAD = 0, 1, 2, 3
+GP_MAX_CLASSES = 4096
+
+
+def eval_workspace_bytes() -> int:
+    """GP_EVAL_WORKSPACE_BYTES of grandplus_eval.h."""
+    return 1024 * 40
+
+
 class GpOptimTensor(ctypes.Structure):
     """gp_optim_tensor of grandplus.h: device pointers as integers."""
     _fields_ = [("param", ctypes.c_void_p), ("grad", ctypes.c_void_p), ("exp_avg", ctypes.c_void_p),
@@ -154,6 +163,13 @@ _SIGNATURES = {
     "gp_internal_warm_device": (_int, [_int], False),
 }
 EXPORTS = tuple(_SIGNATURES)          # every symbol include/grandplus.h declares (tests check the library exports all of them)
+# The evaluation entry points, which include/grandplus_eval.h declares (grandplus.h includes it): the same convention, held
+# against that header type by type by tests/test_host_evaluate.py.
+_EVAL_SIGNATURES = {
+    "gp_eval_head": (_int, [_int, _vp, _i64, _i32, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp], False),
+    "gp_eval_reduce": (_int, [_int, _vp, _vp, _i64, _vp, _vp, _vp, _vp], False),
+}
+EVAL_EXPORTS = tuple(_EVAL_SIGNATURES)
 
 _LIB = None
 
@@ -183,7 +199,7 @@ def lib():
     except ImportError:
         pass
     L = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes, required) in _SIGNATURES.items():
+    for name, (restype, argtypes, required) in {**_SIGNATURES, **_EVAL_SIGNATURES}.items():
         if not required and not hasattr(L, name):
             setattr(L, name, _missing(name))
             continue

@@ -1,0 +1,243 @@
+"""GRAND+'s evaluation on MI355X: `valid` and `predict` resident on the GPU, over the fused head of
+csrc/evaluate.hip.
+
+Reference `valid` (model.py:143-166), per mini-batch of `idx_val`: slice the scipy matrix, build and upload three
+tensors, `random_prop`, the MLP, `log_softmax`; then `cat`, `nll_loss`, `accuracy` and two `.item()`.  Reference
+`predict` (model.py:181-224): propagate in numpy, upload the features 10 000 rows at a time, copy every logit back,
+`argmax` and the comparison with the labels on the host.
+
+Here the row positions of all of `idx_val` are looked up once, every batch runs `random_prop_rows(training=False)`, the
+model in eval mode and `eval_head` into one shared buffer, and one `eval_reduce` gives the two scalars; `predict` runs
+`Graph.propagate_features`, the model over all N rows into one [N, C] device tensor, one `eval_head` with
+`rows = label_rows = idx_test` and one `eval_reduce`.  Both return 0-dim device tensors: `.item()` is the caller's
+choice, and after the position lookup nothing synchronises with the host (both run that part under
+`torch.cuda.set_sync_debug_mode("error")`).
+
+Labels equal to `ignore_index` are left out of the loss as in `F.nll_loss`; other labels outside [0, C) and indices
+outside their array are never used as an address: they are flagged, left out and counted.  The accuracy divides by the
+number of rows, ignored ones included, as the reference's `accuracy` divides by `len(labels)`
+(utils/data_loader.py:165).  There is no CPU fallback.
+"""
+from __future__ import annotations
+
+from typing import NamedTuple
+
+import numpy as np
+import torch
+
+from . import _native
+from ._common import _ptr, _stream
+
+
+class EvalBuffers(NamedTuple):
+    """What `eval_head` fills and `eval_reduce` reads, one entry per evaluated row."""
+    nll: torch.Tensor      # float32: -logp[y], 0 for a row that is ignored or bad
+    pred: torch.Tensor     # int32: argmax of the row (-1: the row index was outside the logits)
+    flag: torch.Tensor     # uint8: _native.GP_EVAL_WRONG / CORRECT / IGNORED / BAD
+
+
+def eval_buffers(n, device):
+    """Buffers for n evaluated rows on `device`."""
+    return EvalBuffers(torch.empty(n, dtype=torch.float32, device=device), torch.empty(n, dtype=torch.int32, device=device),
+                       torch.empty(n, dtype=torch.uint8, device=device))
+
+
+def _index(t, name):
+    if t is None:
+        return None
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.int64:
+        raise TypeError(f"{name} must be an int64 CUDA tensor")
+    return t.reshape(-1).contiguous()
+
+
+def _check_buffers(out):
+    """dtype, layout and common length of (nll, pred, flag); returns the length.  The device is checked by _on_gpu."""
+    if not isinstance(out, tuple) or len(out) != 3:
+        raise TypeError("out must be the (nll, pred, flag) buffers of eval_buffers()")
+    for t, dtype, name in zip(out, (torch.float32, torch.int32, torch.uint8), ("nll", "pred", "flag")):
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.dim() != 1 or not t.is_contiguous():
+            raise TypeError(f"out.{name} must be a contiguous 1-d {dtype} tensor")
+    if not out[0].numel() == out[1].numel() == out[2].numel():
+        raise ValueError("out.nll, out.pred and out.flag must have the same length")
+    return out[0].numel()
+
+
+def _on_gpu(what, first, **tensors):
+    """Every tensor of a call on one GPU, checked last: dtype, shape and size errors are told apart from a CPU tensor."""
+    if not first.is_cuda:
+        raise TypeError(f"{what} runs on the GPU only: its tensors must be CUDA tensors (no CPU fallback)")
+    for name, t in tensors.items():
+        if t is not None and t.device != first.device:
+            raise TypeError(f"{name} must be on {first.device}, got {t.device} (no CPU fallback)")
+
+
+def eval_head(logits, labels, *, rows=None, label_rows=None, ignore_index=-100, out=None, offset=0):
+    """nll, argmax and a flag for n rows of logits, written at out[offset : offset + n]; returns `out` (EvalBuffers).
+
+    logits: float32 CUDA [R, C], 1 <= C <= 4096.  Evaluated row i reads logits[rows[i]] (rows None: logits[i]) and the
+    label labels[label_rows[i]] (label_rows None: labels[i]); labels, rows and label_rows are int64 CUDA tensors.  n is
+    the length of rows, else of label_rows, else R.  out None allocates buffers of offset + n rows; successive calls with
+    the same `out` and rising offsets fill one buffer for `eval_reduce`.  One launch, no host synchronisation."""
+    if not isinstance(logits, torch.Tensor) or logits.dtype != torch.float32 or logits.dim() != 2:
+        raise TypeError("logits must be a float32 [R, C] CUDA tensor")
+    R, C = logits.shape
+    if not 1 <= C <= _native.GP_MAX_CLASSES:
+        raise ValueError(f"the number of classes must be in [1, {_native.GP_MAX_CLASSES}], got {C}")
+    labels = _index(labels, "labels")
+    if labels is None:
+        raise TypeError("labels must be an int64 CUDA tensor")
+    rows = _index(rows, "rows")
+    label_rows = _index(label_rows, "label_rows")
+    if rows is not None and label_rows is not None and rows.numel() != label_rows.numel():
+        raise ValueError(f"rows has {rows.numel()} entries, label_rows {label_rows.numel()}")
+    n = rows.numel() if rows is not None else label_rows.numel() if label_rows is not None else R
+    if rows is None and n > R:
+        raise ValueError(f"label_rows has {n} entries, logits {R} rows (pass rows to pick them)")
+    if label_rows is None and n > labels.numel():
+        raise ValueError(f"labels has {labels.numel()} entries for {n} rows (pass label_rows to pick them)")
+    offset = int(offset)
+    if offset < 0:
+        raise ValueError(f"offset must be >= 0, got {offset}")
+    if out is not None:
+        cap = _check_buffers(out)
+        if offset + n > cap:
+            raise ValueError(f"offset + n = {offset + n} rows do not fit the out buffers of {cap}")
+        _on_gpu("eval_head", logits, labels=labels, rows=rows, label_rows=label_rows, nll=out[0], pred=out[1], flag=out[2])
+    else:
+        _on_gpu("eval_head", logits, labels=labels, rows=rows, label_rows=label_rows)
+        out, cap = eval_buffers(offset + n, logits.device), offset + n
+    z = logits.contiguous()
+    rc = _native.lib().gp_eval_head(z.device.index, z.data_ptr(), R, C, _ptr(rows), labels.data_ptr(), labels.numel(),
+                                    _ptr(label_rows), n, int(ignore_index), offset, cap, out[0].data_ptr(), out[1].data_ptr(),
+                                    out[2].data_ptr(), _stream(z))
+    _native.raise_for_status(rc)
+    return EvalBuffers(*out)
+
+
+def eval_reduce(buffers):
+    """(loss, acc, counts) of filled EvalBuffers: loss = sum(nll) / n_valid and acc = n_correct / n_rows as 0-dim float32
+    device tensors, counts int64 [4] = n_valid, n_correct, n_ignored, n_bad.  No valid row gives a NaN loss.  Two
+    launches, no host synchronisation; bitwise the same however the buffers were filled."""
+    n = _check_buffers(buffers)
+    nll, _pred, flag = buffers
+    _on_gpu("eval_reduce", nll, pred=_pred, flag=flag)
+    out = torch.empty(2, dtype=torch.float32, device=nll.device)
+    counts = torch.empty(4, dtype=torch.int64, device=nll.device)
+    ws = torch.empty(_native.eval_workspace_bytes(), dtype=torch.uint8, device=nll.device)
+    rc = _native.lib().gp_eval_reduce(nll.device.index, nll.data_ptr(), flag.data_ptr(), n, ws.data_ptr(), out.data_ptr(),
+                                      counts.data_ptr(), _stream(nll))
+    _native.raise_for_status(rc)
+    return out[0], out[1], counts
+
+
+def _node_ids(idx, name, device):
+    """A list of node ids (tensor or anything numpy converts) as an int64 tensor on `device`."""
+    if isinstance(idx, torch.Tensor):
+        if idx.dtype != torch.int64:
+            raise TypeError(f"{name} must hold int64 node ids, got {idx.dtype}")
+        t = idx
+    else:
+        a = np.asarray(idx)
+        if a.size and not np.issubdtype(a.dtype, np.integer):
+            raise TypeError(f"{name} must hold integer node ids, got {a.dtype}")
+        t = torch.from_numpy(np.ascontiguousarray(a.reshape(-1), dtype=np.int64))
+    return t.reshape(-1).to(device).contiguous()
+
+
+def _check_common(model, features, labels, what):
+    if not isinstance(model, torch.nn.Module):
+        raise TypeError(f"{what}: model must be a GrandPlusMLP or MagMLP")
+    if not isinstance(features, torch.Tensor) or features.dtype != torch.float32 or features.dim() != 2 or not features.is_contiguous():
+        raise TypeError("features must be a contiguous float32 [N, F] CUDA tensor")
+    if not isinstance(labels, torch.Tensor) or labels.dtype != torch.int64:
+        raise TypeError("labels must be an int64 CUDA tensor")
+    _on_gpu(what, features, labels=labels)
+
+
+class _NoSync:
+    """The body of valid / predict: no gradient, the model in eval mode, host synchronisation an error."""
+
+    def __init__(self, model):
+        self.model = model
+
+    def __enter__(self):
+        self.training = self.model.training
+        self.mode = torch.cuda.get_sync_debug_mode()
+        self.grad = torch.is_grad_enabled()
+        self.model.eval()
+        torch.set_grad_enabled(False)
+        torch.cuda.set_sync_debug_mode("error")
+
+    def __exit__(self, *exc):
+        torch.cuda.set_sync_debug_mode(self.mode)
+        torch.set_grad_enabled(self.grad)
+        self.model.train(self.training)
+        return False
+
+
+def valid(model, rows, features, idx_val, labels, batch_size=10000, dropnode_rate=0.5, return_counts=False):
+    """The reference's `valid` (model.py:143-166) on the GPU: (loss, acc) as 0-dim float32 device tensors.
+
+    rows: the RowMatrix that holds `topk_adj`; features float32 CUDA [N, F]; idx_val: the validation node ids (every one
+    a seed of `rows`); labels int64 CUDA [N], indexed by node id as `labels[idx]` is.  The positions of idx_val in `rows`
+    are looked up once (one check, KeyError for a node that is no seed); from there on nothing synchronises.  The
+    model's training flag is restored on exit.  return_counts adds the int64 [4] device tensor n_valid, n_correct,
+    n_ignored, n_bad (labels outside [0, C) are counted there, not raised).
+
+    model: a GrandPlusMLP, or a MagMLP with `features` = the [N, H] embedding the caller computed in eval mode
+    (`model.emb_csr(...)` over all nodes): the MLP is then applied to the propagated embedding, as model_mag.py does."""
+    from .augment import random_prop_rows
+    from .rows import RowMatrix
+    if not isinstance(rows, RowMatrix):
+        raise TypeError("rows must be a RowMatrix")
+    _check_common(model, features, labels, "valid")
+    if features.shape[0] != rows.n_nodes or features.device != rows.col.device:
+        raise ValueError(f"features must have one row per node ({rows.n_nodes}) on the device of rows ({rows.col.device})")
+    batch_size = int(batch_size)
+    if batch_size < 1:
+        raise ValueError(f"batch_size must be >= 1, got {batch_size}")
+    dev = features.device
+    idx = _node_ids(idx_val, "idx_val", dev)
+    n = idx.numel()
+    pos = rows.batch_positions(idx, check=True) if n else None
+    buf = eval_buffers(n, dev)
+    with _NoSync(model):
+        for start in range(0, n, batch_size):
+            end = min(start + batch_size, n)
+            aug = random_prop_rows(features, rows.col, rows.val, rows.filled, rows.K, batch_rows=pos[start:end],
+                                   dropnode_rate=dropnode_rate, training=False)
+            eval_head(model(aug), labels, label_rows=idx[start:end], out=buf, offset=start)
+        loss, acc, counts = eval_reduce(buf)
+    return (loss, acc, counts) if return_counts else (loss, acc)
+
+
+def predict(graph, features, model, idx_test, labels, prop_mode, order, alpha=0.2, batch_size_logits=10000, return_preds=False):
+    """The reference's `predict` (model.py:181-224) on the GPU: the test accuracy as a 0-dim float32 device tensor, and
+    with return_preds also the int32 [len(idx_test)] predictions.
+
+    graph: the Graph of adj + I; features float32 CUDA [N, F]; model: the MLP (`model.mlp` of the reference); idx_test:
+    node ids (any order, duplicates allowed); labels int64 CUDA [N].  `Graph.propagate_features`, then the model in eval
+    mode over all N rows, batch_size_logits at a time, into one [N, C] device tensor; one head call gathers
+    logits[idx_test] and labels[idx_test].  No logit reaches the host.  An id outside [0, N) is counted as a bad row
+    (prediction -1), never read."""
+    _check_common(model, features, labels, "predict")
+    batch_size_logits = int(batch_size_logits)
+    if batch_size_logits < 1:
+        raise ValueError(f"batch_size_logits must be >= 1, got {batch_size_logits}")
+    dev = features.device
+    idx = _node_ids(idx_test, "idx_test", dev)
+    N = features.shape[0]
+    with _NoSync(model):
+        prop = graph.propagate_features(features, prop_mode, order, alpha)
+        if N <= batch_size_logits:
+            logits = model(prop)
+        else:
+            logits = None
+            for start in range(0, N, batch_size_logits):
+                z = model(prop[start:start + batch_size_logits])
+                if logits is None:
+                    logits = torch.empty((N, z.shape[1]), dtype=torch.float32, device=dev)
+                logits[start:start + z.shape[0]].copy_(z)
+        buf = eval_head(logits, labels, rows=idx, label_rows=idx)
+        _, acc, _ = eval_reduce(buf)
+    return (acc, buf.pred) if return_preds else acc

@@ -508,6 +508,10 @@ int gp_clip_adam_step(int device, const gp_optim_tensor* tensors, int32_t n_tens
                       float max_norm, float lr, double beta1, double beta2, float eps, float weight_decay,
                       float step_size, float rsqrt_bc2, void* d_workspace, float* d_norm_out, void* stream);
 
+/* The head of an evaluation (the two evaluation entry points, the GP_EVAL_* flags and GP_EVAL_WORKSPACE_BYTES):
+ * declared in a header of their own, part of this ABI. */
+#include "grandplus_eval.h"
+
 /* ------------------------------------------------------------------------------------------
  * exact full-graph feature propagation of the inference path, reference
  * predict() (model.py:181-224), lines 186-210.  mode 0 = ppr, 1 = avg, 2 = single (args.prop_mode);
