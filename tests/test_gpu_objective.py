@@ -1,13 +1,16 @@
 """The fused GRAND+ objective against the float64 restatement of the reference in oracle/objective_ref.py:
 log_softmax + F.nll_loss per sample (model.py:323-327) and consis_loss (model.py:123-139), through autograd.
-Tolerances: the loss within 1e-5 |ref| + 1e-7; dz per element within 1e-5 max|ref row| + 1e-7.  Ends with two
-training steps end to end: a Cora-shaped one with BatchNorm and the MAG-shaped one of test_gpu_embedding.py, both
-with --sample 2."""
+Tolerances: the loss within 1e-5 |ref| + 1e-7; dz per element within 1e-5 max|ref row| + 1e-7.  The edge tests
+(upstream gradients, log-prob mode with labels, S up to 16, C from 1 to 4 096, B from 0 to a second grid-stride trip,
+sharpening where fp32 pow underflows, argmax ties, strided inputs) draw their cases from objective_cases.py, which
+test_host_objective.py proves on the CPU first.  Ends with two training steps end to end: a Cora-shaped one with
+BatchNorm and the MAG-shaped one of test_gpu_embedding.py, both with --sample 2."""
 import math
 
 import numpy as np
 import pytest
 
+import objective_cases as oc
 from augment_cases import rows_to_coo
 from oracle.objective_ref import consis_loss_ref, grand_loss_ref
 
@@ -142,6 +145,164 @@ def test_log_prob_mode_is_consis_loss(kind, tem):
     for a, b in zip(lps, lp64):
         tol = 1e-5 * b.grad.abs().amax(dim=-1, keepdim=True) + 1e-7
         assert not bool(((a.grad.double().cpu() - b.grad).abs() > tol).any())
+
+
+def _run(case, coeffs=(1, 0, 0)):
+    """One case of objective_cases.py through the kernels, differentiated as a*loss + b*L_sup + c*L_con (terms with a
+    zero coefficient left out, so autograd passes None for them): value, parts and dz against the float64 reference
+    under the file's tolerance, the four counts against float64 and torch.argmax.  Returns (loss, parts, dz)."""
+    from grand_plus_amd.objective import grand_plus_loss
+    z, labels, n_l, conf = oc.build(case)
+    ref = oc.reference(case, tuple(coeffs))
+    zc = z.cuda().requires_grad_(True)
+    loss, parts = grand_plus_loss(zc, labels.cuda(), n_l, case.w, tem=case.tem, conf=conf, kind=case.kind,
+                                  inputs_are_log_probs=case.log_probs)
+    oc.combine((loss, parts["sup"], parts["con"]), coeffs).backward()
+    oc.assert_matches({"loss": loss, "sup": parts["sup"], "con": parts["con"]}, zc.grad, ref, f"{oc.case_id(case)} {tuple(coeffs)}")
+    want = oc.counts(case)
+    assert {k: int(parts[k]) for k in want} == want
+    return loss, parts, zc.grad
+
+
+@pytest.mark.parametrize("case", oc.UPSTREAM, ids=oc.case_id)
+def test_upstream_gradients_of_the_loss_and_both_parts(case):
+    """c_sup = (g_loss + g_sup) / (S n_valid), c_con = (w g_loss + g_con) / (S n_conf), each upstream gradient present,
+    absent (None) and of either sign; weight positive, 0 and negative."""
+    import torch
+    for coeffs in oc.COEFFS:
+        _, _, dz = _run(case, coeffs)
+        assert float(dz.abs().max()) > 0
+        if coeffs == (0, 1, 0):
+            assert torch.count_nonzero(dz[:, case.n_l:]) == 0 and torch.count_nonzero(dz[:, :case.n_l]) > 0
+        if coeffs == (0, 0, 1):
+            assert torch.count_nonzero(dz[:, :case.n_l]) == 0 and torch.count_nonzero(dz[:, case.n_l:]) > 0
+
+
+@pytest.mark.parametrize("case", oc.LOGPROB, ids=oc.case_id)
+def test_log_prob_mode_with_labels(case):
+    """inputs_are_log_probs=True with labelled rows: the supervised gradient is -c_sup onehot(y), not c_sup (p - onehot)."""
+    import torch
+    for coeffs in ((1, 0, 0), oc.COEFFS[3]):
+        _, parts, dz = _run(case, coeffs)
+        assert int(parts["n_valid"]) == case.n_l - 1
+        assert torch.count_nonzero(dz[:, 3]) == 0                                 # the ignore_index row
+        assert int(torch.count_nonzero(dz[:, :case.n_l])) == case.S * (case.n_l - 1)   # one element per valid row and sample
+
+
+@pytest.mark.parametrize("case", oc.SAMPLES, ids=oc.case_id)
+def test_sample_counts_up_to_the_bound(case):
+    _run(case)
+
+
+def test_seventeen_samples_are_refused_by_the_wrapper():
+    import torch
+    from grand_plus_amd.objective import grand_plus_loss
+    z = torch.zeros((oc.MAX_S + 1, 4, 3), device="cuda", requires_grad=True)
+    with pytest.raises(ValueError, match="number of samples"):                    # the wrapper's own text: no native call was made
+        grand_plus_loss(z, None, 0, 1.0)
+
+
+@pytest.mark.parametrize("case", oc.CLASSES, ids=oc.case_id)
+def test_class_counts_around_the_wave_width_and_at_the_bound(case):
+    import torch
+    loss, parts, dz = _run(case)
+    if case.C == 1:                                                               # logp = 0, p = q = 1: nothing to learn
+        assert float(parts["sup"]) == 0.0 and float(parts["con"]) == 0.0 and torch.count_nonzero(dz) == 0
+    else:
+        assert torch.count_nonzero(dz[:, :case.n_l]) > 0 and torch.count_nonzero(dz[:, case.n_l:]) > 0
+
+
+def test_more_classes_than_the_bound_are_refused():
+    import torch
+    from grand_plus_amd.objective import grand_plus_loss
+    z = torch.zeros((1, 2, oc.MAX_C + 1), device="cuda", requires_grad=True)
+    with pytest.raises(ValueError, match="n_classes outside"):                    # GP_ERR_INVALID_ARG through raise_for_status
+        grand_plus_loss(z, None, 0, 1.0)
+
+
+@pytest.mark.parametrize("case", oc.ROWS, ids=oc.case_id)
+def test_row_counts_below_one_workgroup_and_without_unlabelled_rows(case):
+    loss, parts, dz = _run(case)
+    if case.n_l == case.B:                                                        # no unlabelled row: L_con is a mean over nothing
+        assert math.isnan(float(parts["con"])) and math.isnan(float(loss)) and int(parts["n_conf"]) == 0
+        assert math.isfinite(float(parts["sup"]))
+        assert oc.grad_error(dz, oc.reference(case, (0, 1, 0))["grad"])[1] <= 1.0  # the supervised gradient alone
+    if case.n_l == 0:
+        assert math.isnan(float(parts["sup"])) and math.isnan(float(loss))
+
+
+def test_a_second_grid_stride_trip():
+    """B = 65 535 * 4 + 37: the grid is capped, so the last 37 rows are the second trip of the loops over rows."""
+    import torch
+    case = oc.SECOND_TRIP
+    _, _, dz = _run(case)
+    gref = oc.reference(case)["grad"][:, -37:]
+    assert torch.count_nonzero(gref) > 0 and torch.count_nonzero(dz[:, -37:]) > 0
+    assert oc.grad_error(dz[:, -37:], gref)[1] <= 1.0
+
+
+def test_no_rows_at_all():
+    import torch
+    from grand_plus_amd.objective import grand_plus_loss
+    z = torch.zeros((2, 0, 7), device="cuda", requires_grad=True)
+    loss, parts = grand_plus_loss(z, None, 0, 1.0)
+    loss.backward()
+    assert math.isnan(float(loss)) and math.isnan(float(parts["sup"])) and math.isnan(float(parts["con"]))
+    assert [int(parts[k]) for k in ("n_conf", "n_valid", "n_correct", "n_bad_labels")] == [0, 0, 0, 0]
+    assert z.grad is not None and tuple(z.grad.shape) == (2, 0, 7)
+
+
+@pytest.mark.parametrize("case", oc.SHARPEN, ids=oc.case_id)
+def test_sharpening_where_fp32_pow_underflows(case):
+    """avg_p ** (1 / tem) ~ 2^-240 is 0 in fp32: the reference's own form gives 0 / 0 there, the kernels' log-domain form
+    must not.  n_l = 0, so L_sup and the loss are NaN as always; L_con and dz are finite and match float64."""
+    import torch
+    z, _, _, conf = oc.build(case)
+    lps = [torch.log_softmax(z[s], -1) for s in range(case.S)]
+    assert math.isnan(float(consis_loss_ref(lps, case.tem, conf, case.kind)))     # why the case exists
+    loss, parts, dz = _run(case)
+    assert math.isfinite(float(parts["con"])) and bool(torch.isfinite(dz).all()) and float(dz.abs().max()) > 0
+    assert int(parts["n_conf"]) == case.B
+
+
+def test_argmax_ties_go_to_the_first_index():
+    """Two or three columns share the last sample's row maximum: within a lane (c, c + 64), across adjacent lanes,
+    lanes 0 and 63, the third stride against column 0.  n_correct follows torch.argmax: the first index."""
+    import torch
+    case = oc.TIES
+    z, labels, n_l, _ = oc.build(case)
+    _, parts, _ = _run(case)
+    assert int(parts["n_correct"]) == int((torch.argmax(z[case.S - 1, :n_l], 1) == labels[:n_l]).sum()) == 3
+
+
+def test_a_labelled_row_of_minus_infinity_logits_but_two():
+    import torch
+    _, parts, dz = _run(oc.NEGINF)
+    assert bool(torch.isfinite(dz).all()) and int(torch.count_nonzero(dz[:, 2])) == 2 * oc.NEGINF.S
+    assert math.isfinite(float(parts["sup"])) and math.isfinite(float(parts["con"]))
+
+
+@pytest.mark.parametrize("layout", ["transposed", "padded"])
+def test_strided_input_sends_the_gradient_to_its_base(layout):
+    import torch
+    from grand_plus_amd.objective import grand_plus_loss
+    case = oc.STRIDED
+    z, labels, n_l, conf = oc.build(case)
+    ref = oc.reference(case)
+    if layout == "transposed":
+        base = z.transpose(0, 1).contiguous().cuda().requires_grad_(True)         # [B, S, C]
+        zin = base.transpose(0, 1)
+    else:
+        pad = torch.randn((case.S, case.B, 3), generator=torch.Generator().manual_seed(1))
+        base = torch.cat([z, pad], dim=-1).cuda().requires_grad_(True)            # [S, B, C + 3]
+        zin = base[..., :case.C]
+    assert not zin.is_contiguous()
+    loss, parts = grand_plus_loss(zin, labels.cuda(), n_l, case.w, tem=case.tem, conf=conf, kind=case.kind)
+    loss.backward()
+    got = base.grad.transpose(0, 1) if layout == "transposed" else base.grad[..., :case.C]
+    oc.assert_matches({"loss": loss, "sup": parts["sup"], "con": parts["con"]}, got, ref, f"strided, {layout}")
+    if layout == "padded":
+        assert torch.count_nonzero(base.grad[..., case.C:]) == 0
 
 
 def test_two_runs_are_bitwise_equal():
