@@ -44,6 +44,16 @@ def _check(t, dtype, name):
         raise TypeError(f"{name} must be a contiguous CUDA tensor of dtype {dtype}")
 
 
+def _deterministic(flag):
+    """The `deterministic` keyword of random_prop_rows and the embedding bag: None follows
+    torch.are_deterministic_algorithms_enabled(); anything but None or a bool is refused."""
+    if flag is None:
+        return torch.are_deterministic_algorithms_enabled()
+    if not isinstance(flag, bool):
+        raise TypeError(f"deterministic must be None, True or False, got {flag!r}")
+    return flag
+
+
 def _dev_index(t):
     if not t.is_cuda:
         raise TypeError("random_prop runs on the GPU only: tensors must be CUDA tensors (no CPU fallback)")

@@ -45,6 +45,16 @@ def eval_workspace_bytes() -> int:
     return 1024 * 40
 
 
+def scatter_rows_workspace_bytes(n_samples: int, n_batch: int) -> int:
+    """GP_SCATTER_ROWS_WORKSPACE_BYTES of grandplus_scatter.h."""
+    return 4 * n_samples * n_batch
+
+
+def scatter_bag_workspace_bytes(n_rows: int) -> int:
+    """GP_SCATTER_BAG_WORKSPACE_BYTES of grandplus_scatter.h."""
+    return 4 * n_rows
+
+
 class GpOptimTensor(ctypes.Structure):
     """gp_optim_tensor of grandplus.h: device pointers as integers."""
     _fields_ = [("param", ctypes.c_void_p), ("grad", ctypes.c_void_p), ("exp_avg", ctypes.c_void_p),
@@ -170,6 +180,15 @@ _EVAL_SIGNATURES = {
     "gp_eval_reduce": (_int, [_int, _vp, _vp, _i64, _vp, _vp, _vp, _vp], False),
 }
 EVAL_EXPORTS = tuple(_EVAL_SIGNATURES)
+# The deterministic scatter backwards, which include/grandplus_scatter.h declares (grandplus.h includes it): the same
+# convention, held against that header type by type by tests/test_host_deterministic.py.  Each takes the arguments of its
+# atomic counterpart, then the sorted order (entry numbers, sorted keys[, sorted rows], their length) and the scratch.
+_SCATTER_SIGNATURES = {
+    "gp_random_prop_rows_backward_det": (_int, [_int, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _f32, _int, _u64, _vp, _i64,
+                                                _vp, _i64, _vp, _vp, _i64, _vp, _vp], False),
+    "gp_embedding_bag_backward_det": (_int, _bag[:-1] + [_vp, _vp, _vp, _i64, _vp, _vp], False),
+}
+SCATTER_EXPORTS = tuple(_SCATTER_SIGNATURES)
 
 _LIB = None
 
@@ -199,7 +218,7 @@ def lib():
     except ImportError:
         pass
     L = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes, required) in {**_SIGNATURES, **_EVAL_SIGNATURES}.items():
+    for name, (restype, argtypes, required) in {**_SIGNATURES, **_EVAL_SIGNATURES, **_SCATTER_SIGNATURES}.items():
         if not required and not hasattr(L, name):
             setattr(L, name, _missing(name))
             continue

@@ -30,7 +30,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _native
-from ._common import _check, _dev_index, _new_seed, _ptr, _stream, sample_seed  # noqa: F401  (sample_seed: public here)
+from ._common import _check, _deterministic, _dev_index, _new_seed, _ptr, _stream, sample_seed  # noqa: F401  (sample_seed: public here)
 
 # In the helpers and Functions below `samples` is None for the single-sample C entry point (output [n_out, F]) or an int S for
 # the S-sample one (output [S, n_out, F], S = 1 included).  The public functions pass None for samples=1.
@@ -102,6 +102,38 @@ def _rows_backward(grad_out, col, val, filled, K, batch_rows, B, N, samples, dro
     return grad
 
 
+def _rows_det_order(col, filled, K, batch_rows, N):
+    """The sorted order the deterministic backward takes: (order, keys).  All B*K slots of the batch, entry e = b*K + k,
+    keyed by their column id, or by the sentinel N when the slot is unfilled or its id outside [0, N), so that it sorts
+    last; a stable sort by key.  Device ops only: nothing here reads the host."""
+    cols = col.view(-1, K) if batch_rows is None else col.view(-1, K)[batch_rows.long()]
+    live = (cols >= 0) & (cols < N)
+    if filled is not None:
+        n = filled if batch_rows is None else filled[batch_rows.long()]
+        live &= torch.arange(K, device=col.device)[None, :] < n[:, None]
+    keys, order = torch.sort(torch.where(live, cols.long(), N).reshape(-1), stable=True)
+    return order, keys
+
+
+def _rows_backward_det(grad_out, col, val, filled, K, batch_rows, B, N, samples, dropnode_rate, training, seed, keep):
+    """_rows_backward without atomics (csrc/scatter_det.hip): the batch's slots ordered by column id
+    (_rows_det_order), one gather kernel that sums each gradient row in that order."""
+    g = grad_out.contiguous()
+    F = g.shape[-1]
+    grad = torch.zeros((N, F), dtype=torch.float32, device=g.device)
+    if B == 0:
+        return grad
+    order, keys = _rows_det_order(col, filled, int(K), batch_rows, N)
+    S = 1 if samples is None else samples
+    inv_den = torch.empty(_native.scatter_rows_workspace_bytes(S, B) // 4, dtype=torch.float32, device=g.device)
+    rc = _native.lib().gp_random_prop_rows_backward_det(
+        _dev_index(g), g.data_ptr(), B, F, col.data_ptr(), val.data_ptr(), _ptr(filled), int(K), _ptr(batch_rows), S,
+        float(dropnode_rate), int(bool(training)), ctypes.c_uint64(seed), _ptr(keep), col.numel(), grad.data_ptr(), N,
+        order.data_ptr(), keys.data_ptr(), keys.numel(), inv_den.data_ptr(), _stream(g))
+    _native.raise_for_status(rc)
+    return grad
+
+
 # Both forward helpers under the names the S-sample ones had before the single and S-sample forms were merged (same arguments):
 # tests/test_gpu_multisample.py reaches the S-sample entry points with S = 1 through them.
 _coo_multi_forward, _rows_multi_forward = _coo_forward, _rows_forward
@@ -127,9 +159,11 @@ class _RowsFn(torch.autograd.Function):
     """random_prop_rows with the gradient to features (summed over the samples of an S-sample call)."""
 
     @staticmethod
-    def forward(ctx, features, col, val, filled, K, batch_rows, B, samples, dropnode_rate, training, seed, keep, stream):
+    def forward(ctx, features, col, val, filled, K, batch_rows, B, samples, dropnode_rate, training, seed, keep, stream,
+                deterministic=False):
         ctx.save_for_backward(col, val, filled, batch_rows, keep)
         ctx.args = (K, B, features.shape[0], samples, dropnode_rate, training, seed)
+        ctx.deterministic = deterministic
         return _rows_forward(features, col, val, filled, K, batch_rows, B, samples, dropnode_rate, training, seed, keep, stream)
 
     @staticmethod
@@ -137,7 +171,8 @@ class _RowsFn(torch.autograd.Function):
     def backward(ctx, grad_out):
         col, val, filled, batch_rows, keep = ctx.saved_tensors
         K, B, *rest = ctx.args
-        return (_rows_backward(grad_out, col, val, filled, K, batch_rows, B, *rest, keep),) + (None,) * 12
+        backward = _rows_backward_det if ctx.deterministic else _rows_backward
+        return (backward(grad_out, col, val, filled, K, batch_rows, B, *rest, keep),) + (None,) * 13
 
 
 def random_prop(feats, mat_scores, mat_idx, dropnode_rate, training=True, seed=None, keep=None, stream=None,
@@ -176,7 +211,7 @@ def random_prop(feats, mat_scores, mat_idx, dropnode_rate, training=True, seed=N
 
 
 def random_prop_rows(features, col, val, filled, K, batch_rows=None, dropnode_rate=0.5, training=True,
-                     seed=None, keep=None, stream=None, samples=1):
+                     seed=None, keep=None, stream=None, samples=1, deterministic=None):
     """Fused augmentation straight from the GFPush row matrix.
 
     features [N, F] float32 (node features resident on the GPU); col int32 [S*K], val float64 [S*K],
@@ -184,9 +219,14 @@ def random_prop_rows(features, col, val, filled, K, batch_rows=None, dropnode_ra
     batch's seeds in the seed list (None = all S rows).  Returns [B, F] float32:
         out[b] = sum_k w_k X[col[r,k]] / (sum_k w_k + 1e-12),  r = batch_rows[b]
     Differentiable with respect to `features` (the backward adds into a dense [N, F] gradient with fp32
-    atomics: not bitwise reproducible).
+    atomics: not bitwise reproducible unless `deterministic=True`).
+    `deterministic` chooses the backward alone; the forward is the same bit for bit.  False: the atomic kernel.  True: the
+    batch's slots are sorted by column id and each gradient row is summed in a fixed order with plain stores (DESIGN §7i;
+    slower, bitwise the same run to run, no host synchronisation).  None follows
+    `torch.are_deterministic_algorithms_enabled()`.
     `samples` = S > 1 returns [S, B, F] from one launch (keep: uint8 [S, S_rows * K]); see the module docstring.
     """
+    deterministic = _deterministic(deterministic)
     _check_samples(samples)
     _check(features, torch.float32, "features")
     _check(col, torch.int32, "col")
@@ -204,7 +244,7 @@ def random_prop_rows(features, col, val, filled, K, batch_rows=None, dropnode_ra
     if keep is not None:
         _check_keep(keep, samples, col.numel())
     args = (features, col, val, filled, K, batch_rows, B, samples, dropnode_rate, training, seed, keep, stream)
-    return _RowsFn.apply(*args) if _wants_grad(features) else _rows_forward(*args)
+    return _RowsFn.apply(*args, deterministic) if _wants_grad(features) else _rows_forward(*args)
 
 
 def algorithmic_bytes(n_kept_entries: int, n_out: int, feat_dim: int) -> int:

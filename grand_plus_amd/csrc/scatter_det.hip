@@ -1,0 +1,338 @@
+// scatter_det.hip -- DESIGN §7i: the two scatter backwards of augment.hip (random_prop_rows, embedding bag) without
+// atomics on the gradient, so that it is bitwise the same run to run.  Sort-then-gather: the caller orders the entries
+// of the call by destination row with a stable sort (plumbing, torch.sort); gather_sum_kernel below sums every
+// destination row that occurs sequentially in that order, from 0.0f, and writes it once with plain stores.
+//
+// Order contract (include/grandplus_scatter.h states it in full; tests/test_gpu_deterministic_backward.py pins it):
+//   rows form      entry e = b*K + k (b = position in the batch), contribution
+//                  c_e[f] = sum_{s in order, from 0.0f} (g[s,b,f] * inv_{s,b}) * w'_{s,e}  -- the atomic kernel's expression;
+//                  grad_X[v,f] = left-to-right sum of c_e[f] over the entries with col = v, e ascending.
+//   embedding bag  entry j = position in the batch's entry order (the dropout key's j), contribution
+//                  ((g[m,h] * inv_m) * d_j) * keep_{j,h}*scale;  dW[a,h] = left-to-right sum over a_j = a, j ascending.
+// -ffp-contract=off applies as in the other units: no product is fused into the add that follows it.
+//
+// Mapping.  A wave takes a window of 64 consecutive positions of the sorted list.  Its lanes read their own position's
+// key and ballot the head flags key[i] != key[i-1]; each lane also prepares its own position's entry (the weights and
+// denominators of the rows form, (m, j, d_j, inv_m) of the bag: the hash and the dependent loads run 64 entries at a
+// time).  Then, per head in the window, the 64 lanes cover 64 consecutive floats of the destination row (kCols of
+// them per pass for wider rows) and walk the segment to its end: first through the window's prepared entries, passed
+// round with shuffles, then, when the segment runs past the window, through further groups of 64 prepared the same
+// way.  A position whose key is not a destination (the sentinel N / V, to which the caller keys what does not exist)
+// ends the walk.  A long segment is a serial chain of adds on one wave: the accepted cost of the mode (§7i).
+//
+// BagLayout, bag_of, attr_id and sample_weight restate augment.hip's (internal linkage there, and that file is left as
+// it is): the entry must be found exactly as the forward finds it.
+#include "gp_common.hpp"
+
+#include <algorithm>
+
+namespace {
+
+constexpr int kBlock = 256;           // the pre-pass kernels
+constexpr int kGather = 64;           // gather_sum_kernel: one wave per workgroup, so that few windows still spread over the CUs
+constexpr int kCols = 4;              // 64-column slabs of the destination row per pass of a segment
+constexpr int kStage = 1024;          // = GP_MAX_K
+constexpr int kMaxSamples = 16;
+constexpr int kDenSamples = 4;        // samples whose weights the rows pre-pass stages at a time
+
+__device__ __forceinline__ float sample_weight(float w, long long e, int s, float p, float scale, int training, u64 seed,
+                                               const unsigned char* keep, long long keep_stride)
+{
+    if (!training) return w;
+    return w * (keep ? (keep[(long long)s * keep_stride + e] ? scale : 0.0f) : keep_scale(sample_seed(seed, s), (u64)e, p, scale));
+}
+
+struct BagLayout {
+    const long long* offsets; long long n_src;        // offsets[n_src + 1]
+    const long long* nodes;                             // [n_rows] or NULL
+    const long long* base;                              // [n_rows] or NULL
+    long long n_rows;
+    const void* idx; int idx64;                         // attr ids: int64 (idx64) or int32
+    const float* data;
+};
+
+__device__ __forceinline__ bool bag_of(const BagLayout& L, long long m, long long& s0, long long& s1, long long& jb)
+{
+    const long long src = L.nodes ? L.nodes[m] : m;
+    if (src < 0 || src >= L.n_src) { s0 = s1 = jb = 0; return false; }
+    s0 = L.offsets[src]; s1 = L.offsets[src + 1];
+    jb = L.base ? L.base[m] : s0;
+    return true;
+}
+
+__device__ __forceinline__ long long attr_id(const BagLayout& L, long long e)
+{
+    return L.idx64 ? reinterpret_cast<const long long*>(L.idx)[e] : (long long)reinterpret_cast<const int*>(L.idx)[e];
+}
+
+// ---- pre-pass, rows form: inv_den[s * n_batch + b] = 1 / (den_{s,b} + 1e-12), den summed over k in the forward's order
+__global__ void __launch_bounds__(kBlock)
+rows_inv_den_kernel(const double* __restrict__ val, const int* __restrict__ filled, int K, const int* __restrict__ batch_rows,
+                    int n_batch, int S, float p, int training, u64 seed, const unsigned char* __restrict__ keep,
+                    long long keep_stride, float* __restrict__ inv_den)
+{
+    __shared__ float s_w[kDenSamples][kStage];
+    const float scale = p < 1.0f ? 1.0f / (1.0f - p) : 0.0f;
+    for (int b = blockIdx.x; b < n_batch; b += gridDim.x) {
+        const long long row = batch_rows ? batch_rows[b] : b;
+        const int n = filled ? min(filled[row], K) : K;
+        for (int s0 = 0; s0 < S; s0 += kDenSamples) {
+            const int ns = min(kDenSamples, S - s0);
+            __syncthreads();
+            for (int k = threadIdx.x; k < n; k += kBlock) {
+                const long long e = row * (long long)K + k;
+                const float w = (float)val[e];
+                for (int s = 0; s < ns; ++s) s_w[s][k] = sample_weight(w, e, s0 + s, p, scale, training, seed, keep, keep_stride);
+            }
+            __syncthreads();
+            if (threadIdx.x < ns) {
+                float den = 0.0f;
+                for (int k = 0; k < n; ++k) den += s_w[threadIdx.x][k];
+                inv_den[(size_t)(s0 + threadIdx.x) * n_batch + b] = 1.0f / (den + 1e-12f);
+            }
+        }
+    }
+}
+
+// ---- pre-pass, embedding bag: inv_den[m] = 1 / (den_m + 1e-10), den summed as embedding_bag_backward_kernel sums it;
+// bag sources outside [0, n_src) and ids outside [0, V) are counted as that kernel counts them.
+__global__ void __launch_bounds__(kBlock)
+bag_inv_den_kernel(long long V, BagLayout L, float* __restrict__ inv_den, int* __restrict__ n_bad)
+{
+    const int lane = threadIdx.x & 63;
+    const long long wave = ((long long)blockIdx.x * kBlock + threadIdx.x) >> 6;
+    const long long n_waves = ((long long)gridDim.x * kBlock) >> 6;
+    for (long long m = wave; m < L.n_rows; m += n_waves) {        // wave-uniform loop
+        long long s0, s1, jb;
+        if (!bag_of(L, m, s0, s1, jb)) {
+            if (lane == 0) { inv_den[m] = 0.0f; if (n_bad) atomicAdd(n_bad, 1); }
+            continue;
+        }
+        float den = 0.0f;
+        for (long long c0 = s0; c0 < s1; c0 += 64) {
+            const bool cl = c0 + lane < s1;
+            float part = cl ? L.data[c0 + lane] : 0.0f;
+            if (cl && n_bad) { const long long a = attr_id(L, c0 + lane); if (a < 0 || a >= V) atomicAdd(n_bad, 1); }
+            for (int o = 1; o < 64; o <<= 1) part += __shfl_xor(part, o);
+            den += part;
+        }
+        if (lane == 0) inv_den[m] = 1.0f / (den + 1e-10f);
+    }
+}
+
+// ---- what one sorted position contributes.  load(): every lane prepares the entry of its own position i (key: the
+// position's sorted key; want: the lane has one); an entry that is not there, or whose key is not its destination,
+// comes back dead and adds nothing.  add(): the whole wave adds the entry lane u holds to acc, lane's columns
+// f + 64*c (c < kCols) of the destination row.
+struct RowsOp {
+    const float* g; int F; const int* col; const double* val; const int* filled; int K; const int* batch_rows; int n_batch;
+    int S; float p; int training; u64 seed; const unsigned char* keep; long long keep_stride; const float* inv_den;
+
+    struct Entry { int b; int live; float w[kMaxSamples], inv[kMaxSamples]; };
+
+    __device__ __forceinline__ Entry load(const long long* __restrict__ order, long long i, bool want, long long key) const
+    {
+        Entry E;
+        E.b = 0; E.live = 0;
+#pragma unroll
+        for (int s = 0; s < kMaxSamples; ++s) E.w[s] = E.inv[s] = 0.0f;
+        if (!want) return E;
+        const long long e = order[i];
+        if (e < 0 || e >= (long long)n_batch * K) return E;
+        const int b = (int)(e / K), k = (int)(e - (long long)b * K);
+        const long long row = batch_rows ? batch_rows[b] : b;
+        const int n = filled ? min(filled[row], K) : K;
+        const long long re = row * (long long)K + k;              // the resident slot: keys the mask, as in the forward
+        if (k >= n || (long long)col[re] != key) return E;
+        const float scale = p < 1.0f ? 1.0f / (1.0f - p) : 0.0f;
+        const float w = (float)val[re];
+        bool any = false;
+#pragma unroll
+        for (int s = 0; s < kMaxSamples; ++s) {
+            if (s < S) {
+                E.w[s] = sample_weight(w, re, s, p, scale, training, seed, keep, keep_stride);
+                E.inv[s] = inv_den[(size_t)s * n_batch + b];
+                any |= E.w[s] != 0.0f;
+            }
+        }
+        E.b = b; E.live = any;                                       // dropped in every sample: adds nothing, g is not read
+        return E;
+    }
+
+    __device__ __forceinline__ void add(const Entry& E, int u, int f, float (&acc)[kCols]) const
+    {
+        if (!__shfl(E.live, u)) return;                              // wave-uniform
+        const float* gb = g + (size_t)__shfl(E.b, u) * F;
+        const size_t g_stride = (size_t)n_batch * F;
+        float x[kCols];
+#pragma unroll
+        for (int c = 0; c < kCols; ++c) x[c] = 0.0f;
+#pragma unroll
+        for (int s = 0; s < kMaxSamples; ++s) {
+            if (s < S) {
+                const float inv = __shfl(E.inv[s], u), w = __shfl(E.w[s], u);
+#pragma unroll
+                for (int c = 0; c < kCols; ++c)
+                    if (f + 64 * c < F) x[c] += (gb[s * g_stride + f + 64 * c] * inv) * w;
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < kCols; ++c) acc[c] += x[c];
+    }
+};
+
+struct BagOp {
+    const float* g; int H; BagLayout L; float p; int training; u64 seed; const unsigned char* keep; const float* inv_den;
+    const long long* rows;                                           // [n_sorted]: the output row m of each sorted position
+
+    struct Entry { long long m, j; float d, inv; int live; };
+
+    __device__ __forceinline__ Entry load(const long long* __restrict__ order, long long i, bool want, long long key) const
+    {
+        Entry E;
+        E.m = E.j = 0; E.d = E.inv = 0.0f; E.live = 0;
+        if (!want) return E;
+        const long long j = order[i], m = rows[i];
+        long long s0, s1, jb;
+        if (m < 0 || m >= L.n_rows || !bag_of(L, m, s0, s1, jb)) return E;
+        const long long t = s0 + (j - jb);                           // the entry's storage position
+        if (j < jb || t >= s1 || attr_id(L, t) != key) return E;
+        E.m = m; E.j = j; E.d = L.data[t]; E.inv = inv_den[m]; E.live = 1;
+        return E;
+    }
+
+    __device__ __forceinline__ void add(const Entry& E, int u, int f, float (&acc)[kCols]) const
+    {
+        if (!__shfl(E.live, u)) return;                              // wave-uniform
+        const long long m = __shfl(E.m, u), j = __shfl(E.j, u);
+        const float d = __shfl(E.d, u), inv = __shfl(E.inv, u);
+        const float scale = p < 1.0f ? 1.0f / (1.0f - p) : 0.0f;
+#pragma unroll
+        for (int c = 0; c < kCols; ++c) {
+            const int h = f + 64 * c;
+            if (h >= H) continue;
+            float x = (g[(size_t)m * H + h] * inv) * d;              // embedding_bag_backward_kernel's expression
+            if (training) {
+                const u64 el = (u64)j * (u64)H + (u64)h;
+                x *= keep ? (keep[el] ? scale : 0.0f) : keep_scale(seed, el, p, scale);
+            }
+            acc[c] += x;
+        }
+    }
+};
+
+__device__ __forceinline__ int run_length(u64 same)                 // how many of the lowest bits are set
+{
+    return ~same ? __builtin_ctzll(~same) : 64;
+}
+
+// dst[dest, 0:W] = the sequential sum, from 0.0f, of the entries of dest's segment of the sorted list, for every key
+// dest in [0, n_dest) that occurs.  One wave per workgroup; windows grid-stride.
+template <class Op>
+__global__ void __launch_bounds__(kGather)
+gather_sum_kernel(Op op, const long long* __restrict__ order, const long long* __restrict__ keys, long long n_sorted,
+                  long long n_dest, int W, float* __restrict__ dst)
+{
+    const int lane = threadIdx.x;
+    const long long n_win = (n_sorted + 63) >> 6;
+    for (long long win = blockIdx.x; win < n_win; win += gridDim.x) {          // wave-uniform
+        const long long base = win << 6, i = base + lane;
+        const long long key = i < n_sorted ? keys[i] : n_dest;
+        const bool valid = key >= 0 && key < n_dest;
+        u64 heads = __ballot(valid && (i == 0 || keys[i - 1] != key));
+        if (!heads) continue;
+        const typename Op::Entry mine = op.load(order, i, valid, key);
+        while (heads) {
+            const int l = __builtin_ctzll(heads);
+            heads &= heads - 1;
+            const long long dest = __shfl(key, l);
+            const int n0 = run_length(__ballot(key == dest) >> l);            // the segment's entries inside the window
+            float* out = dst + (size_t)dest * W;
+            for (int f0 = 0; f0 < W; f0 += 64 * kCols) {
+                float acc[kCols];
+#pragma unroll
+                for (int c = 0; c < kCols; ++c) acc[c] = 0.0f;
+                for (int u = 0; u < n0; ++u) op.add(mine, l + u, f0 + lane, acc);
+                if (l + n0 == 64) {                                               // it may run on past the window
+                    for (long long pos = base + 64; pos < n_sorted; pos += 64) {
+                        const long long q = pos + lane;
+                        const int n = run_length(__ballot(q < n_sorted && keys[q] == dest));
+                        if (n == 0) break;
+                        const typename Op::Entry next = op.load(order, q, lane < n, dest);
+                        for (int u = 0; u < n; ++u) op.add(next, u, f0 + lane, acc);
+                        if (n < 64) break;
+                    }
+                }
+#pragma unroll
+                for (int c = 0; c < kCols; ++c)
+                    if (f0 + 64 * c + lane < W) out[f0 + 64 * c + lane] = acc[c];
+            }
+        }
+    }
+}
+
+int gather_grid(int64_t n_sorted) { return (int)std::min<int64_t>(65535, (n_sorted + 63) / 64); }
+
+}  // namespace
+
+extern "C" {
+
+int gp_random_prop_rows_backward_det(int device, const float* d_grad_out, int32_t n_batch, int32_t feat_dim,
+                                     const int32_t* d_col, const double* d_val, const int32_t* d_filled, int32_t K,
+                                     const int32_t* d_batch_rows, int32_t n_samples, float dropnode_rate, int training,
+                                     uint64_t seed, const uint8_t* d_keep, int64_t keep_stride, float* d_grad_x,
+                                     int64_t n_nodes, const int64_t* d_order, const int64_t* d_sorted_keys, int64_t n_sorted,
+                                     float* d_inv_den, void* stream)
+{
+    const char* where = "gp_random_prop_rows_backward_det";
+    if (n_samples < 1 || n_samples > kMaxSamples || !(dropnode_rate >= 0.0f && dropnode_rate <= 1.0f))
+        return fail(GP_ERR_INVALID_ARG, where, "n_samples outside [1, 16] or dropnode_rate outside [0, 1]");
+    if (n_batch < 0 || n_nodes < 1 || feat_dim < 1 || K < 1 || K > GP_MAX_K || n_sorted < 0 || (d_keep && keep_stride < 1))
+        return fail(GP_ERR_INVALID_ARG, where, "bad size, K outside [1, 1024] or keep_stride < 1 with a mask");
+    if (n_batch == 0 || n_sorted == 0) return GP_OK;
+    if (!d_grad_out || !d_col || !d_val || !d_grad_x || !d_order || !d_sorted_keys || !d_inv_den)
+        return fail(GP_ERR_NULL, where, "a device pointer is NULL");
+    if (const int rc = set_device(device, where)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(rows_inv_den_kernel, dim3(std::min(n_batch, 65535)), dim3(kBlock), 0, s, d_val, d_filled, K, d_batch_rows,
+                       n_batch, n_samples, dropnode_rate, training, (u64)seed, d_keep, (long long)keep_stride, d_inv_den);
+    if (const int rc = launch_status("rows_inv_den_kernel")) return rc;
+    const RowsOp op = {d_grad_out, feat_dim, d_col, d_val, d_filled, K, d_batch_rows, n_batch, n_samples, dropnode_rate, training,
+                       (u64)seed, d_keep, (long long)keep_stride, d_inv_den};
+    hipLaunchKernelGGL(gather_sum_kernel<RowsOp>, dim3(gather_grid(n_sorted)), dim3(kGather), 0, s, op, (const long long*)d_order,
+                       (const long long*)d_sorted_keys, (long long)n_sorted, (long long)n_nodes, feat_dim, d_grad_x);
+    return launch_status("gather_sum_kernel<RowsOp>");
+}
+
+int gp_embedding_bag_backward_det(int device, const float* d_grad_out, int64_t n_vocab, int32_t dim,
+                                  const int64_t* d_offsets, int64_t n_src, const int64_t* d_nodes,
+                                  const int64_t* d_entry_base, int64_t n_rows, const void* d_attr_idx, int idx_bytes,
+                                  const float* d_attr_data, float dropout_rate, int training, uint64_t seed,
+                                  const uint8_t* d_keep, float* d_grad_weight, int32_t* d_n_bad, const int64_t* d_order,
+                                  const int64_t* d_sorted_keys, const int64_t* d_sorted_rows, int64_t n_sorted,
+                                  float* d_inv_den, void* stream)
+{
+    const char* where = "gp_embedding_bag_backward_det";
+    if (n_vocab < 0 || dim < 1 || n_src < 0 || n_rows < 0 || n_sorted < 0 || (idx_bytes != 4 && idx_bytes != 8) ||
+        !(dropout_rate >= 0.0f && dropout_rate <= 1.0f))
+        return fail(GP_ERR_INVALID_ARG, where, "negative size, dim < 1, idx_bytes not 4 or 8, or dropout rate outside [0, 1]");
+    if (n_rows == 0) return GP_OK;
+    if (!d_offsets || !d_attr_idx || !d_attr_data || !d_grad_out || !d_inv_den || (n_vocab > 0 && !d_grad_weight) ||
+        (n_sorted > 0 && (!d_order || !d_sorted_keys || !d_sorted_rows)))
+        return fail(GP_ERR_NULL, where, "a device pointer is NULL");
+    if (const int rc = set_device(device, where)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (d_n_bad && hipMemsetAsync(d_n_bad, 0, sizeof(int32_t), s) != hipSuccess) return fail(GP_ERR_HIP, where, "hipMemsetAsync failed");
+    const BagLayout L = {(const long long*)d_offsets, (long long)n_src, (const long long*)d_nodes, (const long long*)d_entry_base,
+                         (long long)n_rows, d_attr_idx, idx_bytes == 8, d_attr_data};
+    const int grid = (int)std::min<long long>(65535, (n_rows + kBlock / 64 - 1) / (kBlock / 64));
+    hipLaunchKernelGGL(bag_inv_den_kernel, dim3(grid), dim3(kBlock), 0, s, (long long)n_vocab, L, d_inv_den, d_n_bad);
+    if (const int rc = launch_status("bag_inv_den_kernel")) return rc;
+    if (n_sorted == 0 || n_vocab == 0) return GP_OK;
+    const BagOp op = {d_grad_out, dim, L, dropout_rate, training, (u64)seed, d_keep, d_inv_den, (const long long*)d_sorted_rows};
+    hipLaunchKernelGGL(gather_sum_kernel<BagOp>, dim3(gather_grid(n_sorted)), dim3(kGather), 0, s, op, (const long long*)d_order,
+                       (const long long*)d_sorted_keys, (long long)n_sorted, (long long)n_vocab, dim, d_grad_weight);
+    return launch_status("gather_sum_kernel<BagOp>");
+}
+
+}  // extern "C"

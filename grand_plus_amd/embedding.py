@@ -17,7 +17,10 @@ order, so the two forms give bitwise-equal outputs for the same seed.  `flatten_
 of a batch into the (neighbour nodes, scores, segment ids) the two consumers take.
 
 Gradients flow to `weight` only (attr_data and scores are constants, as in the reference).  The backward's
-fp32 atomic sums depend on arrival order: `weight.grad` is not bitwise reproducible from run to run.
+fp32 atomic sums depend on arrival order: `weight.grad` is not bitwise reproducible from run to run unless
+`deterministic=True`, which sorts the batch's entries by attribute id and sums each row of dW in a fixed order with
+plain stores (csrc/scatter_det.hip).  The flag chooses the backward alone: the forward is the same bit for
+bit.  None follows `torch.are_deterministic_algorithms_enabled()`.
 """
 from __future__ import annotations
 
@@ -27,7 +30,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _native
-from ._common import _check, _dev_index, _new_seed, _ptr, _stream
+from ._common import _check, _deterministic, _dev_index, _new_seed, _ptr, _stream
 
 
 class _Layout:
@@ -66,11 +69,60 @@ def _backward(weight_shape, grad_out, L, p, training, seed, keep):
     return dW
 
 
+def _det_order(L, n_entries, V):
+    """The sorted order the deterministic backward takes: (order, keys, rows).  Entry j < n_entries, in the batch's entry
+    order, lies in output row m = the first row whose bag ends after j (an empty bag ends where it starts: skipped) at
+    storage position t; its key is its attribute id, or the sentinel V when the id lies outside [0, V) or the entry
+    outside its bag, so that it sorts last.  A stable sort by key: order = the entry numbers j, keys ascending, rows =
+    m of each sorted entry.  Device ops only: nothing here reads the host."""
+    nnz = L.attr_idx.numel()
+    if L.nodes is None:
+        inside = None
+        starts = first = L.offsets[:-1]                                  # storage position = entry number
+        ends = L.offsets[1:]
+    else:
+        inside = (L.nodes >= 0) & (L.nodes < L.n_src)
+        src = L.nodes.clamp(0, max(L.n_src - 1, 0))
+        starts = L.offsets[src]                                          # storage position of the bag's first entry
+        first = L.base                                                   # its entry number
+        ends = first + torch.where(inside, L.offsets[src + 1] - starts, torch.zeros_like(starts))
+    j = torch.arange(n_entries, dtype=torch.int64, device=L.attr_idx.device)
+    m = torch.searchsorted(ends, j, right=True)
+    live = m < L.n_rows
+    m = m.clamp(max=L.n_rows - 1)
+    t = starts[m] + (j - first[m])
+    live &= (j >= first[m]) & (t >= 0) & (t < nnz)
+    if inside is not None:
+        live &= inside[m]
+    a = L.attr_idx[t.clamp(0, nnz - 1)].long()
+    keys, order = torch.sort(torch.where(live & (a >= 0) & (a < V), a, V), stable=True)
+    return order, keys, m[order]
+
+
+def _backward_det(weight_shape, grad_out, L, n_entries, p, training, seed, keep):
+    """_backward without atomics (csrc/scatter_det.hip): the entries ordered by attribute id (_det_order), one
+    gather kernel that sums each row of dW in that order."""
+    V, H = weight_shape
+    g = grad_out.contiguous()
+    dW = torch.zeros((V, H), dtype=torch.float32, device=g.device)
+    if L.n_rows == 0 or n_entries == 0 or L.attr_idx.numel() == 0:
+        return dW
+    order, keys, rows = _det_order(L, n_entries, V)
+    inv_den = torch.empty(_native.scatter_bag_workspace_bytes(L.n_rows) // 4, dtype=torch.float32, device=g.device)
+    rc = _native.lib().gp_embedding_bag_backward_det(
+        _dev_index(g), g.data_ptr(), V, H, *L.args(), float(p), int(bool(training)), ctypes.c_uint64(seed),
+        _ptr(keep), dW.data_ptr(), None, order.data_ptr(), keys.data_ptr(), rows.data_ptr(), order.numel(),
+        inv_den.data_ptr(), _stream(g))
+    _native.raise_for_status(rc)
+    return dW
+
+
 class _BagFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, weight, L, p, training, seed, keep, n_bad):
+    def forward(ctx, weight, L, p, training, seed, keep, n_bad, det_entries=None):
         ctx.save_for_backward(*L.tensors(), keep)
         ctx.args = (weight.shape, L.n_src, L.n_rows, p, training, seed)
+        ctx.det_entries = det_entries                                   # None: the atomic backward; else the entry count
         return _forward(weight, L, p, training, seed, keep, n_bad)
 
     @staticmethod
@@ -79,10 +131,16 @@ class _BagFn(torch.autograd.Function):
         offsets, nodes, base, attr_idx, attr_data, keep = ctx.saved_tensors
         shape, n_src, n_rows, p, training, seed = ctx.args
         L = _Layout(offsets, n_src, nodes, base, n_rows, attr_idx, attr_data)
-        return _backward(shape, grad_out, L, p, training, seed, keep), None, None, None, None, None, None
+        if ctx.det_entries is None:
+            dW = _backward(shape, grad_out, L, p, training, seed, keep)
+        else:
+            dW = _backward_det(shape, grad_out, L, ctx.det_entries, p, training, seed, keep)
+        return dW, None, None, None, None, None, None, None
 
 
-def _run(weight, L, n_entries, input_droprate, training, seed, keep, validate):
+def _run(weight, L, n_entries, input_droprate, training, seed, keep, validate, det_entries=None):
+    """det_entries: None for the atomic backward, else a callable that gives the number of entries the deterministic
+    backward sorts (called only when the gradient is wanted)."""
     _check(weight, torch.float32, "weight")
     if weight.dim() != 2:
         raise TypeError("weight must be a 2-D [V, H] table")
@@ -96,7 +154,8 @@ def _run(weight, L, n_entries, input_droprate, training, seed, keep, validate):
         seed = _new_seed()
     n_bad = torch.zeros(1, dtype=torch.int32, device=weight.device)
     if torch.is_grad_enabled() and weight.requires_grad:
-        out = _BagFn.apply(weight, L, float(input_droprate), bool(training), seed, keep, n_bad)
+        out = _BagFn.apply(weight, L, float(input_droprate), bool(training), seed, keep, n_bad,
+                           det_entries() if det_entries is not None else None)
     else:
         out = _forward(weight, L, input_droprate, training, seed, keep, n_bad)
     if validate:
@@ -107,7 +166,7 @@ def _run(weight, L, n_entries, input_droprate, training, seed, keep, validate):
 
 
 def embedding_bag(weight, attr_idx, node_idx, attr_data, input_droprate=0.0, training=True, seed=None, keep=None,
-                  validate=True):
+                  validate=True, deterministic=None, n_out=None):
     """Drop-in for `MLP.emb(attr_idx, node_idx, attr_data)` (model_mag.py:48-55) on CUDA tensors.
 
     weight [V, H] float32 (the `nn.Embedding` table, on the GPU); attr_idx [nnz] int64; node_idx [nnz] int64
@@ -115,7 +174,10 @@ def embedding_bag(weight, attr_idx, node_idx, attr_data, input_droprate=0.0, tra
     [node_idx[-1] + 1, H] float32; rows with an empty bag are zeros.  `keep` [nnz * H] uint8 replaces the
     internal dropout RNG (parity tests).  validate=True raises IndexError when an id lies outside [0, V)
     (one host synchronisation); with validate=False such ids are skipped, never read or written.
+    `deterministic` (None = torch.are_deterministic_algorithms_enabled()) chooses the backward: see the module docstring.
+    `n_out` (optional) is the number of output rows; given, it saves the host read of node_idx[-1] (as random_prop's).
     """
+    deterministic = _deterministic(deterministic)
     _check(attr_idx, torch.int64, "attr_idx")
     _check(node_idx, torch.int64, "node_idx")
     _check(attr_data, torch.float32, "attr_data")
@@ -125,14 +187,18 @@ def embedding_bag(weight, attr_idx, node_idx, attr_data, input_droprate=0.0, tra
     if nnz == 0:
         _check(weight, torch.float32, "weight")
         return weight.new_zeros((0, weight.shape[1]))
-    n_out = int(node_idx[-1].item()) + 1                                 # model_mag.py:51 dim_size
+    if n_out is None:
+        n_out = int(node_idx[-1].item()) + 1                             # model_mag.py:51 dim_size
+    elif int(n_out) < 1:
+        raise ValueError("n_out must be >= 1")
+    n_out = int(n_out)
     offsets = torch.searchsorted(node_idx, torch.arange(n_out + 1, dtype=torch.int64, device=node_idx.device))
     L = _Layout(offsets, n_out, None, None, n_out, attr_idx, attr_data)
-    return _run(weight, L, lambda: nnz, input_droprate, training, seed, keep, validate)
+    return _run(weight, L, lambda: nnz, input_droprate, training, seed, keep, validate, (lambda: nnz) if deterministic else None)
 
 
 def embedding_bag_csr(weight, attr_indptr, attr_indices, attr_data, nodes=None, input_droprate=0.0, training=True,
-                      seed=None, keep=None, validate=True):
+                      seed=None, keep=None, validate=True, deterministic=None):
     """`MLP.emb` over the bags of `nodes` in a node-attribute CSR resident on the GPU.
 
     attr_indptr [N + 1] int64, attr_indices [nnz] int32, attr_data [nnz] float32 (the scipy CSR's arrays);
@@ -140,7 +206,12 @@ def embedding_bag_csr(weight, attr_indptr, attr_indices, attr_data, nodes=None, 
     row m built from the bag of node nodes[m].  Equals `embedding_bag` on `features[nodes].nonzero()`
     bitwise for the same seed (same entry order, same dropout keys).  Replaces the slicing, `.nonzero()`,
     upload and host-side lookup of model_mag.py:339-347.
+    `deterministic` (None = torch.are_deterministic_algorithms_enabled()) chooses the backward: see the module docstring.
+    With `nodes` given the number of entries of the batch is data-dependent, and the deterministic backward needs it as
+    a host number to size its sort: that one count is read back here, in the forward call (one host synchronisation;
+    only when the gradient is wanted).  With nodes=None the count is `attr_indices.numel()`: no host read.
     """
+    deterministic = _deterministic(deterministic)
     _check(attr_indptr, torch.int64, "attr_indptr")
     _check(attr_indices, torch.int32, "attr_indices")
     _check(attr_data, torch.float32, "attr_data")
@@ -150,6 +221,7 @@ def embedding_bag_csr(weight, attr_indptr, attr_indices, attr_data, nodes=None, 
     if nodes is None:
         L = _Layout(attr_indptr, N, None, None, N, attr_indices, attr_data)
         n_entries = lambda: int(attr_indptr[-1].item())                 # noqa: E731  (j = storage position)
+        det_entries = attr_indices.numel                                # every stored entry is sorted: no host read
     else:
         _check(nodes, torch.int64, "nodes")
         inside = (nodes >= 0) & (nodes < N)
@@ -157,8 +229,8 @@ def embedding_bag_csr(weight, attr_indptr, attr_indices, attr_data, nodes=None, 
         lens = torch.where(inside, attr_indptr[nc + 1] - attr_indptr[nc], torch.zeros_like(nc)) if N > 0 else torch.zeros_like(nodes)
         base = torch.cumsum(lens, 0) - lens                            # entry order: the bags one after another
         L = _Layout(attr_indptr, N, nodes, base, nodes.numel(), attr_indices, attr_data)
-        n_entries = lambda: int(lens.sum().item())                     # noqa: E731
-    return _run(weight, L, n_entries, input_droprate, training, seed, keep, validate)
+        n_entries = det_entries = lambda: int(lens.sum().item())       # noqa: E731
+    return _run(weight, L, n_entries, input_droprate, training, seed, keep, validate, det_entries if deterministic else None)
 
 
 def flatten_rows(col, val, filled, K, batch_rows):

@@ -271,17 +271,19 @@ class MagMLP(_MLPBase, nn.Module):
         self.node_norm = node_norm
         self.reset_param()
 
-    def emb(self, attr_idx, node_idx, attr_data, seed=None, keep=None):
-        """MLP.emb (model_mag.py:48-55) through embedding.embedding_bag (the reference's COO arguments)."""
+    def emb(self, attr_idx, node_idx, attr_data, seed=None, keep=None, deterministic=None):
+        """MLP.emb (model_mag.py:48-55) through embedding.embedding_bag (the reference's COO arguments); `deterministic`
+        is passed through."""
         from .embedding import embedding_bag
         return embedding_bag(self.embeds.weight, attr_idx, node_idx, attr_data, self.input_droprate, self.training,
-                             seed, keep)
+                             seed, keep, deterministic=deterministic)
 
-    def emb_csr(self, attr_indptr, attr_indices, attr_data, nodes=None, seed=None, keep=None):
-        """MLP.emb over the bags of `nodes` in a GPU-resident node-attribute CSR (embedding.embedding_bag_csr)."""
+    def emb_csr(self, attr_indptr, attr_indices, attr_data, nodes=None, seed=None, keep=None, deterministic=None):
+        """MLP.emb over the bags of `nodes` in a GPU-resident node-attribute CSR (embedding.embedding_bag_csr);
+        `deterministic` is passed through."""
         from .embedding import embedding_bag_csr
         return embedding_bag_csr(self.embeds.weight, attr_indptr, attr_indices, attr_data, nodes, self.input_droprate,
-                                 self.training, seed, keep)
+                                 self.training, seed, keep, deterministic=deterministic)
 
     def _layers(self):
         return [(fc, bn if self.use_bn else None, True, bool(self.node_norm), False, self.hidden_droprate)

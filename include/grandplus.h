@@ -285,7 +285,8 @@ int gp_random_prop_coo_backward(int device, const float* d_grad_out, int64_t n_o
                                 float* d_grad_feats, void* stream);
 
 /* d_grad_x[col[r,k],:] += w'_{r,k} / (den_b + 1e-12) * d_grad_out[b,:], r = d_batch_rows[b], into a
- * caller-zeroed d_grad_x[n_nodes x feat_dim].  fp32 global atomics: not bitwise reproducible.
+ * caller-zeroed d_grad_x[n_nodes x feat_dim].  fp32 global atomics: not bitwise reproducible unless `deterministic=True`
+ * (Python), which calls gp_random_prop_rows_backward_det of grandplus_scatter.h in its place.
  * Column ids outside [0, n_nodes) are skipped. */
 int gp_random_prop_rows_backward(int device, const float* d_grad_out, int32_t n_batch, int32_t feat_dim,
                                  const int32_t* d_col, const double* d_val, const int32_t* d_filled, int32_t K,
@@ -310,7 +311,8 @@ int gp_embedding_bag(int device, const float* d_weight, int64_t n_vocab, int32_t
 /* Its backward into a dense, caller-zeroed d_grad_weight[n_vocab x dim] (nn.Embedding(sparse=False)):
  *   dW[a_j,:] += keep_{j,:}/(1-rate) * d_j / (den_m + 1e-10) * d_grad_out[m,:]
  * Same bag layout and counter as gp_embedding_bag; out-of-range ids are never written.  fp32 global
- * atomics (one 256-B wave-instruction per entry at dim = 64): not bitwise reproducible. */
+ * atomics (one 256-B wave-instruction per entry at dim = 64): not bitwise reproducible unless `deterministic=True`
+ * (Python), which calls gp_embedding_bag_backward_det of grandplus_scatter.h in its place. */
 int gp_embedding_bag_backward(int device, const float* d_grad_out, int64_t n_vocab, int32_t dim,
                               const int64_t* d_offsets, int64_t n_src, const int64_t* d_nodes, const int64_t* d_entry_base, int64_t n_rows,
                               const void* d_attr_idx, int idx_bytes, const float* d_attr_data,
@@ -355,7 +357,7 @@ int gp_random_prop_coo_multi_backward(int device, const float* d_grad_out, int64
 
 /* d_grad_x[col[r,k],:] += sum_s w'_{s,r,k} / (den_{s,b} + 1e-12) * d_grad_out[s,b,:] into a caller-zeroed d_grad_x: the
  * samples are summed in registers, then one fp32 atomic per element and entry (per chunk of samples when K > 962).
- * Not bitwise reproducible. */
+ * Not bitwise reproducible unless `deterministic=True` (Python: gp_random_prop_rows_backward_det, grandplus_scatter.h). */
 int gp_random_prop_rows_multi_backward(int device, const float* d_grad_out, int32_t n_batch, int32_t feat_dim,
                                        const int32_t* d_col, const double* d_val, const int32_t* d_filled, int32_t K,
                                        const int32_t* d_batch_rows, int32_t n_samples, float dropnode_rate, int training, uint64_t seed,
@@ -511,6 +513,10 @@ int gp_clip_adam_step(int device, const gp_optim_tensor* tensors, int32_t n_tens
 /* The head of an evaluation (the two evaluation entry points, the GP_EVAL_* flags and GP_EVAL_WORKSPACE_BYTES):
  * declared in a header of their own, part of this ABI. */
 #include "grandplus_eval.h"
+
+/* The deterministic scatter backwards (sort-then-gather forms of the two atomic backwards above, their order
+ * contract and the GP_SCATTER_*_WORKSPACE_BYTES macros): declared in a header of their own, part of this ABI. */
+#include "grandplus_scatter.h"
 
 /* ------------------------------------------------------------------------------------------
  * exact full-graph feature propagation of the inference path, reference
