@@ -81,6 +81,11 @@ def grand_loss_workspace_bytes(n_rows: int) -> int:
     return 20 * n_rows
 
 
+def mlp_infer_workspace_bytes(n_rows: int, f_in: int) -> int:
+    """GP_MLP_INFER_WORKSPACE_BYTES of grandplus_infer.h."""
+    return (4 * (n_rows + 2 * f_in) + 15) // 16 * 16
+
+
 class GpStats(ctypes.Structure):
     _fields_ = [
         ("rows", ctypes.c_int64), ("pushes", ctypes.c_int64), ("edges", ctypes.c_int64),
@@ -189,6 +194,12 @@ _SCATTER_SIGNATURES = {
     "gp_embedding_bag_backward_det": (_int, _bag[:-1] + [_vp, _vp, _vp, _i64, _vp, _vp], False),
 }
 SCATTER_EXPORTS = tuple(_SCATTER_SIGNATURES)
+# The eval-only MLP block, which include/grandplus_infer.h declares (grandplus.h includes it): the same convention, held
+# against that header type by type by tests/test_host_infer.py.
+_INFER_SIGNATURES = {
+    "gp_mlp_infer_block": (_int, [_int, _vp, _i64, _i32, _i32, _vp, _vp, _int, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp], False),
+}
+INFER_EXPORTS = tuple(_INFER_SIGNATURES)
 
 _LIB = None
 
@@ -218,7 +229,7 @@ def lib():
     except ImportError:
         pass
     L = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes, required) in {**_SIGNATURES, **_EVAL_SIGNATURES, **_SCATTER_SIGNATURES}.items():
+    for name, (restype, argtypes, required) in {**_SIGNATURES, **_EVAL_SIGNATURES, **_SCATTER_SIGNATURES, **_INFER_SIGNATURES}.items():
         if not required and not hasattr(L, name):
             setattr(L, name, _missing(name))
             continue

@@ -11,7 +11,8 @@ model in eval mode and `eval_head` into one shared buffer, and one `eval_reduce`
 `Graph.propagate_features`, the model over all N rows into one [N, C] device tensor, one `eval_head` with
 `rows = label_rows = idx_test` and one `eval_reduce`.  Both return 0-dim device tensors: `.item()` is the caller's
 choice, and after the position lookup nothing synchronises with the host (both run that part under
-`torch.cuda.set_sync_debug_mode("error")`).
+`torch.cuda.set_sync_debug_mode("error")`).  `local_logits` is the reference's `get_local_logits` on the device, over
+`model.infer`; `predict(..., infer=True)` uses it.
 
 Labels equal to `ignore_index` are left out of the loss as in `F.nll_loss`; other labels outside [0, C) and indices
 outside their array are never used as an address: they are flagged, left out and counted.  The accuracy divides by the
@@ -211,7 +212,18 @@ def valid(model, rows, features, idx_val, labels, batch_size=10000, dropnode_rat
     return (loss, acc, counts) if return_counts else (loss, acc)
 
 
-def predict(graph, features, model, idx_test, labels, prop_mode, order, alpha=0.2, batch_size_logits=10000, return_preds=False):
+def local_logits(model, attr_mat, batch_size=10000, out=None):
+    """The reference's `get_local_logits` (model.py:169-178) with the logits staying on the device: the model in eval
+    semantics over every row of attr_mat (float32 CUDA [N, F], contiguous), batch_size rows at a time, as one [N, C]
+    device tensor (`out`, if given).  A thin wrapper over `model.infer`: the module's training flag is not
+    touched, nothing synchronises, and the rows get the same bits whatever the batch size."""
+    if not isinstance(model, torch.nn.Module) or not hasattr(model, "infer"):
+        raise TypeError("local_logits: model must be a GrandPlusMLP or MagMLP")
+    return model.infer(attr_mat, out=out, batch_size=batch_size)
+
+
+def predict(graph, features, model, idx_test, labels, prop_mode, order, alpha=0.2, batch_size_logits=10000, return_preds=False,
+            infer=False):
     """The reference's `predict` (model.py:181-224) on the GPU: the test accuracy as a 0-dim float32 device tensor, and
     with return_preds also the int32 [len(idx_test)] predictions.
 
@@ -219,7 +231,8 @@ def predict(graph, features, model, idx_test, labels, prop_mode, order, alpha=0.
     node ids (any order, duplicates allowed); labels int64 CUDA [N].  `Graph.propagate_features`, then the model in eval
     mode over all N rows, batch_size_logits at a time, into one [N, C] device tensor; one head call gathers
     logits[idx_test] and labels[idx_test].  No logit reaches the host.  An id outside [0, N) is counted as a bad row
-    (prediction -1), never read."""
+    (prediction -1), never read.  infer=True runs the model through `local_logits` (the inference GEMM of DESIGN §7j,
+    each batch written straight into the [N, C] tensor) in place of the batch loop over the training kernels."""
     _check_common(model, features, labels, "predict")
     batch_size_logits = int(batch_size_logits)
     if batch_size_logits < 1:
@@ -229,7 +242,9 @@ def predict(graph, features, model, idx_test, labels, prop_mode, order, alpha=0.
     N = features.shape[0]
     with _NoSync(model):
         prop = graph.propagate_features(features, prop_mode, order, alpha)
-        if N <= batch_size_logits:
+        if infer:
+            logits = local_logits(model, prop, batch_size_logits)
+        elif N <= batch_size_logits:
             logits = model(prop)
         else:
             logits = None

@@ -15,6 +15,9 @@ Both keep the reference's submodules (`fcs`, `bns`, `embeds`), so a `state_dict`
 layer l, sample s, entry b * F + f uses the counter hash on `layer_seed(seed, l, s)` (grandplus.h), or an explicit uint8
 keep mask per layer.  Calls without grad (eval, `torch.no_grad`) run the forward kernels only.  There is no fallback:
 `reference_forward` is the torch formulation kept for comparison and benchmarks, never taken silently.
+
+`infer` is the eval-only forward over any number of rows: `gp_mlp_infer_block` of csrc/mlp_infer.hip per
+layer, on a GEMM tiled for millions of rows; it is opt-in and leaves `forward` as it is.
 """
 from __future__ import annotations
 
@@ -191,6 +194,59 @@ def _torch_block(x, fc, bn, relu, norm, detach, p, training):
     return fc(x)
 
 
+def _check_infer(X, out, batch_size, layers):
+    """Every host check of `infer` before the first launch; the CPU-tensor check comes last, as in _check_input."""
+    if not isinstance(X, torch.Tensor):
+        raise ValueError("X must be a tensor")
+    if X.dtype != torch.float32:
+        raise ValueError(f"X must be float32, got {X.dtype}")
+    if X.dim() != 2:
+        raise ValueError(f"infer takes X [B, F] (one sample, any number of rows), got {tuple(X.shape)}")
+    if not X.is_contiguous():
+        raise ValueError("X must be contiguous")
+    B, F = X.shape
+    if batch_size is not None and int(batch_size) < 1:
+        raise ValueError(f"batch_size must be >= 1 or None, got {batch_size}")
+    C = F
+    for fc, bn, *_ in layers:
+        if fc.weight.shape[1] != C:
+            raise ValueError(f"the layer takes {fc.weight.shape[1]} features, its input has {C}")
+        if bn is not None:
+            _check_bn(bn)
+            if bn.num_features != C:
+                raise ValueError(f"BatchNorm1d has {bn.num_features} features, its input has {C}")
+        for name, t in (("weight", fc.weight), ("bias", fc.bias)) + ((("bn weight", bn.weight), ("bn bias", bn.bias),
+                                                                       ("running_mean", bn.running_mean),
+                                                                       ("running_var", bn.running_var)) if bn is not None else ()):
+            if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+                raise ValueError(f"{name} must be a contiguous float32 tensor")
+        C = fc.weight.shape[0]
+    if out is not None:
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError("out must be a contiguous float32 tensor")
+        if tuple(out.shape) != (B, C):
+            raise ValueError(f"out must be [B, C] = {(B, C)}, got {tuple(out.shape)}")
+        if out.device != X.device:
+            raise ValueError(f"out must be on X's device {X.device}, got {out.device}")
+    if not X.is_cuda:
+        raise ValueError("the MLP runs on the GPU only: X must be a CUDA tensor (no CPU fallback)")
+    if layers and layers[0][0].weight.device != X.device:
+        raise ValueError(f"X is on {X.device}, the parameters on {layers[0][0].weight.device}")
+    return C
+
+
+def _infer_block(x, fc, bn, relu, norm, out, ws):
+    """One eval block on x [n, F] into out [n, N] (gp_mlp_infer_block); ws: the caller's scratch."""
+    flags = (_native.GP_MLP_RELU if relu else 0) | (_native.GP_MLP_NORM if norm else 0) | \
+            (_native.GP_MLP_BN if bn is not None else 0)
+    rc = _native.lib().gp_mlp_infer_block(
+        x.device.index, x.data_ptr(), x.shape[0], x.shape[1], fc.weight.shape[0], fc.weight.data_ptr(), _ptr(fc.bias), flags,
+        _ptr(bn.weight) if bn is not None else None, _ptr(bn.bias) if bn is not None else None,
+        _ptr(bn.running_mean) if bn is not None else None, _ptr(bn.running_var) if bn is not None else None,
+        float(bn.eps) if bn is not None else 1e-5, out.data_ptr(), _ptr(ws), _stream(x))
+    _native.raise_for_status(rc)
+
+
 class _MLPBase:
     def reset_param(self):
         for lin in self.fcs:
@@ -203,6 +259,37 @@ class _MLPBase:
         """X [S, B, F] or [B, F] float32 CUDA, contiguous -> [S, B, C] or [B, C].  seed: the dropout seed of this call
         (None = a fresh one); keep: one uint8 [S, B, F_l] mask (or None) per layer in place of the hash."""
         return _run(self, X, seed, keep, self._layers())
+
+    @torch.no_grad()
+    def infer(self, X, out=None, batch_size=None):
+        """The model in eval semantics over any number of rows: X [B, F] float32 CUDA, contiguous (a row
+        slice is fine) -> [B, C].  Running statistics, no dropout, whatever `self.training` says: the flag, the running
+        statistics and num_batches_tracked are neither read nor written, and the result never requires grad.
+        batch_size bounds the hidden activations: rows go through the layers that many at a time (None: all at once),
+        the last layer writing straight into its row slice of the result; every row gets the same bits either way.
+        out: a contiguous float32 [B, C] on X's device, written and returned.  One gp_mlp_infer_block per layer and
+        chunk; no host synchronisation."""
+        layers = self._layers()
+        C = _check_infer(X, out, batch_size, layers)
+        B = X.shape[0]
+        if not layers:                                       # a MagMLP that is its embedding alone
+            return X if out is None else out.copy_(X)
+        if out is None:
+            out = torch.empty((B, C), dtype=torch.float32, device=X.device)
+        step = B if batch_size is None else min(int(batch_size), B)
+        if B == 0:
+            return out
+        need = any(norm or bn is not None for _fc, bn, _relu, norm, *_ in layers)
+        ws = torch.empty(_native.mlp_infer_workspace_bytes(step, max(fc.weight.shape[1] for fc, *_ in layers)),
+                         dtype=torch.uint8, device=X.device) if need else None
+        for start in range(0, B, step):
+            x = X[start:start + step]
+            for l, (fc, bn, relu, norm, _detach, _p) in enumerate(layers):
+                y = out[start:start + step] if l == len(layers) - 1 else \
+                    torch.empty((x.shape[0], fc.weight.shape[0]), dtype=torch.float32, device=X.device)
+                _infer_block(x, fc, bn, relu, norm, y, ws)
+                x = y
+        return out
 
     def reference_forward(self, X):
         """The reference's MLP.forward on one [B, F] sample with torch ops and this module's parameters (torch's own

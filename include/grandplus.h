@@ -518,6 +518,10 @@ int gp_clip_adam_step(int device, const gp_optim_tensor* tensors, int32_t n_tens
  * contract and the GP_SCATTER_*_WORKSPACE_BYTES macros): declared in a header of their own, part of this ABI. */
 #include "grandplus_scatter.h"
 
+/* The eval-only MLP block over any number of rows (the inference entry point, its arithmetic and row-independence
+ * contracts and GP_MLP_INFER_WORKSPACE_BYTES): declared in a header of its own, part of this ABI. */
+#include "grandplus_infer.h"
+
 /* ------------------------------------------------------------------------------------------
  * exact full-graph feature propagation of the inference path, reference
  * predict() (model.py:181-224), lines 186-210.  mode 0 = ppr, 1 = avg, 2 = single (args.prop_mode);
