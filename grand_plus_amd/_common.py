@@ -13,6 +13,7 @@ import torch
 _M64 = 2**64 - 1
 _GOLDEN = 0x9E3779B97F4A7C15
 _LAYER_MUL = 0xA0761D6478BD642F
+_SLOT_MUL = 0xE7037ED1A0B428DB
 
 _seed_counter = itertools.count(0x5EED)
 
@@ -37,6 +38,11 @@ def sample_seed(seed: int, s: int) -> int:
 def layer_seed(seed: int, layer: int, s: int = 0) -> int:
     """Dropout seed of (layer, sample s) of a call with `seed`: GP_MLP_LAYER_SEED(gp_sample_seed(seed, s), layer)."""
     return _mix(sample_seed(seed, s) ^ (((layer + 1) * _LAYER_MUL) & _M64))
+
+
+def mag_slot_seed(seed: int, s: int, e: int) -> int:
+    """Input-dropout seed of (sample s, slot e = r * K + k) of a mag_prop_rows call: GP_MAG_SLOT_SEED of grandplus_mag.h."""
+    return _mix(sample_seed(seed, s) ^ (((e + 1) * _SLOT_MUL) & _M64))
 
 
 def _check(t, dtype, name):

@@ -200,6 +200,15 @@ _INFER_SIGNATURES = {
     "gp_mlp_infer_block": (_int, [_int, _vp, _i64, _i32, _i32, _vp, _vp, _int, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp], False),
 }
 INFER_EXPORTS = tuple(_INFER_SIGNATURES)
+# MAG's fused front end, which include/grandplus_mag.h declares (grandplus.h includes it): the same convention, held
+# against that header type by type by tests/test_host_mag_rows.py.  The backward takes the forward's arguments with
+# grad_out for the table and dW for the output, and no counter.
+_mag = [_i64, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _i32, _f32, _f32, _int, _u64, _vp, _i64]
+_MAG_SIGNATURES = {
+    "gp_mag_prop_rows": (_int, [_int, _vp] + _mag + [_vp, _vp, _vp], False),
+    "gp_mag_prop_rows_backward": (_int, [_int, _vp] + _mag + [_vp, _vp], False),
+}
+MAG_EXPORTS = tuple(_MAG_SIGNATURES)
 
 _LIB = None
 
@@ -229,7 +238,8 @@ def lib():
     except ImportError:
         pass
     L = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes, required) in {**_SIGNATURES, **_EVAL_SIGNATURES, **_SCATTER_SIGNATURES, **_INFER_SIGNATURES}.items():
+    for name, (restype, argtypes, required) in {**_SIGNATURES, **_EVAL_SIGNATURES, **_SCATTER_SIGNATURES, **_INFER_SIGNATURES,
+                                              **_MAG_SIGNATURES}.items():
         if not required and not hasattr(L, name):
             setattr(L, name, _missing(name))
             continue

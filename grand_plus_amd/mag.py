@@ -1,0 +1,197 @@
+"""MAG's front end fused on the resident rows: `MLP.emb` of every neighbour of a batch followed by
+`random_prop` (model_mag.py:48-55, 80-86, 354-356) as ONE op over csrc/mag_prop.hip, and MAG's `valid` / `predict` over it.
+
+    e_{s,k}   = sum_t dropout(W[a_t], input_droprate) * d_t / (sum_t d_t + 1e-10)        t over the bag of col[r, k]
+    out[s, b] = sum_k w'_{s,k} e_{s,k} / (sum_k w'_{s,k} + 1e-12),   w' = float(val[r, k]) * DropNode mask,  r = batch_rows[b]
+
+`mag_prop_rows` replaces `flatten_rows -> embedding_bag_csr(nodes=...) -> random_prop(..., samples=S)`: one launch forward,
+`torch.zeros` and one launch backward, no [B*K, H] intermediate, no bag layout rebuilt per call and no host read, so a MAG
+step runs under `torch.cuda.set_sync_debug_mode("error")` like every other step here.  The DropNode mask is
+`random_prop_rows`'s for the same seed (entry r*K + k); the input dropout of (sample s, slot e, bag position t, column h)
+is keyed (`mag_slot_seed(seed, s, e)`, t*H + h).  out[s] of an S-sample call equals the single-sample call with
+`sample_seed(seed, s)` (or `keep[s]`) bit for bit, and the forward is bitwise the same run to run.
+
+The gradient reaches `weight` only.  The backward adds into a dense dW with fp32 atomics: it is not bitwise reproducible,
+and there is no deterministic variant; asked for one (`deterministic=True`, or torch's deterministic mode), a call that wants
+a gradient raises and names the composed path, which has one.  There is no CPU fallback.
+"""
+from __future__ import annotations
+
+import ctypes
+
+import torch
+from torch.autograd.function import once_differentiable
+
+from . import _native
+from ._common import _check, _deterministic, _dev_index, _new_seed, _ptr, _stream
+
+
+class _Call:
+    """The constant operands of one call, which the forward and the backward pass to the library alike: the attribute
+    CSR, the resident rows, the batch and the masks' parameters."""
+
+    def __init__(self, tensors, S_rows, K, B, samples, p_node, p_in, training, seed):
+        self.tensors = tensors             # attr_indptr, attr_indices, attr_data, col, val, filled, batch_rows, keep
+        self.scalars = (S_rows, K, B, samples, p_node, p_in, training, seed)
+
+    def args(self):
+        attr_indptr, attr_indices, attr_data, col, val, filled, batch_rows, keep = self.tensors
+        S_rows, K, B, samples, p_node, p_in, training, seed = self.scalars
+        return (attr_indptr.data_ptr(), attr_indices.data_ptr(), attr_data.data_ptr(), attr_indptr.numel() - 1, col.data_ptr(),
+                val.data_ptr(), _ptr(filled), S_rows, K, _ptr(batch_rows), B, samples, float(p_node), float(p_in),
+                int(bool(training)), ctypes.c_uint64(seed), _ptr(keep), col.numel())
+
+
+def _forward(weight, call, n_bad):
+    V, H = weight.shape
+    _, _, B, S = call.scalars[:4]
+    out = torch.empty((S, B, H), dtype=torch.float32, device=weight.device)
+    rc = _native.lib().gp_mag_prop_rows(_dev_index(weight), weight.data_ptr(), V, H, *call.args(), out.data_ptr(),
+                                        n_bad.data_ptr(), _stream(weight))
+    _native.raise_for_status(rc)
+    return out
+
+
+def _backward(weight_shape, grad_out, call):
+    V, H = weight_shape
+    g = grad_out.contiguous()
+    dW = torch.zeros((V, H), dtype=torch.float32, device=g.device)
+    rc = _native.lib().gp_mag_prop_rows_backward(_dev_index(g), g.data_ptr(), V, H, *call.args(), dW.data_ptr(), _stream(g))
+    _native.raise_for_status(rc)
+    return dW
+
+
+class _MagRowsFn(torch.autograd.Function):
+    """mag_prop_rows with the gradient to weight (summed over the samples)."""
+
+    @staticmethod
+    def forward(ctx, weight, call, n_bad):
+        ctx.save_for_backward(*call.tensors)
+        ctx.args = (weight.shape, call.scalars)
+        return _forward(weight, call, n_bad)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        shape, scalars = ctx.args
+        return _backward(shape, grad_out, _Call(ctx.saved_tensors, *scalars)), None, None
+
+
+def mag_prop_rows(weight, attr_indptr, attr_indices, attr_data, col, val, filled, K, batch_rows=None, *, samples=1,
+                  dropnode_rate=0.5, input_droprate=0.0, training=True, seed=None, keep=None, validate=False, deterministic=None):
+    """The S augmented embeddings of a batch of resident rows, in one launch.
+
+    weight [V, H] float32 (the `nn.Embedding` table); attr_indptr [N + 1] int64, attr_indices [nnz] int32, attr_data [nnz]
+    float32 (the node-attribute CSR resident on the GPU); col int32 [S_rows * K], val float64 [S_rows * K], filled int32
+    [S_rows] or None (every slot filled) as `Graph.gfpush_device` returns them; batch_rows int32 [B] (None: every row).
+    Returns [B, H] float32 for samples = 1 and [S, B, H] otherwise (keep: uint8 [S, S_rows * K], the DropNode mask of
+    `random_prop_rows`).  Differentiable with respect to `weight`: `torch.zeros` and one launch, fp32 atomics.
+    A batch row outside [0, S_rows), a column outside [0, N) and an attribute id outside [0, V) are never used as an
+    address; they contribute nothing and are counted: validate=True reads the count back (the only host read of this
+    function) and raises IndexError.
+    `deterministic`: None follows `torch.are_deterministic_algorithms_enabled()`; when it resolves to True and a gradient
+    is wanted the call raises RuntimeError (this backward has no deterministic variant)."""
+    deterministic = _deterministic(deterministic)
+    if not isinstance(samples, int) or not 1 <= samples <= _native.GP_MAX_SAMPLES:
+        raise ValueError(f"samples must be an int in [1, {_native.GP_MAX_SAMPLES}], got {samples!r}")
+    _check(weight, torch.float32, "weight")
+    if weight.dim() != 2 or weight.shape[0] < 1 or weight.shape[1] < 1:
+        raise TypeError("weight must be a 2-D [V, H] table")
+    _check(attr_indptr, torch.int64, "attr_indptr")
+    _check(attr_indices, torch.int32, "attr_indices")
+    _check(attr_data, torch.float32, "attr_data")
+    if attr_indptr.numel() < 1 or attr_data.numel() != attr_indices.numel():
+        raise ValueError("attr_indptr needs N + 1 entries; attr_indices and attr_data the same length")
+    _check(col, torch.int32, "col")
+    _check(val, torch.float64, "val")
+    K = int(K)
+    if not 1 <= K <= _native.GP_MAX_K:
+        raise ValueError(f"K must be in [1, {_native.GP_MAX_K}], got {K}")
+    if col.numel() % K or val.numel() != col.numel():
+        raise ValueError("col and val must hold S_rows * K entries each")
+    S_rows = col.numel() // K
+    if filled is not None:
+        _check(filled, torch.int32, "filled")
+        if filled.numel() != S_rows:
+            raise ValueError(f"filled must hold one entry per row ({S_rows}), got {filled.numel()}")
+    if batch_rows is not None:
+        _check(batch_rows, torch.int32, "batch_rows")
+    B = S_rows if batch_rows is None else batch_rows.numel()
+    for name, p in (("dropnode_rate", dropnode_rate), ("input_droprate", input_droprate)):
+        if not 0.0 <= float(p) <= 1.0:
+            raise ValueError(f"{name} must lie in [0, 1]")
+    if keep is not None:
+        _check(keep, torch.uint8, "keep")
+        if keep.numel() != samples * col.numel():
+            raise ValueError(f"keep must hold samples x {col.numel()} = {samples * col.numel()} entries, got {keep.numel()}")
+    for name, t in (("attr_indptr", attr_indptr), ("attr_indices", attr_indices), ("attr_data", attr_data), ("col", col), ("val", val),
+                    ("filled", filled), ("batch_rows", batch_rows), ("keep", keep)):
+        if t is not None and t.device != weight.device:
+            raise TypeError(f"{name} must be on {weight.device}, got {t.device} (no CPU fallback)")
+    wants_grad = torch.is_grad_enabled() and weight.requires_grad
+    if deterministic and wants_grad:
+        raise RuntimeError("mag_prop_rows has no deterministic backward (fp32 atomics into dW); for a reproducible gradient use the "
+                           "composed path with deterministic=True: flatten_rows -> embedding_bag_csr(nodes=..., deterministic=True) "
+                           "-> random_prop")
+    if seed is None:
+        seed = _new_seed()
+    call = _Call((attr_indptr, attr_indices, attr_data, col, val, filled, batch_rows, keep), S_rows, K, B, samples,
+                 float(dropnode_rate), float(input_droprate), bool(training), seed)
+    n_bad = torch.zeros(1, dtype=torch.int32, device=weight.device)
+    out = _MagRowsFn.apply(weight, call, n_bad) if wants_grad else _forward(weight, call, n_bad)
+    if validate:
+        bad = int(n_bad.item())
+        if bad:
+            raise IndexError(f"mag_prop_rows: {bad} batch row(s), column(s) or attribute id(s) out of range")
+    return out[0] if samples == 1 else out
+
+
+def valid_mag(model, rows, attr_indptr, attr_indices, attr_data, idx_val, labels, batch_size=100, dropnode_rate=0.5,
+              return_counts=False):
+    """MAG's `valid` (model_mag.py:145-177) on the GPU: (loss, acc) as 0-dim float32 device tensors.
+
+    model: a MagMLP; rows: the RowMatrix that holds `topk_adj`; the node-attribute CSR as for `mag_prop_rows`; idx_val: the
+    validation node ids (every one a seed of `rows`); labels int64 CUDA [N].  The positions of idx_val are looked up once
+    (one check, KeyError for a node that is no seed); then per batch `model.emb_rows` in eval mode (only the batch's
+    neighbours are embedded, with the weights as they are now), the MLP and `eval_head` into one shared buffer, and one
+    `eval_reduce`: nothing synchronises.  The model's training flag is restored.  Same returns as `valid`."""
+    from .evaluate import _NoSync, _node_ids, _on_gpu, eval_buffers, eval_head, eval_reduce
+    from .rows import RowMatrix
+    if not isinstance(model, torch.nn.Module) or not hasattr(model, "emb_rows"):
+        raise TypeError("valid_mag: model must be a MagMLP")
+    if not isinstance(rows, RowMatrix):
+        raise TypeError("rows must be a RowMatrix")
+    if not isinstance(labels, torch.Tensor) or labels.dtype != torch.int64:
+        raise TypeError("labels must be an int64 CUDA tensor")
+    batch_size = int(batch_size)
+    if batch_size < 1:
+        raise ValueError(f"batch_size must be >= 1, got {batch_size}")
+    _on_gpu("valid_mag", model.embeds.weight, labels=labels, attr_indptr=attr_indptr, col=rows.col)
+    dev = rows.col.device
+    idx = _node_ids(idx_val, "idx_val", dev)
+    n = idx.numel()
+    pos = rows.batch_positions(idx, check=True) if n else None
+    buf = eval_buffers(n, dev)
+    with _NoSync(model):
+        for start in range(0, n, batch_size):
+            end = min(start + batch_size, n)
+            aug = model.emb_rows(attr_indptr, attr_indices, attr_data, rows, batch_rows=pos[start:end], dropnode_rate=dropnode_rate)
+            eval_head(model(aug), labels, label_rows=idx[start:end], out=buf, offset=start)
+        loss, acc, counts = eval_reduce(buf)
+    return (loss, acc, counts) if return_counts else (loss, acc)
+
+
+def predict_mag(graph, attr_indptr, attr_indices, attr_data, model, idx_test, labels, prop_mode, order, alpha=0.2,
+                batch_size_logits=10000, return_preds=False, infer=False):
+    """MAG's `predict` (model_mag.py:192-245) on the GPU: the embedding of every node in eval mode
+    (`embedding_bag_csr(nodes=None)`, model_mag.py:197-205), then `predict` on it.  A composition, no kernel of its own;
+    the whole body is free of host synchronisation.  Same returns as `predict`."""
+    from .embedding import embedding_bag_csr
+    from .evaluate import _NoSync, _node_ids, predict
+    if not isinstance(model, torch.nn.Module) or not hasattr(model, "embeds"):
+        raise TypeError("predict_mag: model must be a MagMLP")
+    _check(model.embeds.weight, torch.float32, "model.embeds.weight")
+    idx_test = _node_ids(idx_test, "idx_test", model.embeds.weight.device)       # the upload of a host list comes first
+    with _NoSync(model):
+        emb = embedding_bag_csr(model.embeds.weight, attr_indptr, attr_indices, attr_data, nodes=None, training=False, validate=False)
+        return predict(graph, emb, model, idx_test, labels, prop_mode, order, alpha, batch_size_logits, return_preds, infer)

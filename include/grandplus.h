@@ -522,6 +522,10 @@ int gp_clip_adam_step(int device, const gp_optim_tensor* tensors, int32_t n_tens
  * contracts and GP_MLP_INFER_WORKSPACE_BYTES): declared in a header of its own, part of this ABI. */
 #include "grandplus_infer.h"
 
+/* MAG's fused front end (resident rows -> S augmented embeddings in one launch, forward and backward, with its
+ * mask formulas, order contract and bounds rules): declared in a header of its own, part of this ABI. */
+#include "grandplus_mag.h"
+
 /* ------------------------------------------------------------------------------------------
  * exact full-graph feature propagation of the inference path, reference
  * predict() (model.py:181-224), lines 186-210.  mode 0 = ppr, 1 = avg, 2 = single (args.prop_mode);
