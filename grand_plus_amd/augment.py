@@ -69,6 +69,9 @@ def _coo_backward(grad_out, mat_scores, mat_idx, M, n_out, samples, dropnode_rat
     F = g.shape[-1]
     L = _native.lib()
     fn, S = (L.gp_random_prop_coo_backward, ()) if samples is None else (L.gp_random_prop_coo_multi_backward, (samples,))
+    if n_out == 0:                                                     # no launch: every entry is cut off
+        return torch.zeros((M, F), dtype=torch.float32, device=g.device)
+    # every row is written by the kernel: an entry's segment writes it, and entries with mat_idx >= n_out get exact zeros
     grad = torch.empty((M, F), dtype=torch.float32, device=g.device)
     rc = fn(_dev_index(g), g.data_ptr(), n_out, F, mat_scores.data_ptr(), mat_idx.data_ptr(), M, *S,
             float(dropnode_rate), int(bool(training)), ctypes.c_uint64(seed), _ptr(keep), grad.data_ptr(), _stream(g))
@@ -182,7 +185,8 @@ def random_prop(feats, mat_scores, mat_idx, dropnode_rate, training=True, seed=N
     feats [M, F] float32, mat_scores [M] float32, mat_idx [M] int64 sorted ascending (the order
     scipy's `.nonzero()` yields, `model.py:312`).  Returns [mat_idx[-1] + 1, F] float32.
     `training` plays the role of `self.training`.  Differentiable with respect to `feats`.
-    `n_out` (optional) is the number of output rows; given, it saves the host read of mat_idx[-1].
+    `n_out` (optional) is the number of output rows; given, it saves the host read of mat_idx[-1].  Above mat_idx[-1] + 1
+    it adds zero rows; below, the output is the first n_out rows and the entries of later rows get a gradient of exactly 0.
     `samples` = S > 1 returns [S, n_out, F] from one launch (keep: uint8 [S, M]); see the module docstring.
     """
     _check_samples(samples)

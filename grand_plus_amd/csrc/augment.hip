@@ -166,7 +166,17 @@ random_prop_coo_kernel(const float* __restrict__ feats, int F, const float* __re
 // (seed, e) or d_keep, same sequential fp32 sum), so the backward applies the forward's mask without storing it.
 
 // COO form: a pure gather and stream.  Workgroup per output row b; every entry of the row's segment is
-// written (dropped entries get exact zeros), so every row of grad_feats is written.  No atomics.
+// written (dropped entries get exact zeros), and the workgroup of the last output row also writes the entries the
+// caller's n_out cuts off (zero_cut_rows), so every row of grad_feats is written.  No atomics.
+
+// Entries [first, n_entries) have idx >= n_out: the forward left them out, so their gradient is exactly 0.  `first` is the
+// last output row's segment end, which that row's workgroup has already searched: no trip when n_out covers every entry.
+__device__ __forceinline__ void zero_cut_rows(float* __restrict__ grad_feats, int F, long long first, long long n_entries)
+{
+    const size_t end = (size_t)n_entries * F;
+    for (size_t t = (size_t)first * F + threadIdx.x; t < end; t += kBlock) grad_feats[t] = 0.0f;
+}
+
 template <int VEC>
 __device__ __forceinline__ void scaled_rows_vec(const float* __restrict__ g_row, int F, const float* s_w, int n,
                                                 float inv, float* __restrict__ out_rows)
@@ -235,6 +245,7 @@ random_prop_coo_backward_kernel(const float* __restrict__ grad_out, int F, const
                 for (int f = threadIdx.x; f < F; f += kBlock) grad_feats[(size_t)e * F + f] = (g_row[f] * inv) * w;
             }
         }
+        if (b == n_out - 1) zero_cut_rows(grad_feats, F, hi, n_entries);
     }
 }
 
@@ -895,6 +906,7 @@ random_prop_coo_multi_backward_kernel(const float* __restrict__ grad_out, int F,
                 }
             }
         }
+        if (b == n_out - 1) zero_cut_rows(grad_feats, F, hi, n_entries);
     }
 }
 

@@ -1,5 +1,5 @@
 """MAG's embedding-bag layer against a float64 restatement of `MLP.emb` (model_mag.py:48-55) kept in
-this file: `index_add_` for torch_scatter's scatter-sum, explicit dropout masks, autograd for the reference
+augment_cases.py: `index_add_` for torch_scatter's scatter-sum, explicit dropout masks, autograd for the reference
 gradients.  Tolerance per element: |d| <= 1e-5 * sum|terms| + 1e-7, sum|terms| = the same quantity with every
 operand replaced by its magnitude.  Ends with a MAG-shaped training step: gfpush_device -> flatten_rows ->
 embedding_bag_csr -> random_prop x 2 -> MLP -> NLL + l2 consistency loss -> backward."""
@@ -8,23 +8,10 @@ import ctypes
 import numpy as np
 import pytest
 
-from augment_cases import close
+from augment_cases import close, emb_ref
 from oracle.objective_ref import consis_loss_ref
 
 pytestmark = pytest.mark.gpu
-
-
-def emb_ref(W, attr_idx, node_idx, attr_data, p, training, keep):
-    """MLP.emb (model_mag.py:48-55) in the dtype of W; keep: [nnz, H] 0/1 mask of F.dropout."""
-    import torch
-    fe = W[attr_idx]                                                             # self.embeds(attr_idx)
-    if training:                                                                 # F.dropout(feat_embeds, p)
-        fe = fe * keep.to(fe.dtype) / (1.0 - p) if p < 1.0 else torch.zeros_like(fe)
-    d = attr_data.to(fe.dtype)
-    n_out = int(node_idx[-1]) + 1
-    num = torch.zeros((n_out, W.shape[1]), dtype=fe.dtype).index_add_(0, node_idx, fe * d[:, None])
-    den = torch.zeros((n_out, 1), dtype=fe.dtype).index_add_(0, node_idx, d[:, None])
-    return num / (den + 1e-10)
 
 
 def _bags(V, n_out, seed, max_len=12):
