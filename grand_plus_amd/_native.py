@@ -209,6 +209,13 @@ _MAG_SIGNATURES = {
     "gp_mag_prop_rows_backward": (_int, [_int, _vp] + _mag + [_vp, _vp], False),
 }
 MAG_EXPORTS = tuple(_MAG_SIGNATURES)
+# The entry points behind option "row_order", which include/grandplus_order.h declares (grandplus.h includes it): the same
+# convention, held against that header type by type by tests/test_host_row_order.py.
+_ORDER_SIGNATURES = {
+    "gp_internal_row_order": (_int, [_vp, _u32p, _i64, _i64p, _intp, _u32p], False),
+    "gp_internal_wg_log": (_int, [_vp, _i64p, _int], False),
+}
+ORDER_EXPORTS = tuple(_ORDER_SIGNATURES)
 
 _LIB = None
 
@@ -239,7 +246,7 @@ def lib():
         pass
     L = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes, required) in {**_SIGNATURES, **_EVAL_SIGNATURES, **_SCATTER_SIGNATURES, **_INFER_SIGNATURES,
-                                              **_MAG_SIGNATURES}.items():
+                                              **_MAG_SIGNATURES, **_ORDER_SIGNATURES}.items():
         if not required and not hasattr(L, name):
             setattr(L, name, _missing(name))
             continue

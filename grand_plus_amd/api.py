@@ -213,6 +213,26 @@ class Graph:
         _native.raise_for_status(_native.lib().gp_internal_diag_counters(self._h, buf, 256))
         return list(buf)
 
+    def row_order(self):
+        """The order in which the first launch of the last gfpush_device call handed out its rows (option "row_order"), as
+        (order uint32[S], deg_shift, deg_sat): the degree field its cost was read from.  order is empty when that call ran in
+        caller order (row_order = 0, or no more rows than workgroups).  Waits for the call."""
+        L = _native.lib()
+        n, shift, sat = ctypes.c_int64(), ctypes.c_int(), ctypes.c_uint32()
+        _native.raise_for_status(L.gp_internal_row_order(self._h, None, 0, ctypes.byref(n), ctypes.byref(shift), ctypes.byref(sat)))
+        order = np.empty(n.value, np.uint32)
+        if n.value:
+            _native.raise_for_status(L.gp_internal_row_order(self._h, _ptr(order, ctypes.c_uint32), n.value, ctypes.byref(n),
+                                                             ctypes.byref(shift), ctypes.byref(sat)))
+        return order, shift.value, sat.value
+
+    def workgroup_log(self, n_workgroups: int):
+        """Per workgroup of the last sketch-kernel launch (entry stamp, exit stamp) in 100 MHz ticks, int64[n_workgroups, 2]:
+        the -DGP_SK_TIMING build keeps it (tools/sk_phases.py), the product library returns zeros."""
+        buf = np.zeros((int(n_workgroups), 2), np.int64)
+        _native.raise_for_status(_native.lib().gp_internal_wg_log(self._h, _ptr(buf, ctypes.c_int64), int(n_workgroups)))
+        return buf
+
     def set_option(self, key: str, value: int):
         _native.raise_for_status(_native.lib().gp_set_option(self._h, key.encode(), int(value)))
 

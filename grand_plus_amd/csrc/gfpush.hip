@@ -96,6 +96,9 @@ struct Workspace {
     Slabs est;                    // general kernel: slabs sized from an estimate of a row's needs (every workgroup; a quarter of them when it only re-runs what the sketch kernel handed back)
     Slabs big;                    // last launch: a few workgroups, slabs sized from the rigorous bounds (n_wg == 0: not needed)
     uint32_t* retry_list = nullptr; uint32_t* retry_list2 = nullptr; int64_t retry_cap = 0;
+    // heaviest rows first (enqueue_row_order): order[retry_cap] = the rows of the call as the first launch's queue hands them out,
+    // cost_cls[retry_cap] = their cost classes, order_hist[64] = rows per class | the scatter's cursors
+    uint32_t* order = nullptr; unsigned char* cost_cls = nullptr; uint32_t* order_hist = nullptr;
     bool dirty = true;            // HBM residue tables need (re)initialising before the next launch
 };
 
@@ -121,6 +124,9 @@ struct gp_graph {
     int64_t workspace_mb = 65536; int force_global = 0; int exact_stats = 0; int diag_flags = 0; int direct_tables = 1; int seedrow = 1; int solo_levels = 1;
     int kernel = 0;                                                        // option: 0 = choose per call, 1 = general kernel, 2 = sketch kernel whenever the call allows it
     int sk_block = 0, sk_lg_mu = 0, sk_lg_mr = 0, sk_target = 0, sk_direct_max = 0;   // options: geometry of the sketch kernel (0 = default)
+    int row_order = 1;                                                     // option: 1 = the first launch of a call takes its rows heaviest first (row_cost_kernel), 0 = in caller order
+    int64_t last_order_rows = 0; uint32_t last_order_sat = 0; int last_order_shift = 0;   // the last call's pre-pass: rows ordered (0: skipped), the degree field it read (gp_internal_row_order)
+    u64* d_wg_log = nullptr;                                               // -DGP_SK_TIMING build: KParams::wg_log (gp_internal_wg_log)
     int sk_seed_merge = 1; int gk_acsr = 1;                                                       // option: the general kernel runs on the self-addressed copy too when the graph is large (0 = packed CSR + indptr)
     int est_kind = 0; int last_kind = 1; bool sk_auto_off = false; double sk_off_rmax = 0.0; int sk_off_n_coef = 0;                                   // which kernel the running estimate / the last call belongs to
     bool last_sk_soft = false;                                             // the last call ran the sketch kernel as an automatic or soft pick, not because option kernel = 2 insisted (grow_estimate)
@@ -367,7 +373,7 @@ int ensure_workspace(gp_graph* g, int n_coef, double rmax, int n_wg, int64_t n_s
             if (bytes_of(e2, b2, s2) <= budget) { est = e2; big = b2; skl = s2; }
         }
         free_workspace(w);
-        const size_t total = bytes_of(est, big, skl) + 8 * (size_t)std::max<int64_t>(n_seeds, 1) + 3 * 4096 + 1024;
+        const size_t total = bytes_of(est, big, skl) + 13 * (size_t)std::max<int64_t>(n_seeds, 1) + 3 * 4096 + 1024;   // (per row: two retry lists, order, cost_cls)
         hipError_t e = hipMalloc(&w.base, total);
         if (e != hipSuccess) {
             (void)hipGetLastError();
@@ -381,6 +387,8 @@ int ensure_workspace(gp_graph* g, int n_coef, double rmax, int n_wg, int64_t n_s
         w.big = big; if (big.n_wg > 0) p += w.big.carve(p, big.n_wg);
         w.retry_cap = std::max<int64_t>(n_seeds, 1);
         w.retry_list = (uint32_t*)p; w.retry_list2 = w.retry_list + w.retry_cap;
+        w.order = w.retry_list2 + w.retry_cap; w.cost_cls = (unsigned char*)(w.order + w.retry_cap);
+        w.order_hist = (uint32_t*)(((uintptr_t)(w.cost_cls + w.retry_cap) + 255) & ~(uintptr_t)255);        // (inside the 13 KB of slack)
         w.dirty = true;
     }
     return GP_OK;
@@ -780,11 +788,11 @@ int plan_sketch(gp_graph* g, const CallArgs& a, const CallShape& shape, SketchPl
 }
 
 // The sketch kernel over every row of the call; what it cannot finish goes to retry_list (count in kRetryRows).
-int launch_sketch(const gp_graph* g, KParams& kp, const CallArgs& a, const SketchPlan& sk)
+int launch_sketch(const gp_graph* g, KParams& kp, const CallArgs& a, const SketchPlan& sk, const u32* order)
 {
     const Workspace& w = g->ws;
     use_slabs(kp, w.skl);
-    kp.row_map = nullptr; kp.n_rows_dev = nullptr; kp.queue_counter = kQueue;
+    kp.row_map = order; kp.n_rows_dev = nullptr; kp.queue_counter = kQueue;
     kp.retry_list = w.retry_list; kp.retry_counter = kRetryRows;
     kp.sk_lg_mu = sk.lg_mu; kp.sk_lg_mr = sk.lg_mr; kp.sk_cx = sk.cx;
     kp.sk_target = (u32)(g->sk_target > 0 ? g->sk_target : 4 * a.K);
@@ -803,7 +811,7 @@ int launch_sketch(const gp_graph* g, KParams& kp, const CallArgs& a, const Sketc
 // (the diagnostic build instruments the general kernel on the packed CSR only: no sketch kernel, nothing to choose by measurement)
 constexpr bool kDiagBuild = true;
 int plan_sketch(gp_graph*, const CallArgs&, const CallShape&, SketchPlan&) { return GP_OK; }
-int launch_sketch(const gp_graph*, KParams&, const CallArgs&, const SketchPlan&) { return GP_OK; }
+int launch_sketch(const gp_graph*, KParams&, const CallArgs&, const SketchPlan&, const u32*) { return GP_OK; }
 #endif
 
 Kernel general_kernel(int block) { return kernel_for<256, 512, 768, 1024>(block, [](auto b) -> Kernel { return gfpush_kernel<decltype(b)::value>; }); }
@@ -886,9 +894,9 @@ KParams call_params(const gp_graph* g, const CallArgs& a, const GeneralPlan& gk,
 }
 
 // One pass of the general kernel and where its rows come from and go to.  rows == nullptr: every row of the call; else the
-// list whose length is counter n_rows.  Rows that outgrow the estimate-sized slabs go to `overflow` (numbered by counter
+// list whose length is counter n_rows; `order` (or nullptr) is then the order in which the queue hands out the call's rows.  Rows that outgrow the estimate-sized slabs go to `overflow` (numbered by counter
 // n_overflow) and, when bound-sized slabs exist, are re-run on those by a second launch that pulls from overflow_queue.
-struct GeneralPass { const u32* rows; int n_rows; int queue; u32* overflow; int n_overflow; int overflow_queue; };
+struct GeneralPass { const u32* rows; int n_rows; int queue; u32* overflow; int n_overflow; int overflow_queue; const u32* order; };
 
 int launch_general(const gp_graph* g, KParams& kp, const GeneralPlan& gk, bool gk_acsr, const GeneralPass& pass, hipStream_t s)
 {
@@ -896,7 +904,7 @@ int launch_general(const gp_graph* g, KParams& kp, const GeneralPlan& gk, bool g
     const bool two_tier = w.big.n_wg > 0;
     use_csr(kp, g, gk_acsr, true);
     use_slabs(kp, w.est);
-    kp.row_map = pass.rows; kp.n_rows_dev = pass.rows ? kp.counters + pass.n_rows : nullptr; kp.queue_counter = pass.queue;
+    kp.row_map = pass.rows ? pass.rows : pass.order; kp.n_rows_dev = pass.rows ? kp.counters + pass.n_rows : nullptr; kp.queue_counter = pass.queue;
     kp.retry_list = two_tier ? pass.overflow : nullptr; kp.retry_counter = pass.n_overflow;
     const Kernel k = pass.rows ? retry_kernel(gk.block_threads) : general_kernel(gk.block_threads);
     int rc = launch_kernel(k, gk.block_threads, kp, gk.n_wg, gk.lds_bytes + g->lds_pad, s);
@@ -907,6 +915,24 @@ int launch_general(const gp_graph* g, KParams& kp, const GeneralPlan& gk, bool g
     kp.row_map = pass.overflow; kp.n_rows_dev = kp.counters + pass.n_overflow; kp.queue_counter = pass.overflow_queue;
     kp.retry_list = nullptr;
     return launch_kernel(retry_kernel(gk.block_threads), gk.block_threads, kp, w.big.n_wg, gk.lds_bytes + g->lds_pad, s);
+}
+
+// Heaviest rows first: the pre-pass in front of the first launch of a call (no host synchronisation).  row_cost_kernel classes
+// every row by the edges of its levels 1 and 2, read off the degree fields of the seed's columns in the copy of the graph the
+// call runs on; row_order_kernel lists the rows by class.  Three launches of microseconds (a memset, two kernels).
+int enqueue_row_order(gp_graph* g, const CallArgs& a, bool acsr, hipStream_t s)
+{
+    const Workspace& w = g->ws;
+    HIP_TRY(hipMemsetAsync(w.order_hist, 0, sizeof(uint32_t) * 64, s));
+    const int shift = acsr ? g->a_shift : g->deg_shift;
+    const u32 sat = acsr ? g->a_sat : g->deg_sat;
+    const unsigned cost_wgs = (unsigned)std::min<int64_t>((a.n_seeds + 15) / 16, 4096), order_wgs = (unsigned)std::min<int64_t>((a.n_seeds + 255) / 256, 1024);
+    hipLaunchKernelGGL(row_cost_kernel, dim3(cost_wgs), dim3(256), 0, s, a.d_seeds, (long long)a.n_seeds, (int)g->n_nodes, g->d_indptr,
+                       acsr ? g->d_acsr : g->d_indices, acsr ? g->d_node_pos : (const u32*)nullptr, shift, sat, a.rmax, w.cost_cls, w.order_hist);
+    hipLaunchKernelGGL(row_order_kernel, dim3(order_wgs), dim3(256), 0, s, w.cost_cls, (long long)a.n_seeds, w.order_hist, w.order_hist + 32, w.order);
+    HIP_TRY(hipGetLastError());
+    g->last_order_rows = a.n_seeds; g->last_order_sat = sat; g->last_order_shift = shift;
+    return GP_OK;
 }
 
 // Plans and enqueues one call on a.s: everything behind gp_gfpush_device's argument checks, for the caller's call and for
@@ -965,13 +991,26 @@ int enqueue_call(gp_graph* g, const CallArgs& a, const CallShape& shape)
     if (gk_acsr) { rc = ensure_acsr(g, s); if (rc) return rc; gk_acsr = g->acsr_state == 1; }
 
     HIP_TRY(hipEventRecord(g->ev0, s));
+    // (a call of no more rows than the first launch has workgroups: every workgroup takes at most one row, nothing to order)
+    const u32* order = nullptr;
+    g->last_order_rows = 0;
+    if (g->row_order && a.n_seeds > (sk.use ? sk.wg : gk.n_wg) && a.n_seeds <= w.retry_cap && a.n_seeds <= (int64_t)0xFFFFFFFFll) {
+        rc = enqueue_row_order(g, a, sk.use || gk_acsr, s);
+        if (rc) return rc;
+        order = w.order;
+    }
+#ifdef GP_SK_TIMING
+    if (!g->d_wg_log) { HIP_TRY(hipMalloc(&g->d_wg_log, sizeof(u64) * 2 * 65536)); }
+    HIP_TRY(hipMemsetAsync(g->d_wg_log, 0, sizeof(u64) * 2 * 65536, s));
+    kp.wg_log = g->d_wg_log;
+#endif
     if (a.n_seeds > 0 && !sk.use) {
-        rc = launch_general(g, kp, gk, gk_acsr, GeneralPass{nullptr, 0, kQueue, w.retry_list, kRetryRows, kQueueRetry}, s);
+        rc = launch_general(g, kp, gk, gk_acsr, GeneralPass{nullptr, 0, kQueue, w.retry_list, kRetryRows, kQueueRetry, order}, s);
     } else if (a.n_seeds > 0) {
         // 1. the sketch kernel over every row; 2. the general kernel over its retry list (a quarter of the chip: the list is a
         //    per-cent of the call); rows that outgrow ITS estimate-sized slabs go to retry_list2 ... 3. ... which the bound-sized slabs take
-        rc = launch_sketch(g, kp, a, sk);
-        if (!rc) rc = launch_general(g, kp, gk, gk_acsr, GeneralPass{w.retry_list, kRetryRows, kQueueRetry, w.retry_list2, kRetryRows2, kQueueRetry2}, s);
+        rc = launch_sketch(g, kp, a, sk, order);
+        if (!rc) rc = launch_general(g, kp, gk, gk_acsr, GeneralPass{w.retry_list, kRetryRows, kQueueRetry, w.retry_list2, kRetryRows2, kQueueRetry2, nullptr}, s);
     }
     if (rc) return rc;
     HIP_TRY(hipEventRecord(g->ev1, s));
@@ -1129,6 +1168,30 @@ int gp_internal_diag_counters(gp_graph* g, int64_t* out, int n) {
     return GP_OK;
 }
 
+int gp_internal_row_order(gp_graph* g, uint32_t* h_order, int64_t cap, int64_t* n_rows, int* deg_shift, uint32_t* deg_sat) {
+    if (!g || !n_rows || !deg_shift || !deg_sat) return fail(GP_ERR_NULL, "null argument");
+    if (g->multi) return fail(GP_ERR_INVALID_ARG, "gp_internal_row_order needs a single-GPU graph");
+    HIP_TRY(hipSetDevice(g->device));
+    if (g->launched) HIP_TRY(hipStreamSynchronize(g->last_stream));
+    const int64_t n = g->launched && g->ws.order ? g->last_order_rows : 0;
+    *n_rows = n; *deg_shift = g->last_order_shift; *deg_sat = g->last_order_sat;
+    if (h_order && n > 0) {
+        if (cap < n) return fail(GP_ERR_INVALID_ARG, "gp_internal_row_order: room for %lld rows, the last call ordered %lld", (long long)cap, (long long)n);
+        HIP_TRY(hipMemcpy(h_order, g->ws.order, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost));
+    }
+    return GP_OK;
+}
+
+int gp_internal_wg_log(gp_graph* g, int64_t* out, int n_workgroups) {
+    if (!g || !out || n_workgroups < 0 || n_workgroups > 65536) return fail(GP_ERR_INVALID_ARG, "gp_internal_wg_log: bad argument");
+    for (int i = 0; i < 2 * n_workgroups; ++i) out[i] = 0;
+    if (!g->d_wg_log || !g->launched) return GP_OK;           // (only the -DGP_SK_TIMING build keeps the log)
+    HIP_TRY(hipSetDevice(g->device));
+    HIP_TRY(hipStreamSynchronize(g->last_stream));
+    HIP_TRY(hipMemcpy(out, g->d_wg_log, sizeof(int64_t) * 2 * (size_t)n_workgroups, hipMemcpyDeviceToHost));
+    return GP_OK;
+}
+
 void gp_internal_set_error(int status, const char* where, const char* detail) {
     (void)fail(status, "%s: %s", where ? where : "", detail ? detail : "");
 }
@@ -1251,6 +1314,7 @@ void gp_graph_destroy(gp_graph* g) {
     if (g->d_unit_info) (void)hipFree(g->d_unit_info);
     if (g->d_counters) (void)hipFree(g->d_counters);
     if (g->d_cal_counters) (void)hipFree(g->d_cal_counters);
+    if (g->d_wg_log) (void)hipFree(g->d_wg_log);
     if (g->h_counters) (void)hipHostFree(g->h_counters);
     if (g->d_coef) (void)hipFree(g->d_coef);
     if (g->d_seeds) (void)hipFree(g->d_seeds);
@@ -1305,6 +1369,8 @@ int gp_set_option(gp_graph* g, const char* key, int64_t value) {
         g->sk_direct_max = (int)value;          // levels of up to this many edges insert straight into the exact table (0 = three quarters of its slots, the most the kernel allows)
     } else if (k == "sk_seed_merge") {
         g->sk_seed_merge = value ? 1 : 0;
+    } else if (k == "row_order") {
+        g->row_order = value ? 1 : 0;            // 0 = the first launch takes its rows in caller order (A/B; what is measured per recipe does not depend on it)
     } else if (k == "gk_acsr") {
         g->gk_acsr = value ? 1 : 0;
     } else if (k == "sk_target") {
@@ -1643,7 +1709,7 @@ int replicate_part(gp_graph* g, int d) {
     q->block_threads = src->block_threads; q->lds_bytes = src->lds_bytes; q->max_workgroups = src->max_workgroups;
     q->workspace_mb = src->workspace_mb; q->force_global = src->force_global; q->exact_stats = src->exact_stats;
     q->direct_tables = src->direct_tables; q->est_level_edges = src->est_level_edges; q->seedrow = src->seedrow; q->solo_levels = src->solo_levels;
-    q->kernel = src->kernel; q->gk_acsr = src->gk_acsr; q->sk_seed_merge = src->sk_seed_merge; q->sk_block = src->sk_block; q->sk_lg_mu = src->sk_lg_mu; q->sk_lg_mr = src->sk_lg_mr; q->sk_target = src->sk_target; q->lds_pad = src->lds_pad; q->sk_direct_max = src->sk_direct_max;
+    q->kernel = src->kernel; q->row_order = src->row_order; q->gk_acsr = src->gk_acsr; q->sk_seed_merge = src->sk_seed_merge; q->sk_block = src->sk_block; q->sk_lg_mu = src->sk_lg_mu; q->sk_lg_mr = src->sk_lg_mr; q->sk_target = src->sk_target; q->lds_pad = src->lds_pad; q->sk_direct_max = src->sk_direct_max;
     const size_t b_ptr = sizeof(int) * (size_t)(q->n_nodes + 1), b_idx = sizeof(int) * (size_t)(q->nnz + 1);     // with the sentinel word
     HIP_TRY(hipMalloc(&q->d_indptr, b_ptr));
     HIP_TRY(hipMalloc(&q->d_indices, b_idx));

@@ -294,7 +294,8 @@ struct KParams {
     // Two launches per call.  The first gives every workgroup a slab sized from an ESTIMATE of a row's needs; a row that
     // outgrows it is not failed but appended to retry_list.  The second launch (a few workgroups, slabs sized from the
     // rigorous bounds) takes its rows from that list: row_map / n_rows_dev are then set, retry_list is NULL and a
-    // row that still does not fit is reported (GP_ERR_OVERFLOW).
+    // row that still does not fit is reported (GP_ERR_OVERFLOW).  A first launch may have row_map set too (n_rows_dev NULL): the
+    // order in which its queue hands out the call's rows (row_order_kernel).  Everything a caller sees stays indexed by ROW.
     const u32* row_map; const u64* n_rows_dev; u32* retry_list; int queue_counter;
     int retry_counter; int pad_rc;        // the counter that numbers retry_list's entries (kRetryRows / kRetryRows2)
     // sketch kernel (gfpush_sketch.hpp): log2 cells of the level sketch U and of the reserve sketch R (built by TOP-K in the level
@@ -310,6 +311,8 @@ struct KParams {
     u32 sk_hub_units; u32 gk_acsr;        // sk_hub_units 1: deg >= deg_sat implies >= 2 units, the exact degree of a saturated node is unit_info[unit + 1];
                                           // gk_acsr 1 (round 6): the GENERAL kernel runs on the self-addressed copy too (keys are unit numbers; csr_row / out_col)
     int diag_flags;                       // GP_DIAG builds only (instruction attribution by difference): bit 0 = skip TOP-K, bit 1 = run EXPAND twice, bit 2 = walk the drained table once more
+    int pad_df;
+    u64* wg_log;                          // -DGP_SK_TIMING only (else NULL): per workgroup of the sketch launch { stamp at entry, stamp at leaving the row loop } (tools/sk_phases.py)
 };
 // The launch parameters where the hardware put them: the kernel argument segment (KParams is the kernels' only argument),
 // read with scalar loads.  __builtin_amdgcn_kernarg_segment_ptr() is only meaningful inside the kernel function itself
@@ -2578,7 +2581,7 @@ __device__ __forceinline__ void gfpush_rows()
 #pragma unroll
         for (int i = 0; i < sNumStats; ++i)
             if (ctl->st[i]) __hip_atomic_fetch_add(&p.counters[dst[i]], ctl->st[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (p.row_map && blockIdx.x == 0 && n_rows > 0)
+        if (p.n_rows_dev && blockIdx.x == 0 && n_rows > 0)         // (a retry launch: its rows come from a list with a device-side length)
             __hip_atomic_fetch_add(&p.counters[kRetriedTotal], (u64)n_rows, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (max_e) __hip_atomic_fetch_max(&p.counters[kMaxLevelEdges], (u64)max_e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (max_log) __hip_atomic_fetch_max(&p.counters[kMaxLogRecords], (u64)max_log, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -2654,6 +2657,87 @@ __global__ void __launch_bounds__(256) pack_degree_kernel(const int* indptr, int
         const int v = indices[j];
         const u32 d = (u32)(indptr[v + 1] - indptr[v]);
         indices[j] = (int)((u32)v | (min(d, deg_sat) << deg_shift));
+    }
+}
+
+// ---------------------------------------------------------------- heaviest rows first (option "row_order")
+// The row queue hands rows out in the order of `row_map`.  In caller order a row several times the mean that is drawn late
+// holds the launch open while every other workgroup is idle; handed out heaviest-first the long rows run while there is
+// still work for everybody.  The cost of a row is the edge count of its levels 1 and 2, which the seed's own columns give:
+//   c = 0                                                           the seed is invalid, dangling or fails its push test (graph.h:94)
+//   c = d0 + floor(d0 * sum / n)   sum = SUM over the first n = min(d0, kCostCols) columns u of [1/d0 >= rmax * deg(u)] * deg(u)
+// with deg(u) the packed degree field of the column word (a saturated field counts as deg_sat: an estimate may be off).
+// Class = min(31, ilog2(c + 1)); `order` lists the rows by class, highest first (grand_plus_amd/row_cost.py restates both).
+constexpr u32 kCostCols = 256;            // columns read per seed (a hub seed spreads 1/d0 so thin that little pushes)
+
+__device__ __forceinline__ u32 row_cost_class(u64 c) { return min(31u, 63u - (u32)__builtin_clzll(c + 1ull)); }
+
+// One 16-lane group per seed.  cols / col_base: the self-addressed copy (col_base = node_pos: the row starts at unit
+// node_pos[seed]) or the packed CSR (col_base == nullptr: the row starts at indptr[seed]).  cls[r] = class of row r, hist[k] += 1.
+__global__ void __launch_bounds__(256) row_cost_kernel(const int* seeds, long long n_seeds, int n_nodes, const int* indptr, const int* cols,
+                                                       const u32* col_base, int deg_shift, u32 deg_sat, double rmax,
+                                                       unsigned char* cls, u32* hist)
+{
+    __shared__ u32 h[32];
+    if (threadIdx.x < 32) h[threadIdx.x] = 0;
+    __syncthreads();
+    const u32 sub = threadIdx.x & 15u;
+    const long long step = (long long)gridDim.x * 16;
+    for (long long base = (long long)blockIdx.x * 16; base < n_seeds; base += step) {        // (uniform per workgroup: every lane reaches the shuffles)
+        const long long r = base + (long long)(threadIdx.x >> 4);
+        unsigned long long sum = 0; u32 d0 = 0, n_read = 0;
+        if (r < n_seeds) {
+            const int seed = seeds[r];
+            if (seed >= 0 && seed < n_nodes) {                                               // the device API does not pre-validate seeds
+                const int s0 = indptr[seed];
+                const u32 d = (u32)(indptr[seed + 1] - s0);
+                if (d != 0 && 1.0 >= rmax * (double)d) {                                     // graph.h:94 for the seed itself
+                    d0 = d; n_read = min(d, kCostCols);
+                    const double share = 1.0 / (double)d;                                    // graph.h:95
+                    const long long start = col_base ? (long long)col_base[seed] << 5 : (long long)s0;
+                    for (u32 j = sub; j < n_read; j += 16u) {
+                        const u32 dg = min((u32)cols[start + j] >> deg_shift, deg_sat);
+                        if (share >= rmax * (double)dg) sum += dg;
+                    }
+                }
+            }
+        }
+        for (int m = 8; m > 0; m >>= 1) sum += __shfl_xor(sum, m, 16);
+        if (sub == 0 && r < n_seeds) {
+            // floor(d0 * sum / n_read) without leaving 64 bits: sum < 2^38, d0 < 2^31
+            const u64 c = d0 ? (u64)d0 + sum * (d0 / n_read) + sum * (d0 % n_read) / n_read : 0ull;
+            const u32 k = row_cost_class(c);
+            cls[r] = (unsigned char)k;
+            atomicAdd(&h[k], 1u);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 32 && h[threadIdx.x]) atomicAdd(&hist[threadIdx.x], h[threadIdx.x]);
+}
+
+// Counting sort by class, highest class first: class k starts behind every row of a higher class (a 32-entry scan of hist that
+// each workgroup redoes), a workgroup reserves room for its rows of a class with one atomic on cursor[k].  The order inside a
+// class is whatever the atomics give; order[0 .. n) is a permutation of the rows.
+__global__ void __launch_bounds__(256) row_order_kernel(const unsigned char* cls, long long n, const u32* hist, u32* cursor, u32* order)
+{
+    __shared__ u32 cnt[32], at[32];
+    const long long step = (long long)gridDim.x * 256;
+    for (long long c0 = (long long)blockIdx.x * 256; c0 < n; c0 += step) {
+        if (threadIdx.x < 32) cnt[threadIdx.x] = 0;
+        __syncthreads();
+        const long long r = c0 + (long long)threadIdx.x;
+        const u32 k = r < n ? (u32)cls[r] & 31u : 0u;
+        const u32 mine = r < n ? atomicAdd(&cnt[k], 1u) : 0u;
+        __syncthreads();
+        if (threadIdx.x < 32 && cnt[threadIdx.x]) {
+            u32 first = 0;
+            for (u32 j = threadIdx.x + 1u; j < 32u; ++j) first += hist[j];
+            at[threadIdx.x] = first + atomicAdd(&cursor[threadIdx.x], cnt[threadIdx.x]);
+        }
+        __syncthreads();
+        // (at[k] + mine < n: the classes' counts are hist's, which was built from the same cls)
+        if (r < n && (long long)at[k] + mine < n) order[at[k] + mine] = (u32)r;
+        __syncthreads();
     }
 }
 

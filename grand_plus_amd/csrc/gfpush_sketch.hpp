@@ -86,6 +86,8 @@ struct CtlS {
 #ifdef GP_SK_TIMING
     u64 tacc[16]; u64 tlast;              // -DGP_SK_TIMING: 100 MHz ticks thread 0 spent per phase (flushed to the diag_sub counters)
     u64 tacc2[14]; u64 tlast2;            // ... and inside FILTER / SCAN / STREAM (tools/sk_phases.py)
+    u64 t_enter, t_row, row_sum, row_max; // the end of a launch: stamp at entry, at the top of the row in flight; ticks of this workgroup's rows and of its longest
+    u64 row_hist[32];                     // ... and its rows by ilog2 of their ticks (flushed to diag counters [16], [17], [32 .. 63]; entry / exit stamps to wg_log)
 #endif
 };
 // -DGP_SK_TIMING (tools/sk_phases.py): thread 0 stamps the phases with the constant 100 MHz clock.  [0] row prologue + level 0,
@@ -1372,6 +1374,8 @@ __device__ __forceinline__ void gfpush_sk_rows()
 #ifdef GP_SK_TIMING
     if (tid < 16) ctl->tacc[tid] = 0;
     if (tid < 14) ctl->tacc2[tid] = 0;
+    if (tid < 32) ctl->row_hist[tid] = 0;
+    if (tid == 0) { ctl->t_enter = wall_clock64(); ctl->row_sum = 0; ctl->row_max = 0; }
 #endif
     if (tid < kSkMaxCoef) { ctl->cand_q[tid] = 0; if (tid < p.n_coef) ctl->coef[tid] = p.coef[tid]; }
     if (tid == 0) {
@@ -1390,8 +1394,14 @@ __device__ __forceinline__ void gfpush_sk_rows()
         GP_SYNC();
         SKT_BEGIN(ctl);
         if (tid == 0) {
-            ctl->row = (long long)__hip_atomic_fetch_add(&p.counters[p.queue_counter], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            // the queue hands out positions; row_map (row_order_kernel: heaviest rows first) says which row stands there
+            long long q = (long long)__hip_atomic_fetch_add(&p.counters[p.queue_counter], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (p.row_map && q < n_rows) q = (long long)p.row_map[q];
+            ctl->row = q;
             ctl->fail = 0; ctl->ovf = 0;
+#ifdef GP_SK_TIMING
+            ctl->t_row = ctl->tlast;
+#endif
         }
         GP_SYNC();
         const long long row = uni(ctl->row);
@@ -1434,7 +1444,16 @@ __device__ __forceinline__ void gfpush_sk_rows()
         GP_SYNC();
         phase_sk_wipe<BLOCK>(lds0, 1u, 0u, 0u);                                                            // TOP-K used the level tables' bytes; R is per row
         SKT(ctl, 10);
+#ifdef GP_SK_TIMING
+        if (tid == 0) {
+            const u64 dt = ctl->tlast - ctl->t_row;
+            ctl->row_sum += dt; ctl->row_max = max(ctl->row_max, dt); ++ctl->row_hist[min(31u, 63u - (u32)__builtin_clzll(dt | 1ull))];
+        }
+#endif
     }
+#ifdef GP_SK_TIMING
+    if (tid == 0 && p.wg_log) { p.wg_log[2u * blockIdx.x] = ctl->t_enter; p.wg_log[2u * blockIdx.x + 1u] = wall_clock64(); }
+#endif
     GP_SYNC();
     if (tid == 0) {
         const Counter dst[zNumStats] = { kPushes, kEdges, kDegLookups, kFilled, kLdsLevels, kFailedRows, kSkCandEdges, kSkSweep2 };
@@ -1446,6 +1465,10 @@ __device__ __forceinline__ void gfpush_sk_rows()
 #ifdef GP_SK_TIMING
         for (int i = 0; i < 16; ++i) __hip_atomic_fetch_add(&p.counters[kDiag0 + i], ctl->tacc[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         for (int i = 0; i < 14; ++i) __hip_atomic_fetch_add(&p.counters[kDiagX0 + i], ctl->tacc2[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_add(&p.counters[kDiagX0 + 16], ctl->row_sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_max(&p.counters[kDiagX0 + 17], ctl->row_max, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        for (int i = 0; i < 32; ++i)
+            if (ctl->row_hist[i]) __hip_atomic_fetch_add(&p.counters[kDiagX0 + 32 + i], ctl->row_hist[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #endif
     }
 }

@@ -216,6 +216,11 @@ int gp_reset_stats(gp_graph* g);
  *   "gk_acsr"         0 = the general kernel always runs on the packed CSR + indptr (default 1: on graphs of >= 65 536 nodes
  *                      it runs on the self-addressed copy -- rows at 128-byte units, a pusher's row start and degree in
  *                      its key -- like the sketch kernel)
+ *   "row_order"       0 = the first launch of a call takes its rows in caller order (default 1: heaviest first -- a pre-pass of
+ *                      two small kernels classes every row by the edges of its levels 1 and 2, read off its seed's columns, and
+ *                      the row queue hands the classes out in descending order, so that no long row is drawn last and holds the
+ *                      launch open; calls of no more rows than workgroups skip it).  Results, `filled` and the statistics do
+ *                      not depend on it: everything stays indexed by row
  *   "verify_merge"    1 = gp_gfpush (host buffers) compares every row it merged while the kernel was running with the pinned
  *                      slab once the launches have retired and fails with GP_ERR_HIP if one differs (a debugging aid: the
  *                      merge rule relies on stores to host memory arriving whole; default 0)
@@ -525,6 +530,10 @@ int gp_clip_adam_step(int device, const gp_optim_tensor* tensors, int32_t n_tens
 /* MAG's fused front end (resident rows -> S augmented embeddings in one launch, forward and backward, with its
  * mask formulas, order contract and bounds rules): declared in a header of its own, part of this ABI. */
 #include "grandplus_mag.h"
+
+/* Heaviest rows first (option "row_order"): the internal entry points that expose the order a call's rows were handed
+ * out in, and the sketch kernel's per-workgroup exit stamps: declared in a header of their own, part of this ABI. */
+#include "grandplus_order.h"
 
 /* ------------------------------------------------------------------------------------------
  * exact full-graph feature propagation of the inference path, reference

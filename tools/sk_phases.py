@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-phase time of the sketch kernel (thread 0's 100 MHz stamps, -DGP_SK_TIMING build = libgrandplus_skt.so; the stamps cost a
-few per cent).  Usage: GRANDPLUS_LIB=libgrandplus_skt.so python tools/sk_phases.py [workload] [rows] [key=value ...]"""
+few per cent), and the end of the launch: when each workgroup left the row loop, how long it then sat idle, how long rows take.  Usage: GRANDPLUS_LIB=libgrandplus_skt.so python tools/sk_phases.py [workload] [rows] [key=value ...]"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -37,4 +37,19 @@ n2 = ["filter: call -> entry", "filter: body", "filter: -> returned", "filter: -
 print(f"   filter calls/row {d[11] / rows:.2f}  scan calls/row {d[12] / rows:.2f}  second rounds {st['sketch_second_sweeps']}  candidate edges {st['sketch_candidate_edges'] / max(st['edges'], 1):.3f}")
 for i, n in enumerate(n2):
     print(f"   {n:55s} {x[i] / rows / 100:8.2f} us/row")
+# the end of the launch (100 MHz ticks -> us): a workgroup that finds the queue empty idles until the slowest one has finished
+log = g.workgroup_log(st["workgroups"]).astype(np.float64)
+t0 = log[:, 0].min()
+leave = (log[:, 1] - t0) / 100.0
+end = leave.max()
+idle = end - leave
+print(f"   end of the launch (row_order {extra.get('row_order', '1')}): last workgroup leaves at {end:.1f} us; workgroups leave at mean {leave.mean():.1f} / p50 {np.percentile(leave, 50):.1f} / "
+      f"p99 {np.percentile(leave, 99):.1f} us; entry spread {(log[:, 0].max() - t0) / 100.0:.1f} us")
+print(f"   idle behind the last row: mean {idle.mean():.1f} us = {100.0 * idle.mean() / end:.2f} % of the launch, p50 {np.percentile(idle, 50):.1f}, max {idle.max():.1f} us")
+hist = x[32:64]
+n_rows = max(sum(hist), 1)
+print(f"   row duration: mean {x[16] / n_rows / 100:.1f} us, max {x[17] / 100:.1f} us (max / mean {x[17] * n_rows / max(x[16], 1):.1f}); rows by duration:")
+for b, c in enumerate(hist):
+    if c:
+        print(f"      [{2 ** b / 100:9.2f}, {2 ** (b + 1) / 100:9.2f}) us  {c:8d}  {c / n_rows:7.4f}")
 g.close()
