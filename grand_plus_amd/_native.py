@@ -86,6 +86,14 @@ def mlp_infer_workspace_bytes(n_rows: int, f_in: int) -> int:
     return (4 * (n_rows + 2 * f_in) + 15) // 16 * 16
 
 
+GP_MLP_CHAIN_MAX_HIDDEN, GP_MLP_CHAIN_MAX_OUT = 1024, 64
+
+
+def mlp_infer_chain_workspace_bytes(n_rows: int, f_in: int, f_hidden: int) -> int:
+    """GP_MLP_INFER_CHAIN_WORKSPACE_BYTES of grandplus_infer_chain.h."""
+    return (4 * (n_rows + 2 * f_in + 2 * f_hidden) + 15) // 16 * 16
+
+
 class GpStats(ctypes.Structure):
     _fields_ = [
         ("rows", ctypes.c_int64), ("pushes", ctypes.c_int64), ("edges", ctypes.c_int64),
@@ -216,6 +224,14 @@ _ORDER_SIGNATURES = {
     "gp_internal_wg_log": (_int, [_vp, _i64p, _int], False),
 }
 ORDER_EXPORTS = tuple(_ORDER_SIGNATURES)
+# The last two eval blocks as one kernel, which include/grandplus_infer_chain.h declares (grandplus.h includes it): the same
+# convention, held against that header type by type by tests/test_host_infer_chain.py.  Each block's arguments are
+# gp_mlp_infer_block's: weight, bias, flags, the four BatchNorm tensors and eps.
+_chain_block = [_vp, _vp, _int, _vp, _vp, _vp, _vp, _f32]
+_CHAIN_SIGNATURES = {
+    "gp_mlp_infer_chain2": (_int, [_int, _vp, _i64, _i32, _i32, _i32] + _chain_block + _chain_block + [_vp, _vp, _vp], False),
+}
+CHAIN_EXPORTS = tuple(_CHAIN_SIGNATURES)
 
 _LIB = None
 
@@ -246,7 +262,7 @@ def lib():
         pass
     L = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes, required) in {**_SIGNATURES, **_EVAL_SIGNATURES, **_SCATTER_SIGNATURES, **_INFER_SIGNATURES,
-                                              **_MAG_SIGNATURES, **_ORDER_SIGNATURES}.items():
+                                              **_MAG_SIGNATURES, **_ORDER_SIGNATURES, **_CHAIN_SIGNATURES}.items():
         if not required and not hasattr(L, name):
             setattr(L, name, _missing(name))
             continue

@@ -212,18 +212,19 @@ def valid(model, rows, features, idx_val, labels, batch_size=10000, dropnode_rat
     return (loss, acc, counts) if return_counts else (loss, acc)
 
 
-def local_logits(model, attr_mat, batch_size=10000, out=None):
+def local_logits(model, attr_mat, batch_size=10000, out=None, fused=False):
     """The reference's `get_local_logits` (model.py:169-178) with the logits staying on the device: the model in eval
     semantics over every row of attr_mat (float32 CUDA [N, F], contiguous), batch_size rows at a time, as one [N, C]
     device tensor (`out`, if given).  A thin wrapper over `model.infer`: the module's training flag is not
-    touched, nothing synchronises, and the rows get the same bits whatever the batch size."""
+    touched, nothing synchronises, and the rows get the same bits whatever the batch size.  fused=True is `infer`'s: the
+    last two blocks as one kernel, the same bits."""
     if not isinstance(model, torch.nn.Module) or not hasattr(model, "infer"):
         raise TypeError("local_logits: model must be a GrandPlusMLP or MagMLP")
-    return model.infer(attr_mat, out=out, batch_size=batch_size)
+    return model.infer(attr_mat, out=out, batch_size=batch_size, fused=fused)
 
 
 def predict(graph, features, model, idx_test, labels, prop_mode, order, alpha=0.2, batch_size_logits=10000, return_preds=False,
-            infer=False):
+            infer=False, fused=False):
     """The reference's `predict` (model.py:181-224) on the GPU: the test accuracy as a 0-dim float32 device tensor, and
     with return_preds also the int32 [len(idx_test)] predictions.
 
@@ -232,7 +233,10 @@ def predict(graph, features, model, idx_test, labels, prop_mode, order, alpha=0.
     mode over all N rows, batch_size_logits at a time, into one [N, C] device tensor; one head call gathers
     logits[idx_test] and labels[idx_test].  No logit reaches the host.  An id outside [0, N) is counted as a bad row
     (prediction -1), never read.  infer=True runs the model through `local_logits` (the inference GEMM of DESIGN §7j,
-    each batch written straight into the [N, C] tensor) in place of the batch loop over the training kernels."""
+    each batch written straight into the [N, C] tensor) in place of the batch loop over the training kernels; with it,
+    fused=True runs the model's last two blocks as one kernel (the same bits); fused=True alone is refused."""
+    if fused and not infer:
+        raise ValueError("predict: fused=True needs infer=True (the fused kernel is an inference path)")
     _check_common(model, features, labels, "predict")
     batch_size_logits = int(batch_size_logits)
     if batch_size_logits < 1:
@@ -243,7 +247,7 @@ def predict(graph, features, model, idx_test, labels, prop_mode, order, alpha=0.
     with _NoSync(model):
         prop = graph.propagate_features(features, prop_mode, order, alpha)
         if infer:
-            logits = local_logits(model, prop, batch_size_logits)
+            logits = local_logits(model, prop, batch_size_logits, fused=fused)
         elif N <= batch_size_logits:
             logits = model(prop)
         else:

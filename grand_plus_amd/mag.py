@@ -182,7 +182,7 @@ def valid_mag(model, rows, attr_indptr, attr_indices, attr_data, idx_val, labels
 
 
 def predict_mag(graph, attr_indptr, attr_indices, attr_data, model, idx_test, labels, prop_mode, order, alpha=0.2,
-                batch_size_logits=10000, return_preds=False, infer=False):
+                batch_size_logits=10000, return_preds=False, infer=False, fused=False):
     """MAG's `predict` (model_mag.py:192-245) on the GPU: the embedding of every node in eval mode
     (`embedding_bag_csr(nodes=None)`, model_mag.py:197-205), then `predict` on it.  A composition, no kernel of its own;
     the whole body is free of host synchronisation.  Same returns as `predict`."""
@@ -194,4 +194,4 @@ def predict_mag(graph, attr_indptr, attr_indices, attr_data, model, idx_test, la
     idx_test = _node_ids(idx_test, "idx_test", model.embeds.weight.device)       # the upload of a host list comes first
     with _NoSync(model):
         emb = embedding_bag_csr(model.embeds.weight, attr_indptr, attr_indices, attr_data, nodes=None, training=False, validate=False)
-        return predict(graph, emb, model, idx_test, labels, prop_mode, order, alpha, batch_size_logits, return_preds, infer)
+        return predict(graph, emb, model, idx_test, labels, prop_mode, order, alpha, batch_size_logits, return_preds, infer, fused)

@@ -17,7 +17,9 @@ keep mask per layer.  Calls without grad (eval, `torch.no_grad`) run the forward
 `reference_forward` is the torch formulation kept for comparison and benchmarks, never taken silently.
 
 `infer` is the eval-only forward over any number of rows: `gp_mlp_infer_block` of csrc/mlp_infer.hip per
-layer, on a GEMM tiled for millions of rows; it is opt-in and leaves `forward` as it is.
+layer, on a GEMM tiled for millions of rows; it is opt-in and leaves `forward` as it is.  `infer(fused=True)` runs the
+last two blocks as one kernel, `gp_mlp_infer_chain2` of csrc/mlp_chain.hip: the hidden activations stay in
+LDS, and the result has the bits of the unfused path.
 """
 from __future__ import annotations
 
@@ -194,7 +196,7 @@ def _torch_block(x, fc, bn, relu, norm, detach, p, training):
     return fc(x)
 
 
-def _check_infer(X, out, batch_size, layers):
+def _check_infer(X, out, batch_size, layers, fused=False):
     """Every host check of `infer` before the first launch; the CPU-tensor check comes last, as in _check_input."""
     if not isinstance(X, torch.Tensor):
         raise ValueError("X must be a tensor")
@@ -228,6 +230,15 @@ def _check_infer(X, out, batch_size, layers):
             raise ValueError(f"out must be [B, C] = {(B, C)}, got {tuple(out.shape)}")
         if out.device != X.device:
             raise ValueError(f"out must be on X's device {X.device}, got {out.device}")
+    if fused:                                                # the limits of gp_mlp_infer_chain2 (grandplus_infer_chain.h)
+        if len(layers) < 2:
+            raise ValueError(f"infer(fused=True) fuses the last two blocks: the model has {len(layers)}, fewer than two blocks")
+        hidden = layers[-1][0].weight.shape[1]
+        if hidden > _native.GP_MLP_CHAIN_MAX_HIDDEN:
+            raise ValueError(f"infer(fused=True) keeps the hidden tile in LDS: hidden size {hidden} is above the limit of "
+                             f"{_native.GP_MLP_CHAIN_MAX_HIDDEN}")
+        if C > _native.GP_MLP_CHAIN_MAX_OUT:
+            raise ValueError(f"infer(fused=True): {C} classes are above the limit of {_native.GP_MLP_CHAIN_MAX_OUT}")
     if not X.is_cuda:
         raise ValueError("the MLP runs on the GPU only: X must be a CUDA tensor (no CPU fallback)")
     if layers and layers[0][0].weight.device != X.device:
@@ -247,6 +258,24 @@ def _infer_block(x, fc, bn, relu, norm, out, ws):
     _native.raise_for_status(rc)
 
 
+def _block_args(fc, bn, relu, norm):
+    """A block's arguments as gp_mlp_infer_block and gp_mlp_infer_chain2 take them: weight, bias, flags, BatchNorm, eps."""
+    flags = (_native.GP_MLP_RELU if relu else 0) | (_native.GP_MLP_NORM if norm else 0) | \
+            (_native.GP_MLP_BN if bn is not None else 0)
+    return (fc.weight.data_ptr(), _ptr(fc.bias), flags,
+            _ptr(bn.weight) if bn is not None else None, _ptr(bn.bias) if bn is not None else None,
+            _ptr(bn.running_mean) if bn is not None else None, _ptr(bn.running_var) if bn is not None else None,
+            float(bn.eps) if bn is not None else 1e-5)
+
+
+def _infer_chain2(x, first, second, out, ws):
+    """Two eval blocks on x [n, F] into out [n, C] as one kernel (gp_mlp_infer_chain2); ws: the caller's scratch."""
+    rc = _native.lib().gp_mlp_infer_chain2(
+        x.device.index, x.data_ptr(), x.shape[0], x.shape[1], first[0].weight.shape[0], second[0].weight.shape[0],
+        *_block_args(*first[:4]), *_block_args(*second[:4]), out.data_ptr(), _ptr(ws), _stream(x))
+    _native.raise_for_status(rc)
+
+
 class _MLPBase:
     def reset_param(self):
         for lin in self.fcs:
@@ -261,16 +290,19 @@ class _MLPBase:
         return _run(self, X, seed, keep, self._layers())
 
     @torch.no_grad()
-    def infer(self, X, out=None, batch_size=None):
+    def infer(self, X, out=None, batch_size=None, fused=False):
         """The model in eval semantics over any number of rows: X [B, F] float32 CUDA, contiguous (a row
         slice is fine) -> [B, C].  Running statistics, no dropout, whatever `self.training` says: the flag, the running
         statistics and num_batches_tracked are neither read nor written, and the result never requires grad.
         batch_size bounds the hidden activations: rows go through the layers that many at a time (None: all at once),
         the last layer writing straight into its row slice of the result; every row gets the same bits either way.
         out: a contiguous float32 [B, C] on X's device, written and returned.  One gp_mlp_infer_block per layer and
-        chunk; no host synchronisation."""
+        chunk; no host synchronisation.
+        fused=True: the last two blocks of a chunk are one gp_mlp_infer_chain2 call, their hidden activations
+        stay in LDS and no [rows, hidden] tensor is allocated for them; earlier blocks run as above.  The bits are those of
+        fused=False.  It needs at least two blocks, a last hidden size <= 1024 and <= 64 classes (ValueError)."""
         layers = self._layers()
-        C = _check_infer(X, out, batch_size, layers)
+        C = _check_infer(X, out, batch_size, layers, fused)
         B = X.shape[0]
         if not layers:                                       # a MagMLP that is its embedding alone
             return X if out is None else out.copy_(X)
@@ -279,16 +311,23 @@ class _MLPBase:
         step = B if batch_size is None else min(int(batch_size), B)
         if B == 0:
             return out
-        need = any(norm or bn is not None for _fc, bn, _relu, norm, *_ in layers)
-        ws = torch.empty(_native.mlp_infer_workspace_bytes(step, max(fc.weight.shape[1] for fc, *_ in layers)),
+        single = layers[:-2] if fused else layers            # the blocks that go one gp_mlp_infer_block each
+        need = any(norm or bn is not None for _fc, bn, _relu, norm, *_ in single)
+        ws = torch.empty(_native.mlp_infer_workspace_bytes(step, max(fc.weight.shape[1] for fc, *_ in single)),
                          dtype=torch.uint8, device=X.device) if need else None
+        if fused:
+            (fc1, *_), (fc2, *_) = layers[-2:]
+            ws2 = torch.empty(_native.mlp_infer_chain_workspace_bytes(step, fc1.weight.shape[1], fc2.weight.shape[1]),
+                              dtype=torch.uint8, device=X.device)
         for start in range(0, B, step):
             x = X[start:start + step]
-            for l, (fc, bn, relu, norm, _detach, _p) in enumerate(layers):
+            for l, (fc, bn, relu, norm, _detach, _p) in enumerate(single):
                 y = out[start:start + step] if l == len(layers) - 1 else \
                     torch.empty((x.shape[0], fc.weight.shape[0]), dtype=torch.float32, device=X.device)
                 _infer_block(x, fc, bn, relu, norm, y, ws)
                 x = y
+            if fused:
+                _infer_chain2(x, layers[-2], layers[-1], out[start:start + step], ws2)
         return out
 
     def reference_forward(self, X):

@@ -527,6 +527,11 @@ int gp_clip_adam_step(int device, const gp_optim_tensor* tensors, int32_t n_tens
  * contracts and GP_MLP_INFER_WORKSPACE_BYTES): declared in a header of its own, part of this ABI. */
 #include "grandplus_infer.h"
 
+/* The last two eval blocks as one kernel, the hidden activations staying in LDS (the entry point, its bitwise
+ * contract against two gp_mlp_infer_block calls and GP_MLP_INFER_CHAIN_WORKSPACE_BYTES): declared in a header of its own,
+ * part of this ABI. */
+#include "grandplus_infer_chain.h"
+
 /* MAG's fused front end (resident rows -> S augmented embeddings in one launch, forward and backward, with its
  * mask formulas, order contract and bounds rules): declared in a header of its own, part of this ABI. */
 #include "grandplus_mag.h"
