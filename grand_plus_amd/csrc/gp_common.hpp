@@ -1,7 +1,8 @@
-// gp_common.hpp -- what the translation units of a training step (augment.hip, mlp.hip, objective.hip, propagate.hip)
-// share: the dropout counter hash and the seed derivations that grandplus.h fixes bit for bit, the wave reductions,
-// the float vector map, and the host helpers every entry point uses (error record, device selection, launch status,
-// feature-column launch geometry).  Everything has internal linkage: no symbol leaves a translation unit.
+// gp_common.hpp -- what the translation units outside GFPush share (augment.hip, evaluate.hip, mag_prop.hip,
+// objective.hip, optim.hip, propagate.hip, scatter_det.hip, and through mlp_eval.hpp mlp.hip, mlp_infer.hip and
+// mlp_chain.hip): the dropout counter hash and the seed derivations that grandplus.h fixes bit for bit, the wave
+// reductions, the float vector map, and the host helpers every entry point uses (error record, device selection,
+// launch status, feature-column launch geometry).  Everything has internal linkage: no symbol leaves a translation unit.
 #pragma once
 
 #include <hip/hip_runtime.h>

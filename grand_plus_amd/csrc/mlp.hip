@@ -15,15 +15,11 @@
 // Backward: dA = dY W (GEMM), BN's column sums and dn (mlp_bn_backward_kernel), the row norm and ReLU
 // (mlp_row_backward_kernel, only when dX is wanted), dW = dY^T a over the saved a (GEMM, split-M partials summed in a
 // fixed order), db (mlp_colsum_kernel).  No atomics anywhere: every result is bitwise reproducible.
-#include "gp_common.hpp"
+#include "mlp_eval.hpp"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kBlock = 256;
-constexpr int kTile = 64;             // GEMM output tile (rows and columns)
-constexpr int kBK = 16;               // reduction depth staged per step (4 MFMA k-steps)
+constexpr int kTile = 64;             // GEMM output tile (rows and columns); kBK = 16 deep per step: 4 MFMA k-steps
 constexpr int kLdsStride = kTile + 16;
 constexpr int kMaxS = 16;
 constexpr long long kTargetTiles = 128;   // split the reduction until about this many tiles per sample exist
@@ -184,13 +180,8 @@ mlp_row_kernel(Block P, long long M, float* __restrict__ r)
     const long long n_waves = (long long)gridDim.x * (kBlock / 64);
     for (long long m = (long long)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6); m < M; m += n_waves) {
         const float* xr = P.x + m * P.K;
-        float ss = 0.0f;
-        for (int k = lane; k < P.K; k += 64) {
-            const float u = P.relu ? fmaxf(xr[k], 0.0f) : xr[k];
-            ss += u * u;
-        }
-        ss = wave_sum(ss);
-        if (lane == 0) r[m] = 1.0f / (1e-12f + sqrtf(ss));                      // model.py:45-46
+        const float rm = row_inv_norm(P.K, lane, [&](int k) { return P.relu ? fmaxf(xr[k], 0.0f) : xr[k]; });
+        if (lane == 0) r[m] = rm;
     }
 }
 
@@ -228,7 +219,7 @@ mlp_bn_stats_kernel(Block P, BnArgs a)
             const float mu = a.rmean[k], is = 1.0f / sqrtf(a.rvar[k] + a.eps);
             const float g = a.gamma ? a.gamma[k] : 1.0f, be = a.beta ? a.beta[k] : 0.0f;
             a.mean[k] = mu; a.invstd[k] = is;
-            a.mul[k] = g * is; a.add[k] = be - mu * (g * is);
+            bn_affine(mu, is, g, be, &a.mul[k], &a.add[k]);
         }
         return;
     }
@@ -251,7 +242,7 @@ mlp_bn_stats_kernel(Block P, BnArgs a)
             const float g = a.gamma ? a.gamma[k] : 1.0f, be = a.beta ? a.beta[k] : 0.0f;
             const long long o = (long long)s * P.K + k;
             a.mean[o] = mu; a.invstd[o] = is;
-            a.mul[o] = g * is; a.add[o] = be - mu * (g * is);
+            bn_affine(mu, is, g, be, &a.mul[o], &a.add[o]);
             if (a.rmean) {                           // once per sample, in sample order, as S calls of bn(x)
                 const float m = a.momentum;
                 a.rmean[k] = (1.0f - m) * a.rmean[k] + m * mu;
@@ -363,8 +354,6 @@ mlp_colsum_kernel(const float* __restrict__ dy, long long M, int N, float* __res
 }
 
 // ---- host side
-long long cdiv(long long a, long long b) { return (a + b - 1) / b; }
-
 // chunk of the reduction dimension: enough splits that the (row tiles x column tiles) of one sample reach kTargetTiles,
 // at least 64 deep each, at most kMaxSplits
 long long k_chunk(long long tiles, long long K)

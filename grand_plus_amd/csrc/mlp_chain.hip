@@ -5,16 +5,14 @@
 //     r2_m       = 1 / (1e-12 + |relu?(y1_m)|_2)                                        from the tile
 //     out[BM x C] = a2 W2^T + b2       a2 = (relu?(y1) * r2_m) * mul2_k + add2_k        applied as the tile is read
 //
-//   mlp_chain_row_kernel   r1: mlp_infer.hip's mlp_infer_row_kernel restated                    (GP_MLP_NORM of block 1)
-//   mlp_chain_fold_kernel  mul / add: mlp_infer.hip's mlp_infer_fold_kernel restated            (GP_MLP_BN, once per block)
+//   mlp_eval_row_kernel    r1                                                                   (GP_MLP_NORM of block 1)
+//   mlp_eval_fold_kernel   mul / add                                                            (GP_MLP_BN, once per block)
 //   mlp_chain_kernel       the three steps above; BM = 128 (H <= 128), 64 (H <= 512), 32 (H <= 1024)
 //
 // Arithmetic contract: the bits of gp_mlp_infer_block for block 1 into a [n_rows x H] buffer followed by
-// gp_mlp_infer_block for block 2.  Every output of either block is one chain
-//     acc = +0;  for k ascending: acc = fma(a[m,k], W[n,k], acc);  y = acc + b[n]
-// (the k tail up to the next multiple of 16 adds fma(0, 0, acc), as there), r2 takes mlp_infer_row_kernel's order (lane l
-// of a wave sums k = l, l + 64, ..., then the butterfly), the fold and the NaN-keeping relu are restated line by line,
-// and r2 is NOT pulled out of the second product.  -ffp-contract=off.  No atomics.
+// gp_mlp_infer_block for block 2.  Both units take every formula from mlp_eval.hpp: the prologue, the row sum (r2 through
+// row_inv_norm, over the tile), the fold and the NaN-keeping relu.  The k tail up to the next
+// multiple of 16 adds fma(0, 0, acc) as there, and r2 is NOT pulled out of the second product.  No atomics.
 //
 // Block 1 loops over chunks of 128 hidden columns and, inside a chunk, over k in stages of 16 through two LDS stages
 // (mlp_infer.hip's pipeline and LDS image: rows 20 floats apart, the k of a row permuted when written so that one
@@ -23,20 +21,13 @@
 // kperm16 being the permutation of the 16x16x4 operand: block 2 (v_mfma_f32_16x16x4_f32, 32 k per stage of W2, mul2 and
 // add2) reads its A operand from the tile with one ds_read_b128 per 16 k.  k of one output is never split across waves:
 // the waves share the output fragments.
-#include "gp_common.hpp"
+#include "mlp_eval.hpp"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kBlock = 256;
-constexpr int kBK = 16;               // reduction depth of an LDS row
-constexpr int kStride = kBK + 4;      // floats between the LDS rows of a stage
 constexpr int kCN = 128;              // hidden columns per chunk of block 1
 constexpr int kSub = 2;               // block 2: 16-deep sub-stages per stage
 constexpr int kSubRows = GP_MLP_CHAIN_MAX_OUT + 2;   // W2's rows, then mul2 and add2
-constexpr long long kMaxGrid = 1ll << 22;            // workgroups per launch
 
 struct Chain {
     const float* x; long long M; int K; int H; int C;
@@ -49,27 +40,8 @@ struct Chain {
     int hs;                               // floats between the rows of the hidden tile
 };
 
-// where k (0 ... 15) of an LDS row is stored (mlp_infer.hip's kperm): the k of one lane, in step order, are contiguous
-__device__ __forceinline__ int kperm32(int k) { return (k & 1) * 8 + (k >> 1); }
-__device__ __forceinline__ int kperm16(int k) { return (k & 3) * 4 + (k >> 2); }
+// where hidden column k is stored in its row of the tile: block 2's A operand, permuted when written
 __device__ __forceinline__ int hid_pos(int k) { return (k & ~15) + kperm16(k & 15); }
-
-// mlp_infer.hip's relu: a NaN stays a NaN; every other value is fmaxf(v, 0), bit for bit
-__device__ __forceinline__ float relu_nan(float v) { return v != v ? v : fmaxf(v, 0.0f); }
-
-// four consecutive k of one row from global memory; VEC: one 16-byte load (K % 4 == 0: all in or all out)
-template <bool VEC>
-__device__ __forceinline__ void load_quad(const float* __restrict__ p, bool row_ok, int k, int K, float* v)
-{
-    if (VEC) {
-        float4 t = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        if (row_ok && k < K) t = *reinterpret_cast<const float4*>(p + k);
-        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = (row_ok && k + j < K) ? p[k + j] : 0.0f;
-    }
-}
 
 constexpr int chain_stage_floats(int BM) { return (BM + kCN) * kStride; }
 constexpr int chain_lds_floats(int BM, int hs) { return BM * hs + BM + 2 * chain_stage_floats(BM); }
@@ -120,7 +92,7 @@ mlp_chain_kernel(Chain g)
 #pragma unroll
                 for (int i = 0; i < NA; ++i) {
                     if (BM * 4 < kBlock && t >= BM * 4) continue;
-                    load_quad<VEC1>(ap[i], a_ok[i], k0 + ak[i], K, xa[i]);
+                    load_row<4, VEC1>(ap[i], a_ok[i], k0 + ak[i], K, xa[i]);
                     if (g.mul1) {
 #pragma unroll
                         for (int j = 0; j < 4; ++j) {
@@ -131,7 +103,7 @@ mlp_chain_kernel(Chain g)
                     }
                 }
 #pragma unroll
-                for (int i = 0; i < NW; ++i) load_quad<VEC1>(bp[i], b_ok[i], k0 + bk[i], K, wb[i]);
+                for (int i = 0; i < NW; ++i) load_row<4, VEC1>(bp[i], b_ok[i], k0 + bk[i], K, wb[i]);
             };
             auto stage = [&](int k0, float* buf) {
 #pragma unroll
@@ -140,13 +112,8 @@ mlp_chain_kernel(Chain g)
                     float* arow = buf + ar[i] * kStride;
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
-                        float v = 0.0f;
-                        if (a_ok[i] && k0 + ak[i] + j < K) {
-                            v = xa[i][j];
-                            if (g.relu1) v = relu_nan(v);
-                            if (g.r1) v = v * rm[i];
-                            if (g.mul1) v = v * mu[i][j] + ad[i][j];
-                        }
+                        const bool ok = a_ok[i] && k0 + ak[i] + j < K;
+                        const float v = ok ? eval_prologue(xa[i][j], g.relu1, g.r1, rm[i], g.mul1, mu[i][j], ad[i][j]) : 0.0f;
                         arow[kperm32(ak[i] + j)] = v;
                     }
                 }
@@ -224,18 +191,12 @@ mlp_chain_kernel(Chain g)
     }
     __syncthreads();
 
-    // ------------------------------------------------------------------- r2: mlp_infer_row_kernel's order, from the tile
+    // -------------------------------------------------------------------------- r2: the row sum of mlp_eval.hpp, from the tile
     if (g.norm2) {
         for (int row = wave; row < BM; row += kBlock / 64) {
             const float* hr = hid + row * hs;
-            float ss = 0.0f;
-            for (int k = lane; k < H; k += 64) {
-                const float v = hr[hid_pos(k)];
-                const float u = g.relu2 ? relu_nan(v) : v;
-                ss += u * u;
-            }
-            ss = wave_sum(ss);
-            if (lane == 0) r2[row] = 1.0f / (1e-12f + sqrtf(ss));
+            const float rm = row_inv_norm(H, lane, [&](int k) { return g.relu2 ? relu_nan(hr[hid_pos(k)]) : hr[hid_pos(k)]; });
+            if (lane == 0) r2[row] = rm;
         }
     }
     // (the barrier after stage 0 of block 2 orders r2 before its first read)
@@ -262,7 +223,7 @@ mlp_chain_kernel(Chain g)
         float wb[NQ][4], ma = 0.0f;
         auto load = [&](int k0) {
 #pragma unroll
-            for (int i = 0; i < NQ; ++i) load_quad<VEC2>(bp[i], b_ok[i], k0 + kq[i], H, wb[i]);
+            for (int i = 0; i < NQ; ++i) load_row<4, VEC2>(bp[i], b_ok[i], k0 + kq[i], H, wb[i]);
             if (t < 64) {                                    // mul2 (t < 32) and add2 of this stage's 32 k
                 const int k = k0 + (t & 31);
                 ma = (g.mul2 && k < H) ? (t < 32 ? g.mul2[k] : g.add2[k]) : 0.0f;
@@ -308,10 +269,7 @@ mlp_chain_kernel(Chain g)
                     const f32x4 y = *reinterpret_cast<const f32x4*>(hid + ((wrg * RPW + i) * 16 + fl) * hs + ks + 4 * fh);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        float v = y[e];
-                        if (g.relu2) v = relu_nan(v);
-                        if (g.norm2) v = v * rmv[i];
-                        if (g.mul2) v = v * mu[e] + ad[e];
+                        const float v = eval_prologue(y[e], g.relu2, g.norm2, rmv[i], g.mul2, mu[e], ad[e]);
                         a[i][e] = ks + fh + 4 * e < H ? v : 0.0f;
                     }
                 }
@@ -351,39 +309,7 @@ mlp_chain_kernel(Chain g)
     }
 }
 
-// ---- row scales of x: mlp_infer.hip's mlp_infer_row_kernel restated (one wave per row, lanes over columns, the butterfly)
-__global__ void __launch_bounds__(kBlock)
-mlp_chain_row_kernel(const float* __restrict__ x, long long M, int K, int relu, float* __restrict__ r)
-{
-    const int lane = threadIdx.x & 63;
-    const long long n_waves = (long long)gridDim.x * (kBlock / 64);
-    for (long long m = (long long)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6); m < M; m += n_waves) {
-        const float* xr = x + m * K;
-        float ss = 0.0f;
-        for (int k = lane; k < K; k += 64) {
-            const float u = relu ? relu_nan(xr[k]) : xr[k];
-            ss += u * u;
-        }
-        ss = wave_sum(ss);
-        if (lane == 0) r[m] = 1.0f / (1e-12f + sqrtf(ss));
-    }
-}
-
-// ---- mlp_infer.hip's mlp_infer_fold_kernel restated: BN(u)_k = u * mul_k + add_k
-__global__ void __launch_bounds__(kBlock)
-mlp_chain_fold_kernel(int K, const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ rmean,
-                      const float* __restrict__ rvar, float eps, float* __restrict__ mul, float* __restrict__ add)
-{
-    const int k = blockIdx.x * kBlock + threadIdx.x;
-    if (k >= K) return;
-    const float mu = rmean[k], is = 1.0f / sqrtf(rvar[k] + eps);
-    const float g = gamma ? gamma[k] : 1.0f, be = beta ? beta[k] : 0.0f;
-    mul[k] = g * is; add[k] = be - mu * (g * is);
-}
-
 // ---- host side
-long long cdiv(long long a, long long b) { return (a + b - 1) / b; }
-
 typedef void (*ChainKernel)(Chain);
 
 template <int BM>
@@ -459,24 +385,17 @@ int gp_mlp_infer_chain2(int device, const float* d_x, int64_t n_rows, int32_t f_
     g.out = d_out;
     if (norm1) {
         g.r1 = ws;
-        const long long grid = cdiv(n_rows, kBlock / 64);
-        hipLaunchKernelGGL(mlp_chain_row_kernel, dim3((u32)(grid < kMaxGrid ? grid : kMaxGrid)), dim3(kBlock), 0, st, d_x,
-                           (long long)n_rows, (int)f_in, g.relu1, ws);
-        if (const int rc = launch_status("mlp_chain_row_kernel")) return rc;
+        if (const int rc = launch_row_scales(d_x, n_rows, f_in, g.relu1, ws, st)) return rc;
     }
     if (bn1) {
         float* mul = ws + n_rows;
         g.mul1 = mul; g.add1 = mul + f_in;
-        hipLaunchKernelGGL(mlp_chain_fold_kernel, dim3((u32)cdiv(f_in, kBlock)), dim3(kBlock), 0, st, (int)f_in, d_bn1_weight,
-                           d_bn1_bias, d_bn1_mean, d_bn1_var, bn1_eps, mul, mul + f_in);
-        if (const int rc = launch_status("mlp_chain_fold_kernel")) return rc;
+        if (const int rc = launch_bn_fold(f_in, d_bn1_weight, d_bn1_bias, d_bn1_mean, d_bn1_var, bn1_eps, mul, st)) return rc;
     }
     if (bn2) {
         float* mul = ws + n_rows + 2ll * f_in;
         g.mul2 = mul; g.add2 = mul + f_hidden;
-        hipLaunchKernelGGL(mlp_chain_fold_kernel, dim3((u32)cdiv(f_hidden, kBlock)), dim3(kBlock), 0, st, (int)f_hidden, d_bn2_weight,
-                           d_bn2_bias, d_bn2_mean, d_bn2_var, bn2_eps, mul, mul + f_hidden);
-        if (const int rc = launch_status("mlp_chain_fold_kernel")) return rc;
+        if (const int rc = launch_bn_fold(f_hidden, d_bn2_weight, d_bn2_bias, d_bn2_mean, d_bn2_var, bn2_eps, mul, st)) return rc;
     }
     return run_chain(g, st);
 }

@@ -3,18 +3,14 @@
 //
 //     y[M x N] = a W^T + b,      a = BN_running( node_norm( relu?(x) ) ),      node_norm(u) = u / (1e-12 + |u|_2)
 //
-//   mlp_infer_row_kernel   one wave per row: r_m = 1 / (1e-12 + |relu?(x_m)|_2)                        (GP_MLP_NORM only)
-//   mlp_infer_fold_kernel  the running statistics folded into one affine map per column: mul_k, add_k    (GP_MLP_BN only)
+//   mlp_eval_row_kernel    one wave per row: r_m = 1 / (1e-12 + |relu?(x_m)|_2)                        (GP_MLP_NORM only)
+//   mlp_eval_fold_kernel   the running statistics folded into one affine map per column: mul_k, add_k    (GP_MLP_BN only)
 //   mlp_infer_gemm_kernel  fp32-input MFMA; a = (relu?(x) * r_m) * mul_k + add_k is computed while the A tile is staged
 //
-// Arithmetic contract (every instantiation, whatever the tile, M or N; -ffp-contract=off):
-//     acc = +0;  for k = 0 ... F-1 ascending: acc = fma(a[m,k], W[n,k], acc);  y[m,n] = acc + b[n]
-// one chain per output (the k tail up to the next multiple of 16 adds fma(0, 0, acc), as mlp.hip's kernel does).  r_m,
-// mul_k and add_k are restated from mlp.hip's eval mode line by line (mlp_row_kernel's strided sums and butterfly, the
-// fold of mlp_bn_stats_kernel), so a layer equals gp_mlp_block_forward bit for bit wherever that takes one k-chain.
-// Output row m depends on input row m and the parameters only; no atomics; no sample dimension, dropout or split-K.
-// A NaN in input row m makes output row m NaN through every layer: relu keeps a NaN here (torch's rule), where the
-// block kernel's fmaxf turns it into 0; on every other value the two agree bit for bit.
+// The arithmetic contract (one fma chain per output in ascending k, the order of the row sums, the fold, the
+// NaN-keeping relu) is mlp_eval.hpp's, which also defines the first two kernels; mlp.hip's eval mode calls the same
+// row sum and fold, so a layer equals gp_mlp_block_forward bit for bit wherever that takes one k-chain.  Every
+// instantiation here keeps the contract, whatever the tile, M or N.  No sample dimension, dropout or split-K.
 //
 // The GEMM: 256 threads, k-depth 16 per stage, two LDS stages (the next A/W tile is loaded from global memory while
 // the current one is multiplied; one barrier per k-step).
@@ -24,18 +20,11 @@
 // ds_read_b128 is conflict-free for the wide tile, at most 2-way for the narrow one).  A lane of 32x32x2 holds
 // k = 2 s + (lane >> 5) of step s, a lane of 16x16x4 k = 4 s + (lane >> 4): the k of a row are permuted when they are
 // WRITTEN (kperm) so that one ds_read_b128 hands a lane its k of four consecutive steps, and the chain stays in k order.
-#include "gp_common.hpp"
+#include "mlp_eval.hpp"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kBlock = 256;
 constexpr int kBM = 128;              // rows of an output tile, both instantiations
-constexpr int kBK = 16;               // reduction depth per stage
-constexpr int kStride = kBK + 4;      // floats between the LDS rows
-constexpr long long kMaxGrid = 1ll << 22;   // workgroups per launch (grid.x * 256 threads stays below 2^32)
 
 struct Infer {
     const float* x; long long M; int K; int N;
@@ -47,32 +36,8 @@ struct Infer {
     int nct;                          // column tiles
 };
 
-// where k (0 ... 15) of a tile row is stored: the k of one lane, in step order, are contiguous
-template <bool WIDE> __device__ __forceinline__ int kperm(int k)
-{
-    return WIDE ? (k & 1) * 8 + (k >> 1) : (k & 3) * 4 + (k >> 2);
-}
-
-// relu that keeps a NaN (fmaxf alone gives 0, and a bad input row would come out finite after the first hidden layer);
-// for every other value it is fmaxf(v, 0), bit for bit
-__device__ __forceinline__ float relu_nan(float v) { return v != v ? v : fmaxf(v, 0.0f); }
-
-// PER consecutive k of one row from global memory: float4 where VEC says the pointers and K allow it
-template <int PER, bool VEC>
-__device__ __forceinline__ void load_row(const float* __restrict__ p, bool row_ok, int k, int K, float* v)
-{
-    if (VEC) {
-#pragma unroll
-        for (int q = 0; q < PER / 4; ++q) {
-            float4 t = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            if (row_ok && k + 4 * q < K) t = *reinterpret_cast<const float4*>(p + k + 4 * q);   // K % 4 == 0: all in or all out
-            v[4 * q] = t.x; v[4 * q + 1] = t.y; v[4 * q + 2] = t.z; v[4 * q + 3] = t.w;
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < PER; ++j) v[j] = (row_ok && k + j < K) ? p[k + j] : 0.0f;
-    }
-}
+// where k (0 ... 15) of a tile row is stored: the permutation of this instantiation's MFMA operand
+template <bool WIDE> __device__ __forceinline__ int kperm(int k) { return WIDE ? kperm32(k) : kperm16(k); }
 
 template <bool WIDE, bool VEC>
 __global__ void __launch_bounds__(kBlock, 2)
@@ -112,13 +77,8 @@ mlp_infer_gemm_kernel(Infer g)
         float* brow = buf + (kBM + br) * kStride;
 #pragma unroll
         for (int j = 0; j < PA; ++j) {
-            float v = 0.0f;
-            if (a_ok && k0 + ak + j < g.K) {
-                v = xa[j];
-                if (g.relu) v = relu_nan(v);
-                if (g.r) v = v * rm;
-                if (g.mul) v = v * mu[j] + ad[j];
-            }
+            const bool ok = a_ok && k0 + ak + j < g.K;
+            const float v = ok ? eval_prologue(xa[j], g.relu, g.r, rm, g.mul, mu[j], ad[j]) : 0.0f;
             arow[kperm<WIDE>(ak + j)] = v;
         }
 #pragma unroll
@@ -198,39 +158,7 @@ mlp_infer_gemm_kernel(Infer g)
         }
 }
 
-// ---- row scales: mlp.hip's mlp_row_kernel restated (one wave per row, lanes over columns, then the butterfly)
-__global__ void __launch_bounds__(kBlock)
-mlp_infer_row_kernel(const float* __restrict__ x, long long M, int K, int relu, float* __restrict__ r)
-{
-    const int lane = threadIdx.x & 63;
-    const long long n_waves = (long long)gridDim.x * (kBlock / 64);
-    for (long long m = (long long)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6); m < M; m += n_waves) {
-        const float* xr = x + m * K;
-        float ss = 0.0f;
-        for (int k = lane; k < K; k += 64) {
-            const float u = relu ? relu_nan(xr[k]) : xr[k];
-            ss += u * u;
-        }
-        ss = wave_sum(ss);
-        if (lane == 0) r[m] = 1.0f / (1e-12f + sqrtf(ss));
-    }
-}
-
-// ---- the eval fold of mlp.hip's mlp_bn_stats_kernel restated: BN(u)_k = u * mul_k + add_k
-__global__ void __launch_bounds__(kBlock)
-mlp_infer_fold_kernel(int K, const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ rmean,
-                      const float* __restrict__ rvar, float eps, float* __restrict__ mul, float* __restrict__ add)
-{
-    const int k = blockIdx.x * kBlock + threadIdx.x;
-    if (k >= K) return;
-    const float mu = rmean[k], is = 1.0f / sqrtf(rvar[k] + eps);
-    const float g = gamma ? gamma[k] : 1.0f, be = beta ? beta[k] : 0.0f;
-    mul[k] = g * is; add[k] = be - mu * (g * is);
-}
-
 // ---- host side
-long long cdiv(long long a, long long b) { return (a + b - 1) / b; }
-
 template <bool WIDE>
 int run_gemm(Infer g, hipStream_t st)
 {
@@ -285,16 +213,11 @@ int gp_mlp_infer_block(int device, const float* d_x, int64_t n_rows, int32_t f_i
     g.relu = (flags & GP_MLP_RELU) != 0;
     if (norm) {
         g.r = ws;
-        const long long grid = cdiv(n_rows, kBlock / 64);
-        hipLaunchKernelGGL(mlp_infer_row_kernel, dim3((u32)(grid < kMaxGrid ? grid : kMaxGrid)), dim3(kBlock), 0, st, d_x,
-                           (long long)n_rows, (int)f_in, g.relu, ws);
-        if (const int rc = launch_status("mlp_infer_row_kernel")) return rc;
+        if (const int rc = launch_row_scales(d_x, n_rows, f_in, g.relu, ws, st)) return rc;
     }
     if (bn) {
         g.mul = ws + n_rows; g.add = ws + n_rows + f_in;
-        hipLaunchKernelGGL(mlp_infer_fold_kernel, dim3((u32)cdiv(f_in, kBlock)), dim3(kBlock), 0, st, (int)f_in, d_bn_weight,
-                           d_bn_bias, d_running_mean, d_running_var, bn_eps, ws + n_rows, ws + n_rows + f_in);
-        if (const int rc = launch_status("mlp_infer_fold_kernel")) return rc;
+        if (const int rc = launch_bn_fold(f_in, d_bn_weight, d_bn_bias, d_running_mean, d_running_var, bn_eps, ws + n_rows, st)) return rc;
     }
     return f_out > 64 ? run_gemm<true>(g, st) : run_gemm<false>(g, st);
 }

@@ -246,18 +246,6 @@ def _check_infer(X, out, batch_size, layers, fused=False):
     return C
 
 
-def _infer_block(x, fc, bn, relu, norm, out, ws):
-    """One eval block on x [n, F] into out [n, N] (gp_mlp_infer_block); ws: the caller's scratch."""
-    flags = (_native.GP_MLP_RELU if relu else 0) | (_native.GP_MLP_NORM if norm else 0) | \
-            (_native.GP_MLP_BN if bn is not None else 0)
-    rc = _native.lib().gp_mlp_infer_block(
-        x.device.index, x.data_ptr(), x.shape[0], x.shape[1], fc.weight.shape[0], fc.weight.data_ptr(), _ptr(fc.bias), flags,
-        _ptr(bn.weight) if bn is not None else None, _ptr(bn.bias) if bn is not None else None,
-        _ptr(bn.running_mean) if bn is not None else None, _ptr(bn.running_var) if bn is not None else None,
-        float(bn.eps) if bn is not None else 1e-5, out.data_ptr(), _ptr(ws), _stream(x))
-    _native.raise_for_status(rc)
-
-
 def _block_args(fc, bn, relu, norm):
     """A block's arguments as gp_mlp_infer_block and gp_mlp_infer_chain2 take them: weight, bias, flags, BatchNorm, eps."""
     flags = (_native.GP_MLP_RELU if relu else 0) | (_native.GP_MLP_NORM if norm else 0) | \
@@ -266,6 +254,14 @@ def _block_args(fc, bn, relu, norm):
             _ptr(bn.weight) if bn is not None else None, _ptr(bn.bias) if bn is not None else None,
             _ptr(bn.running_mean) if bn is not None else None, _ptr(bn.running_var) if bn is not None else None,
             float(bn.eps) if bn is not None else 1e-5)
+
+
+def _infer_block(x, fc, bn, relu, norm, out, ws):
+    """One eval block on x [n, F] into out [n, N] (gp_mlp_infer_block); ws: the caller's scratch."""
+    rc = _native.lib().gp_mlp_infer_block(
+        x.device.index, x.data_ptr(), x.shape[0], x.shape[1], fc.weight.shape[0], *_block_args(fc, bn, relu, norm),
+        out.data_ptr(), _ptr(ws), _stream(x))
+    _native.raise_for_status(rc)
 
 
 def _infer_chain2(x, first, second, out, ws):
