@@ -44,6 +44,7 @@ class _Cfg:
 def _forward(x, weight, bias, gamma, beta, c, save_a):
     S, B, F = x.shape
     N = weight.shape[0]
+    # tests/test_gpu_mlp_block.py names these allocations by their order (out, saved, a, workspace): keep its list in step
     out = torch.empty((S, B, N), dtype=torch.float32, device=x.device)
     saved = None
     if c.flags & (_native.GP_MLP_NORM | _native.GP_MLP_BN):
@@ -80,6 +81,7 @@ class _BlockFn(torch.autograd.Function):
         N = weight.shape[0]
         gy = gy.contiguous()
         nx, nw, nb, ng, nbe = ctx.needs_input_grad[:5]
+        # ... and these (gx, gw, gb, gg, gbe, workspace)
         new = lambda need, shape: torch.empty(shape, dtype=torch.float32, device=x.device) if need else None  # noqa: E731
         gx, gw, gb = new(nx, x.shape), new(nw, weight.shape), new(nb, (N,))
         gg = new(ng and gamma is not None, (F,))
@@ -100,10 +102,38 @@ def _check_bn(bn):
         raise ValueError("BatchNorm1d without running statistics is not supported (the reference tracks them)")
 
 
+def _check_layout(X, ranks, shapes, contiguous):
+    """What the kernels assume of an input they take by raw pointer: a float32 tensor of one of `ranks`, contiguous."""
+    if not isinstance(X, torch.Tensor):
+        raise ValueError("X must be a tensor")
+    if X.dtype != torch.float32:
+        raise ValueError(f"X must be float32, got {X.dtype}")
+    if X.dim() not in ranks:
+        raise ValueError(f"X must be {shapes}, got {tuple(X.shape)}")
+    if not X.is_contiguous():
+        raise ValueError(contiguous)
+
+
+def _check_samples(S, B):
+    if not 1 <= S <= _native.GP_MAX_SAMPLES:
+        raise ValueError(f"the number of samples must be in [1, {_native.GP_MAX_SAMPLES}], got {S}")
+    if B < 1:
+        raise ValueError("X has no rows")
+
+
+def _check_cuda(X):
+    if not X.is_cuda:
+        raise ValueError("the MLP runs on the GPU only: X must be a CUDA tensor (no CPU fallback)")
+
+
 def block(x, fc, bn, *, relu, node_norm, training, dropout, seed, layer, keep=None):
     """One block on x [S, B, F] (contiguous float32 CUDA): Linear(dropout(BN(node_norm(relu?(x))))).  bn None = no
-    BatchNorm.  Differentiable with respect to x, fc's and bn's parameters; running statistics update in training."""
+    BatchNorm.  Differentiable with respect to x, fc's and bn's parameters; running statistics update in training.
+    Anything else for x is a ValueError before the first launch (the kernels take x by raw pointer); the CPU-tensor
+    check comes last, as in _check_input."""
+    _check_layout(x, (3,), "[S, B, F]", "X must be contiguous (what random_prop*(samples=S) returns)")
     S, B, F = x.shape
+    _check_samples(S, B)
     flags = (_native.GP_MLP_RELU if relu else 0) | (_native.GP_MLP_NORM if node_norm else 0) | \
             (_native.GP_MLP_BN if bn is not None else 0) | (_native.GP_MLP_TRAINING if training else 0)
     if fc.weight.shape[1] != F:
@@ -124,6 +154,7 @@ def block(x, fc, bn, *, relu, node_norm, training, dropout, seed, layer, keep=No
             raise ValueError("keep must be a contiguous uint8 tensor on the input's device")
         if keep.numel() != S * B * F:
             raise ValueError(f"keep must hold S x B x F = {S * B * F} entries, got {keep.numel()}")
+    _check_cuda(x)
     c = _Cfg(flags, bn, float(dropout), int(seed) & _M64, int(layer), keep if training and dropout > 0 else None)
     gamma = bn.weight if bn is not None else None
     beta = bn.bias if bn is not None else None
@@ -135,27 +166,16 @@ def block(x, fc, bn, *, relu, node_norm, training, dropout, seed, layer, keep=No
 
 def _check_input(X, layers, training):
     """Every host check before the first launch: shape, dtype, layout, sample count, BatchNorm's batch size, device."""
-    if not isinstance(X, torch.Tensor):
-        raise ValueError("X must be a tensor")
-    if X.dtype != torch.float32:
-        raise ValueError(f"X must be float32, got {X.dtype}")
-    if X.dim() not in (2, 3):
-        raise ValueError(f"X must be [B, F] or [S, B, F], got {tuple(X.shape)}")
-    if not X.is_contiguous():
-        raise ValueError("X must be contiguous (what random_prop*(samples=S) returns)")
+    _check_layout(X, (2, 3), "[B, F] or [S, B, F]", "X must be contiguous (what random_prop*(samples=S) returns)")
     x = X[None] if X.dim() == 2 else X
     S, B, _ = x.shape
-    if not 1 <= S <= _native.GP_MAX_SAMPLES:
-        raise ValueError(f"the number of samples must be in [1, {_native.GP_MAX_SAMPLES}], got {S}")
-    if B < 1:
-        raise ValueError("X has no rows")
+    _check_samples(S, B)
     for _fc, bn, *_ in layers:
         if bn is not None:
             _check_bn(bn)
             if training and B < 2:
                 raise ValueError(f"Expected more than 1 value per channel when training, got input size {[B, bn.num_features]}")
-    if not X.is_cuda:
-        raise ValueError("the MLP runs on the GPU only: X must be a CUDA tensor (no CPU fallback)")
+    _check_cuda(X)
     if layers and layers[0][0].weight.device != X.device:
         raise ValueError(f"X is on {X.device}, the parameters on {layers[0][0].weight.device}")
     return x

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from augment_cases import rows_to_coo
+from mlp_block_cases import hashed_keep
 from oracle.mlp_ref import RefMagMLP, RefMLP
 from oracle.objective_ref import grand_loss_ref
 
@@ -399,18 +400,8 @@ def test_hashed_masks_are_the_mirrored_layer_seed_formula():
     m = GrandPlusMLP(40, 5, 24, 3, True, 0.3, 0.6, True).cuda().train()
     seed = 0xDEADBEEF12345
 
-    def mask(layer, F, p):
-        out = np.zeros((S, B, F), np.uint8)
-        e = np.arange(B * F, dtype=np.uint64)
-        with np.errstate(over="ignore"):
-            for s in range(S):
-                x = np.uint64(layer_seed(seed, layer, s)) + e * np.uint64(0x9E3779B97F4A7C15)
-                x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-                x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-                x ^= x >> np.uint64(31)
-                u = (x >> np.uint64(40)).astype(np.float32) * np.float32(1.0 / 16777216.0)
-                out[s] = (u >= np.float32(p)).reshape(B, F)
-        return torch.from_numpy(out).cuda()
+    def mask(layer, F, p):                                   # the host mirror, shared with tests/test_gpu_mlp_block.py
+        return hashed_keep(seed, layer, S, B, F, p).cuda()
 
     keeps = [mask(0, 40, 0.3), mask(1, 24, 0.6), mask(2, 24, 0.6)]
     X = torch.randn((S, B, 40), device="cuda")
