@@ -16,14 +16,14 @@
 //                         per-step upload (the caller side of model.py:310-316).
 //   gp_random_prop_coo  : the reference's own argument shape (gathered feats [M x F],
 //                         scores [M], sorted segment ids [M]).
-#include "gp_common.hpp"
+// The DropNode weight, the row length, the denominators and the bag are dropnode.hpp's, shared with scatter_det.hip and mag_prop.hip.
+#include "dropnode.hpp"
 
 #include <algorithm>
 
 namespace {
 
 constexpr int kBlock = 256;
-constexpr int kStage = 1024;          // most neighbours of one output row staged per pass (= GP_MAX_K)
 
 // Accumulates out[b, f0:f1] = sum_k w_k * X[c_k, f0:f1] / (sum_k w_k + 1e-12) for the staged (c_k, w_k).
 // VEC floats per lane per access (4 when F % 4 == 0, 2 when F % 2 == 0, else 1); blockIdx.y selects
@@ -36,7 +36,7 @@ __device__ __forceinline__ void weighted_rows_vec(const float* __restrict__ X, i
     typedef typename VecT<VEC>::type V;
     float den = 0.0f;
     for (int k = 0; k < n; ++k) den += s_w[k];                                    // model.py:85-86
-    const float inv = 1.0f / (den + 1e-12f);                                      // model.py:87
+    const float inv = inv_den_rows(den);                                      // model.py:87
     for (int f = (blockIdx.y * kBlock + threadIdx.x) * VEC; f < F; f += gridDim.y * kBlock * VEC) {
         float acc[VEC];
 #pragma unroll
@@ -88,10 +88,10 @@ random_prop_rows_kernel(const float* __restrict__ X, int F, const int* __restric
 {
     __shared__ int s_col[kStage];
     __shared__ float s_w[kStage];
-    const float scale = p < 1.0f ? 1.0f / (1.0f - p) : 0.0f;
+    const float scale = inv_keep(p);
     for (int b = blockIdx.x; b < n_batch; b += gridDim.x) {
         const long long row = batch_rows ? batch_rows[b] : b;
-        const int n = filled ? min(filled[row], K) : K;
+        const int n = row_len(filled, row, K);
         __syncthreads();
         for (int k = threadIdx.x; k < n; k += kBlock) {
             const long long e = row * (long long)K + k;
@@ -114,7 +114,7 @@ random_prop_coo_kernel(const float* __restrict__ feats, int F, const float* __re
     __shared__ int s_col[kStage];
     __shared__ float s_w[kStage];
     __shared__ long long s_lo, s_hi;
-    const float scale = p < 1.0f ? 1.0f / (1.0f - p) : 0.0f;
+    const float scale = inv_keep(p);
     for (long long b = blockIdx.x; b < n_out; b += gridDim.x) {
         __syncthreads();
         if (threadIdx.x < 2) {                        // segment of output row b in the sorted id array
@@ -145,7 +145,7 @@ random_prop_coo_kernel(const float* __restrict__ feats, int F, const float* __re
                 if (training) w *= keep ? (keep[e] ? scale : 0.0f) : keep_scale(seed, (u64)e, p, scale);
                 den += w;
             }
-            const float inv = 1.0f / (den + 1e-12f);
+            const float inv = inv_den_rows(den);
             for (int f = blockIdx.y * kBlock + threadIdx.x; f < F; f += gridDim.y * kBlock) {
                 float acc = 0.0f;
                 for (long long e = lo; e < hi; ++e) {
@@ -203,7 +203,7 @@ random_prop_coo_backward_kernel(const float* __restrict__ grad_out, int F, const
 {
     __shared__ float s_w[kStage];
     __shared__ long long s_lo, s_hi;
-    const float scale = p < 1.0f ? 1.0f / (1.0f - p) : 0.0f;
+    const float scale = inv_keep(p);
     for (long long b = blockIdx.x; b < n_out; b += gridDim.x) {
         __syncthreads();
         if (threadIdx.x < 2) {                        // the forward's segment search
@@ -226,7 +226,7 @@ random_prop_coo_backward_kernel(const float* __restrict__ grad_out, int F, const
             __syncthreads();
             float den = 0.0f;
             for (int k = 0; k < n; ++k) den += s_w[k];                      // the forward's order
-            const float inv = 1.0f / (den + 1e-12f);
+            const float inv = inv_den_rows(den);
             float* rows = grad_feats + (size_t)lo * F;
             if ((F & 3) == 0)      scaled_rows_vec<4>(g_row, F, s_w, n, inv, rows);
             else if ((F & 1) == 0) scaled_rows_vec<2>(g_row, F, s_w, n, inv, rows);
@@ -238,7 +238,7 @@ random_prop_coo_backward_kernel(const float* __restrict__ grad_out, int F, const
                 if (training) w *= keep ? (keep[e] ? scale : 0.0f) : keep_scale(seed, (u64)e, p, scale);
                 den += w;
             }
-            const float inv = 1.0f / (den + 1e-12f);
+            const float inv = inv_den_rows(den);
             for (long long e = lo; e < hi; ++e) {
                 float w = scores[e];
                 if (training) w *= keep ? (keep[e] ? scale : 0.0f) : keep_scale(seed, (u64)e, p, scale);
@@ -262,11 +262,11 @@ random_prop_rows_backward_kernel(const float* __restrict__ grad_out, int F, cons
 {
     __shared__ int s_col[kStage];
     __shared__ float s_w[kStage];
-    const float scale = p < 1.0f ? 1.0f / (1.0f - p) : 0.0f;
+    const float scale = inv_keep(p);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int b = blockIdx.x; b < n_batch; b += gridDim.x) {
         const long long row = batch_rows ? batch_rows[b] : b;
-        const int n = filled ? min(filled[row], K) : K;
+        const int n = row_len(filled, row, K);
         __syncthreads();
         for (int k = threadIdx.x; k < n; k += kBlock) {                  // the forward's staging
             const long long e = row * (long long)K + k;
@@ -278,7 +278,7 @@ random_prop_rows_backward_kernel(const float* __restrict__ grad_out, int F, cons
         __syncthreads();
         float den = 0.0f;
         for (int k = 0; k < n; ++k) den += s_w[k];
-        const float inv = 1.0f / (den + 1e-12f);
+        const float inv = inv_den_rows(den);
         const float* g_row = grad_out + (size_t)b * F;
         for (int k = wave; k < n; k += kBlock / 64) {
             const float w = s_w[k];
@@ -290,34 +290,7 @@ random_prop_rows_backward_kernel(const float* __restrict__ grad_out, int F, cons
     }
 }
 
-// ---- Embedding-bag (MAG's sparse first layer, MLP.emb, model_mag.py:48-55):
-//     out[m, :] = sum_j keep_{j,:} s d_j W[a_j, :] / (sum_j d_j + 1e-10)
-// Bag of output row m: storage entries [offsets[src], offsets[src + 1]) of (attr_idx, attr_data), src = nodes[m]
-// (nodes != NULL: rows of a device-resident node-attribute CSR) or m.  j = entry_base[m] + t (entry_base != NULL)
-// or the storage position itself: the entry's position in the batch's entry order, which keys the dropout of
-// element (j, h) as (seed, j*H + h).  Attribute ids outside [0, V) are never read or written; they add to *n_bad.
-struct BagLayout {
-    const long long* offsets; long long n_src;        // offsets[n_src + 1]
-    const long long* nodes;                             // [n_rows] or NULL
-    const long long* base;                              // [n_rows] or NULL
-    long long n_rows;
-    const void* idx; int idx64;                         // attr ids: int64 (idx64) or int32
-    const float* data;
-};
-
-__device__ __forceinline__ bool bag_of(const BagLayout& L, long long m, long long& s0, long long& s1, long long& jb)
-{
-    const long long src = L.nodes ? L.nodes[m] : m;
-    if (src < 0 || src >= L.n_src) { s0 = s1 = jb = 0; return false; }
-    s0 = L.offsets[src]; s1 = L.offsets[src + 1];
-    jb = L.base ? L.base[m] : s0;
-    return true;
-}
-
-__device__ __forceinline__ long long attr_id(const BagLayout& L, long long e)
-{
-    return L.idx64 ? reinterpret_cast<const long long*>(L.idx)[e] : (long long)reinterpret_cast<const int*>(L.idx)[e];
-}
+// ---- Embedding-bag: dropnode.hpp states the bag and holds BagLayout, bag_of and attr_id.
 
 // Forward: propagate.hip's mapping -- a group of G = 2^log2g lanes owns one output row (G*VEC >= H when H
 // allows), fp32 sums.  The group's lanes first read G entries' (id, weight) at once, one per lane, and pass
@@ -330,7 +303,7 @@ embedding_bag_kernel(const float* __restrict__ W, long long V, int H, BagLayout 
                      const unsigned char* __restrict__ keep, float* __restrict__ out, int* __restrict__ n_bad, int log2g)
 {
     typedef typename VecT<VEC>::type Vt;
-    const float scale = p < 1.0f ? 1.0f / (1.0f - p) : 0.0f;
+    const float scale = inv_keep(p);
     const int lane = threadIdx.x & 63;
     const int G = 1 << log2g, gl = lane & (G - 1), grp = lane >> log2g, rows_per_wave = 64 >> log2g;
     const long long wave = ((long long)blockIdx.x * kBlock + threadIdx.x) >> 6;
@@ -389,7 +362,7 @@ embedding_bag_kernel(const float* __restrict__ W, long long V, int H, BagLayout 
             if (row_live && f_live) {
                 Vt o; float* po = reinterpret_cast<float*>(&o);
 #pragma unroll
-                for (int i = 0; i < VEC; ++i) po[i] = acc[i] / (den + 1e-10f); // model_mag.py:54
+                for (int i = 0; i < VEC; ++i) po[i] = acc[i] / (den + 1e-10f); // model_mag.py:54 (a quotient; inv_den_bag's epsilon)
                 *reinterpret_cast<Vt*>(out + (size_t)m * H + f) = o;
             }
         }
@@ -407,7 +380,7 @@ embedding_bag_backward_kernel(long long V, int H, BagLayout L, float p, int trai
                               const unsigned char* __restrict__ keep, const float* __restrict__ grad_out,
                               float* __restrict__ dW, int* __restrict__ n_bad)
 {
-    const float scale = p < 1.0f ? 1.0f / (1.0f - p) : 0.0f;
+    const float scale = inv_keep(p);
     const int lane = threadIdx.x & 63;
     const long long wave = ((long long)blockIdx.x * kBlock + threadIdx.x) >> 6;
     const long long n_waves = ((long long)gridDim.x * kBlock) >> 6;
@@ -420,7 +393,7 @@ embedding_bag_backward_kernel(long long V, int H, BagLayout L, float p, int trai
             for (int o = 1; o < 64; o <<= 1) part += __shfl_xor(part, o);
             den += part;
         }
-        const float inv = 1.0f / (den + 1e-10f);
+        const float inv = inv_den_bag(den);
         for (int h0 = 0; h0 < H; h0 += 64) {
             const int h = h0 + lane;
             const bool live_h = h < H;
@@ -633,8 +606,7 @@ int gp_embedding_bag(int device, const float* d_weight, int64_t n_vocab, int32_t
     if (const int rc = set_device(device, where)) return rc;
     hipStream_t s = (hipStream_t)stream;
     if (d_n_bad && hipMemsetAsync(d_n_bad, 0, sizeof(int32_t), s) != hipSuccess) return fail(GP_ERR_HIP, where, "hipMemsetAsync failed");
-    const BagLayout L = {(const long long*)d_offsets, (long long)n_src, (const long long*)d_nodes, (const long long*)d_entry_base,
-                         (long long)n_rows, d_attr_idx, idx_bytes == 8, d_attr_data};
+    const BagLayout L = bag_layout(d_offsets, n_src, d_nodes, d_entry_base, n_rows, d_attr_idx, idx_bytes, d_attr_data);
     const int vec = vec_width(dim);
     const int log2g = lane_group_log2(dim, vec);
     const long long rows_per_block = (kBlock / 64) * (64 >> log2g);
@@ -658,8 +630,7 @@ int gp_embedding_bag_backward(int device, const float* d_grad_out, int64_t n_voc
     if (const int rc = set_device(device, where)) return rc;
     hipStream_t s = (hipStream_t)stream;
     if (d_n_bad && hipMemsetAsync(d_n_bad, 0, sizeof(int32_t), s) != hipSuccess) return fail(GP_ERR_HIP, where, "hipMemsetAsync failed");
-    const BagLayout L = {(const long long*)d_offsets, (long long)n_src, (const long long*)d_nodes, (const long long*)d_entry_base,
-                         (long long)n_rows, d_attr_idx, idx_bytes == 8, d_attr_data};
+    const BagLayout L = bag_layout(d_offsets, n_src, d_nodes, d_entry_base, n_rows, d_attr_idx, idx_bytes, d_attr_data);
     const int grid = (int)std::min<long long>(65535ll * 16, (n_rows + kBlock / 64 - 1) / (kBlock / 64));
     hipLaunchKernelGGL(embedding_bag_backward_kernel, dim3(grid), dim3(kBlock), 0, s, (long long)n_vocab, dim, L, dropout_rate,
                        training, (u64)seed, d_keep, d_grad_out, d_grad_weight, d_n_bad);
@@ -677,15 +648,7 @@ int gp_embedding_bag_backward(int device, const float* d_grad_out, int64_t n_voc
 // seed_s bit for bit; a dropped entry adds 0 * x, which leaves a finite sum unchanged.
 namespace {
 
-constexpr int kMaxSamples = 16;
 constexpr int kMultiLdsBytes = 65536;
-
-__device__ __forceinline__ float sample_weight(float w, long long e, int s, float p, float scale, int training, u64 seed,
-                                               const unsigned char* keep, long long keep_stride)
-{
-    if (!training) return w;
-    return w * (keep ? (keep[(long long)s * keep_stride + e] ? scale : 0.0f) : keep_scale(sample_seed(seed, s), (u64)e, p, scale));
-}
 
 // out[s0 + s][f] for s < ns from the staged columns (s_col, or col_base + k when s_col is NULL) and weights
 // s_w[s * stage + k].  NS >= ns is the unrolled accumulator count; samples ns..NS-1 see weight 0 and are not written.
@@ -700,7 +663,7 @@ __device__ __forceinline__ void weighted_rows_multi(const float* __restrict__ X,
     for (int s = 0; s < NS; ++s) {
         float den = 0.0f;
         if (s < ns) for (int k = 0; k < n; ++k) den += s_w[s * stage + k];   // model.py:85-86, the single kernel's order
-        inv[s] = 1.0f / (den + 1e-12f);
+        inv[s] = 1.0f / (den + 1e-12f);                                       // inv_den_rows by hand (dropnode.hpp): the call changes this unit's code
     }
     for (int f = (blockIdx.y * kBlock + threadIdx.x) * VEC; f < F; f += gridDim.y * kBlock * VEC) {
         float acc[NS][VEC];
@@ -760,11 +723,11 @@ random_prop_rows_multi_kernel(const float* __restrict__ X, int F, const int* __r
     extern __shared__ float smem[];
     int* s_col = reinterpret_cast<int*>(smem);
     float* s_w = smem + K;
-    const float scale = p < 1.0f ? 1.0f / (1.0f - p) : 0.0f;
+    const float scale = inv_keep(p);
     const size_t out_stride = (size_t)n_batch * F;
     for (int b = blockIdx.x; b < n_batch; b += gridDim.x) {
         const long long row = batch_rows ? batch_rows[b] : b;
-        const int n = filled ? min(filled[row], K) : K;
+        const int n = row_len(filled, row, K);
         for (int s0 = 0; s0 < S; s0 += nsc) {
             const int ns = min(nsc, S - s0);
             __syncthreads();
@@ -800,7 +763,7 @@ random_prop_coo_multi_kernel(const float* __restrict__ feats, int F, const float
                              float* __restrict__ out)
 {
     extern __shared__ float s_w[];
-    const float scale = p < 1.0f ? 1.0f / (1.0f - p) : 0.0f;
+    const float scale = inv_keep(p);
     const size_t out_stride = (size_t)n_out * F;
     for (long long b = blockIdx.x; b < n_out; b += gridDim.x) {
         long long lo, hi;
@@ -819,7 +782,7 @@ random_prop_coo_multi_kernel(const float* __restrict__ feats, int F, const float
             for (int s = 0; s < S; ++s) {
                 float den = 0.0f;
                 for (long long e = lo; e < hi; ++e) den += sample_weight(scores[e], e, s, p, scale, training, seed, keep, n_entries);
-                const float inv = 1.0f / (den + 1e-12f);
+                const float inv = inv_den_rows(den);
                 float* out_row = out + s * out_stride + (size_t)b * F;
                 for (int f = blockIdx.y * kBlock + threadIdx.x; f < F; f += gridDim.y * kBlock) {
                     float acc = 0.0f;
@@ -865,7 +828,7 @@ random_prop_coo_multi_backward_kernel(const float* __restrict__ grad_out, int F,
                                       float* __restrict__ grad_feats)
 {
     extern __shared__ float s_w[];
-    const float scale = p < 1.0f ? 1.0f / (1.0f - p) : 0.0f;
+    const float scale = inv_keep(p);
     const size_t g_stride = (size_t)n_out * F;
     for (long long b = blockIdx.x; b < n_out; b += gridDim.x) {
         long long lo, hi;
@@ -884,7 +847,7 @@ random_prop_coo_multi_backward_kernel(const float* __restrict__ grad_out, int F,
                 for (int s = 0; s < ns; ++s) {
                     float den = 0.0f;
                     for (int k = 0; k < n; ++k) den += s_w[s * kStage + k];          // the forward's order
-                    inv[s] = 1.0f / (den + 1e-12f);
+                    inv[s] = inv_den_rows(den);
                 }
                 const float* g = g_row + s0 * g_stride;
                 if ((F & 3) == 0)      scaled_rows_multi<4>(g, g_stride, F, s_w, kStage, n, ns, inv, s0 == 0, rows);
@@ -895,7 +858,7 @@ random_prop_coo_multi_backward_kernel(const float* __restrict__ grad_out, int F,
             for (int s = 0; s < S; ++s) {
                 float den = 0.0f;
                 for (long long e = lo; e < hi; ++e) den += sample_weight(scores[e], e, s, p, scale, training, seed, keep, n_entries);
-                const float inv = 1.0f / (den + 1e-12f);
+                const float inv = inv_den_rows(den);
                 const float* g = g_row + s * g_stride;
                 for (long long e = lo; e < hi; ++e) {
                     const float w = sample_weight(scores[e], e, s, p, scale, training, seed, keep, n_entries);
@@ -923,12 +886,12 @@ random_prop_rows_multi_backward_kernel(const float* __restrict__ grad_out, int F
     int* s_col = reinterpret_cast<int*>(smem);
     float* s_inv = smem + K;                              // [nsc]
     float* s_w = s_inv + kMaxSamples;                     // [nsc][K]
-    const float scale = p < 1.0f ? 1.0f / (1.0f - p) : 0.0f;
+    const float scale = inv_keep(p);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const size_t g_stride = (size_t)n_batch * F;
     for (int b = blockIdx.x; b < n_batch; b += gridDim.x) {
         const long long row = batch_rows ? batch_rows[b] : b;
-        const int n = filled ? min(filled[row], K) : K;
+        const int n = row_len(filled, row, K);
         for (int s0 = 0; s0 < S; s0 += nsc) {
             const int ns = min(nsc, S - s0);
             __syncthreads();
@@ -942,7 +905,7 @@ random_prop_rows_multi_backward_kernel(const float* __restrict__ grad_out, int F
             if (threadIdx.x < ns) {
                 float den = 0.0f;
                 for (int k = 0; k < n; ++k) den += s_w[threadIdx.x * K + k];
-                s_inv[threadIdx.x] = 1.0f / (den + 1e-12f);
+                s_inv[threadIdx.x] = inv_den_rows(den);
             }
             __syncthreads();
             const float* g = grad_out + s0 * g_stride + (size_t)b * F;

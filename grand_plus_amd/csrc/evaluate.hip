@@ -84,29 +84,6 @@ eval_head_kernel(HeadArgs a, float* __restrict__ nll, int* __restrict__ pred, un
     }
 }
 
-// fixed trees: xor butterfly inside a wave (both partners add the same two values), then the waves in order
-__device__ __forceinline__ double block_sum(double v, double* lds)
-{
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double s = lds[0];
-    for (int w = 1; w < kWaves; ++w) s += lds[w];
-    return s;
-}
-
-__device__ __forceinline__ long long block_count(long long v, long long* lds)
-{
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-    __syncthreads();
-    long long s = lds[0];
-    for (int w = 1; w < kWaves; ++w) s += lds[w];
-    return s;
-}
-
 // Workspace: sums[kSlots] (f64), then counts[4][kSlots] (int64) = valid, correct, ignored, bad.
 // stage 1 (grid = the slices of n): workgroup b sums rows [b * slice, min(n, (b + 1) * slice)) into slot b.
 // stage 2 (grid = 1): out = {sum / n_valid, n_correct / n}; 0 / 0 = NaN, as torch's mean of nothing.
@@ -135,8 +112,8 @@ eval_reduce_kernel(int stage, const float* __restrict__ nll, const unsigned char
             cnt[k] = c[0] + c[1] + c[2] + c[3];
         }
     }
-    s = block_sum(s, lds_d);
-    for (int k = 0; k < 4; ++k) cnt[k] = block_count(cnt[k], lds_c);
+    s = block_sum<kWaves>(s, lds_d);                         // gp_common.hpp's fixed tree, for the sum and the counts
+    for (int k = 0; k < 4; ++k) cnt[k] = block_sum<kWaves>(cnt[k], lds_c);
     if (stage == 1) {
         if (tid == 0) {
             sums[blockIdx.x] = s;
@@ -151,12 +128,6 @@ eval_reduce_kernel(int stage, const float* __restrict__ nll, const unsigned char
         out[1] = (float)((double)cnt[1] / (double)n);         // len(labels), utils/data_loader.py:165: every row counts
         for (int k = 0; k < 4; ++k) out_counts[k] = cnt[k];
     }
-}
-
-int row_grid(long long n)
-{
-    const long long g = (n + kWaves - 1) / kWaves;
-    return (int)(g < 65535 ? (g > 0 ? g : 1) : 65535);
 }
 
 }  // namespace
@@ -181,7 +152,7 @@ int gp_eval_head(int device, const float* d_logits, int64_t n_logit_rows, int32_
     const HeadArgs a = {d_logits, (long long)n_logit_rows, n_classes, (const long long*)d_row_idx, (const long long*)d_labels,
                         (long long)n_labels, (const long long*)d_label_idx, (long long)n_rows, (long long)ignore_index,
                         (long long)out_offset};
-    hipLaunchKernelGGL(eval_head_kernel, dim3(row_grid(n_rows)), dim3(kBlock), 0, (hipStream_t)stream, a, d_nll, (int*)d_pred,
+    hipLaunchKernelGGL(eval_head_kernel, dim3(row_grid(n_rows, kWaves)), dim3(kBlock), 0, (hipStream_t)stream, a, d_nll, (int*)d_pred,
                        (unsigned char*)d_flag);
     return launch_status("eval_head_kernel");
 }

@@ -1,7 +1,7 @@
 // gp_common.hpp -- what the translation units outside GFPush share (augment.hip, evaluate.hip, mag_prop.hip,
 // objective.hip, optim.hip, propagate.hip, scatter_det.hip, and through mlp_eval.hpp mlp.hip, mlp_infer.hip and
 // mlp_chain.hip): the dropout counter hash and the seed derivations that grandplus.h fixes bit for bit, the wave
-// reductions, the float vector map, and the host helpers every entry point uses (error record, device selection,
+// and workgroup reductions, the float vector map, and the host helpers every entry point uses (error record, device selection,
 // launch status, feature-column launch geometry).  Everything has internal linkage: no symbol leaves a translation unit.
 #pragma once
 
@@ -58,6 +58,20 @@ __device__ __forceinline__ float wave_max(float v)
     return v;
 }
 
+// The sum of v over a workgroup of NW waves, in every thread, through lds[NW] (T: double, long long).  A fixed tree: the
+// xor butterfly inside a wave (both partners add the same two values), then the waves in order.
+template <int NW, class T>
+__device__ __forceinline__ T block_sum(T v, T* lds)
+{
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
+    __syncthreads();
+    T s = lds[0];
+    for (int w = 1; w < NW; ++w) s += lds[w];
+    return s;
+}
+
 // ---- device: VEC floats per lane per access
 template <int VEC> struct VecT;
 template <> struct VecT<4> { typedef float4 type; };
@@ -87,6 +101,13 @@ inline int launch_status(const char* where)
 // columns cover F (lanes: the threads that span the columns, a workgroup or a wave).
 inline int vec_width(int F) { return (F & 3) == 0 ? 4 : (F & 1) == 0 ? 2 : 1; }
 inline int feature_slabs(int F, int vec, int lanes) { return (F + lanes * vec - 1) / (lanes * vec); }
+
+// workgroups of `waves` waves for a kernel whose waves take rows grid-stride: at least one, at most 65 535
+inline int row_grid(long long n, int waves)
+{
+    const long long g = (n + waves - 1) / waves;
+    return (int)(g < 65535 ? (g > 0 ? g : 1) : 65535);
+}
 
 // log2 of the smallest lane group G with G * vec >= F, at most a wave: a wave then handles 64 / G rows at once
 inline int lane_group_log2(int F, int vec)

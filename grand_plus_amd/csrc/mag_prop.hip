@@ -7,26 +7,18 @@
 //   per slot the 64 lanes read 64 (id, d) pairs at once and pass them round by shuffle; the lanes sit on 64 consecutive
 //   floats of W[a] (H = 64: one 256-B wave load per entry), 8 loads in flight; H > 64 loops over 64-column chunks;
 //   the waves' sums meet in LDS and are added in wave order (no atomics in the forward).
-// The order contract, the mask formulas and the bounds rules are stated in grandplus_mag.h.
-#include "gp_common.hpp"
+// The order contract, the mask formulas and the bounds rules are stated in grandplus_mag.h.  The DropNode weight of
+// (sample s, entry e) is dropnode.hpp's sample_weight, the line gp_random_prop_rows_multi calls: the same mask for the same seed.
+#include "dropnode.hpp"
 
 #include <algorithm>
 
 namespace {
 
-constexpr int kMaxSamples = 16;
 constexpr int kMaxWaves = 16;
 constexpr int kLdsFloats = 65536 / 4;
 constexpr int kGridCap = 8192;                         // workgroups of up to 1 024 threads: 32 per CU on 256 CUs
 constexpr u64 kSlotMul = 0xE7037ED1A0B428DBull;        // GP_MAG_SLOT_SEED's multiplier: no other derivation uses it
-
-// gp_random_prop_rows_multi's weight of (sample s, entry e): the same DropNode mask for the same seed
-__device__ __forceinline__ float sample_weight(float w, long long e, int s, float p, float scale, int training, u64 seed,
-                                               const unsigned char* keep, long long keep_stride)
-{
-    if (!training) return w;
-    return w * (keep ? (keep[(long long)s * keep_stride + e] ? scale : 0.0f) : keep_scale(sample_seed(seed, s), (u64)e, p, scale));
-}
 
 // GP_MAG_SLOT_SEED(seed, s, e)
 __device__ __forceinline__ u64 slot_seed(u64 seed, int s, long long e)
@@ -76,8 +68,8 @@ mag_prop_rows_kernel(const float* __restrict__ W, MagArgs A, float* __restrict__
     float* s_w = s_inv + kMaxSamples;
     float* s_red = s_w + nsc * K;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n_waves = blockDim.x >> 6;
-    const float scale_node = A.p_node < 1.0f ? 1.0f / (1.0f - A.p_node) : 0.0f;
-    const float scale_in = A.p_in < 1.0f ? 1.0f / (1.0f - A.p_in) : 0.0f;
+    const float scale_node = inv_keep(A.p_node);
+    const float scale_in = inv_keep(A.p_in);
     const size_t out_stride = (size_t)A.B * H;
     for (int b = blockIdx.x; b < A.B; b += gridDim.x) {
         const long long row = A.batch_rows ? (long long)A.batch_rows[b] : (long long)b;
@@ -89,7 +81,7 @@ mag_prop_rows_kernel(const float* __restrict__ W, MagArgs A, float* __restrict__
             }
             continue;
         }
-        const int n = A.filled ? max(0, min(A.filled[row], K)) : K;
+        const int n = A.filled ? max(0, min(A.filled[row], K)) : K;             // not row_len: a negative filled[row] is 0 here
         for (int s0 = 0; s0 < A.S; s0 += nsc) {
             const int ns = min(nsc, A.S - s0);
             __syncthreads();
@@ -98,7 +90,7 @@ mag_prop_rows_kernel(const float* __restrict__ W, MagArgs A, float* __restrict__
             if (threadIdx.x < ns) {
                 float den = 0.0f;
                 for (int k = 0; k < n; ++k) den += s_w[threadIdx.x * K + k];      // model_mag.py:85-86, sequentially in k
-                s_inv[threadIdx.x] = 1.0f / (den + 1e-12f);
+                s_inv[threadIdx.x] = inv_den_rows(den);
             }
             for (int hc = 0; hc < H; hc += 64) {
                 const int h = hc + lane;
@@ -155,7 +147,7 @@ mag_prop_rows_kernel(const float* __restrict__ W, MagArgs A, float* __restrict__
                             }
                         }
                     }
-                    const float inv_den = 1.0f / (den + 1e-10f);                  // model_mag.py:54
+                    const float inv_den = inv_den_bag(den);                  // model_mag.py:54
 #pragma unroll
                     for (int s = 0; s < NS; ++s) acc[s] += w[s] * (e_acc[DROP ? s : 0] * inv_den);   // model_mag.py:83-84
                 }
@@ -188,13 +180,13 @@ mag_prop_rows_backward_kernel(const float* __restrict__ grad_out, MagArgs A, flo
     float* s_inv = smem + K;
     float* s_w = s_inv + kMaxSamples;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n_waves = blockDim.x >> 6;
-    const float scale_node = A.p_node < 1.0f ? 1.0f / (1.0f - A.p_node) : 0.0f;
-    const float scale_in = A.p_in < 1.0f ? 1.0f / (1.0f - A.p_in) : 0.0f;
+    const float scale_node = inv_keep(A.p_node);
+    const float scale_in = inv_keep(A.p_in);
     const size_t g_stride = (size_t)A.B * H;
     for (int b = blockIdx.x; b < A.B; b += gridDim.x) {
         const long long row = A.batch_rows ? (long long)A.batch_rows[b] : (long long)b;
         if (row < 0 || row >= A.n_rows) continue;                                 // workgroup-uniform
-        const int n = A.filled ? max(0, min(A.filled[row], K)) : K;
+        const int n = A.filled ? max(0, min(A.filled[row], K)) : K;             // as the forward: not row_len
         for (int s0 = 0; s0 < A.S; s0 += nsc) {
             const int ns = min(nsc, A.S - s0);
             __syncthreads();
@@ -203,7 +195,7 @@ mag_prop_rows_backward_kernel(const float* __restrict__ grad_out, MagArgs A, flo
             if (threadIdx.x < ns) {
                 float den = 0.0f;
                 for (int k = 0; k < n; ++k) den += s_w[threadIdx.x * K + k];      // the forward's order
-                s_inv[threadIdx.x] = 1.0f / (den + 1e-12f);
+                s_inv[threadIdx.x] = inv_den_rows(den);
             }
             __syncthreads();
             for (int hc = 0; hc < H; hc += 64) {
@@ -225,7 +217,7 @@ mag_prop_rows_backward_kernel(const float* __restrict__ grad_out, MagArgs A, flo
                         const int cnt = (int)(hi - c0 < 64 ? hi - c0 : 64);
                         for (int u = 0; u < cnt; ++u) den += __shfl(my_d, u);
                     }
-                    const float inv_den = 1.0f / (den + 1e-10f);
+                    const float inv_den = inv_den_bag(den);
                     float cs[MS], c = 0.0f;
                     u64 sseed[MS];
 #pragma unroll

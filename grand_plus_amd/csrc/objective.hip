@@ -296,12 +296,6 @@ int check_loss_args(const char* where, const float* d_z, int32_t S, int64_t B, i
     return GP_OK;
 }
 
-int row_grid(long long B)
-{
-    const long long g = (B + kWaves - 1) / kWaves;
-    return (int)(g < 65535 ? (g > 0 ? g : 1) : 65535);
-}
-
 }  // namespace
 
 extern "C" {
@@ -320,7 +314,7 @@ int gp_grand_loss(int device, const float* d_z, int32_t n_samples, int64_t n_row
     const LossArgs a = {d_z, n_samples, (long long)n_rows, n_classes, (const long long*)d_labels, (long long)n_labeled,
                         (long long)ignore_index, tem, conf, kind, inputs_are_log_probs != 0};
     if (n_rows > 0) {
-        hipLaunchKernelGGL(grand_loss_rows_kernel, dim3(row_grid(n_rows)), dim3(kBlock), 0, s, a, part, flags);
+        hipLaunchKernelGGL(grand_loss_rows_kernel, dim3(row_grid(n_rows, kWaves)), dim3(kBlock), 0, s, a, part, flags);
         if (const int rc = launch_status("grand_loss_rows_kernel")) return rc;
     }
     hipLaunchKernelGGL(grand_loss_reduce_kernel, dim3(1), dim3(kBlock), 0, s, part, flags, (long long)n_rows, n_samples, weight,
@@ -340,7 +334,7 @@ int gp_grand_loss_backward(int device, const float* d_z, int32_t n_samples, int6
     if (const int rc = set_device(device, where)) return rc;
     const LossArgs a = {d_z, n_samples, (long long)n_rows, n_classes, (const long long*)d_labels, (long long)n_labeled,
                         (long long)ignore_index, tem, conf, kind, inputs_are_log_probs != 0};
-    hipLaunchKernelGGL(grand_loss_backward_kernel, dim3(row_grid(n_rows)), dim3(kBlock), 0, (hipStream_t)stream, a, weight,
+    hipLaunchKernelGGL(grand_loss_backward_kernel, dim3(row_grid(n_rows, kWaves)), dim3(kBlock), 0, (hipStream_t)stream, a, weight,
                        d_grad_loss, d_grad_sup, d_grad_con, (const int*)d_counts, d_grad_z);
     return launch_status("grand_loss_backward_kernel");
 }

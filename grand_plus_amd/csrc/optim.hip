@@ -59,18 +59,6 @@ __device__ __forceinline__ int entry_of(const OptimTable& tab, long long c)
     return lo;
 }
 
-// fixed tree: xor butterfly inside a wave (both partners add the same two values), then the waves in order
-__device__ __forceinline__ double block_sum(double v, double* lds)
-{
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double s = lds[0];
-    for (int w = 1; w < kWaves; ++w) s += lds[w];
-    return s;
-}
-
 __device__ __forceinline__ double sq(float x) { return (double)x * (double)x; }
 
 __global__ __launch_bounds__(kBlock) void optim_sqnorm_kernel(const OptimTable tab, double* __restrict__ partials, int accumulate)
@@ -98,7 +86,7 @@ __global__ __launch_bounds__(kBlock) void optim_sqnorm_kernel(const OptimTable t
             for (int i = tid; i < n; i += kBlock) acc += sq(g[i]);
         }
     }
-    const double s = block_sum(acc, lds);
+    const double s = block_sum<kWaves>(acc, lds);
     // slot blockIdx.x holds this workgroup's sum; a first launch also zeroes the slots no workgroup owns
     if (tid == 0) partials[blockIdx.x] = accumulate ? partials[blockIdx.x] + s : s;
     if (!accumulate)
@@ -119,7 +107,7 @@ __global__ __launch_bounds__(kBlock) void optim_clip_adam_kernel(const OptimTabl
     __shared__ double lds[kWaves];
     const int tid = threadIdx.x;
     const double* q = partials + tid * 4;
-    const double sum = block_sum(((q[0] + q[1]) + q[2]) + q[3], lds);
+    const double sum = block_sum<kWaves>(((q[0] + q[1]) + q[2]) + q[3], lds);
     const float norm = (float)sqrt(sum);
     float coef = 1.0f;
     if (a.max_norm > 0.0f) {

@@ -20,9 +20,9 @@
 // way.  A position whose key is not a destination (the sentinel N / V, to which the caller keys what does not exist)
 // ends the walk.  A long segment is a serial chain of adds on one wave: the accepted cost of the mode (§7i).
 //
-// BagLayout, bag_of, attr_id and sample_weight restate augment.hip's (internal linkage there, and that file is left as
-// it is): the entry must be found exactly as the forward finds it.
-#include "gp_common.hpp"
+// The entry must be found exactly as the forward finds it: BagLayout, bag_of, attr_id, sample_weight and the
+// denominators are dropnode.hpp's, the lines augment.hip calls.
+#include "dropnode.hpp"
 
 #include <algorithm>
 
@@ -31,39 +31,7 @@ namespace {
 constexpr int kBlock = 256;           // the pre-pass kernels
 constexpr int kGather = 64;           // gather_sum_kernel: one wave per workgroup, so that few windows still spread over the CUs
 constexpr int kCols = 4;              // 64-column slabs of the destination row per pass of a segment
-constexpr int kStage = 1024;          // = GP_MAX_K
-constexpr int kMaxSamples = 16;
 constexpr int kDenSamples = 4;        // samples whose weights the rows pre-pass stages at a time
-
-__device__ __forceinline__ float sample_weight(float w, long long e, int s, float p, float scale, int training, u64 seed,
-                                               const unsigned char* keep, long long keep_stride)
-{
-    if (!training) return w;
-    return w * (keep ? (keep[(long long)s * keep_stride + e] ? scale : 0.0f) : keep_scale(sample_seed(seed, s), (u64)e, p, scale));
-}
-
-struct BagLayout {
-    const long long* offsets; long long n_src;        // offsets[n_src + 1]
-    const long long* nodes;                             // [n_rows] or NULL
-    const long long* base;                              // [n_rows] or NULL
-    long long n_rows;
-    const void* idx; int idx64;                         // attr ids: int64 (idx64) or int32
-    const float* data;
-};
-
-__device__ __forceinline__ bool bag_of(const BagLayout& L, long long m, long long& s0, long long& s1, long long& jb)
-{
-    const long long src = L.nodes ? L.nodes[m] : m;
-    if (src < 0 || src >= L.n_src) { s0 = s1 = jb = 0; return false; }
-    s0 = L.offsets[src]; s1 = L.offsets[src + 1];
-    jb = L.base ? L.base[m] : s0;
-    return true;
-}
-
-__device__ __forceinline__ long long attr_id(const BagLayout& L, long long e)
-{
-    return L.idx64 ? reinterpret_cast<const long long*>(L.idx)[e] : (long long)reinterpret_cast<const int*>(L.idx)[e];
-}
 
 // ---- pre-pass, rows form: inv_den[s * n_batch + b] = 1 / (den_{s,b} + 1e-12), den summed over k in the forward's order
 __global__ void __launch_bounds__(kBlock)
@@ -72,10 +40,10 @@ rows_inv_den_kernel(const double* __restrict__ val, const int* __restrict__ fill
                     long long keep_stride, float* __restrict__ inv_den)
 {
     __shared__ float s_w[kDenSamples][kStage];
-    const float scale = p < 1.0f ? 1.0f / (1.0f - p) : 0.0f;
+    const float scale = inv_keep(p);
     for (int b = blockIdx.x; b < n_batch; b += gridDim.x) {
         const long long row = batch_rows ? batch_rows[b] : b;
-        const int n = filled ? min(filled[row], K) : K;
+        const int n = row_len(filled, row, K);
         for (int s0 = 0; s0 < S; s0 += kDenSamples) {
             const int ns = min(kDenSamples, S - s0);
             __syncthreads();
@@ -88,7 +56,7 @@ rows_inv_den_kernel(const double* __restrict__ val, const int* __restrict__ fill
             if (threadIdx.x < ns) {
                 float den = 0.0f;
                 for (int k = 0; k < n; ++k) den += s_w[threadIdx.x][k];
-                inv_den[(size_t)(s0 + threadIdx.x) * n_batch + b] = 1.0f / (den + 1e-12f);
+                inv_den[(size_t)(s0 + threadIdx.x) * n_batch + b] = inv_den_rows(den);
             }
         }
     }
@@ -116,7 +84,7 @@ bag_inv_den_kernel(long long V, BagLayout L, float* __restrict__ inv_den, int* _
             for (int o = 1; o < 64; o <<= 1) part += __shfl_xor(part, o);
             den += part;
         }
-        if (lane == 0) inv_den[m] = 1.0f / (den + 1e-10f);
+        if (lane == 0) inv_den[m] = inv_den_bag(den);
     }
 }
 
@@ -141,10 +109,10 @@ struct RowsOp {
         if (e < 0 || e >= (long long)n_batch * K) return E;
         const int b = (int)(e / K), k = (int)(e - (long long)b * K);
         const long long row = batch_rows ? batch_rows[b] : b;
-        const int n = filled ? min(filled[row], K) : K;
+        const int n = row_len(filled, row, K);
         const long long re = row * (long long)K + k;              // the resident slot: keys the mask, as in the forward
         if (k >= n || (long long)col[re] != key) return E;
-        const float scale = p < 1.0f ? 1.0f / (1.0f - p) : 0.0f;
+        const float scale = inv_keep(p);
         const float w = (float)val[re];
         bool any = false;
 #pragma unroll
@@ -206,7 +174,7 @@ struct BagOp {
         if (!__shfl(E.live, u)) return;                              // wave-uniform
         const long long m = __shfl(E.m, u), j = __shfl(E.j, u);
         const float d = __shfl(E.d, u), inv = __shfl(E.inv, u);
-        const float scale = p < 1.0f ? 1.0f / (1.0f - p) : 0.0f;
+        const float scale = inv_keep(p);
 #pragma unroll
         for (int c = 0; c < kCols; ++c) {
             const int h = f + 64 * c;
@@ -323,8 +291,7 @@ int gp_embedding_bag_backward_det(int device, const float* d_grad_out, int64_t n
     if (const int rc = set_device(device, where)) return rc;
     hipStream_t s = (hipStream_t)stream;
     if (d_n_bad && hipMemsetAsync(d_n_bad, 0, sizeof(int32_t), s) != hipSuccess) return fail(GP_ERR_HIP, where, "hipMemsetAsync failed");
-    const BagLayout L = {(const long long*)d_offsets, (long long)n_src, (const long long*)d_nodes, (const long long*)d_entry_base,
-                         (long long)n_rows, d_attr_idx, idx_bytes == 8, d_attr_data};
+    const BagLayout L = bag_layout(d_offsets, n_src, d_nodes, d_entry_base, n_rows, d_attr_idx, idx_bytes, d_attr_data);
     const int grid = (int)std::min<long long>(65535, (n_rows + kBlock / 64 - 1) / (kBlock / 64));
     hipLaunchKernelGGL(bag_inv_den_kernel, dim3(grid), dim3(kBlock), 0, s, (long long)n_vocab, L, d_inv_den, d_n_bad);
     if (const int rc = launch_status("bag_inv_den_kernel")) return rc;
