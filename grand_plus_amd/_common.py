@@ -14,6 +14,7 @@ _M64 = 2**64 - 1
 _GOLDEN = 0x9E3779B97F4A7C15
 _LAYER_MUL = 0xA0761D6478BD642F
 _SLOT_MUL = 0xE7037ED1A0B428DB
+_STEP_MUL = 0x8CB92BA72F3D8DD7
 
 _seed_counter = itertools.count(0x5EED)
 
@@ -43,6 +44,11 @@ def layer_seed(seed: int, layer: int, s: int = 0) -> int:
 def mag_slot_seed(seed: int, s: int, e: int) -> int:
     """Input-dropout seed of (sample s, slot e = r * K + k) of a mag_prop_rows call: GP_MAG_SLOT_SEED of grandplus_mag.h."""
     return _mix(sample_seed(seed, s) ^ (((e + 1) * _SLOT_MUL) & _M64))
+
+
+def step_seed(base: int, t: int) -> int:
+    """Seed of step t >= 1 of a training run with `base` (gp_step_state.seed of grandplus_step.h): mix(base ^ t * GP_STEP_MUL)."""
+    return _mix((base & _M64) ^ ((t * _STEP_MUL) & _M64))
 
 
 def _check(t, dtype, name):

@@ -55,6 +55,24 @@ def scatter_bag_workspace_bytes(n_rows: int) -> int:
     return 4 * n_rows
 
 
+GP_STEP_MAX_GROUPS, GP_STEP_MAX_LAYERS = 8, 8
+GP_STEP_SEG_ROWS, GP_STEP_SEG_LAYER = 0, 1
+
+
+class GpStepState(ctypes.Structure):
+    """gp_step_state of grandplus_step.h: the image of the device struct (StepState.read copies it to the host)."""
+    _fields_ = [("tick", ctypes.c_uint64), ("seed", ctypes.c_uint64), ("weight", ctypes.c_float),
+                ("step_size", ctypes.c_float * GP_STEP_MAX_GROUPS), ("rsqrt_bc2", ctypes.c_float * GP_STEP_MAX_GROUPS)]
+
+
+class GpStepSegment(ctypes.Structure):
+    """gp_step_segment of grandplus_step.h: device pointers as integers."""
+    _fields_ = [("keep", ctypes.c_void_p), ("keep_stride", ctypes.c_int64), ("batch_rows", ctypes.c_void_p),
+                ("filled", ctypes.c_void_p), ("kind", ctypes.c_int32), ("n_samples", ctypes.c_int32),
+                ("n_batch", ctypes.c_int32), ("K", ctypes.c_int32), ("width", ctypes.c_int32), ("layer", ctypes.c_int32),
+                ("p", ctypes.c_float), ("pad", ctypes.c_int32)]
+
+
 class GpOptimTensor(ctypes.Structure):
     """gp_optim_tensor of grandplus.h: device pointers as integers."""
     _fields_ = [("param", ctypes.c_void_p), ("grad", ctypes.c_void_p), ("exp_avg", ctypes.c_void_p),
@@ -232,6 +250,16 @@ _CHAIN_SIGNATURES = {
     "gp_mlp_infer_chain2": (_int, [_int, _vp, _i64, _i32, _i32, _i32] + _chain_block + _chain_block + [_vp, _vp, _vp], False),
 }
 CHAIN_EXPORTS = tuple(_CHAIN_SIGNATURES)
+# The device-resident step state, which include/grandplus_step.h declares (grandplus.h includes it): the same convention,
+# held against that header type by type by tests/test_host_step.py.  gp_clip_adam_step_dev is gp_clip_adam_step with two
+# device pointers where that takes step_size and rsqrt_bc2.
+_STEP_SIGNATURES = {
+    "gp_step_advance": (_int, [_int, _vp, _u64, _f64, _f64, _i32, _f64p, _f64p, _f64p, _vp], False),
+    "gp_step_masks": (_int, [_int, _vp, ctypes.POINTER(GpStepSegment), _i32, _vp], False),
+    "gp_clip_adam_step_dev": (_int, [_int, ctypes.POINTER(GpOptimTensor), _i32, _int, _f32, _f32, _f64, _f64, _f32, _f32, _vp, _vp,
+                                     _vp, _vp, _vp], False),
+}
+STEP_EXPORTS = tuple(_STEP_SIGNATURES)
 
 _LIB = None
 
@@ -262,7 +290,8 @@ def lib():
         pass
     L = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes, required) in {**_SIGNATURES, **_EVAL_SIGNATURES, **_SCATTER_SIGNATURES, **_INFER_SIGNATURES,
-                                              **_MAG_SIGNATURES, **_ORDER_SIGNATURES, **_CHAIN_SIGNATURES}.items():
+                                              **_MAG_SIGNATURES, **_ORDER_SIGNATURES, **_CHAIN_SIGNATURES,
+                                              **_STEP_SIGNATURES}.items():
         if not required and not hasattr(L, name):
             setattr(L, name, _missing(name))
             continue

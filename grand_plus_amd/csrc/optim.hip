@@ -12,7 +12,9 @@
 //                           partial per workgroup in one of kSlots workspace slots (the rest are zeroed);
 //   optim_clip_adam_kernel  every workgroup sums the kSlots partials in index order with the same fixed tree, so all hold
 //                           the same bits; norm, clip coefficient, then the Adam update (or, with GP_OPTIM_CLIP_ONLY,
-//                           grad * coef written back) over its chunks.
+//                           grad * coef written back) over its chunks.  A template on where step_size and rsqrt_bc2 come
+//                           from: the kernel arguments (gp_clip_adam_step), or two device floats of a gp_step_state
+//                           (gp_clip_adam_step_dev), read once per thread before the same arithmetic.
 // A chunk whose four pointers are 16-byte aligned moves as float4; any other takes a scalar path with the same
 // per-element arithmetic (-ffp-contract=off: no fused multiply-add), so an element's result never depends on where it lies.
 #include "gp_common.hpp"
@@ -101,10 +103,15 @@ __device__ __forceinline__ void adam_element(float& p, float g, float& m, float&
     p -= a.step_size * (m / (sqrtf(v) * a.rsqrt_bc2 + a.eps));
 }
 
+template <bool kDeviceSteps>
 __global__ __launch_bounds__(kBlock) void optim_clip_adam_kernel(const OptimTable tab, const double* __restrict__ partials,
-                                                                  float* __restrict__ norm_out, long long n_chunks, const AdamArgs a)
+                                                                  float* __restrict__ norm_out, long long n_chunks, const AdamArgs a_in,
+                                                                  const float* __restrict__ d_step_size,
+                                                                  const float* __restrict__ d_rsqrt_bc2)
 {
     __shared__ double lds[kWaves];
+    AdamArgs a = a_in;
+    if (kDeviceSteps) { a.step_size = *d_step_size; a.rsqrt_bc2 = *d_rsqrt_bc2; }
     const int tid = threadIdx.x;
     const double* q = partials + tid * 4;
     const double sum = block_sum<kWaves>(((q[0] + q[1]) + q[2]) + q[3], lds);
@@ -202,15 +209,13 @@ long long fill_table(OptimTable& tab, const gp_optim_tensor* tensors, int first,
     return chunks;
 }
 
-}  // namespace
-
-extern "C" {
-
-int gp_clip_adam_step(int device, const gp_optim_tensor* tensors, int32_t n_tensors, int flags,
-                      float max_norm, float lr, double beta1, double beta2, float eps, float weight_decay,
-                      float step_size, float rsqrt_bc2, void* d_workspace, float* d_norm_out, void* stream)
+// both entry points: kDeviceSteps says whether step_size / rsqrt_bc2 are the two values or the two device pointers
+template <bool kDeviceSteps>
+int clip_adam_step(const char* where, int device, const gp_optim_tensor* tensors, int32_t n_tensors, int flags,
+                   float max_norm, float lr, double beta1, double beta2, float eps, float weight_decay,
+                   float step_size, float rsqrt_bc2, const float* d_step_size, const float* d_rsqrt_bc2,
+                   void* d_workspace, float* d_norm_out, void* stream)
 {
-    const char* where = "gp_clip_adam_step";
     const int known = GP_OPTIM_CLIP_ONLY | GP_OPTIM_NORM_ONLY | GP_OPTIM_NORM_READY;
     const bool clip_only = flags & GP_OPTIM_CLIP_ONLY, norm_only = flags & GP_OPTIM_NORM_ONLY, norm_ready = flags & GP_OPTIM_NORM_READY;
     if (n_tensors < 0 || (flags & ~known) || (norm_only && norm_ready))
@@ -220,6 +225,8 @@ int gp_clip_adam_step(int device, const gp_optim_tensor* tensors, int32_t n_tens
         return fail(GP_ERR_INVALID_ARG, where, "a hyper-parameter is not finite");
     if ((n_tensors > 0 && !tensors) || !d_workspace || (!norm_only && !d_norm_out))
         return fail(GP_ERR_NULL, where, "the tensor table, the workspace or the norm output is NULL");
+    if (kDeviceSteps && !norm_only && (!d_step_size || !d_rsqrt_bc2))
+        return fail(GP_ERR_NULL, where, "d_step_size or d_rsqrt_bc2 is NULL");
     for (int i = 0; i < n_tensors; ++i) {
         const gp_optim_tensor& t = tensors[i];
         if (t.numel < 0) return fail(GP_ERR_INVALID_ARG, where, "a tensor has a negative element count");
@@ -260,11 +267,31 @@ int gp_clip_adam_step(int device, const gp_optim_tensor* tensors, int32_t n_tens
         const int count = n_tensors - first < GP_OPTIM_MAX_TENSORS ? n_tensors - first : GP_OPTIM_MAX_TENSORS;
         const long long chunks = fill_table(tab, tensors, first, writes ? count : 0);
         if (g > 0 && chunks == 0) continue;
-        hipLaunchKernelGGL(optim_clip_adam_kernel, dim3(grid_of(chunks)), dim3(kBlock), 0, s, tab, (const double*)partials,
-                           g == 0 ? d_norm_out : (float*)nullptr, chunks, a);
+        hipLaunchKernelGGL(optim_clip_adam_kernel<kDeviceSteps>, dim3(grid_of(chunks)), dim3(kBlock), 0, s, tab,
+                           (const double*)partials, g == 0 ? d_norm_out : (float*)nullptr, chunks, a, d_step_size, d_rsqrt_bc2);
         if (const int rc = launch_status("optim_clip_adam_kernel")) return rc;
     }
     return GP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gp_clip_adam_step(int device, const gp_optim_tensor* tensors, int32_t n_tensors, int flags,
+                      float max_norm, float lr, double beta1, double beta2, float eps, float weight_decay,
+                      float step_size, float rsqrt_bc2, void* d_workspace, float* d_norm_out, void* stream)
+{
+    return clip_adam_step<false>("gp_clip_adam_step", device, tensors, n_tensors, flags, max_norm, lr, beta1, beta2, eps,
+                                 weight_decay, step_size, rsqrt_bc2, nullptr, nullptr, d_workspace, d_norm_out, stream);
+}
+
+int gp_clip_adam_step_dev(int device, const gp_optim_tensor* tensors, int32_t n_tensors, int flags,
+                          float max_norm, float lr, double beta1, double beta2, float eps, float weight_decay,
+                          const float* d_step_size, const float* d_rsqrt_bc2, void* d_workspace, float* d_norm_out, void* stream)
+{
+    return clip_adam_step<true>("gp_clip_adam_step_dev", device, tensors, n_tensors, flags, max_norm, lr, beta1, beta2, eps,
+                                weight_decay, 0.0f, 0.0f, d_step_size, d_rsqrt_bc2, d_workspace, d_norm_out, stream);
 }
 
 }  // extern "C"

@@ -68,6 +68,14 @@ def _call(dev, like, entries, flags, ws, norm, max_norm=0.0, lr=0.0, betas=(0.0,
     _native.raise_for_status(rc)
 
 
+def _call_dev(dev, like, entries, flags, ws, norm, d_step_size, d_rsqrt_bc2, max_norm, lr, betas, eps, weight_decay):
+    """_call with the two bias corrections read on the device (gp_clip_adam_step_dev): addresses inside a gp_step_state."""
+    rc = _native.lib().gp_clip_adam_step_dev(dev.index, _table(entries), len(entries), flags, max_norm, lr, betas[0], betas[1],
+                                             eps, weight_decay, d_step_size, d_rsqrt_bc2, ws.data_ptr(), norm.data_ptr(),
+                                             _stream(like))
+    _native.raise_for_status(rc)
+
+
 def clip_grad_norm(params, max_norm):
     """Drop-in for the reference's `clip_grad_norm(params, max_norm)` (model.py:116-120): the 2-norm of all gradients as a
     0-dim float32 device tensor; with max_norm > 0 the gradients are scaled in place by min(max_norm / (norm + 1e-6), 1)
@@ -99,12 +107,28 @@ class ClipAdam(torch.optim.Optimizer):
     Every parameter that has a gradient must be a contiguous float32 CUDA tensor, all on one device: `step()` raises
     TypeError otherwise, before anything is launched or any state changes (the constructor accepts a model that is still
     on the CPU).  The same holds for `exp_avg` and `exp_avg_sq` of a loaded checkpoint.
+
+    capturable=True, state=<step.StepState> keeps the step count on the device, so that `step()` is a fixed
+    sequence of launches with fixed arguments and can be replayed from a captured graph.  The count is `tick` of the
+    StepState given here as `state` (capturable=True without one is a TypeError: a required argument is missing); the
+    caller advances it once per step (`state.advance(optimizer)`), and `step()` reads lr / (1 - beta1^t) and
+    1 / sqrt(1 - beta2^t) from it on the device.  One count serves every parameter, so `step()` raises ValueError, before
+    any launch, for a parameter without a gradient, for parameters whose loaded `step` values differ from one another and
+    for more than 8 parameter groups.  `state_dict()` reports `step` as the number torch.optim.Adam would hold (one host
+    read of `tick`); `load_state_dict()` sets `tick` from it.  `lr` and the betas are read when the state advances: under a
+    captured graph they are the values of the capture.
     """
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, clip_norm=0.0, *,
-                 amsgrad=False, maximize=False):
+                 amsgrad=False, maximize=False, capturable=False, state=None):
         if amsgrad or maximize:
             raise ValueError("ClipAdam does not implement amsgrad or maximize")
+        if capturable and state is None:
+            raise TypeError("ClipAdam(capturable=True) is missing its StepState: pass state=StepState(device, seed, lam, warmup)")
+        if state is not None and not capturable:
+            raise ValueError("state= is the step count of ClipAdam(capturable=True); without capturable the count is a host number")
+        self.capturable = bool(capturable)
+        self.step_state = state
         if isinstance(lr, torch.Tensor) or any(isinstance(b, torch.Tensor) for b in betas):
             raise ValueError("ClipAdam takes lr and betas as Python numbers, not Tensors")
         if not math.isfinite(float(clip_norm)):
@@ -115,10 +139,24 @@ class ClipAdam(torch.optim.Optimizer):
         super().__init__(params, dict(probe.defaults))
 
     def load_state_dict(self, state_dict):
+        if self.capturable:
+            steps = {self._number(s["step"]) for s in state_dict["state"].values() if "step" in s}
+            if len(steps) > 1:
+                raise ValueError(f"a capturable ClipAdam keeps one step count for all parameters: the checkpoint holds {sorted(steps)}")
         super().load_state_dict(state_dict)
         for s in self.state.values():                                # torch.optim.Adam keeps `step` as a tensor
             if "step" in s:
                 s["step"] = self._number(s["step"])
+        if self.capturable:
+            self.step_state.set_tick(steps.pop() if steps else 0)
+
+    def state_dict(self):
+        out = super().state_dict()
+        if self.capturable and out["state"]:
+            # in self.state `step` is what a checkpoint brought (the same for all, 0 without one) and never moves
+            t = self.step_state.read().tick
+            out["state"] = {k: {**s, "step": t} if "step" in s else s for k, s in out["state"].items()}
+        return out
 
     @staticmethod
     def _number(step):
@@ -130,6 +168,8 @@ class ClipAdam(torch.optim.Optimizer):
             with torch.enable_grad():
                 closure()
         todo, calls, dev = [], {}, None                              # calls: (group index, step count) -> entries
+        if self.capturable:
+            self._check_capturable()
         for gi, group in enumerate(self.param_groups):
             if group.get("amsgrad") or group.get("maximize") or group.get("decoupled_weight_decay"):
                 raise ValueError("ClipAdam does not implement amsgrad, maximize or decoupled_weight_decay")
@@ -150,6 +190,8 @@ class ClipAdam(torch.optim.Optimizer):
                     if s.device != dev or s.shape != p.shape:
                         raise TypeError(f"{key} must have its parameter's device and shape, got {tuple(s.shape)} on {s.device}")
                 todo.append((gi, p, g))
+        if self.capturable:
+            return self._step_capturable(todo, dev)
         for gi, p, g in todo:                                        # every check has passed: now the state may change
             state = self.state[p]
             if len(state) == 0:
@@ -172,4 +214,47 @@ class ClipAdam(torch.optim.Optimizer):
             _call(dev, like, entries, flags, ws, norm, max_norm=self.clip_norm, lr=lr, betas=(float(beta1), float(beta2)),
                   eps=float(group["eps"]), weight_decay=float(group["weight_decay"]),
                   step_size=lr / (1.0 - beta1 ** t), rsqrt_bc2=1.0 / math.sqrt(1.0 - beta2 ** t))
+        return norm
+
+    def _check_capturable(self):
+        """What one device-resident step count cannot serve: ValueError before anything is launched or any state changes."""
+        if len(self.param_groups) > _native.GP_STEP_MAX_GROUPS:
+            raise ValueError(f"ClipAdam(capturable=True) takes at most {_native.GP_STEP_MAX_GROUPS} parameter groups, "
+                             f"got {len(self.param_groups)}")
+        steps = set()
+        for group in self.param_groups:
+            for p in group["params"]:
+                if p.grad is None:
+                    raise ValueError("ClipAdam(capturable=True) steps every parameter with one step count: a parameter has no "
+                                     "gradient (give the optimiser only the parameters that are trained)")
+                steps.add(self._number((self.state.get(p) or {}).get("step", 0)))
+        if len(steps) > 1:
+            raise ValueError(f"ClipAdam(capturable=True) keeps one step count for all parameters: the loaded values are {sorted(steps)}")
+
+    def _step_capturable(self, todo, dev):
+        """The launches of step() with the bias corrections of group gi read from the optimiser's gp_step_state."""
+        calls = {}
+        for gi, p, g in todo:
+            state = self.state[p]
+            if len(state) == 0:
+                state["step"] = 0                                    # the count itself is the state's tick
+                state["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+                state["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+            calls.setdefault(gi, []).append((p, g, state["exp_avg"], state["exp_avg_sq"]))
+        if dev is None:
+            return _no_gradients([p for group in self.param_groups for p in group["params"]])
+        if self.step_state.device != dev:
+            raise TypeError(f"the StepState is on {self.step_state.device}, the parameters on {dev}")
+        ws, norm = _buffers(dev)
+        like = next(iter(calls.values()))[0][0]
+        flags = 0
+        if len(calls) > 1:
+            _call(dev, like, [e for entries in calls.values() for e in entries], _native.GP_OPTIM_NORM_ONLY, ws, norm)
+            flags = _native.GP_OPTIM_NORM_READY
+        for gi, entries in calls.items():
+            group = self.param_groups[gi]
+            beta1, beta2 = group["betas"]
+            d_step_size, d_rsqrt_bc2 = self.step_state.correction_ptrs(gi)
+            _call_dev(dev, like, entries, flags, ws, norm, d_step_size, d_rsqrt_bc2, max_norm=self.clip_norm, lr=float(group["lr"]),
+                      betas=(float(beta1), float(beta2)), eps=float(group["eps"]), weight_decay=float(group["weight_decay"]))
         return norm

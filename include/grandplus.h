@@ -540,6 +540,11 @@ int gp_clip_adam_step(int device, const gp_optim_tensor* tensors, int32_t n_tens
  * out in, and the sketch kernel's per-workgroup exit stamps: declared in a header of their own, part of this ABI. */
 #include "grandplus_order.h"
 
+/* The device-resident state of a training step (gp_step_state, the launch that advances it, the launch that
+ * writes a step's dropout masks from its seed, and gp_clip_adam_step with its bias corrections read from it): declared in
+ * a header of their own, part of this ABI. */
+#include "grandplus_step.h"
+
 /* ------------------------------------------------------------------------------------------
  * exact full-graph feature propagation of the inference path, reference
  * predict() (model.py:181-224), lines 186-210.  mode 0 = ppr, 1 = avg, 2 = single (args.prop_mode);
