@@ -138,128 +138,115 @@ class GpStats(ctypes.Structure):
         return d
 
 
-# The C ABI of include/grandplus.h, declared once: name -> (restype, argtypes, required).  tests/test_host_logic.py holds every
-# entry against the header's prototype, type by type.  The pointer convention:
-#   * device pointers (and streams) travel as c_void_p integers, from tensor.data_ptr();
-#   * host arrays travel as typed POINTER(...);
-#   * gp_graph* is c_void_p, gp_graph** (and any other T**) is POINTER(c_void_p);
-#   * const char* is c_char_p.
+# The C ABI, declared once: public header (in the order include/grandplus.h includes them) -> entry point -> (restype,
+# argtypes, required).  tests/test_host_abi.py holds every entry against its header's prototype, type by type.  The convention:
+#   * a pointer parameter named d_* travels as c_void_p (an integer, from tensor.data_ptr()); so do void* (untyped device
+#     memory, a stream), gp_graph* and gp_step_state*;
+#   * T** is POINTER(c_void_p);
+#   * const char* is c_char_p;
+#   * every other T* is a host array and travels as POINTER(T), with gp_stats, gp_optim_tensor and gp_step_segment mapping to
+#     their Structure classes;
+#   * scalars map one to one.
 # A name that is not required may be missing from an older build selected with GRANDPLUS_LIB (an A/B run): calling it there
 # raises a clear error.  A missing required name fails at load.  (gp_internal_graph_csr, gp_internal_multi_plan and
-# gp_internal_set_error were never needed at load, so they are not required either.)
+# gp_internal_set_error were never needed at load, so they are not required either; nothing outside grandplus.h is.)
 _int, _i32, _i64, _u32, _u64, _f32, _f64 = (ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32, ctypes.c_uint64,
                                             ctypes.c_float, ctypes.c_double)
 _vp, _str = ctypes.c_void_p, ctypes.c_char_p
 _intp, _i32p, _i64p, _u32p, _f64p, _vpp = (ctypes.POINTER(t) for t in (_int, _i32, _i64, _u32, _f64, _vp))
 _bag = [_int, _vp, _i64, _i32, _vp, _i64, _vp, _vp, _i64, _vp, _int, _vp, _f32, _int, _u64, _vp, _vp, _vp, _vp]
 _loss = [_int, _vp, _i32, _i64, _i32, _vp, _i64, _i64, _f32, _f32, _f32, _int, _int]
-_SIGNATURES = {
-    "gp_abi_version": (_int, [], True),
-    "gp_strerror": (_str, [_int], True),
-    "gp_last_error": (_str, [], True),
-    "gp_device_count": (_int, [], True),
-    "gp_graph_create": (_int, [_i32p, _i64, _i32p, _i64, _int, _vpp], True),
-    "gp_graph_create_multi": (_int, [_i32p, _i64, _i32p, _i64, _int, _vpp], True),
-    "gp_graph_create_multi_on": (_int, [_i32p, _i64, _i32p, _i64, _intp, _int, _vpp], False),
-    "gp_graph_num_gpus": (_int, [_vp], True),
-    "gp_graph_destroy": (None, [_vp], True),
-    "gp_graph_num_nodes": (_i64, [_vp], True),
-    "gp_graph_nnz": (_i64, [_vp], True),
-    "gp_graph_device": (_int, [_vp], True),
-    "gp_gfpush": (_int, [_vp, _i32p, _i64, _f64p, _int, _f64, _int, _i32p, _i32p, _f64p], True),
-    "gp_gfpush_device": (_int, [_vp, _vp, _i64, _f64p, _int, _f64, _int, _vp, _vp, _vp, _vp, _vp], True),
-    "gp_get_stats": (_int, [_vp, ctypes.POINTER(GpStats)], True),
-    "gp_reset_stats": (_int, [_vp], True),
-    "gp_set_option": (_int, [_vp, _str, _i64], True),
-    "gp_random_prop_rows": (_int, [_int, _vp, _i64, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _f32, _int, _u64, _vp, _vp, _vp], True),
-    "gp_seed_positions": (_int, [_int, _vp, _i64, _i64, _vp, _vp, _vp], False),
-    "gp_batch_positions": (_int, [_int, _vp, _i64, _vp, _i64, _vp, _vp, _vp], False),
-    "gp_random_prop_coo": (_int, [_int, _vp, _i64, _i32, _vp, _vp, _i64, _f32, _int, _u64, _vp, _vp, _vp], True),
-    "gp_random_prop_coo_backward": (_int, [_int, _vp, _i64, _i32, _vp, _vp, _i64, _f32, _int, _u64, _vp, _vp, _vp], False),
-    "gp_random_prop_rows_backward": (_int, [_int, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _f32, _int, _u64, _vp, _vp, _i64, _vp],
-                                     False),
-    "gp_embedding_bag": (_int, _bag, False),
-    "gp_embedding_bag_backward": (_int, _bag, False),
-    "gp_random_prop_rows_multi": (_int, [_int, _vp, _i64, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _f32, _int, _u64, _vp, _i64,
-                                         _vp, _vp], False),
-    "gp_random_prop_coo_multi": (_int, [_int, _vp, _i64, _i32, _vp, _vp, _i64, _i32, _f32, _int, _u64, _vp, _vp, _vp], False),
-    "gp_random_prop_coo_multi_backward": (_int, [_int, _vp, _i64, _i32, _vp, _vp, _i64, _i32, _f32, _int, _u64, _vp, _vp, _vp], False),
-    "gp_random_prop_rows_multi_backward": (_int, [_int, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _f32, _int, _u64, _vp, _i64,
-                                                  _vp, _i64, _vp], False),
-    "gp_grand_loss": (_int, _loss + [_vp, _vp, _vp, _vp], False),
-    "gp_grand_loss_backward": (_int, _loss + [_vp, _vp, _vp, _vp, _vp, _vp], False),
-    "gp_mlp_block_forward": (_int, [_int, _vp, _i32, _i64, _i32, _i32, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _f32, _f32,
-                                    _f32, _u64, _i32, _vp, _vp, _vp, _vp, _vp, _vp], False),
-    "gp_mlp_block_backward": (_int, [_int, _vp, _i32, _i64, _i32, _i32, _vp, _int, _vp, _f32, _u64, _i32, _vp,
-                                     _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], False),
-    "gp_clip_adam_step": (_int, [_int, ctypes.POINTER(GpOptimTensor), _i32, _int, _f32, _f32, _f64, _f64, _f32, _f32, _f32, _f32,
-                                 _vp, _vp, _vp], False),
-    "gp_propagate_features": (_int, [_vp, _vp, _i32, _vp, _int, _int, _f64, _vp, _vp], True),
-    "gp_internal_graph_csr": (_int, [_vp, _vpp, _vpp, _u32p, _vp], False),
-    "gp_internal_graph_acsr": (_int, [_vp, _vp, _vp, _vp, _i64p, _intp, _u32p], False),
-    "gp_internal_diag_counters": (_int, [_vp, _i64p, _int], True),
-    "gp_internal_multi_plan": (_int, [_i64, _int, _int, _i64, _int, _int, _i64p, _int], False),
-    "gp_internal_set_error": (None, [_int, _str, _str], False),
-    "gp_internal_create_ms": (None, [_f64p], False),
-    "gp_internal_warm_device": (_int, [_int], False),
-}
-EXPORTS = tuple(_SIGNATURES)          # every symbol include/grandplus.h declares (tests check the library exports all of them)
-# The evaluation entry points, which include/grandplus_eval.h declares (grandplus.h includes it): the same convention, held
-# against that header type by type by tests/test_host_evaluate.py.
-_EVAL_SIGNATURES = {
-    "gp_eval_head": (_int, [_int, _vp, _i64, _i32, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp], False),
-    "gp_eval_reduce": (_int, [_int, _vp, _vp, _i64, _vp, _vp, _vp, _vp], False),
-}
-EVAL_EXPORTS = tuple(_EVAL_SIGNATURES)
-# The deterministic scatter backwards, which include/grandplus_scatter.h declares (grandplus.h includes it): the same
-# convention, held against that header type by type by tests/test_host_deterministic.py.  Each takes the arguments of its
-# atomic counterpart, then the sorted order (entry numbers, sorted keys[, sorted rows], their length) and the scratch.
-_SCATTER_SIGNATURES = {
-    "gp_random_prop_rows_backward_det": (_int, [_int, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _f32, _int, _u64, _vp, _i64,
-                                                _vp, _i64, _vp, _vp, _i64, _vp, _vp], False),
-    "gp_embedding_bag_backward_det": (_int, _bag[:-1] + [_vp, _vp, _vp, _i64, _vp, _vp], False),
-}
-SCATTER_EXPORTS = tuple(_SCATTER_SIGNATURES)
-# The eval-only MLP block, which include/grandplus_infer.h declares (grandplus.h includes it): the same convention, held
-# against that header type by type by tests/test_host_infer.py.
-_INFER_SIGNATURES = {
-    "gp_mlp_infer_block": (_int, [_int, _vp, _i64, _i32, _i32, _vp, _vp, _int, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp], False),
-}
-INFER_EXPORTS = tuple(_INFER_SIGNATURES)
-# MAG's fused front end, which include/grandplus_mag.h declares (grandplus.h includes it): the same convention, held
-# against that header type by type by tests/test_host_mag_rows.py.  The backward takes the forward's arguments with
-# grad_out for the table and dW for the output, and no counter.
+# gp_mag_prop_rows' arguments between the table and the outputs; a block of the eval MLP: weight, bias, flags, the four
+# BatchNorm tensors and eps
 _mag = [_i64, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _i32, _f32, _f32, _int, _u64, _vp, _i64]
-_MAG_SIGNATURES = {
-    "gp_mag_prop_rows": (_int, [_int, _vp] + _mag + [_vp, _vp, _vp], False),
-    "gp_mag_prop_rows_backward": (_int, [_int, _vp] + _mag + [_vp, _vp], False),
-}
-MAG_EXPORTS = tuple(_MAG_SIGNATURES)
-# The entry points behind option "row_order", which include/grandplus_order.h declares (grandplus.h includes it): the same
-# convention, held against that header type by type by tests/test_host_row_order.py.
-_ORDER_SIGNATURES = {
-    "gp_internal_row_order": (_int, [_vp, _u32p, _i64, _i64p, _intp, _u32p], False),
-    "gp_internal_wg_log": (_int, [_vp, _i64p, _int], False),
-}
-ORDER_EXPORTS = tuple(_ORDER_SIGNATURES)
-# The last two eval blocks as one kernel, which include/grandplus_infer_chain.h declares (grandplus.h includes it): the same
-# convention, held against that header type by type by tests/test_host_infer_chain.py.  Each block's arguments are
-# gp_mlp_infer_block's: weight, bias, flags, the four BatchNorm tensors and eps.
-_chain_block = [_vp, _vp, _int, _vp, _vp, _vp, _vp, _f32]
-_CHAIN_SIGNATURES = {
-    "gp_mlp_infer_chain2": (_int, [_int, _vp, _i64, _i32, _i32, _i32] + _chain_block + _chain_block + [_vp, _vp, _vp], False),
-}
-CHAIN_EXPORTS = tuple(_CHAIN_SIGNATURES)
-# The device-resident step state, which include/grandplus_step.h declares (grandplus.h includes it): the same convention,
-# held against that header type by type by tests/test_host_step.py.  gp_clip_adam_step_dev is gp_clip_adam_step with two
-# device pointers where that takes step_size and rsqrt_bc2.
-_STEP_SIGNATURES = {
-    "gp_step_advance": (_int, [_int, _vp, _u64, _f64, _f64, _i32, _f64p, _f64p, _f64p, _vp], False),
-    "gp_step_masks": (_int, [_int, _vp, ctypes.POINTER(GpStepSegment), _i32, _vp], False),
-    "gp_clip_adam_step_dev": (_int, [_int, ctypes.POINTER(GpOptimTensor), _i32, _int, _f32, _f32, _f64, _f64, _f32, _f32, _vp, _vp,
+_block = [_vp, _vp, _int, _vp, _vp, _vp, _vp, _f32]
+ABI = {
+    "grandplus.h": {
+        "gp_abi_version": (_int, [], True),
+        "gp_strerror": (_str, [_int], True),
+        "gp_last_error": (_str, [], True),
+        "gp_device_count": (_int, [], True),
+        "gp_graph_create": (_int, [_i32p, _i64, _i32p, _i64, _int, _vpp], True),
+        "gp_graph_create_multi": (_int, [_i32p, _i64, _i32p, _i64, _int, _vpp], True),
+        "gp_graph_create_multi_on": (_int, [_i32p, _i64, _i32p, _i64, _intp, _int, _vpp], False),
+        "gp_graph_num_gpus": (_int, [_vp], True),
+        "gp_graph_destroy": (None, [_vp], True),
+        "gp_graph_num_nodes": (_i64, [_vp], True),
+        "gp_graph_nnz": (_i64, [_vp], True),
+        "gp_graph_device": (_int, [_vp], True),
+        "gp_gfpush": (_int, [_vp, _i32p, _i64, _f64p, _int, _f64, _int, _i32p, _i32p, _f64p], True),
+        "gp_gfpush_device": (_int, [_vp, _vp, _i64, _f64p, _int, _f64, _int, _vp, _vp, _vp, _vp, _vp], True),
+        "gp_get_stats": (_int, [_vp, ctypes.POINTER(GpStats)], True),
+        "gp_reset_stats": (_int, [_vp], True),
+        "gp_set_option": (_int, [_vp, _str, _i64], True),
+        "gp_random_prop_rows": (_int, [_int, _vp, _i64, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _f32, _int, _u64, _vp, _vp, _vp], True),
+        "gp_seed_positions": (_int, [_int, _vp, _i64, _i64, _vp, _vp, _vp], False),
+        "gp_batch_positions": (_int, [_int, _vp, _i64, _vp, _i64, _vp, _vp, _vp], False),
+        "gp_random_prop_coo": (_int, [_int, _vp, _i64, _i32, _vp, _vp, _i64, _f32, _int, _u64, _vp, _vp, _vp], True),
+        "gp_random_prop_coo_backward": (_int, [_int, _vp, _i64, _i32, _vp, _vp, _i64, _f32, _int, _u64, _vp, _vp, _vp], False),
+        "gp_random_prop_rows_backward": (_int, [_int, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _f32, _int, _u64, _vp, _vp, _i64, _vp],
+                                         False),
+        "gp_embedding_bag": (_int, _bag, False),
+        "gp_embedding_bag_backward": (_int, _bag, False),
+        "gp_random_prop_rows_multi": (_int, [_int, _vp, _i64, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _f32, _int, _u64, _vp, _i64,
+                                             _vp, _vp], False),
+        "gp_random_prop_coo_multi": (_int, [_int, _vp, _i64, _i32, _vp, _vp, _i64, _i32, _f32, _int, _u64, _vp, _vp, _vp], False),
+        "gp_random_prop_coo_multi_backward": (_int, [_int, _vp, _i64, _i32, _vp, _vp, _i64, _i32, _f32, _int, _u64, _vp, _vp, _vp], False),
+        "gp_random_prop_rows_multi_backward": (_int, [_int, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _f32, _int, _u64, _vp, _i64,
+                                                      _vp, _i64, _vp], False),
+        "gp_grand_loss": (_int, _loss + [_vp, _vp, _vp, _vp], False),
+        "gp_grand_loss_backward": (_int, _loss + [_vp, _vp, _vp, _vp, _vp, _vp], False),
+        "gp_mlp_block_forward": (_int, [_int, _vp, _i32, _i64, _i32, _i32, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _f32, _f32,
+                                        _f32, _u64, _i32, _vp, _vp, _vp, _vp, _vp, _vp], False),
+        "gp_mlp_block_backward": (_int, [_int, _vp, _i32, _i64, _i32, _i32, _vp, _int, _vp, _f32, _u64, _i32, _vp,
+                                         _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], False),
+        "gp_clip_adam_step": (_int, [_int, ctypes.POINTER(GpOptimTensor), _i32, _int, _f32, _f32, _f64, _f64, _f32, _f32, _f32, _f32,
                                      _vp, _vp, _vp], False),
+        "gp_propagate_features": (_int, [_vp, _vp, _i32, _vp, _int, _int, _f64, _vp, _vp], True),
+        "gp_internal_graph_csr": (_int, [_vp, _vpp, _vpp, _u32p, _vp], False),
+        # h_acsr, h_node_pos and h_unit_info are host arrays declared c_void_p, the three exceptions to the convention: the one
+        # caller (api.Graph) passes .ctypes.data_as(c_void_p), and a typed pointer would change that call site
+        "gp_internal_graph_acsr": (_int, [_vp, _vp, _vp, _vp, _i64p, _intp, _u32p], False),
+        "gp_internal_diag_counters": (_int, [_vp, _i64p, _int], True),
+        "gp_internal_multi_plan": (_int, [_i64, _int, _int, _i64, _int, _int, _i64p, _int], False),
+        "gp_internal_set_error": (None, [_int, _str, _str], False),
+        "gp_internal_create_ms": (None, [_f64p], False),
+        "gp_internal_warm_device": (_int, [_int], False),
+    },
+    "grandplus_eval.h": {
+        "gp_eval_head": (_int, [_int, _vp, _i64, _i32, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp], False),
+        "gp_eval_reduce": (_int, [_int, _vp, _vp, _i64, _vp, _vp, _vp, _vp], False),
+    },
+    # each takes the arguments of its atomic counterpart, then the sorted order (entry numbers, sorted keys[, sorted rows],
+    # their length) and the scratch
+    "grandplus_scatter.h": {
+        "gp_random_prop_rows_backward_det": (_int, [_int, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _f32, _int, _u64, _vp, _i64,
+                                                    _vp, _i64, _vp, _vp, _i64, _vp, _vp], False),
+        "gp_embedding_bag_backward_det": (_int, _bag[:-1] + [_vp, _vp, _vp, _i64, _vp, _vp], False),
+    },
+    "grandplus_infer.h": {
+        "gp_mlp_infer_block": (_int, [_int, _vp, _i64, _i32, _i32] + _block + [_vp, _vp, _vp], False),
+    },
+    "grandplus_infer_chain.h": {
+        "gp_mlp_infer_chain2": (_int, [_int, _vp, _i64, _i32, _i32, _i32] + _block + _block + [_vp, _vp, _vp], False),
+    },
+    # the backward takes the forward's arguments with grad_out for the table and dW for the output, and no counter
+    "grandplus_mag.h": {
+        "gp_mag_prop_rows": (_int, [_int, _vp] + _mag + [_vp, _vp, _vp], False),
+        "gp_mag_prop_rows_backward": (_int, [_int, _vp] + _mag + [_vp, _vp], False),
+    },
+    "grandplus_order.h": {
+        "gp_internal_row_order": (_int, [_vp, _u32p, _i64, _i64p, _intp, _u32p], False),
+        "gp_internal_wg_log": (_int, [_vp, _i64p, _int], False),
+    },
+    # gp_clip_adam_step_dev is gp_clip_adam_step with two device pointers where that takes step_size and rsqrt_bc2
+    "grandplus_step.h": {
+        "gp_step_advance": (_int, [_int, _vp, _u64, _f64, _f64, _i32, _f64p, _f64p, _f64p, _vp], False),
+        "gp_step_masks": (_int, [_int, _vp, ctypes.POINTER(GpStepSegment), _i32, _vp], False),
+        "gp_clip_adam_step_dev": (_int, [_int, ctypes.POINTER(GpOptimTensor), _i32, _int, _f32, _f32, _f64, _f64, _f32, _f32, _vp, _vp,
+                                         _vp, _vp, _vp], False),
+    },
 }
-STEP_EXPORTS = tuple(_STEP_SIGNATURES)
 
 _LIB = None
 
@@ -289,14 +276,13 @@ def lib():
     except ImportError:
         pass
     L = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes, required) in {**_SIGNATURES, **_EVAL_SIGNATURES, **_SCATTER_SIGNATURES, **_INFER_SIGNATURES,
-                                              **_MAG_SIGNATURES, **_ORDER_SIGNATURES, **_CHAIN_SIGNATURES,
-                                              **_STEP_SIGNATURES}.items():
-        if not required and not hasattr(L, name):
-            setattr(L, name, _missing(name))
-            continue
-        f = getattr(L, name)
-        f.restype, f.argtypes = restype, argtypes
+    for entries in ABI.values():
+        for name, (restype, argtypes, required) in entries.items():
+            if not required and not hasattr(L, name):
+                setattr(L, name, _missing(name))
+                continue
+            f = getattr(L, name)
+            f.restype, f.argtypes = restype, argtypes
     # (ABI 3 is accepted only for an older build named explicitly through GRANDPLUS_LIB for an A/B run: its gp_stats is a prefix of
     #  this one, and the entry points it lacks raise a clear error where they are called -- _missing)
     abi = L.gp_abi_version()

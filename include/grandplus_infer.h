@@ -3,7 +3,7 @@
  *
  * Part of the ABI that grandplus.h describes (GP_ABI_VERSION, the status codes and the GP_MLP_* flags are defined
  * there): grandplus.h includes this file, so callers include grandplus.h alone.  The ctypes binding declares the entry
- * point in _native._INFER_SIGNATURES, and tests/test_host_infer.py holds that table against this file type by type.
+ * point under this file's name in _native.ABI, and tests/test_host_abi.py holds that table against this file type by type.
  */
 #ifndef GRANDPLUS_INFER_H
 #define GRANDPLUS_INFER_H

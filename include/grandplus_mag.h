@@ -2,10 +2,9 @@
  * grandplus_mag.h -- MAG's fused front end of the C ABI: resident GFPush rows -> S augmented embeddings, forward and
  * backward (implemented by grand_plus_amd/csrc/mag_prop.hip).
  *
- * Part of the ABI that grandplus.h describes (GP_ABI_VERSION, GP_MAX_K, GP_MAX_SAMPLES and the status codes are defined
- * there): grandplus.h includes this file, so callers include grandplus.h alone.  The ctypes binding declares these
- * entry points in _native._MAG_SIGNATURES, and tests/test_host_mag_rows.py holds that table against this file type by
- * type.
+ * Part of the ABI that grandplus.h describes (GP_ABI_VERSION, GP_MAX_K and the status codes are defined there):
+ * grandplus.h includes this file, so callers include grandplus.h alone.  The ctypes binding declares these entry points
+ * under this file's name in _native.ABI, and tests/test_host_abi.py holds that table against this file type by type.
  */
 #ifndef GRANDPLUS_MAG_H
 #define GRANDPLUS_MAG_H

@@ -2,8 +2,8 @@
  * grandplus_order.h -- the internal entry points behind option "row_order" (implemented by grand_plus_amd/csrc/gfpush.hip).
  *
  * Part of the ABI that grandplus.h describes (gp_graph and the status codes are defined there): grandplus.h includes this
- * file, so callers include grandplus.h alone.  The ctypes binding declares the entry points in _native._ORDER_SIGNATURES,
- * and tests/test_host_row_order.py holds that table against this file type by type.
+ * file, so callers include grandplus.h alone.  The ctypes binding declares the entry points under this file's name in
+ * _native.ABI, and tests/test_host_abi.py holds that table against this file type by type.
  */
 #ifndef GRANDPLUS_ORDER_H
 #define GRANDPLUS_ORDER_H

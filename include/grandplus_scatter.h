@@ -3,8 +3,8 @@
  * grand_plus_amd/csrc/scatter_det.hip).
  *
  * Part of the ABI that grandplus.h describes (GP_ABI_VERSION and the status codes are defined there): grandplus.h
- * includes this file, so callers include grandplus.h alone.  The ctypes binding declares these entry points in
- * _native._SCATTER_SIGNATURES, and tests/test_host_deterministic.py holds that table against this file type by type.
+ * includes this file, so callers include grandplus.h alone.  The ctypes binding declares these entry points under this
+ * file's name in _native.ABI, and tests/test_host_abi.py holds that table against this file type by type.
  */
 #ifndef GRANDPLUS_SCATTER_H
 #define GRANDPLUS_SCATTER_H

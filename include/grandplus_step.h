@@ -4,8 +4,8 @@
  *
  * Part of the ABI that grandplus.h describes (GP_ABI_VERSION, the status codes, gp_optim_tensor and the GP_OPTIM_* flags
  * are defined there): grandplus.h includes this file, so callers include grandplus.h alone.  The ctypes binding declares
- * the entry points in _native._STEP_SIGNATURES and mirrors the two structs, and tests/test_host_step.py holds both
- * against this file type by type.
+ * the entry points under this file's name in _native.ABI and mirrors the two structs, and tests/test_host_abi.py holds
+ * both against this file type by type.
  */
 #ifndef GRANDPLUS_STEP_H
 #define GRANDPLUS_STEP_H

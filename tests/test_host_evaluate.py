@@ -1,8 +1,6 @@
 """CPU tests of the evaluation path: eval_head / eval_reduce / valid / predict refuse what they cannot run
-before any launch (there is no CPU fallback), the ctypes mirrors follow the header, and the C entry points return their
-error codes before any GPU work."""
+before any launch (there is no CPU fallback), and the C entry points return their error codes before any GPU work."""
 import ctypes
-import os
 import re
 
 import pytest
@@ -10,7 +8,6 @@ import torch
 
 from grand_plus_amd import _native
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 P = ctypes.c_void_p(16)
 
 
@@ -101,58 +98,6 @@ def test_valid_and_predict_refuse_before_any_launch(monkeypatch):
     with pytest.raises(TypeError, match="no CPU fallback"):
         predict(None, X, model, [0, 1], y, "ppr", 2)
     assert model.training                                            # nothing touched the model
-
-
-def _eval_header():
-    text = open(os.path.join(ROOT, "include", "grandplus_eval.h")).read()
-    return re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-
-
-def test_native_mirrors_follow_the_header():
-    text = open(os.path.join(ROOT, "include", "grandplus_eval.h")).read()
-    m = re.search(r"#define GP_EVAL_WORKSPACE_BYTES \((\d+) \* (\d+)\)", text)
-    assert m and int(m.group(1)) * int(m.group(2)) == _native.eval_workspace_bytes() == 1024 * (8 + 4 * 8)
-    macro = {k: int(v) for k, v in re.findall(r"#define (GP_EVAL_[A-Z]+) (\d+)\n", text)}
-    assert macro == {"GP_EVAL_WRONG": _native.GP_EVAL_WRONG, "GP_EVAL_CORRECT": _native.GP_EVAL_CORRECT,
-                     "GP_EVAL_IGNORED": _native.GP_EVAL_IGNORED, "GP_EVAL_BAD": _native.GP_EVAL_BAD}
-    main = open(os.path.join(ROOT, "include", "grandplus.h")).read()
-    assert '#include "grandplus_eval.h"' in main and "#define GP_ABI_VERSION 4\n" in main   # one ABI, still version 4
-
-
-_CTYPES = {("int", 0): (ctypes.c_int,), ("int32_t", 0): (ctypes.c_int32,), ("int64_t", 0): (ctypes.c_int64,),
-           ("void", 1): (ctypes.c_void_p,),
-           # a device pointer travels as an integer (the convention stated above _native._SIGNATURES)
-           ("float", 1): (ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)),
-           ("int32_t", 1): (ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32)),
-           ("int64_t", 1): (ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)),
-           ("uint8_t", 1): (ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint8))}
-
-
-def test_eval_signatures_match_the_header_type_by_type():
-    """The evaluation entry points of the binding against the prototypes of grandplus_eval.h: the names, the count, each
-    type in its position; the built library exports both and the loaded one carries their argtypes."""
-    def ctype(decl):
-        m = re.fullmatch(r"(?:const\s+)?(\w+)\s*(\**)", decl.strip())
-        assert m, decl
-        return m.group(1), len(m.group(2))
-
-    protos = {}
-    for ret, name, params in re.findall(r"\b((?:const\s+)?\w+\s*\**)\s*\b(gp_[a-z_0-9]+)\s*\(([^)]*)\)\s*;", _eval_header()):
-        assert name not in protos
-        protos[name] = (ctype(ret), [ctype(re.sub(r"\w+$", "", q.strip())) for q in params.split(",")])
-    assert sorted(protos) == ["gp_eval_head", "gp_eval_reduce"] == sorted(_native._EVAL_SIGNATURES) == sorted(_native.EVAL_EXPORTS)
-    assert sorted(set(re.findall(r"\b(gp_[a-z_0-9]+)\s*\(", _eval_header()))) == sorted(protos)
-    assert not set(_native._EVAL_SIGNATURES) & set(_native._SIGNATURES)
-    built = ctypes.CDLL(_native.LIB_PATH)
-    for name, (ret, params) in protos.items():
-        restype, argtypes, required = _native._EVAL_SIGNATURES[name]
-        assert required is False
-        assert restype in _CTYPES[ret], f"{name}: restype {restype} for {ret}"
-        assert len(argtypes) == len(params), f"{name}: {len(argtypes)} argtypes for {len(params)} parameters"
-        for i, (got, want) in enumerate(zip(argtypes, params)):
-            assert got in _CTYPES[want], f"{name}: argument {i} is {got} for {want}"
-        assert hasattr(built, name), f"libgrandplus.so does not export {name}"
-        assert getattr(_native.lib(), name).argtypes == argtypes
 
 
 def _head(logits=P, n_z=4, C=3, labels=P, n_labels=4, n=4, off=0, cap=4, nll=P, pred=P, flag=P, rows=None, lrows=None):

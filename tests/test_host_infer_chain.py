@@ -1,8 +1,7 @@
-"""CPU tests of the fused inference path: the binding follows grandplus_infer_chain.h type by type, the C
-entry point returns its error codes before any GPU work, `infer(fused=True)` and `predict(fused=True)` refuse what they
-cannot run before any launch, and fused=False reaches none of the new code."""
+"""CPU tests of the fused inference path: the C entry point returns its error codes before any GPU work,
+`infer(fused=True)` and `predict(fused=True)` refuse what they cannot run before any launch, and fused=False reaches
+none of the new code."""
 import ctypes
-import os
 import re
 
 import pytest
@@ -11,74 +10,7 @@ import torch
 import infer_chain_cases as cc
 from grand_plus_amd import _native
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 P = ctypes.c_void_p(16)
-
-
-def _header():
-    text = open(os.path.join(ROOT, "include", "grandplus_infer_chain.h")).read()
-    return text, re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-
-
-def test_the_main_header_includes_the_chain_header_and_keeps_abi_4():
-    main = open(os.path.join(ROOT, "include", "grandplus.h")).read()
-    assert '#include "grandplus_infer_chain.h"' in main and "#define GP_ABI_VERSION 4\n" in main
-    import __graft_entry__ as entry
-    assert os.path.join(ROOT, "include", "grandplus_infer_chain.h") in entry.lib_sources()
-    assert "mlp_chain.hip" in entry.LIB_UNITS
-    assert os.path.join(entry.CSRC, "mlp_chain.hip") in entry.lib_sources()
-
-
-def test_the_limits_mirror_the_header():
-    text, _ = _header()
-    assert "#define GP_MLP_CHAIN_MAX_HIDDEN 1024\n" in text and "#define GP_MLP_CHAIN_MAX_OUT 64\n" in text
-    assert (_native.GP_MLP_CHAIN_MAX_HIDDEN, _native.GP_MLP_CHAIN_MAX_OUT) == (1024, 64)
-
-
-@pytest.mark.parametrize("n_rows,f_in,f_hidden", [(0, 1, 1), (1, 1, 1), (2, 1, 2), (3, 7, 33), (10000, 100, 1024),
-                                                  (2449029, 100, 1024), (2 ** 40, 2 ** 30, 1024)])
-def test_workspace_mirror_equals_the_macro(n_rows, f_in, f_hidden):
-    text, _ = _header()
-    m = re.search(r"#define GP_MLP_INFER_CHAIN_WORKSPACE_BYTES\(n_rows, f_in, f_hidden\) (.*)\n", text)
-    assert m
-    expr = m.group(1).replace("(int64_t)", "").replace("/", "//")
-    want = eval(expr, {"n_rows": n_rows, "f_in": f_in, "f_hidden": f_hidden})
-    assert _native.mlp_infer_chain_workspace_bytes(n_rows, f_in, f_hidden) == want
-    assert want % 16 == 0 and 0 <= want - 4 * (n_rows + 2 * f_in + 2 * f_hidden) < 16
-
-
-_CTYPES = {("int", 0): (ctypes.c_int,), ("int32_t", 0): (ctypes.c_int32,), ("int64_t", 0): (ctypes.c_int64,),
-           ("float", 0): (ctypes.c_float,), ("void", 1): (ctypes.c_void_p,),
-           # a device pointer travels as an integer (the convention stated above _native._SIGNATURES)
-           ("float", 1): (ctypes.c_void_p,)}
-
-
-def test_chain_signatures_match_the_header_type_by_type():
-    def ctype(decl):
-        m = re.fullmatch(r"(?:const\s+)?(\w+)\s*(\**)", decl.strip())
-        assert m, decl
-        return m.group(1), len(m.group(2))
-
-    _, code = _header()
-    protos = {}
-    for ret, name, params in re.findall(r"\b((?:const\s+)?\w+\s*\**)\s*\b(gp_[a-z_0-9]+)\s*\(([^)]*)\)\s*;", code):
-        assert name not in protos
-        protos[name] = (ctype(ret), [ctype(re.sub(r"\w+$", "", q.strip())) for q in params.split(",")])
-    assert sorted(protos) == ["gp_mlp_infer_chain2"] == sorted(_native._CHAIN_SIGNATURES) == sorted(_native.CHAIN_EXPORTS)
-    assert sorted(set(re.findall(r"\b(gp_[a-z_0-9]+)\s*\(", code))) == sorted(protos)
-    for other in (_native._SIGNATURES, _native._EVAL_SIGNATURES, _native._SCATTER_SIGNATURES, _native._INFER_SIGNATURES,
-                  _native._MAG_SIGNATURES, _native._ORDER_SIGNATURES):
-        assert not set(_native._CHAIN_SIGNATURES) & set(other)
-    built = ctypes.CDLL(_native.LIB_PATH)
-    for name, (ret, params) in protos.items():
-        restype, argtypes, required = _native._CHAIN_SIGNATURES[name]
-        assert required is False
-        assert restype in _CTYPES[ret], f"{name}: restype {restype} for {ret}"
-        assert len(argtypes) == len(params) == 25, f"{name}: {len(argtypes)} argtypes for {len(params)} parameters"
-        for i, (got, want) in enumerate(zip(argtypes, params)):
-            assert got in _CTYPES[want], f"{name}: argument {i} is {got} for {want}"
-        assert hasattr(built, name), f"libgrandplus.so does not export {name}"
-        assert getattr(_native.lib(), name).argtypes == argtypes
 
 
 def _call(x=P, n=4, f_in=3, f_hidden=5, f_out=2, w1=P, b1=P, flags1=0, g1=P, be1=P, rm1=P, rv1=P, eps1=1e-5,

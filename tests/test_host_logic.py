@@ -1,5 +1,5 @@
-"""CPU tests of the host logic: C-ABI exports, error behaviour without a GPU, caller-side
-recipes, the tie-aware comparator, the synthetic generator's committed checksums."""
+"""CPU tests of the host logic: error behaviour without a GPU, caller-side recipes, the tie-aware
+comparator, the synthetic generator's committed checksums.  (The C ABI's binding: tests/test_host_abi.py.)"""
 import ctypes
 import json
 import os
@@ -12,79 +12,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")
 
 
-def _declared_symbols():
-    text = open(os.path.join(ROOT, "include", "grandplus.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(gp_[a-z_0-9]+)\s*\(", text)))
-
-
-def test_library_exports_every_declared_symbol():
-    from grand_plus_amd import _native
-    declared = _declared_symbols()
-    assert declared == sorted(_native.EXPORTS)
-    lib = ctypes.CDLL(_native.LIB_PATH)
-    for name in declared:
-        assert hasattr(lib, name), f"libgrandplus.so does not export {name}"
-    assert _native.lib().gp_abi_version() == 4
-    assert _native.lib().gp_strerror(2) == b"invalid CSR"
-    for name in _native.EXPORTS:                      # declared on the loaded library, or the stub of a name an older build lacks
-        f = getattr(_native.lib(), name)
-        assert f.argtypes is not None if isinstance(f, ctypes._CFuncPtr) else f.__name__ == "missing", name
-
-
-_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint32_t": ctypes.c_uint32,
-            "uint64_t": ctypes.c_uint64, "float": ctypes.c_float, "double": ctypes.c_double}
-
-
-def _declared_prototypes():
-    """name -> (return type, [parameter types]) of every gp_* prototype, each type as (base type without const, number of *)."""
-    text = open(os.path.join(ROOT, "include", "grandplus.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-
-    def ctype(decl):
-        m = re.fullmatch(r"(?:const\s+)?(\w+)\s*(\**)", decl.strip())
-        assert m, decl
-        return m.group(1), len(m.group(2))
-
-    protos = {}
-    for ret, name, params in re.findall(r"\b((?:const\s+)?\w+\s*\**)\s*\b(gp_[a-z_0-9]+)\s*\(([^)]*)\)\s*;", text):
-        params = [] if params.strip() == "void" else [re.sub(r"\w+$", "", p.strip()) for p in params.split(",")]
-        assert name not in protos
-        protos[name] = (ctype(ret), [ctype(p) for p in params])
-    return protos
-
-
-def _allowed_ctypes(base, stars):
-    """The ctypes types the binding may declare for a C type (the pointer convention stated above _native._SIGNATURES)."""
-    from grand_plus_amd import _native
-    if stars == 0:
-        return (None,) if base == "void" else (_SCALARS[base],)
-    if (base, stars) == ("char", 1):
-        return (ctypes.c_char_p,)
-    if stars == 2:                                    # gp_graph**, const int**: an array of pointers held as integers
-        return (ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p))
-    assert stars == 1, (base, stars)
-    if base in ("void", "gp_graph"):                  # untyped device memory, a stream, the opaque handle
-        return (ctypes.c_void_p,)
-    pointee = {"gp_stats": _native.GpStats, "gp_optim_tensor": _native.GpOptimTensor, "uint8_t": ctypes.c_uint8}.get(base) or _SCALARS[base]
-    return (ctypes.c_void_p, ctypes.POINTER(pointee))
-
-
-def test_binding_signatures_match_header():
-    """Every entry of the binding's table against the header's prototype: the count, and each type in its position."""
-    from grand_plus_amd import _native
-    protos = _declared_prototypes()
-    assert len(protos) == 42 and sorted(protos) == _declared_symbols()
-    assert sorted(_native._SIGNATURES) == sorted(protos)
-    for name, (ret, params) in protos.items():
-        restype, argtypes, required = _native._SIGNATURES[name]
-        assert isinstance(required, bool)
-        assert restype in _allowed_ctypes(*ret), f"{name}: restype {restype} for {ret}"
-        assert len(argtypes) == len(params), f"{name}: {len(argtypes)} argtypes for {len(params)} parameters"
-        for i, (got, want) in enumerate(zip(argtypes, params)):
-            assert got in _allowed_ctypes(*want), f"{name}: argument {i} is {got} for {want}"
-
-
 def test_importing_the_package_loads_neither_torch_nor_the_library():
     import subprocess
     import sys
@@ -94,18 +21,6 @@ def test_importing_the_package_loads_neither_torch_nor_the_library():
     r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stderr
     assert r.stdout.split() == ["False", "None"]
-
-
-def test_stats_struct_matches_header():
-    from grand_plus_amd import _native
-    text = open(os.path.join(ROOT, "include", "grandplus.h")).read()
-    body = text[text.index("typedef struct gp_stats {"):text.index("} gp_stats;")]
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    names = []
-    for decl in re.findall(r"(?:int64_t|int32_t|double|float)\s+([^;]+);", body):
-        for item in decl.split(","):
-            names.append(re.sub(r"\[.*\]", "", item).strip())
-    assert names == [n for n, _ in _native.GpStats._fields_]
 
 
 def test_pybind_module_surface_is_the_references():

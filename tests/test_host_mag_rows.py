@@ -1,7 +1,7 @@
-"""CPU tests of MAG's fused front end: the binding follows grandplus_mag.h type by type, the C entry points
-return their error codes before any GPU work, `mag_prop_rows` / `valid_mag` / `predict_mag` refuse what they cannot run
-before any launch (there is no CPU fallback), `mag_slot_seed` is the header's formula, the order contract's own float32
-rounding stays inside the tolerance of every case, and the valid_mag inputs are decided in float64."""
+"""CPU tests of MAG's fused front end: the C entry points return their error codes before any GPU work,
+`mag_prop_rows` / `valid_mag` / `predict_mag` refuse what they cannot run before any launch (there is no CPU fallback),
+`mag_slot_seed` is the header's formula, the order contract's own float32 rounding stays inside the tolerance of every
+case, and the valid_mag inputs are decided in float64."""
 import ctypes
 import os
 import re
@@ -9,6 +9,7 @@ import re
 import pytest
 import torch
 
+import abi_header
 import evaluate_cases as ec
 import mag_cases as mc
 from grand_plus_amd import _common, _native
@@ -18,11 +19,6 @@ P = ctypes.c_void_p(16)
 NAMES = ["gp_mag_prop_rows", "gp_mag_prop_rows_backward"]
 
 
-def _header():
-    text = open(os.path.join(ROOT, "include", "grandplus_mag.h")).read()
-    return text, re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-
-
 def test_the_public_names_are_importable_from_the_package():
     import grand_plus_amd
     from grand_plus_amd import mag_prop_rows, predict_mag, valid_mag
@@ -30,50 +26,6 @@ def test_the_public_names_are_importable_from_the_package():
         assert f.__module__ == "grand_plus_amd.mag" and f.__name__ not in grand_plus_amd.__all__
     from grand_plus_amd.mlp import MagMLP
     assert callable(MagMLP.emb_rows)
-
-
-def test_the_main_header_includes_the_mag_header_and_keeps_abi_4():
-    main = open(os.path.join(ROOT, "include", "grandplus.h")).read()
-    assert '#include "grandplus_mag.h"' in main and "#define GP_ABI_VERSION 4\n" in main
-    import __graft_entry__ as entry
-    assert os.path.join(ROOT, "include", "grandplus_mag.h") in entry.lib_sources()
-    assert "mag_prop.hip" in entry.LIB_UNITS
-    assert _native.lib().gp_abi_version() == 4
-
-
-_CTYPES = {("int", 0): ctypes.c_int, ("int32_t", 0): ctypes.c_int32, ("int64_t", 0): ctypes.c_int64, ("uint64_t", 0): ctypes.c_uint64,
-           ("float", 0): ctypes.c_float,
-           # a device pointer travels as an integer (the convention stated above _native._SIGNATURES)
-           ("void", 1): ctypes.c_void_p, ("float", 1): ctypes.c_void_p, ("double", 1): ctypes.c_void_p,
-           ("int32_t", 1): ctypes.c_void_p, ("int64_t", 1): ctypes.c_void_p, ("uint8_t", 1): ctypes.c_void_p}
-
-
-def test_mag_signatures_match_the_header_type_by_type():
-    def ctype(decl):
-        m = re.fullmatch(r"(?:const\s+)?(\w+)\s*(\**)", decl.strip())
-        assert m, decl
-        return m.group(1), len(m.group(2))
-
-    _, code = _header()
-    protos = {}
-    for ret, name, params in re.findall(r"\b((?:const\s+)?\w+\s*\**)\s*\b(gp_[a-z_0-9]+)\s*\(([^)]*)\)\s*;", code):
-        assert name not in protos
-        protos[name] = (ctype(ret), [ctype(re.sub(r"\w+$", "", q.strip())) for q in params.split(",")])
-    assert sorted(protos) == NAMES == sorted(_native._MAG_SIGNATURES) == sorted(_native.MAG_EXPORTS)
-    assert sorted(set(re.findall(r"\b(gp_[a-z_0-9]+)\s*\(", code))) == sorted(protos)
-    for other in (_native._SIGNATURES, _native._EVAL_SIGNATURES, _native._SCATTER_SIGNATURES, _native._INFER_SIGNATURES):
-        assert not set(_native._MAG_SIGNATURES) & set(other)
-    built = ctypes.CDLL(_native.LIB_PATH)
-    for name, n_args in zip(NAMES, (25, 24)):
-        ret, params = protos[name]
-        restype, argtypes, required = _native._MAG_SIGNATURES[name]
-        assert required is False
-        assert restype is _CTYPES[ret], f"{name}: restype {restype} for {ret}"
-        assert len(argtypes) == len(params) == n_args, f"{name}: {len(argtypes)} argtypes for {len(params)} parameters"
-        for i, (got, want) in enumerate(zip(argtypes, params)):
-            assert got is _CTYPES[want], f"{name}: argument {i} is {got} for {want}"
-        assert hasattr(built, name), f"libgrandplus.so does not export {name}"
-        assert getattr(_native.lib(), name).argtypes == argtypes
 
 
 def _call(name, w=P, V=5, H=4, ip=P, ix=P, dt=P, N=3, col=P, val=P, filled=P, S_rows=2, K=3, rows=P, B=2, S=1, p_node=0.5, p_in=0.0,
@@ -106,7 +58,7 @@ def test_the_entries_return_their_error_codes_before_any_gpu_work(name):
 
 @pytest.mark.parametrize("seed,s,e", [(0, 0, 0), (1, 0, 0), (0x5EED0FACADE, 3, 191), (2 ** 64 - 1, 15, 2 ** 31 + 5), (123456789, 1, 1023)])
 def test_mag_slot_seed_is_the_formula_of_the_header(seed, s, e):
-    text, _ = _header()
+    text, _ = abi_header.read("grandplus_mag.h")
     m = re.search(r"GP_MAG_SLOT_SEED\(seed, s, e\) = mix\(gp_sample_seed\(seed, s\) \^ \(\(e \+ 1\) \* (0x[0-9A-F]{16})\)\)", text)
     assert m, "the header states the formula"
     mul = int(m.group(1), 16)

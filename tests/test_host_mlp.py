@@ -51,12 +51,6 @@ def test_entries_check_sizes_flags_and_pointers_before_the_device():
     assert _bwd(gw=P, a=NULL) == N                                    # the weight gradient needs the saved input
 
 
-def test_workspace_sizes_mirror_the_header():
-    assert _native.mlp_saved_floats(2, 250, 602) == 2 * 250 + 4 * 2 * 602
-    assert _native.mlp_forward_workspace_bytes(3) == 3 * 2097152
-    assert _native.mlp_backward_workspace_bytes(2, 250, 602) == 4 * (2 * 250 * 602 + 524288)
-
-
 def _mix(x):
     x = (x + 0x9E3779B97F4A7C15) & M64
     x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & M64

@@ -1,13 +1,6 @@
 """CPU tests of option "row_order" (DESIGN §8): the cost and class definition that row_cost_kernel implements, pinned on a
-hand-made graph through its numpy restatement (grand_plus_amd/row_cost.py), and the binding of the two internal entry points
-against include/grandplus_order.h."""
-import ctypes
-import os
-import re
-
+hand-made graph through its numpy restatement (grand_plus_amd/row_cost.py)."""
 import numpy as np
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # 8 nodes; degrees 3, 1, 4, 7, 0 (dangling), 8, 1, 2
 ROWS = [[1, 2, 3], [0], [0, 1, 3, 4], [0, 1, 2, 4, 5, 6, 7], [], [0, 1, 2, 3, 4, 5, 6, 7], [4], [3, 5]]
@@ -53,28 +46,3 @@ def test_a_seed_that_fails_its_own_push_test_costs_nothing_and_the_column_cap_sc
     # two columns read of seed 3's seven: node 0 fails, node 1 pushes 1 edge -> 7 + floor(7 * 1 / 2)
     assert row_costs(INDPTR, INDICES, [3], 0.05, deg_sat=1 << 20, cols=2).tolist() == [10]
     assert cost_class([0, 1, 2, 3, 2 ** 31 - 2, 2 ** 31 - 1, 2 ** 40]).tolist() == [0, 1, 1, 2, 30, 31, 31]
-
-
-def test_binding_matches_the_order_header():
-    from grand_plus_amd import _native
-    import __graft_entry__ as entry
-    text = open(os.path.join(ROOT, "include", "grandplus_order.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    protos = dict((name, [p.strip() for p in params.split(",")])
-                  for name, params in re.findall(r"\bint\s+(gp_[a-z_0-9]+)\s*\(([^)]*)\)\s*;", text))
-    assert sorted(protos) == sorted(_native.ORDER_EXPORTS) == ["gp_internal_row_order", "gp_internal_wg_log"]
-    scalars = {"int": ctypes.c_int, "int64_t": ctypes.c_int64}
-    pointers = {"gp_graph*": ctypes.c_void_p, "uint32_t*": ctypes.POINTER(ctypes.c_uint32), "int64_t*": ctypes.POINTER(ctypes.c_int64),
-                "int*": ctypes.POINTER(ctypes.c_int)}
-    for name, params in protos.items():
-        restype, argtypes, required = _native._ORDER_SIGNATURES[name]
-        assert restype is ctypes.c_int and required is False and len(argtypes) == len(params)
-        for got, decl in zip(argtypes, params):
-            ctype = re.sub(r"\s*\w+$", "", decl).replace(" ", "")
-            assert got is (pointers[ctype] if ctype.endswith("*") else scalars[ctype]), (name, decl)
-    main = open(os.path.join(ROOT, "include", "grandplus.h")).read()
-    assert '#include "grandplus_order.h"' in main and '"row_order"' in main
-    assert os.path.join(ROOT, "include", "grandplus_order.h") in entry.lib_sources()
-    lib = ctypes.CDLL(_native.LIB_PATH)
-    for name in protos:
-        assert hasattr(lib, name), f"libgrandplus.so does not export {name}"

@@ -1,116 +1,20 @@
-"""CPU tests of the device-resident step state: the binding follows grandplus_step.h type by type, the two
-structs have the header's layout, the seed and weight mirrors follow their formulas, the C entry points return their
-error codes before any GPU work, and ClipAdam(capturable=True) and TrainStep refuse what they cannot run before any
-device call."""
+"""CPU tests of the device-resident step state: the seed and weight mirrors follow their formulas, the C
+entry points return their error codes before any GPU work, and ClipAdam(capturable=True) and TrainStep refuse what they
+cannot run before any device call."""
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import abi_header
 from grand_plus_amd import _common, _native
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 P = ctypes.c_void_p(16)
 M = 2 ** 64 - 1
-
-
-def _header():
-    text = open(os.path.join(ROOT, "include", "grandplus_step.h")).read()
-    return text, re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-
-
-def test_the_main_header_includes_the_step_header_and_keeps_abi_4():
-    main = open(os.path.join(ROOT, "include", "grandplus.h")).read()
-    assert '#include "grandplus_step.h"' in main and "#define GP_ABI_VERSION 4\n" in main
-    import __graft_entry__ as entry
-    assert os.path.join(ROOT, "include", "grandplus_step.h") in entry.lib_sources()
-    assert "step_state.hip" in entry.LIB_UNITS
-    assert os.path.join(entry.CSRC, "step_state.hip") in entry.lib_sources()
-
-
-def test_the_limits_mirror_the_header():
-    text, _ = _header()
-    for name, value in (("GP_STEP_MAX_GROUPS", 8), ("GP_STEP_MAX_LAYERS", 8), ("GP_STEP_SEG_ROWS", 0), ("GP_STEP_SEG_LAYER", 1)):
-        assert f"#define {name} {value}\n" in text
-        assert getattr(_native, name) == value
-
-
-_FIELD = {"uint64_t": ctypes.c_uint64, "int64_t": ctypes.c_int64, "int32_t": ctypes.c_int32, "float": ctypes.c_float}
-
-
-@pytest.mark.parametrize("struct,mirror", [("gp_step_state", "GpStepState"), ("gp_step_segment", "GpStepSegment")])
-def test_the_struct_mirrors_have_the_headers_fields_size_and_offsets(struct, mirror, tmp_path):
-    """Field by field against the header's text, then sizeof and every offsetof as the C compiler lays the struct out."""
-    _, code = _header()
-    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (struct, struct), code, flags=re.S).group(1)
-    cls = getattr(_native, mirror)
-    fields = []
-    for decl in filter(None, (d.strip() for d in body.split(";"))):
-        m = re.fullmatch(r"(?:const\s+)?(\w+)\s*(\*?)\s*(\w+)(?:\[(\w+)\])?", decl)
-        assert m, decl
-        base, star, name, count = m.groups()
-        want = ctypes.c_void_p if star else _FIELD[base]           # a device pointer travels as an integer
-        if count:
-            want = want * getattr(_native, count)
-        fields.append((name, want))
-    assert [(n, t) for n, t in cls._fields_] == fields
-    names = [n for n, _ in fields]
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "grandplus.h"\nint main(void) {\n'
-                   f'  printf("%zu", sizeof({struct}));\n' +
-                   "".join(f'  printf(" %zu", offsetof({struct}, {n}));\n' for n in names) + "  return 0;\n}\n")
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I" + os.path.join(ROOT, "include"), "-o", str(exe), str(src)], check=True)
-    got = [int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    assert got == [ctypes.sizeof(cls)] + [getattr(cls, n).offset for n in names]
-    if struct == "gp_step_state":
-        assert got == [88, 0, 8, 16, 20, 52]
-
-
-_CTYPES = {("int", 0): (ctypes.c_int,), ("int32_t", 0): (ctypes.c_int32,), ("uint64_t", 0): (ctypes.c_uint64,),
-           ("float", 0): (ctypes.c_float,), ("double", 0): (ctypes.c_double,), ("void", 1): (ctypes.c_void_p,),
-           # device memory travels as an integer, host arrays as typed pointers (the convention stated above _native._SIGNATURES)
-           ("float", 1): (ctypes.c_void_p,), ("gp_step_state", 1): (ctypes.c_void_p,),
-           ("double", 1): (ctypes.POINTER(ctypes.c_double),),
-           ("gp_step_segment", 1): (ctypes.POINTER(_native.GpStepSegment),),
-           ("gp_optim_tensor", 1): (ctypes.POINTER(_native.GpOptimTensor),)}
-
-
-def test_step_signatures_match_the_header_type_by_type():
-    def ctype(decl):
-        m = re.fullmatch(r"(?:const\s+)?(\w+)\s*(\**)", decl.strip())
-        assert m, decl
-        return m.group(1), len(m.group(2))
-
-    _, code = _header()
-    protos = {}
-    for ret, name, params in re.findall(r"\b((?:const\s+)?\w+\s*\**)\s*\b(gp_[a-z_0-9]+)\s*\(([^)]*)\)\s*;", code):
-        assert name not in protos
-        protos[name] = (ctype(ret), [ctype(re.sub(r"\w+$", "", q.strip())) for q in params.split(",")])
-    names = ["gp_clip_adam_step_dev", "gp_step_advance", "gp_step_masks"]
-    assert sorted(protos) == names == sorted(_native._STEP_SIGNATURES) == sorted(_native.STEP_EXPORTS)
-    assert sorted(set(re.findall(r"\b(gp_[a-z_0-9]+)\s*\(", code))) == names
-    for other in (_native._SIGNATURES, _native._EVAL_SIGNATURES, _native._SCATTER_SIGNATURES, _native._INFER_SIGNATURES,
-                  _native._MAG_SIGNATURES, _native._ORDER_SIGNATURES, _native._CHAIN_SIGNATURES):
-        assert not set(_native._STEP_SIGNATURES) & set(other)
-    built = ctypes.CDLL(_native.LIB_PATH)
-    for name, (ret, params) in protos.items():
-        restype, argtypes, required = _native._STEP_SIGNATURES[name]
-        assert required is False
-        assert restype in _CTYPES[ret], f"{name}: restype {restype} for {ret}"
-        assert len(argtypes) == len(params), f"{name}: {len(argtypes)} argtypes for {len(params)} parameters"
-        for i, (got, want) in enumerate(zip(argtypes, params)):
-            assert got in _CTYPES[want], f"{name}: argument {i} is {got} for {want}"
-        assert hasattr(built, name), f"libgrandplus.so does not export {name}"
-        assert getattr(_native.lib(), name).argtypes == argtypes
-    # the device form takes the value form's arguments, with two device pointers where that takes the two floats
-    val, dev = _native._SIGNATURES["gp_clip_adam_step"][1], _native._STEP_SIGNATURES["gp_clip_adam_step_dev"][1]
-    assert len(val) == len(dev) == 15 and [i for i in range(15) if val[i] != dev[i]] == [10, 11]
-    assert val[10] == val[11] == ctypes.c_float and dev[10] == dev[11] == ctypes.c_void_p
 
 
 def _fmix(x):
@@ -120,7 +24,7 @@ def _fmix(x):
 
 
 def test_step_seed_is_the_formula_of_the_header_with_known_answers():
-    text, _ = _header()
+    text, _ = abi_header.read("grandplus_step.h")
     m = re.search(r"#define GP_STEP_MUL (0x[0-9A-F]{16})ull\n", text)
     assert m and "mix(base_seed ^ tick * GP_STEP_MUL)" in text
     mul = int(m.group(1), 16)
