@@ -6,8 +6,13 @@
 // The CSR is copied once into HBM and stays resident; each call sizes a per-workgroup
 // scratch area from rigorous bounds (below), launches ONE persistent kernel
 // (gfpush_kernels.hpp) on the caller's stream and brackets it with HIP events.
+//
+// What a call's shape is DECIDED by -- which kernel, workgroups and LDS, slab sizes, the workspace plan, the estimate's growth,
+// the measured choice, the multi-GPU cut, the merge rule -- lives in gfpush_plan.hpp as functions of plain values (run on a
+// CPU by tests/test_host_gfpush_plan.py).  This file gathers their inputs, calls them and applies the outcome with HIP calls.
 #include "gfpush_kernels.hpp"
 #include "gfpush_sketch.hpp"
+#include "gfpush_plan.hpp"
 #include "grandplus.h"
 
 #include <dlfcn.h>
@@ -29,6 +34,7 @@
 #include <vector>
 
 using namespace gp;
+using namespace gp::planning;
 
 namespace {
 
@@ -50,43 +56,28 @@ int fail(int status, const char* fmt, ...) {
                         #expr, hipGetErrorString(e_));                                      \
     } while (0)
 
-// One set of per-workgroup scratch slabs (all caps are per workgroup).
-struct Slabs {
-    int n_wg = 0;
-    u64 push_cap = 0, resg_cap = 0, log_cap = 0, cand_cap = 0, bucket_cap = 0, bt_cap = 0;
+// What the decisions of gfpush_plan.hpp read of the kernel headers' constants, in this build.
+#ifndef GP_DIAG
+const KernelConsts kConsts{kCtlBytes, kThreeLds, (int)kMinCap, kTopkBins, kBucketCap, (int)kUnitShift, (int)kSkMaxPushers, kSkMaxCoef, (int)kSkTie};
+#else
+const KernelConsts kConsts{kCtlBytes, kThreeLds, (int)kMinCap, kTopkBins, kBucketCap, (int)kUnitShift, (int)kSkMaxPushers, 0, 0};   // (no sketch kernel in the diagnostic build)
+#endif
+
+// One set of per-workgroup scratch slabs on the device: the capacities (gfpush_plan.hpp) and where carve() laid the arrays out.
+struct Slabs : SlabCaps {
     PushEntry* push = nullptr; ResRec* resg = nullptr; ResRec* bucket = nullptr; u32* bt = nullptr;
     int* log_key = nullptr; double* log_val = nullptr; Cand* cand = nullptr;
-    // sketch kernel (arch_cap > 0): its log record is (column word, 16-bit pusher number) -- log_val is not allocated -- and every
-    // pusher of the row leaves coef * share in `arch`
-    u64 arch_cap = 0; unsigned short* log_pu = nullptr; double* arch = nullptr;
-    size_t log_bytes() const { return arch_cap ? 6 * (size_t)log_cap + 8 * (size_t)arch_cap : 12 * (size_t)log_cap; }
-    size_t per_wg() const { return 16 * (size_t)(2 * push_cap + resg_cap + cand_cap + bucket_cap) + log_bytes() + 8 * (size_t)bt_cap + 64; }
+    unsigned short* log_pu = nullptr; double* arch = nullptr;
+    Slabs() = default;
+    Slabs(const SlabCaps& c) : SlabCaps(c) {}
     size_t carve(char* p, int wgs) {                                   // lays the arrays out at p, returns the bytes used
         n_wg = wgs;
-        char* q = p;
-        push = (PushEntry*)q;  q += 16 * (size_t)wgs * 2 * push_cap;
-        resg = (ResRec*)q;     q += 16 * (size_t)wgs * resg_cap;
-        cand = (Cand*)q;       q += 16 * (size_t)wgs * cand_cap;
-        bucket = (ResRec*)q;   q += 16 * (size_t)wgs * bucket_cap;
-        if (arch_cap) { arch = (double*)q; q += 8 * (size_t)wgs * arch_cap; log_val = nullptr; }
-        else          { log_val = (double*)q; q += 8 * (size_t)wgs * log_cap; }
-        log_key = (int*)q;     q += 4 * (size_t)wgs * log_cap;
-        bt = (u32*)q;          q += 4 * (size_t)wgs * 2 * bt_cap;
-        if (arch_cap) { log_pu = (unsigned short*)q; q += 2 * (size_t)wgs * log_cap; }
-        return ((size_t)(q - p) + 255) & ~(size_t)255;
-    }
-    bool covers(const Slabs& o) const {
-        if (o.n_wg == 0) return true;                                  // nothing is asked for
-        return n_wg >= o.n_wg && push_cap >= o.push_cap && resg_cap >= o.resg_cap && log_cap >= o.log_cap &&
-               cand_cap >= o.cand_cap && bucket_cap >= o.bucket_cap && bt_cap >= o.bt_cap && arch_cap >= o.arch_cap && (arch_cap != 0) == (o.arch_cap != 0);
-    }
-    // the larger of two layouts of the same kind, field by field (a workspace that has served one recipe keeps serving it
-    // when it is re-allocated for another: calls that alternate between recipes must not re-allocate every time -- ADVICE r4)
-    void widen(const Slabs& o) {
-        if (o.n_wg == 0 || (n_wg != 0 && (arch_cap != 0) != (o.arch_cap != 0))) return;
-        n_wg = std::max(n_wg, o.n_wg); push_cap = std::max(push_cap, o.push_cap); resg_cap = std::max(resg_cap, o.resg_cap);
-        log_cap = std::max(log_cap, o.log_cap); cand_cap = std::max(cand_cap, o.cand_cap); bucket_cap = std::max(bucket_cap, o.bucket_cap);
-        bt_cap = std::max(bt_cap, o.bt_cap); arch_cap = std::max(arch_cap, o.arch_cap);
+        const SlabOffsets o = carve_offsets(*this, wgs);
+        push = (PushEntry*)(p + o.push); resg = (ResRec*)(p + o.resg); cand = (Cand*)(p + o.cand); bucket = (ResRec*)(p + o.bucket);
+        if (arch_cap) { arch = (double*)(p + o.arch); log_val = nullptr; log_pu = (unsigned short*)(p + o.log_pu); }
+        else          log_val = (double*)(p + o.log_val);
+        log_key = (int*)(p + o.log_key); bt = (u32*)(p + o.bt);
+        return o.bytes;
     }
 };
 
@@ -100,6 +91,7 @@ struct Workspace {
     // cost_cls[retry_cap] = their cost classes, order_hist[64] = rows per class | the scatter's cursors
     uint32_t* order = nullptr; unsigned char* cost_cls = nullptr; uint32_t* order_hist = nullptr;
     bool dirty = true;            // HBM residue tables need (re)initialising before the next launch
+    Held held() const { Held h; h.have = base != nullptr; h.est = est; h.skl = skl; h.big = big; h.retry_cap = retry_cap; h.bytes = bytes; return h; }
 };
 
 }  // namespace
@@ -109,7 +101,7 @@ struct gp_graph {
     int64_t n_nodes = 0, nnz = 0;
     int* d_indptr = nullptr; int* d_indices = nullptr; void* d_csr_block = nullptr;   // (d_csr_block: both arrays live in one allocation -- gp_graph_create; a replica allocates them one by one)
     int deg_shift = 31; uint32_t node_mask = 0x7FFFFFFFu, deg_sat = 0;   // packed column ids (see pack_degree_kernel)
-    bool packed = false; int max_degree_bits = 31;                        // packing happens at the first gfpush call
+    bool packed = false;                                                  // packing happens at the first gfpush call (option max_degree_bits restricts it)
     // self-addressed CSR of the sketch kernel (ensure_acsr; built at the first call that kernel takes): rows at 128-byte units,
     // column word = unit number of the target | min(deg, a_sat) << a_shift
     int acsr_state = 0;                                                   // 0: not built yet, 1: built, -1: the graph does not allow it (unit numbers leave too few degree bits)
@@ -117,23 +109,10 @@ struct gp_graph {
     int64_t n_units = 0; int a_shift = 31; uint32_t a_mask = 0x7FFFFFFFu, a_sat = 0;
     bool rows_distinct = false;                                           // every CSR row holds strictly increasing column ids
     int num_cus = 0;
-    // options
-    int block_threads = 0; int lds_bytes = 0; int max_workgroups = 0;     // 0 = choose per graph
-    int verify_merge = 0;                                                 // gp_gfpush re-checks every merged row against the slab once the launches have retired (option "verify_merge")
-    int lds_pad = 0; int pretouch = 0;                                    // experiment knobs: extra dynamic LDS per workgroup that the tables do not use (forces fewer workgroups per CU); memset the workspace when it is allocated
-    int64_t workspace_mb = 65536; int force_global = 0; int exact_stats = 0; int diag_flags = 0; int direct_tables = 1; int seedrow = 1; int solo_levels = 1;
-    int kernel = 0;                                                        // option: 0 = choose per call, 1 = general kernel, 2 = sketch kernel whenever the call allows it
-    int sk_block = 0, sk_lg_mu = 0, sk_lg_mr = 0, sk_target = 0, sk_direct_max = 0;   // options: geometry of the sketch kernel (0 = default)
-    int row_order = 1;                                                     // option: 1 = the first launch of a call takes its rows heaviest first (row_cost_kernel), 0 = in caller order
+    Options opt;                                                          // what gp_set_option writes (gfpush_plan.hpp)
+    Estimate est;                                                         // the running estimate of a row's needs, with its sketch-off memory (gfpush_plan.hpp)
     int64_t last_order_rows = 0; uint32_t last_order_sat = 0; int last_order_shift = 0;   // the last call's pre-pass: rows ordered (0: skipped), the degree field it read (gp_internal_row_order)
     u64* d_wg_log = nullptr;                                               // -DGP_SK_TIMING build: KParams::wg_log (gp_internal_wg_log)
-    int sk_seed_merge = 1; int gk_acsr = 1;                                                       // option: the general kernel runs on the self-addressed copy too when the graph is large (0 = packed CSR + indptr)
-    int est_kind = 0; int last_kind = 1; bool sk_auto_off = false; double sk_off_rmax = 0.0; int sk_off_n_coef = 0;                                   // which kernel the running estimate / the last call belongs to
-    bool last_sk_soft = false;                                             // the last call ran the sketch kernel as an automatic or soft pick, not because option kernel = 2 insisted (grow_estimate)
-    int64_t est_level_edges = 0;                                           // option: edges per level the first-launch slabs are sized for (0 = automatic)
-    double est_edges = 0.0, est_log = 0.0;                                 // running estimate (grows from the observed maxima)
-    double est_rmax = -1.0; int est_n_coef = 0;                            // the call parameters that estimate belongs to
-    bool est_recipe_changed = false; double cur_e_est = 0.0, cur_log_est = 0.0; int64_t last_call_rows = 0; bool grown_for_call = true;
     // per-call state
     Workspace ws;
     u64* d_counters = nullptr; u64* h_counters = nullptr;      // pinned host mirror
@@ -141,12 +120,8 @@ struct gp_graph {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     hipStream_t stream = nullptr;                               // used by the host-buffer entry point
     bool launched = false; hipStream_t last_stream = nullptr;
-    // Measured choice: which kernel and launch shape run a recipe on this graph is decided by timing the
-    // candidates -- they are exact and interchangeable -- on the first rows of the first large call of the recipe, not by
-    // thresholds on rmax and graph size.  One entry per (rmax, n_coef, K); ms[] = general kernel in the shape the old
-    // thresholds pick / sketch kernel / general kernel in the other shape (0: not a candidate).
-    struct Choice { double rmax; int n_coef, K; int kernel, block_threads, lds_bytes; float ms[3]; };
-    std::vector<Choice> choices; int measure_choice = 1; u64* d_cal_counters = nullptr;
+    using Choice = gp::planning::Choice;                        // the measured choice of a recipe (gfpush_plan.hpp)
+    std::vector<Choice> choices; u64* d_cal_counters = nullptr;
     float last_cal_ms[3] = {0.f, 0.f, 0.f};
     bool reset_pending = true; int64_t rows_total = 0;
     gp_stats last{};
@@ -247,172 +222,35 @@ struct Stager {
     }
 };
 
-// Per-workgroup slab sizes for levels of up to `e_max` edges each (and `log_records` reserve-log records per row; 0 =
-// the bound that follows from e_max).  With e_max = the rigorous bound this is the worst case:
-// the residue mass of a level never exceeds 1.0 (up to fp64 rounding) and a pushed node has deg <= r/rmax, so the degrees
-// pushed in one level sum to <= 1/rmax; the 0.1 % + 16 slack covers the rounding.
-//   E_max  = edges traversed in one level  <= min(nnz, 1.001/rmax + 16)
-//   F_max  = frontier size of one level    <= min(N, E_max) + 1          (+1: dangling -> seed)
-//   reserve-log records of a row           <= (L+1) * F_max
-//   support of the reserve map             <= min(N, 1 + L*F_max)
-double level_edge_bound_of(const gp_graph* g) { return (double)g->nnz + 16.0; }     // no level traverses more than every stored entry
-
-Slabs slab_sizes(const gp_graph* g, int n_coef, double e_max, double log_records) {
-    const double n_d = (double)g->n_nodes;
-    const double f_max = std::min(n_d, e_max) + 1.0;
-    const double L = (double)(n_coef - 1);
-    double logn = (L + 1.0) * f_max + 64.0;
-    if (log_records > 0.0) logn = std::min(logn, log_records + 64.0);
-    const double supp = std::max(1.0, std::min(std::min(n_d, 1.0 + L * f_max), logn));
-    Slabs sl;
-    sl.resg_cap = (u64)std::max(2048.0, 2.0 * f_max);
-    sl.log_cap = ((u64)logn + 3) & ~3ull;
-    sl.cand_cap = (u64)supp + 1;
-    sl.push_cap = (u64)(f_max + 2.0);                        // one entry per pushing node
-    // one boundary-table word per 64 edges of a level.  Cheap (1/16 byte per edge), so it is sized well beyond the estimate:
-    // a level that outgrows e_max edges but not the entry / log capacities must not send its row to the retry launch
-    const double e_bt = std::min(level_edge_bound_of(g), std::max(8.0 * e_max, 1048576.0));
-    sl.bt_cap = (((u64)std::max(e_max, e_bt) >> kUnitShift) + 4) & ~1ull;
-    sl.bucket_cap = (u64)e_max + 2;                 // (key, share) records of one bucketed level
-    return sl;
-}
-
-// The sketch kernel's slab: two push lists, two boundary tables and the per-EDGE reserve log (`log_records` = edges of a row).
-Slabs sk_slab_sizes(const gp_graph* g, double e_max, double log_records, bool at_bound) {
-    Slabs sl;
-    sl.log_cap = ((u64)std::min(log_records + 64.0, 4.0e9) + 3) & ~3ull;     // (log positions are 32-bit words in the kernel: a row with more records outgrows its slab and is retried)
-    // one entry per pushing node: a few per cent of a level's edges on the graphs the estimate is for (a level with more: general
-    // kernel); every node of the level when the slabs are sized from the bound anyway (small graphs)
-    sl.push_cap = (u64)(std::min((double)g->n_nodes, at_bound ? e_max : std::max(e_max / 4.0, 4096.0)) + 2.0);
-    const double e_bt = std::min(level_edge_bound_of(g), std::max(8.0 * e_max, 1048576.0));
-    sl.bt_cap = (((u64)std::max(e_max, e_bt) >> kUnitShift) + 4) & ~1ull;
-    // one coef * share per pusher of the ROW (and per level one for the mass dangling nodes return): a few per cent of its edges
-    // where this kernel is chosen; pusher numbers are 16 bits in the log, a row with more goes to the general kernel
-    sl.arch_cap = (u64)std::min((double)kSkMaxPushers, std::max(at_bound ? (double)sl.log_cap : (double)sl.log_cap / 4.0, 4096.0));
-    sl.arch_cap = (sl.arch_cap + 3) & ~3ull;
-    return sl;
-}
-
-double level_edge_bound(const gp_graph* g, double rmax) {
-    double e = (double)g->nnz;
-    if (rmax > 0.0) e = std::min(e, std::floor(1.001 / rmax) + 16.0);
-    return e;
-}
-
-// Workspace policy.  Sizing every workgroup's slab from the 1/rmax bound does not scale: the Cora recipe's
-// rmax 1e-7 on a large graph asks for ~2 GB per workgroup, and a fixed budget then silently cut the launch to a few dozen
-// workgroups.  Now ALL resident workgroups get a slab sized for what rows of this graph and recipe actually need -- an
-// estimate that starts at max(32 Ki edges per level, bound / 4), is capped so that the slabs fit HALF the budget, and grows
-// from the maxima the kernel observes -- and a handful of workgroups of a second launch hold bound-sized slabs for the rows
-// that outgrow the estimate (they are detected exactly as before and moved to a retry list instead of failing).
-int ensure_workspace(gp_graph* g, int n_coef, double rmax, int n_wg, int64_t n_seeds, int sk_wg) {
-    // sk_wg > 0: the sketch kernel runs the call on sk_wg workgroups (own, smaller slabs: no HBM residue table, no candidate /
-    // bucket buffers); the general kernel then only re-runs the rows handed back, on n_wg workgroups.
-    const double bound = level_edge_bound(g, rmax);
-    {
-        const Slabs worst = slab_sizes(g, n_coef, bound, 0.0);
-        if (2.0 * (double)worst.resg_cap > 8.0e9 || (double)worst.log_cap > 4.0e9)
-            return fail(GP_ERR_INVALID_ARG, "workspace bound exceeds 32-bit record space (order %d, rmax %g)", n_coef - 1, rmax);
-    }
-    size_t budget = (size_t)g->workspace_mb << 20;
-    {   // never plan beyond what the device can give right now: our own cached workspace counts as free
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) budget = std::min(budget, (size_t)(0.9 * (double)(free_b + g->ws.bytes)));
-        else (void)hipGetLastError();
-    }
-    const int kind = sk_wg > 0 ? 2 : 1;
-    if (g->est_rmax != rmax || g->est_n_coef != n_coef || g->est_kind != kind) {   // a new recipe (or the other kernel, whose log counts edges): forget the running estimate
-        g->est_rmax = rmax; g->est_n_coef = n_coef; g->est_kind = kind; g->est_edges = 0.0; g->est_log = 0.0;
-        g->est_recipe_changed = true;                                // (the observed maxima on the device belong to the old recipe)
-    }
-    double e_est = g->est_level_edges > 0 ? (double)g->est_level_edges
-                                          : std::max(g->est_edges, std::max(32768.0, bound / 4.0));
-    e_est = std::min(e_est, bound);
-    double log_est = e_est >= bound ? 0.0 : std::max(g->est_log, 4.0 * e_est);
-    Slabs est, skl;
-    auto plan = [&]() {
-        est = slab_sizes(g, n_coef, e_est, log_est);
-        if (sk_wg > 0) skl = sk_slab_sizes(g, e_est, log_est > 0.0 ? log_est : (double)n_coef * e_est, !(log_est > 0.0));
-        return (double)est.per_wg() * n_wg + (sk_wg > 0 ? (double)skl.per_wg() * sk_wg : 0.0);
-    };
-    while (plan() > 0.5 * (double)budget && e_est > 4096.0) {        // shrink the slabs, not the launch
-        e_est *= 0.75; log_est = std::max(4096.0, 0.75 * (log_est > 0.0 ? log_est : (double)est.log_cap));
-    }
-    if (plan() > 0.5 * (double)budget) {
-        // (the caller re-plans with the general kernel alone unless option kernel = 2 insists)
-        if (sk_wg > 0) return fail(GP_ERR_NOMEM, "workspace_mb too small for the sketch kernel's slabs");
-        n_wg = (int)std::max<size_t>(1, budget / 2 / est.per_wg());
-    }
-    g->cur_e_est = e_est; g->cur_log_est = log_est;
-    est.n_wg = n_wg; skl.n_wg = sk_wg;
-    Slabs big;                                                       // needed only if the estimate is below the bound
-    if (e_est < bound || log_est > 0.0) {
-        big = slab_sizes(g, n_coef, bound, 0.0);
-        const size_t used = est.per_wg() * (size_t)n_wg + skl.per_wg() * (size_t)sk_wg;
-        const size_t left = budget - std::min(budget, used);
-        int nb = (int)std::min<size_t>(8, left / std::max<size_t>(1, big.per_wg()));
-        if (nb < 1) {                                                // not even one worst-case slab fits: give it what is left
-            double e_big = bound;
-            while (e_big > e_est && slab_sizes(g, n_coef, e_big, 0.0).per_wg() > left) e_big *= 0.8;
-            big = slab_sizes(g, n_coef, std::max(e_big, e_est), 0.0);
-            nb = 1;
-        }
-        big.n_wg = std::min(nb, n_wg);
-    }
-
+// Frees the held workspace, then allocates and carves the layout `h` (decided by plan_general, gfpush_plan.hpp).
+int allocate_workspace(gp_graph* g, const Held& h) {
     Workspace& w = g->ws;
-    const bool fits = w.base && w.est.covers(est) && w.big.covers(big) && w.skl.covers(skl) && w.retry_cap >= n_seeds;
-    if (!fits) {
-        auto bytes_of = [&](const Slabs& a, const Slabs& b, const Slabs& c) {
-            return a.per_wg() * (size_t)a.n_wg + b.per_wg() * (size_t)b.n_wg + c.per_wg() * (size_t)c.n_wg;
-        };
-        if (w.base) {                                                // keep what the previous recipes needed, while both fit the budget
-            Slabs e2 = est, b2 = big, s2 = skl;
-            e2.widen(w.est); b2.widen(w.big); s2.widen(w.skl);
-            n_seeds = std::max<int64_t>(n_seeds, w.retry_cap);
-            if (bytes_of(e2, b2, s2) <= budget) { est = e2; big = b2; skl = s2; }
-        }
-        free_workspace(w);
-        const size_t total = bytes_of(est, big, skl) + 13 * (size_t)std::max<int64_t>(n_seeds, 1) + 3 * 4096 + 1024;   // (per row: two retry lists, order, cost_cls)
-        hipError_t e = hipMalloc(&w.base, total);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(GP_ERR_NOMEM, "hipMalloc(%zu bytes of gfpush workspace): %s", total, hipGetErrorString(e));
-        }
-        w.bytes = total;
-        if (g->pretouch && hipMemset(w.base, 0, total) != hipSuccess) (void)hipGetLastError();
-        char* p = (char*)w.base;
-        w.skl = skl; if (skl.n_wg > 0) p += w.skl.carve(p, skl.n_wg);
-        w.est = est; p += w.est.carve(p, est.n_wg);
-        w.big = big; if (big.n_wg > 0) p += w.big.carve(p, big.n_wg);
-        w.retry_cap = std::max<int64_t>(n_seeds, 1);
-        w.retry_list = (uint32_t*)p; w.retry_list2 = w.retry_list + w.retry_cap;
-        w.order = w.retry_list2 + w.retry_cap; w.cost_cls = (unsigned char*)(w.order + w.retry_cap);
-        w.order_hist = (uint32_t*)(((uintptr_t)(w.cost_cls + w.retry_cap) + 255) & ~(uintptr_t)255);        // (inside the 13 KB of slack)
-        w.dirty = true;
+    free_workspace(w);
+    const size_t total = h.bytes;
+    hipError_t e = hipMalloc(&w.base, total);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(GP_ERR_NOMEM, "hipMalloc(%zu bytes of gfpush workspace): %s", total, hipGetErrorString(e));
     }
+    w.bytes = total;
+    if (g->opt.pretouch && hipMemset(w.base, 0, total) != hipSuccess) (void)hipGetLastError();
+    char* p = (char*)w.base;
+    w.skl = h.skl; if (h.skl.n_wg > 0) p += w.skl.carve(p, h.skl.n_wg);
+    w.est = h.est; p += w.est.carve(p, h.est.n_wg);
+    w.big = h.big; if (h.big.n_wg > 0) p += w.big.carve(p, h.big.n_wg);
+    w.retry_cap = h.retry_cap;
+    w.retry_list = (uint32_t*)p; w.retry_list2 = w.retry_list + w.retry_cap;
+    w.order = w.retry_list2 + w.retry_cap; w.cost_cls = (unsigned char*)(w.order + w.retry_cap);
+    w.order_hist = (uint32_t*)(((uintptr_t)(w.cost_cls + w.retry_cap) + 255) & ~(uintptr_t)255);        // (inside the 13 KB of slack)
+    w.dirty = true;
     return GP_OK;
 }
 
-// Slab sizing follows the RETRY RATE, not the largest row ever seen (sizing 768 slabs for 1.5 x the maximum made a
-// 13.6 GB workspace of which a row touches 0.4 MB).  The estimate starts at max(32 Ki edges per level, bound / 4) and grows by
-// half when more than 0.1 % of a completed call's rows outgrew their slab (they were re-run exactly by the next launch), and
-// doubles above 2 %.  Called when the previous call is known to have completed; applied once per call (grown_for_call is false
-// from the moment a call is enqueued until its counters have been looked at).
+// Grows the slab estimate from the counters of the last call, which has completed (the rule: grow_estimate, gfpush_plan.hpp).
 void grow_estimate(gp_graph* g) {
-    if (g->est_level_edges != 0 || g->grown_for_call || g->last_call_rows <= 0) return;
-    g->grown_for_call = true;
-    const double rows = (double)g->last_call_rows;
-    const double outgrown = (double)(g->last_kind == 2 ? g->h_counters[kSkSlabFails] : g->h_counters[kRetryRows]);
-    if (outgrown > 0.02 * rows) g->est_edges = std::max(g->est_edges, 2.0 * g->cur_e_est);
-    else if (outgrown > 0.001 * rows) g->est_edges = std::max(g->est_edges, 1.5 * g->cur_e_est);
-    if (outgrown > 0.001 * rows && g->cur_log_est > 0.0) g->est_log = std::max(g->est_log, 1.5 * g->cur_log_est);
-    // the automatic choice of the sketch kernel is a guess from (rmax, graph size): when a call hands more than 5 % of its rows
-    // back for other reasons than slab size -- each of them runs twice, the second time on an eighth of the chip -- later calls
-    // of this recipe go to the general kernel
-    if (g->last_kind == 2 && g->last_sk_soft && (double)g->h_counters[kRetryRows] - outgrown > 0.05 * rows) {
-        g->sk_auto_off = true; g->sk_off_rmax = g->est_rmax; g->sk_off_n_coef = g->est_n_coef;
-    }
+    const double handed_back = (double)g->h_counters[kRetryRows];
+    const double outgrown = g->est.last_kind == 2 ? (double)g->h_counters[kSkSlabFails] : handed_back;
+    grow_estimate(g->est, g->opt.est_level_edges, g->est.last_call_rows, outgrown, handed_back);
 }
 
 // Let the degree of every column ride in the spare bits above its id (sign bit stays clear).
@@ -423,7 +261,7 @@ int ensure_packed(gp_graph* g, hipStream_t s) {
     g->packed = true;
     int id_bits = 1;
     while (id_bits < 31 && ((int64_t)1 << id_bits) < g->n_nodes) ++id_bits;
-    const int spare = std::min(31 - id_bits, g->max_degree_bits);
+    const int spare = std::min(31 - id_bits, g->opt.max_degree_bits);
     if (spare >= 2 && g->nnz > 0) {
         g->deg_shift = id_bits; g->node_mask = (1u << id_bits) - 1u; g->deg_sat = (1u << spare) - 1u;
         hipLaunchKernelGGL(pack_degree_kernel, dim3(4096), dim3(256), 0, s, g->d_indptr, g->d_indices,
@@ -533,7 +371,7 @@ int ensure_acsr(gp_graph* g, hipStream_t s) {
     HIP_TRY(hipStreamSynchronize(s));
     int pos_bits = 1;
     while (pos_bits < 31 && (1ull << pos_bits) < total + 1) ++pos_bits;
-    const int spare = std::min(31 - pos_bits, g->max_degree_bits);
+    const int spare = std::min(31 - pos_bits, g->opt.max_degree_bits);
     // (32 * units + the sentinel must stay a 31-bit word index; fewer than two degree bits: nothing for the cheap push test to read)
     if (total == 0 || total >= (1ull << 26) || spare < 2) { g->acsr_state = -1; return GP_OK; }
     g->n_units = (int64_t)total; g->a_shift = pos_bits; g->a_mask = (1u << pos_bits) - 1u; g->a_sat = (1u << spare) - 1u;
@@ -613,32 +451,6 @@ int load_rccl() {
         if (r_ != ncclSuccess) return fail(GP_ERR_HIP, "%s: %s", #expr, g_rccl.GetErrorString(r_)); \
     } while (0)
 
-// bytes one GPU contributes to the gather: [val f64 | row i32 | col i32 | filled i32] for `per` rows, 16-byte padded
-// (the layout of grand_plus_amd/sharded.py:packed_stride, so both multi-GPU drivers move the same slab)
-size_t packed_stride(int64_t per, int K) { return ((size_t)16 * per * K + (size_t)4 * per + 15) / 16 * 16; }
-
-// How one call is cut over the GPUs of a multi-GPU handle (pure host arithmetic: gp_internal_multi_plan exposes it to the
-// CPU tests, because the >= 2-GPU branch cannot run on a one-GPU box).
-//   G   GPUs that compute (1 when the call is too small to shard and no collective is forced)
-//   Gc  GPUs that take part in the gather (the whole communicator for the RCCL path, else G)
-//   per rows every participant contributes to the gather = ceil(S / G); GPU d computes rows [d per, min((d+1) per, S))
-//   single: the call is handed to part[0] as it is (no slab, no gather)
-struct MultiPlan { int G = 1, Gc = 1; int64_t per = 0; size_t stride = 0; bool single = true; };
-MultiPlan plan_multi(int64_t n_seeds, int K, int n_parts, int64_t min_rows_per_gpu, bool force_collective, bool gather_host) {
-    MultiPlan m;
-    m.G = n_parts;
-    if (n_seeds < min_rows_per_gpu * (int64_t)m.G && !force_collective) m.G = 1;       // small calls stay on one GPU
-    m.single = m.G == 1 && !force_collective;
-    m.per = (n_seeds + m.G - 1) / m.G;
-    m.stride = packed_stride(m.per, K);
-    m.Gc = gather_host ? m.G : n_parts;                    // the communicator spans every GPU of the handle
-    return m;
-}
-void plan_block(const MultiPlan& m, int d, int64_t n_seeds, int64_t* lo, int64_t* n) {
-    *lo = std::min<int64_t>((int64_t)d * m.per, n_seeds);
-    *n = d < m.G ? std::min<int64_t>(*lo + m.per, n_seeds) - *lo : 0;
-}
-
 // ------------------------------------------------------------------ one call: what it is asked to run, its plan, its launches
 
 // The arguments of one gp_gfpush_device call.
@@ -647,48 +459,15 @@ struct CallArgs {
     int32_t* d_row; int32_t* d_col; double* d_val; int32_t* d_filled; hipStream_t s;
 };
 
-// What a call is asked to run: built by gp_gfpush_device from the handle's options or from the recipe's measured Choice, and by
-// calibrate_choice for each candidate.  enqueue_call takes kernel, shape and softness from here, never from the handle.
-struct CallShape {
-    int kernel = 0;                          // 0 = the thresholds choose, 1 = general kernel, 2 = sketch kernel whenever the call allows it
-    int block_threads = 0, lds_bytes = 0;    // launch shape of the general kernel (0 = choose)
-    bool soft = false;                       // kernel 2 is CHOSEN, not insisted on: where the sketch kernel cannot run or keeps handing rows back, the general kernel takes over as in the automatic path
+// What a call is asked to run (Shape, gfpush_plan.hpp): built by gp_gfpush_device from the handle's options or from the recipe's
+// measured Choice, and by calibrate_choice for each candidate.  enqueue_call takes kernel, shape and softness from here, never
+// from the handle.
+struct CallShape : Shape {
     // A timing run of calibrate_choice: the counters accumulate in this block (zeroed in full first); the handle's own block and
     // the caller's statistics (last, rows_total, reset_pending, launched, last_cal_ms) stay as they are.  nullptr: an ordinary call.
     u64* timing_counters = nullptr;
-    bool insists_on_sketch() const { return kernel == 2 && !soft; }
+    CallShape(const Shape& s, u64* tc = nullptr) : Shape(s), timing_counters(tc) {}
 };
-
-// Geometry.  Two 512-thread workgroups per CU (80 KB of LDS each) or one 1024-thread workgroup owning all
-// 160 KB.  All waves of a workgroup move through a row's phases together, so they wait for memory together
-// and compete for issue slots together; a second, independent workgroup on the CU fills those gaps (one
-// row's barriers, memory stalls and TOP-K overlap the other row's inserts).  The half-size table costs extra
-// hash partitions on the biggest levels, which the one-lane-per-edge EXPAND made cheap (a partition pass
-// re-reads and filters at ~25 wave-instructions per 64 edges).  Measured on MI355X, 65 536 rows (tools/exp_run2.sh):
-// MAG-shape +13 %, Reddit-shape +15 %, Pubmed +20 %, Cora +74 %; the Amazon2M recipe (rmax 1e-6: levels of
-// ~100 k edges, 14+ partitions even with 160 KB) loses 36 % and keeps 1 x 1024, as does any rmax < 5e-6 on a
-// graph that is neither tiny nor sparse.
-// Three 512-thread workgroups per CU (52 KB of LDS each, 6 waves per SIMD at 80 VGPRs): a third resident row hides
-// more of each row's barriers and latency than the smaller table costs in extra hash partitions, once TOP-K no
-// longer falls off a cliff at that size (its histogram and tie bucket now live inside the aggregation table's bytes
-// and tau is read off a 16x finer histogram).  Measured on MI355X (round 3, 65 536 rows) against 2 x 768 x 80 KB:
-// MAG-shape +2.9 %, Reddit-shape +1.3 %, Pubmed +13 %, Cora +10 %.  K > 128 keeps 2 x 768 (sel[K] eats the table).
-// The threshold pick of the general kernel's shape, as workgroups per CU: 3, 2 or 1 (plan_general gives their threads and LDS).
-int threshold_wgs_per_cu(const gp_graph* g, double rmax, int K) {
-    const bool tiny = (double)g->n_nodes <= 0.75 * (double)((80 * 1024 - kCtlBytes) / 12);
-    const bool sparse = g->nnz < 8 * g->n_nodes;
-    const bool two_per_cu = K <= 256 && (tiny || sparse || rmax >= 5e-6);
-    return !two_per_cu ? 1 : K <= 128 ? 3 : 2;
-}
-
-// The threshold pick of the kernel -- the sketch kernel for the recipes whose push test filters (rmax >= 5e-6; at 1e-6 and
-// below most of a frontier pushes and the sketch has nothing to remove) on large graphs (measured, 65 536 rows: MAG-shape
-// +15 %, Reddit-shape +36 % over the general kernel; the 19.7 k-node Pubmed graph, where half of a frontier pushes, -18 %)
-bool threshold_picks_sketch(const gp_graph* g, double rmax) { return rmax >= 5e-6 && g->n_nodes >= 65536; }
-
-// How the sketch kernel runs a call (use == false: it does not) and how the general kernel does, or re-runs what was handed back.
-struct SketchPlan { bool use = false; int block = 0, lds = 0, wg = 0; u32 lg_mu = 0, lg_mr = 0, cx = 0; double coef_sum = 0.0; };
-struct GeneralPlan { int block_threads = 0, lds_bytes = 0, n_wg = 0; u32 lds_slots = 0; };
 
 // The one place a run-time block size becomes a template argument: f(std::integral_constant<int, BLOCK>()) names the kernel
 // built for `block` threads, out of the sizes listed (nullptr: none of them; gp_set_option admits no other, and the first HIP
@@ -740,50 +519,33 @@ void use_csr(KParams& kp, const gp_graph* g, bool acsr, bool general) {
     kp.gk_acsr = acsr && general ? 1u : 0u;
 }
 
+// A decision's status (gfpush_plan.hpp) as the C ABI's, with its message.
+int plan_status(Status st, const std::string& err) {
+    return st == kOk ? GP_OK : fail(st == kNoMem ? GP_ERR_NOMEM : GP_ERR_INVALID_ARG, "%s", err.c_str());
+}
+
 #ifndef GP_DIAG
 constexpr bool kDiagBuild = false;
 Kernel sketch_kernel(int block) { return kernel_for<512, 1024, 768>(block, [](auto b) -> Kernel { return gfpush_sk_kernel<decltype(b)::value>; }); }
 
-// ---- which kernel.  The sketch kernel (gfpush_sketch.hpp) keeps exact fp64 accumulators only for the targets that may
-// push and reads the top-K off a cumulative upper-bound table; it needs coef >= 0 (upper bounds add up), a recipe that
-// fits its control block, and a threshold the fixed-point sketch can resolve.  Rows it cannot finish come back on a
-// retry list and the general kernel runs them.  p: whether it takes the call, and its geometry if it does.
+// p: whether the sketch kernel takes the call, and its geometry and workgroups if it does (the decisions: sketch_wanted,
+// sketch_geometry, cap_workgroups; here: the self-addressed CSR it runs on and the occupancy query).
 int plan_sketch(gp_graph* g, const CallArgs& a, const CallShape& shape, SketchPlan& p)
 {
-    const int K = a.K;
-    bool ok = shape.kernel != 1 && a.n_coef <= kSkMaxCoef && K <= 128 && a.rmax * 2147483648.0 >= 64.0 && !g->force_global && !g->exact_stats &&
-              a.n_seeds > 0;
-    for (int i = 0; i < a.n_coef; ++i) { if (a.coef[i] < 0.0) ok = false; p.coef_sum += a.coef[i]; }
-    if (!(p.coef_sum < 1.0e6)) ok = false;
-    const bool sk_off = g->sk_auto_off && g->sk_off_rmax == a.rmax && g->sk_off_n_coef == a.n_coef;   // (this recipe kept handing rows back)
-    p.use = ok && (shape.insists_on_sketch() || (!sk_off && (shape.kernel == 2 || threshold_picks_sketch(g, a.rmax))));
+    sketch_wanted(kConsts, g->opt, g->est, shape, g->n_nodes, a.n_seeds, a.coef, a.n_coef, a.rmax, a.K, p);
     if (p.use) {                                       // it runs on the self-addressed CSR (built now if this is the first such call)
         int rc = ensure_acsr(g, a.s);
         if (rc) return rc;
         if (g->acsr_state != 1) p.use = false;
     }
     if (!p.use) return GP_OK;
-    p.block = g->sk_block ? g->sk_block : 768;
-    p.lds = p.block == 512 ? kThreeLds : p.block == 1024 ? 160 * 1024 : 80 * 1024;
-    p.lg_mu = (u32)(g->sk_lg_mu ? g->sk_lg_mu : (p.block == 512 ? 12 : p.block == 1024 ? 14 : 13));
-    // the reserve sketch resolves the K-th total when ~4K of its cells are heavy: 2 048 cells for K <= 32 (the MAG recipe: 1 024 / 4 096
-    // cells +4 % / +5 % kernel time), 4 096 beyond (the Reddit recipe, K = 64: -5 %; the exact table pays for them with 680 slots)
-    p.lg_mr = (u32)(g->sk_lg_mr ? g->sk_lg_mr : (K > 32 && p.block >= 768 ? 12 : 11));
-    const int64_t x_bytes = (int64_t)p.lds - kCtlBytes - (4ll << p.lg_mu) - (4ll << p.lg_mr);
-    p.cx = x_bytes > 0 ? (u32)(x_bytes / 12) & ~3u : 0u;
-    // the exact table, and the aggregation table TOP-K builds over the level sketch + exact table, need >= kMinCap slots
-    const int64_t ca = ((4ll << p.lg_mu) + 12ll * p.cx - 16ll * ((int64_t)kSkTie + K)) / 12;
-    if (p.cx < kMinCap || ca < (int64_t)kMinCap) {
-        if (shape.insists_on_sketch() && (g->sk_lg_mu || g->sk_lg_mr)) return fail(GP_ERR_INVALID_ARG, "sketch sizes leave no room for the exact table (sk_lg_mu %u, sk_lg_mr %u)", p.lg_mu, p.lg_mr);
-        p.use = false;
-        return GP_OK;
-    }
+    std::string err;
+    int rc = plan_status(sketch_geometry(kConsts, g->opt, shape, a.K, p, err), err);
+    if (rc || !p.use) return rc;
     int per_cu = 1;
-    int rc = resident_blocks(sketch_kernel(p.block), p.block, p.lds + g->lds_pad, &per_cu);
+    rc = resident_blocks(sketch_kernel(p.block), p.block, p.lds + g->opt.lds_pad, &per_cu);
     if (rc) return rc;
-    p.wg = g->num_cus * per_cu;
-    if (g->max_workgroups > 0) p.wg = std::min(p.wg, g->max_workgroups);
-    p.wg = (int)std::max<int64_t>(1, std::min<int64_t>(p.wg, a.n_seeds));
+    p.wg = cap_workgroups(g->num_cus * per_cu, g->opt.max_workgroups, a.n_seeds);
     return GP_OK;
 }
 
@@ -795,8 +557,8 @@ int launch_sketch(const gp_graph* g, KParams& kp, const CallArgs& a, const Sketc
     kp.row_map = order; kp.n_rows_dev = nullptr; kp.queue_counter = kQueue;
     kp.retry_list = w.retry_list; kp.retry_counter = kRetryRows;
     kp.sk_lg_mu = sk.lg_mu; kp.sk_lg_mr = sk.lg_mr; kp.sk_cx = sk.cx;
-    kp.sk_target = (u32)(g->sk_target > 0 ? g->sk_target : 4 * a.K);
-    kp.sk_direct_max = g->sk_direct_max > 0 ? (u32)g->sk_direct_max : 0xFFFFFFFFu;
+    kp.sk_target = (u32)(g->opt.sk_target > 0 ? g->opt.sk_target : 4 * a.K);
+    kp.sk_direct_max = g->opt.sk_direct_max > 0 ? (u32)g->opt.sk_direct_max : 0xFFFFFFFFu;
     kp.sk_rscale = 2147483648.0 / std::max(1.0, sk.coef_sum);
     {   // rmax * 2^31 * (1 - 2^-10), rounded DOWN to fp32: cell >= packed degree * this is necessary for r >= rmax * deg
         float t = (float)(a.rmax * 2147483648.0 * (1.0 - 1.0 / 1024.0));
@@ -805,7 +567,7 @@ int launch_sketch(const gp_graph* g, KParams& kp, const CallArgs& a, const Sketc
     }
     // ... on the self-addressed CSR: keys are unit numbers under the packed degree
     use_csr(kp, g, true, false);
-    return launch_kernel(sketch_kernel(sk.block), sk.block, kp, sk.wg, sk.lds + g->lds_pad, a.s);
+    return launch_kernel(sketch_kernel(sk.block), sk.block, kp, sk.wg, sk.lds + g->opt.lds_pad, a.s);
 }
 #else
 // (the diagnostic build instruments the general kernel on the packed CSR only: no sketch kernel, nothing to choose by measurement)
@@ -818,56 +580,35 @@ Kernel general_kernel(int block) { return kernel_for<256, 512, 768, 1024>(block,
 // (the retry launch is its own symbol: see gfpush_retry_kernel)
 Kernel retry_kernel(int block) { return kernel_for<256, 512, 768, 1024>(block, [](auto b) -> Kernel { return gfpush_retry_kernel<decltype(b)::value>; }); }
 
-// The general kernel's launch shape, its workgroups, and the workspace of the whole call.  Three fall-backs: the sketch
-// kernel's slabs do not fit (sk.use is cleared: the general kernel alone), three workgroups per CU -> two, two -> one.
+// The general kernel's launch shape and workgroups and the workspace of the whole call: plan_general (gfpush_plan.hpp) decides
+// from the budget and the occupancy queried here, shape by shape as its ladder asks for them; this allocates what it decided.
 int plan_general(gp_graph* g, const CallArgs& a, const CallShape& shape, SketchPlan& sk, GeneralPlan& p)
 {
-    const int K = a.K;
-    const bool auto_shape = shape.block_threads == 0 && shape.lds_bytes == 0;
-    int wgs_per_cu = auto_shape ? threshold_wgs_per_cu(g, a.rmax, K) : 1;
+    CallInputs in;
+    in.n_nodes = g->n_nodes; in.nnz = g->nnz; in.num_cus = g->num_cus;
+    in.n_coef = a.n_coef; in.rmax = a.rmax; in.K = a.K; in.n_seeds = a.n_seeds;
+    Occupancy occ;
     for (;;) {
-        p.block_threads = shape.block_threads; p.lds_bytes = shape.lds_bytes;
-        if (auto_shape) {
-            // 12 waves per row: with the phases compiled as separate functions (32-66 VGPRs each) two 768-thread workgroups
-            // fit a CU at 80 VGPRs without spilling the loops (round 3: MAG +11 %, Reddit +7 %, Pubmed +3 % over 2 x 512);
-            // (direct-indexed tables of small graphs are instantiated for both two-per-CU shapes: Cora +11 % at 768)
-            p.block_threads = wgs_per_cu == 3 ? 512 : wgs_per_cu == 2 ? 768 : 1024;
-            p.lds_bytes = wgs_per_cu == 3 ? kThreeLds : wgs_per_cu == 2 ? 80 * 1024 : 160 * 1024;
-        } else {
-            if (p.block_threads == 0) p.block_threads = 1024;
-            if (p.lds_bytes == 0) p.lds_bytes = 160 * 1024;
+        size_t free_b = 0, total_b = 0;
+        const bool have_free = hipMemGetInfo(&free_b, &total_b) == hipSuccess;
+        if (!have_free) (void)hipGetLastError();
+        in.budget = workspace_budget(g->opt.workspace_mb, have_free, free_b, g->ws.bytes);
+        Held held = g->ws.held();
+        bool realloc = false; int need = 0; std::string err;
+        Status st;
+        while ((st = plan_general(kConsts, in, g->opt, shape, occ, sk, p, g->est, held, &realloc, &need, err)) == kNeedOccupancy) {
+            int rc = resident_blocks(general_kernel(p.block_threads), p.block_threads, p.lds_bytes + g->opt.lds_pad, &occ.general[need]);
+            if (rc) return rc;
         }
-        p.lds_slots = (u32)((p.lds_bytes - kCtlBytes) / 12) & ~3u;     // multiple of 4: 128-bit LDS accesses on both arrays
-        // TOP-K carves sel[K] out of the table region and aggregates in what is
-        // left; like every LDS table that aggregation table needs >= kMinCap slots (home_lds: cap - kProbeSpan)
-        const size_t topk_fixed = 16 * (size_t)K;
-        const size_t topk_region = std::max<size_t>(12 * (size_t)kMinCap, kTopkBins * 4 + 16 * (size_t)kBucketCap);   // table, or histogram + compacted bucket
-        if ((size_t)p.lds_slots * 12 < topk_fixed + topk_region)
-            return fail(GP_ERR_INVALID_ARG, "lds_bytes = %d too small for K = %d (top-K needs %zu bytes of LDS)",
-                        p.lds_bytes, K, topk_fixed + topk_region + kCtlBytes);
-
-        int per_cu = 1;
-        int rc = resident_blocks(general_kernel(p.block_threads), p.block_threads, p.lds_bytes + g->lds_pad, &per_cu);
-        if (rc) return rc;
-        p.n_wg = g->num_cus * per_cu;
-        if (g->max_workgroups > 0) p.n_wg = std::min(p.n_wg, g->max_workgroups);
-        if (sk.use) p.n_wg = std::min(p.n_wg, std::max(8, g->num_cus / 2));  // the general kernel only re-runs what the sketch kernel hands back (a per-mille of the call)
-        p.n_wg = (int)std::max<int64_t>(1, std::min<int64_t>(p.n_wg, a.n_seeds));
-        rc = ensure_workspace(g, a.n_coef, a.rmax, p.n_wg, a.n_seeds, sk.use ? sk.wg : 0);
+        if (st) return plan_status(st, err);
+        if (!realloc) return GP_OK;
+        int rc = allocate_workspace(g, held);
         if (rc == GP_ERR_NOMEM && sk.use && !shape.insists_on_sketch()) {          // the automatic choice must not fail where the general kernel alone fits
             sk.use = false; g_last_error.clear();
             continue;
         }
-        if (rc) return rc;
-        if (sk.use) break;
-        // the workspace budget could not hold two workgroups per CU: one big workgroup per CU is better than
-        // a half-empty chip
-        if (wgs_per_cu == 3 && g->ws.est.n_wg < p.n_wg && g->ws.est.n_wg < 3 * g->num_cus) { wgs_per_cu = 2; continue; }
-        if (wgs_per_cu == 2 && g->ws.est.n_wg < p.n_wg && g->ws.est.n_wg < 2 * g->num_cus) { wgs_per_cu = 1; continue; }
-        break;
+        return rc;
     }
-    p.n_wg = std::min(p.n_wg, g->ws.est.n_wg);
-    return GP_OK;
 }
 
 // Everything of KParams that is the same for every launch of the call (use_slabs / use_csr and the launch sequences set the rest).
@@ -882,14 +623,12 @@ KParams call_params(const gp_graph* g, const CallArgs& a, const GeneralPlan& gk,
     kp.out_row = a.d_row; kp.out_col = a.d_col; kp.out_val = a.d_val; kp.out_filled = a.d_filled;
     kp.counters = counters;
     kp.lds_slots = gk.lds_slots;
-    kp.force_global = g->force_global;
-    kp.prune = g->exact_stats ? 0 : 1;
-    kp.diag_flags = g->diag_flags;
-    kp.rows_distinct = g->rows_distinct && g->seedrow ? 1u : 0u;
-    kp.solo = (g->solo_levels ? 1u : 0u) | (g->sk_seed_merge ? 2u : 0u);      // (bit 1: the sketch kernel's wave 0 does level 1 in the call of level 0)
-    // direct-indexed level tables: the whole graph fits the table of the 512-thread kernel (Cora, Citeseer)
-    kp.direct = ((gk.block_threads == 512 || gk.block_threads == 768) && (u64)g->n_nodes + 4 <= (u64)gk.lds_slots && g->direct_tables) ? 1 : 0;
-    for (int i = 0; i < a.n_coef; ++i) if (a.coef[i] < 0.0) kp.prune = 0;      // the bound needs coef >= 0
+    kp.force_global = g->opt.force_global;
+    kp.prune = prune_allowed(g->opt, a.coef, a.n_coef) ? 1 : 0;
+    kp.diag_flags = g->opt.diag_flags;
+    kp.rows_distinct = g->rows_distinct && g->opt.seedrow ? 1u : 0u;
+    kp.solo = (g->opt.solo_levels ? 1u : 0u) | (g->opt.sk_seed_merge ? 2u : 0u);      // (bit 1: the sketch kernel's wave 0 does level 1 in the call of level 0)
+    kp.direct = direct_tables(g->opt, g->n_nodes, gk) ? 1 : 0;
     return kp;
 }
 
@@ -907,14 +646,14 @@ int launch_general(const gp_graph* g, KParams& kp, const GeneralPlan& gk, bool g
     kp.row_map = pass.rows ? pass.rows : pass.order; kp.n_rows_dev = pass.rows ? kp.counters + pass.n_rows : nullptr; kp.queue_counter = pass.queue;
     kp.retry_list = two_tier ? pass.overflow : nullptr; kp.retry_counter = pass.n_overflow;
     const Kernel k = pass.rows ? retry_kernel(gk.block_threads) : general_kernel(gk.block_threads);
-    int rc = launch_kernel(k, gk.block_threads, kp, gk.n_wg, gk.lds_bytes + g->lds_pad, s);
+    int rc = launch_kernel(k, gk.block_threads, kp, gk.n_wg, gk.lds_bytes + g->opt.lds_pad, s);
     if (rc || !two_tier) return rc;
     // Retry launch, enqueued unconditionally (no host synchronisation): it reads the number of rows that outgrew
     // their slab from device memory and is a few microseconds of nothing when that number is zero.
     use_slabs(kp, w.big);
     kp.row_map = pass.overflow; kp.n_rows_dev = kp.counters + pass.n_overflow; kp.queue_counter = pass.overflow_queue;
     kp.retry_list = nullptr;
-    return launch_kernel(retry_kernel(gk.block_threads), gk.block_threads, kp, w.big.n_wg, gk.lds_bytes + g->lds_pad, s);
+    return launch_kernel(retry_kernel(gk.block_threads), gk.block_threads, kp, w.big.n_wg, gk.lds_bytes + g->opt.lds_pad, s);
 }
 
 // Heaviest rows first: the pre-pass in front of the first launch of a call (no host synchronisation).  row_cost_kernel classes
@@ -947,7 +686,7 @@ int enqueue_call(gp_graph* g, const CallArgs& a, const CallShape& shape)
     if (g->launched && g->last_stream != s) HIP_TRY(hipStreamSynchronize(g->last_stream));
     // Grow the slab estimate from what the previous call observed, whether or not the caller ever asks for statistics
     // (ADVICE r2): once that call has completed, its counters are in the pinned mirror.
-    if (!g->grown_for_call && g->est_rmax == a.rmax && g->est_n_coef == a.n_coef) {
+    if (!g->est.grown_for_call && g->est.rmax == a.rmax && g->est.n_coef == a.n_coef) {
         const hipError_t qs = hipStreamQuery(g->last_stream);
         if (qs == hipSuccess) grow_estimate(g);
         else if (qs != hipErrorNotReady) (void)hipGetLastError();
@@ -974,10 +713,10 @@ int enqueue_call(gp_graph* g, const CallArgs& a, const CallShape& shape)
         if (!timing) { g->reset_pending = false; g->rows_total = 0; }
     } else {
         HIP_TRY(hipMemsetAsync(counters, 0, sizeof(u64) * (kSkSlabFails + 1), s));  // the queue heads and the retry counts (per call: ADVICE r4)
-        if (g->est_recipe_changed)                                                          // maxima of another recipe must not size this one's slabs
+        if (g->est.recipe_changed)                                                          // maxima of another recipe must not size this one's slabs
             HIP_TRY(hipMemsetAsync(counters + kMaxLevelEdges, 0, sizeof(u64) * 2, s));
     }
-    g->est_recipe_changed = false;
+    g->est.recipe_changed = false;
     if (w.dirty) {
         hipLaunchKernelGGL(init_tables_kernel, dim3(4096), dim3(256), 0, s, w.est.resg, (u64)w.est.n_wg * w.est.resg_cap);
         if (w.big.n_wg > 0)
@@ -987,14 +726,14 @@ int enqueue_call(gp_graph* g, const CallArgs& a, const CallShape& shape)
     }
 
     KParams kp = call_params(g, a, gk, counters);
-    bool gk_acsr = !kDiagBuild && g->gk_acsr && !kp.direct && !g->force_global && g->n_nodes >= 65536 && a.n_seeds > 0;
+    bool gk_acsr = general_wants_acsr(kDiagBuild, g->opt, kp.direct != 0, g->n_nodes, a.n_seeds);
     if (gk_acsr) { rc = ensure_acsr(g, s); if (rc) return rc; gk_acsr = g->acsr_state == 1; }
 
     HIP_TRY(hipEventRecord(g->ev0, s));
     // (a call of no more rows than the first launch has workgroups: every workgroup takes at most one row, nothing to order)
     const u32* order = nullptr;
     g->last_order_rows = 0;
-    if (g->row_order && a.n_seeds > (sk.use ? sk.wg : gk.n_wg) && a.n_seeds <= w.retry_cap && a.n_seeds <= (int64_t)0xFFFFFFFFll) {
+    if (g->opt.row_order && a.n_seeds > (sk.use ? sk.wg : gk.n_wg) && a.n_seeds <= w.retry_cap && a.n_seeds <= (int64_t)0xFFFFFFFFll) {
         rc = enqueue_row_order(g, a, sk.use || gk_acsr, s);
         if (rc) return rc;
         order = w.order;
@@ -1015,25 +754,19 @@ int enqueue_call(gp_graph* g, const CallArgs& a, const CallShape& shape)
     if (rc) return rc;
     HIP_TRY(hipEventRecord(g->ev1, s));
     HIP_TRY(hipMemcpyAsync(g->h_counters, counters, sizeof(u64) * kNumCounters, hipMemcpyDeviceToHost, s));
-    g->last_stream = s; g->last_call_rows = a.n_seeds; g->grown_for_call = false;
-    g->last_kind = sk.use ? 2 : 1; g->last_sk_soft = sk.use && !shape.insists_on_sketch();
+    g->last_stream = s; g->est.last_call_rows = a.n_seeds; g->est.grown_for_call = false;
+    g->est.last_kind = sk.use ? 2 : 1; g->est.last_sk_soft = sk.use && !shape.insists_on_sketch();
     if (timing) return GP_OK;
     g->launched = true;
     std::memset(&g->last, 0, sizeof g->last);
     g->rows_total += a.n_seeds;
     g->last.rows = g->rows_total;
-    g->last.kernel = g->last_kind;
+    g->last.kernel = g->est.last_kind;
     g->last.workgroups = sk.use ? sk.wg : gk.n_wg; g->last.block_threads = sk.use ? sk.block : gk.block_threads;
     g->last.lds_bytes = sk.use ? sk.lds : gk.lds_bytes; g->last.lds_slots = sk.use ? (int)sk.cx : (int)gk.lds_slots;
     g->last.workspace_bytes = (int64_t)w.bytes;
     return GP_OK;
 }
-
-// Rows timed per candidate / smallest call that is worth a calibration.  16 384 rows are ~30 rows per resident workgroup: both
-// kernels LEARN per workgroup how to plan a level (cand_q / ratio_q) and pay for an overflowed pass while they do; on 2 048 rows
-// (4 per workgroup) the MAG line's sketch kernel timed 2.0 ms against 1.4 ms for the general kernel in its slowest shape, which
-// takes 36 ms against 21 ms on a full call.
-constexpr int64_t kCalRows = 16384, kCalMinRows = 32768;
 
 // Times the candidates on the first kCalRows rows of the call and records the fastest as the choice for (rmax, n_coef, K).
 // The candidates write into SCRATCH output buffers of their own (round 6, VERDICT r5 weak #1 / ADVICE r5 high): the caller's
@@ -1046,47 +779,38 @@ int calibrate_choice(gp_graph* g, const CallArgs& call)
     if (!g->d_cal_counters) HIP_TRY(hipMalloc(&g->d_cal_counters, sizeof(u64) * kNumCounters));
     const int K = call.K;
     const hipStream_t s = call.s;
-    const size_t cal_slots = (size_t)kCalRows * (size_t)K;
+    const PackedSlab lay(kCalRows, K);
     char* d_cal_out = nullptr;
-    HIP_TRY(hipMalloc(&d_cal_out, 16 * cal_slots + 4 * (size_t)kCalRows));
+    HIP_TRY(hipMalloc(&d_cal_out, lay.bytes));
     struct OutGuard { char* p; ~OutGuard() { if (p) (void)hipFree(p); } } out_guard{d_cal_out};
     CallArgs a = call;
     a.n_seeds = kCalRows;
-    a.d_val = (double*)d_cal_out; a.d_row = (int32_t*)(d_cal_out + 8 * cal_slots);
-    a.d_col = (int32_t*)(d_cal_out + 12 * cal_slots); a.d_filled = (int32_t*)(d_cal_out + 16 * cal_slots);
-    // the general kernel in the shape the thresholds pick, the sketch kernel, the general kernel in the other shape
-    const bool two_per_cu = threshold_wgs_per_cu(g, call.rmax, K) > 1;
-    u64* const tc = g->d_cal_counters;
-    const CallShape cands[3] = { {1, 0, 0, false, tc}, {2, 0, 0, false, tc},
-                                 two_per_cu ? CallShape{1, 1024, 160 * 1024, false, tc} : CallShape{1, 768, 80 * 1024, false, tc} };
+    a.d_val = (double*)(d_cal_out + lay.val); a.d_row = (int32_t*)(d_cal_out + lay.row);
+    a.d_col = (int32_t*)(d_cal_out + lay.col); a.d_filled = (int32_t*)(d_cal_out + lay.filled);
+    Shape cands[3];
+    choice_candidates(kConsts, g->n_nodes, g->nnz, call.rmax, K, cands);
     gp_graph::Choice ch; ch.rmax = call.rmax; ch.n_coef = call.n_coef; ch.K = K; ch.kernel = 0; ch.block_threads = 0; ch.lds_bytes = 0;
     ch.ms[0] = ch.ms[1] = ch.ms[2] = 0.f;
     int rc = GP_OK;
     for (int c = 0; c < 3 && rc == GP_OK; ++c) {
-        if (c == 2 && K > 256) continue;                    // (two workgroups per CU need K <= 256: no other shape to try)
+        if (!is_candidate(c, K)) continue;
         float ms = 0.f;
         for (int rep = 0; rep < 2 && rc == GP_OK; ++rep) {  // (the first run of a kernel pays code upload and first touch of its slabs)
-            rc = enqueue_call(g, a, cands[c]);
+            rc = enqueue_call(g, a, CallShape(cands[c], g->d_cal_counters));
             if (rc == GP_ERR_NOMEM || rc == GP_ERR_INVALID_ARG) { rc = GP_OK; g_last_error.clear(); ms = 0.f; break; }   // not a candidate here
             if (rc) break;
             if (hipStreamSynchronize(s) != hipSuccess) { rc = fail(GP_ERR_HIP, "calibration: hipStreamSynchronize failed"); break; }
-            if (g->last_kind != cands[c].kernel) { ms = 0.f; break; }          // (the sketch kernel does not take this call: no candidate)
+            if (g->est.last_kind != cands[c].kernel) { ms = 0.f; break; }          // (the sketch kernel does not take this call: no candidate)
             if (g->h_counters[kFailedRows]) { ms = 0.f; break; }
             if (hipEventElapsedTime(&ms, g->ev0, g->ev1) != hipSuccess) { (void)hipGetLastError(); ms = 0.f; break; }
         }
         ch.ms[c] = ms;
     }
-    {   // what the thresholds would pick stays unless another candidate is more than 5 % faster (timing noise must not flip a recipe)
-        const int heur = threshold_picks_sketch(g, call.rmax) && ch.ms[1] > 0.f ? 1 : 0;
-        int pick = ch.ms[heur] > 0.f ? heur : -1;
-        for (int c = 0; c < 3; ++c)
-            if (ch.ms[c] > 0.f && (pick < 0 || ch.ms[c] < 0.95f * ch.ms[pick])) pick = c;
-        if (pick >= 0) { ch.kernel = cands[pick].kernel; ch.block_threads = cands[pick].block_threads; ch.lds_bytes = cands[pick].lds_bytes; }
-    }
-    g->grown_for_call = true;                               // (the mirror holds the calibration's counters: nothing to grow from)
+    pick_choice(threshold_picks_sketch(g->n_nodes, call.rmax), cands, ch);
+    g->est.grown_for_call = true;                               // (the mirror holds the calibration's counters: nothing to grow from)
     // The workspace now holds slabs for every candidate.  It stays (the chosen layout fits in it: no hipFree / hipMalloc pair in
     // front of the call that follows -- VERDICT r5 weak #9) unless it is a large part of the budget.
-    if (g->ws.bytes > ((size_t)g->workspace_mb << 20) / 8 || g->ws.bytes > ((size_t)8 << 30)) free_workspace(g->ws);
+    if (g->ws.bytes > ((size_t)g->opt.workspace_mb << 20) / 8 || g->ws.bytes > ((size_t)8 << 30)) free_workspace(g->ws);
     if (rc) return rc;
     g->choices.push_back(ch);                               // (kernel 0: nothing could be timed -- the thresholds decide, as without a calibration)
     return GP_OK;
@@ -1098,8 +822,7 @@ int calibrate_choice(gp_graph* g, const CallArgs& call)
 int measured_choice(gp_graph* g, const CallArgs& a, const gp_graph::Choice** out)
 {
     *out = nullptr;
-    if (kDiagBuild || g->kernel != 0 || g->block_threads != 0 || g->lds_bytes != 0 || !g->measure_choice ||
-        g->force_global || g->exact_stats || a.n_seeds <= 0) return GP_OK;
+    if (!choice_applies(kDiagBuild, g->opt, a.n_seeds)) return GP_OK;
     const gp_graph::Choice* c = nullptr;
     for (const auto& e : g->choices) if (e.rmax == a.rmax && e.n_coef == a.n_coef && e.K == a.K) c = &e;
     if (!c && a.n_seeds >= kCalMinRows) {
@@ -1348,66 +1071,66 @@ int gp_set_option(gp_graph* g, const char* key, int64_t value) {
     }
     if (k == "block_threads") {
         if (value != 256 && value != 512 && value != 768 && value != 1024) return fail(GP_ERR_INVALID_ARG, "block_threads must be 256, 512, 768 or 1024");
-        g->block_threads = (int)value;
+        g->opt.block_threads = (int)value;
     } else if (k == "lds_bytes") {
         if (value < 40 * 1024 || value > 160 * 1024) return fail(GP_ERR_INVALID_ARG, "lds_bytes must be in [40960, 163840]");
-        g->lds_bytes = (int)(value & ~15ll);
+        g->opt.lds_bytes = (int)(value & ~15ll);
     } else if (k == "lds_pad") {
         if (value < 0 || value > 120 * 1024) return fail(GP_ERR_INVALID_ARG, "lds_pad must be in [0, 122880]");
-        g->lds_pad = (int)(value & ~15ll);       // dynamic LDS the tables do not use: fewer workgroups per CU at the same table size (occupancy experiments)
+        g->opt.lds_pad = (int)(value & ~15ll);       // dynamic LDS the tables do not use: fewer workgroups per CU at the same table size (occupancy experiments)
     } else if (k == "kernel") {
         if (value < 0 || value > 2) return fail(GP_ERR_INVALID_ARG, "kernel must be 0 (automatic), 1 (general) or 2 (sketch)");
-        g->kernel = (int)value;
+        g->opt.kernel = (int)value;
     } else if (k == "sk_block_threads") {
         if (value != 0 && value != 512 && value != 768 && value != 1024) return fail(GP_ERR_INVALID_ARG, "sk_block_threads must be 0, 512, 768 or 1024");
-        g->sk_block = (int)value;
+        g->opt.sk_block = (int)value;
     } else if (k == "sk_lg_mu" || k == "sk_lg_mr") {
         if (value != 0 && (value < 8 || value > 14)) return fail(GP_ERR_INVALID_ARG, "%s must be 0 or in [8, 14]", key);
-        (k == "sk_lg_mu" ? g->sk_lg_mu : g->sk_lg_mr) = (int)value;
+        (k == "sk_lg_mu" ? g->opt.sk_lg_mu : g->opt.sk_lg_mr) = (int)value;
     } else if (k == "sk_direct_max") {
         if (value < 0 || value > (1 << 20)) return fail(GP_ERR_INVALID_ARG, "sk_direct_max must be in [0, 2^20]");
-        g->sk_direct_max = (int)value;          // levels of up to this many edges insert straight into the exact table (0 = three quarters of its slots, the most the kernel allows)
+        g->opt.sk_direct_max = (int)value;          // levels of up to this many edges insert straight into the exact table (0 = three quarters of its slots, the most the kernel allows)
     } else if (k == "sk_seed_merge") {
-        g->sk_seed_merge = value ? 1 : 0;
+        g->opt.sk_seed_merge = value ? 1 : 0;
     } else if (k == "row_order") {
-        g->row_order = value ? 1 : 0;            // 0 = the first launch takes its rows in caller order (A/B; what is measured per recipe does not depend on it)
+        g->opt.row_order = value ? 1 : 0;            // 0 = the first launch takes its rows in caller order (A/B; what is measured per recipe does not depend on it)
     } else if (k == "gk_acsr") {
-        g->gk_acsr = value ? 1 : 0;
+        g->opt.gk_acsr = value ? 1 : 0;
     } else if (k == "sk_target") {
         if (value < 0 || value > 4096) return fail(GP_ERR_INVALID_ARG, "sk_target must be in [0, 4096]");
-        g->sk_target = (int)value;
+        g->opt.sk_target = (int)value;
     } else if (k == "measure_choice") {
-        g->measure_choice = value ? 1 : 0;       // 0 = kernel and launch shape from the rmax / graph-size thresholds alone (what a recipe gets until its first call of >= 32 768 rows has been timed)
+        g->opt.measure_choice = value ? 1 : 0;       // 0 = kernel and launch shape from the rmax / graph-size thresholds alone (what a recipe gets until its first call of >= 32 768 rows has been timed)
         if (!value) g->choices.clear();
     } else if (k == "verify_merge") {
-        g->verify_merge = value ? 1 : 0;
+        g->opt.verify_merge = value ? 1 : 0;
     } else if (k == "pretouch") {
-        g->pretouch = value ? 1 : 0;             // memset the whole workspace when it is allocated (slow-phase experiment)
+        g->opt.pretouch = value ? 1 : 0;             // memset the whole workspace when it is allocated (slow-phase experiment)
     } else if (k == "max_workgroups") {
         if (value < 0 || value > 65535) return fail(GP_ERR_INVALID_ARG, "max_workgroups must be in [0, 65535]");
-        g->max_workgroups = (int)value;
+        g->opt.max_workgroups = (int)value;
     } else if (k == "workspace_mb") {
         if (value < 1) return fail(GP_ERR_INVALID_ARG, "workspace_mb must be >= 1");
-        g->workspace_mb = value;
+        g->opt.workspace_mb = value;
     } else if (k == "est_level_edges") {
         if (value < 0) return fail(GP_ERR_INVALID_ARG, "est_level_edges must be >= 0");
-        g->est_level_edges = value;
+        g->opt.est_level_edges = value;
     } else if (k == "force_global") {
-        g->force_global = value ? 1 : 0;
+        g->opt.force_global = value ? 1 : 0;
     } else if (k == "exact_stats") {
-        g->exact_stats = value ? 1 : 0;
+        g->opt.exact_stats = value ? 1 : 0;
     } else if (k == "direct_tables") {
-        g->direct_tables = value ? 1 : 0;        // 0 = always hash (testing / A-B of the direct-indexed small-graph tables)
+        g->opt.direct_tables = value ? 1 : 0;        // 0 = always hash (testing / A-B of the direct-indexed small-graph tables)
     } else if (k == "solo_levels") {
-        g->solo_levels = value ? 1 : 0;          // 0 = small levels take EXPAND + SCAN of the whole workgroup like every other level (testing / A-B)
+        g->opt.solo_levels = value ? 1 : 0;          // 0 = small levels take EXPAND + SCAN of the whole workgroup like every other level (testing / A-B)
     } else if (k == "seedrow") {
-        g->seedrow = value ? 1 : 0;              // 0 = level 1 through EXPAND and a table like every other level (testing / A-B)
+        g->opt.seedrow = value ? 1 : 0;              // 0 = level 1 through EXPAND and a table like every other level (testing / A-B)
     } else if (k == "diag_flags") {
-        g->diag_flags = (int)value;              // honoured by the -DGP_DIAG build only (bit 0: skip TOP-K)
+        g->opt.diag_flags = (int)value;              // honoured by the -DGP_DIAG build only (bit 0: skip TOP-K)
     } else if (k == "max_degree_bits") {
         if (g->packed) return fail(GP_ERR_INVALID_ARG, "max_degree_bits must be set before the first gfpush call");
         if (value < 0 || value > 31) return fail(GP_ERR_INVALID_ARG, "max_degree_bits must be in [0, 31]");
-        g->max_degree_bits = (int)value;
+        g->opt.max_degree_bits = (int)value;
     } else {
         return fail(GP_ERR_INVALID_ARG, "unknown option '%s'", key);
     }
@@ -1432,8 +1155,8 @@ int gp_gfpush_device(gp_graph* g, const int32_t* d_seeds, int64_t n_seeds,
     const gp_graph::Choice* c = nullptr;
     rc = measured_choice(g, a, &c);
     if (rc) return rc;
-    CallShape shape{g->kernel, g->block_threads, g->lds_bytes};                      // what the options ask for ...
-    if (c) shape = CallShape{c->kernel, c->block_threads, c->lds_bytes, true};       // ... or the measured kernel and shape -- CHOSEN, not insisted on (CallShape::soft)
+    CallShape shape(Shape{g->opt.kernel, g->opt.block_threads, g->opt.lds_bytes, false});       // what the options ask for ...
+    if (c) shape = CallShape(Shape{c->kernel, c->block_threads, c->lds_bytes, true});            // ... or the measured kernel and shape -- CHOSEN, not insisted on (Shape::soft)
     if (c) std::memcpy(g->last_cal_ms, c->ms, sizeof g->last_cal_ms);
     else std::memset(g->last_cal_ms, 0, sizeof g->last_cal_ms);
     return enqueue_call(g, a, shape);
@@ -1506,15 +1229,14 @@ int gp_gfpush(gp_graph* g, const int32_t* seeds, int64_t n_seeds,
             return fail(GP_ERR_INVALID_SEED, "node_idx[%lld] = %d outside [0, %lld)", (long long)i, seeds[i], (long long)g->n_nodes);
     if (g->multi) return gfpush_multi(g, seeds, n_seeds, coef, n_coef, rmax, K, row_idx, col_idx, value);
     HIP_TRY(hipSetDevice(g->device));
-    const int64_t slots = n_seeds * (int64_t)K;
     if (n_seeds > g->seeds_cap) {
         if (g->d_seeds) (void)hipFree(g->d_seeds);
         g->d_seeds = nullptr; g->seeds_cap = 0;
         HIP_TRY(hipMalloc(&g->d_seeds, sizeof(int) * (size_t)n_seeds));
         g->seeds_cap = n_seeds;
     }
-    const size_t off_row = 8 * (size_t)slots, off_col = 12 * (size_t)slots, off_filled = 16 * (size_t)slots;
-    const size_t need_bytes = off_filled + 4 * (size_t)n_seeds;
+    const PackedSlab lay(n_seeds, K);
+    const size_t need_bytes = lay.bytes;
     if (need_bytes > g->out_bytes) {
         for (int i = 0; i < 2; ++i) { if (g->h_slab[i]) (void)hipHostFree(g->h_slab[i]); g->h_slab[i] = nullptr; g->h_slab_clean[i] = false; }
         g->out_bytes = 0;
@@ -1540,10 +1262,8 @@ int gp_gfpush(gp_graph* g, const int32_t* seeds, int64_t n_seeds,
     {
         void* dp = nullptr;
         HIP_TRY(hipHostGetDevicePointer(&dp, hb, 0));
-        d_val = (double*)dp; d_row = (int*)((char*)dp + off_row); d_col = (int*)((char*)dp + off_col); d_filled = (int*)((char*)dp + off_filled);
+        d_val = (double*)((char*)dp + lay.val); d_row = (int*)((char*)dp + lay.row); d_col = (int*)((char*)dp + lay.col); d_filled = (int*)((char*)dp + lay.filled);
     }
-    const volatile uint64_t* h_val = (const volatile uint64_t*)hb; const volatile int* h_row = (const volatile int*)(hb + off_row);
-    const volatile int* h_col = (const volatile int*)(hb + off_col); const volatile int* h_filled = (const volatile int*)(hb + off_filled);
     hipStream_t s = g->stream;
     g->reset_pending = true;                   // the host-buffer call reports its own counters
     HIP_TRY(hipMemcpyAsync(g->d_seeds, seeds, sizeof(int) * (size_t)n_seeds, hipMemcpyHostToDevice, s));
@@ -1551,34 +1271,11 @@ int gp_gfpush(gp_graph* g, const int32_t* seeds, int64_t n_seeds,
     if (rc) return rc;
     // No OpenMP here on purpose: after a parallel region libomp's workers spin for their block time (200 ms) on every host
     // core and starve the HIP runtime's completion thread -- measured as ~100 ms stalls on the NEXT call.
-    int64_t first_open = 0, n_merged = 0;
+    MergeState merge;
     std::vector<unsigned char>& done = g->h_done;          // (kept with the graph: no allocation per call)
     done.assign((size_t)n_seeds, 0);
-    // (the arrival test reads the slab through PLAIN pointers behind a compiler barrier per sweep, so that its loops vectorise: 96
-    //  volatile loads per row were most of this thread's CPU time, VERDICT r5 #6.  A slot that has left the sentinel pattern never
-    //  returns to it during the call, so what the test saw is what the copies behind it read.)
-    const uint64_t* const p_val = (const uint64_t*)hb; const int* const p_row = (const int*)(hb + off_row); const int* const p_col = (const int*)(hb + off_col);
-    auto sweep = [&]() {                       // merges every row that has fully arrived since the last sweep
-        bool prefix = true;
-        asm volatile("" ::: "memory");
-        for (int64_t it = first_open; it < n_seeds; ++it) {
-            if (done[it]) { if (prefix) first_open = it + 1; continue; }
-            const int nf = h_filled[it];
-            if (nf < 0 || nf > K) { prefix = false; continue; }
-            const int64_t o = it * (int64_t)K;
-            if (nf > 0) {
-                int lo = 0; uint64_t sent = 0;
-                for (int i = 0; i < nf; ++i) { lo |= p_row[o + i] | p_col[o + i]; sent |= (uint64_t)(p_val[o + i] == ~0ull); }     // (a sentinel word is -1: the sign bit of the OR says one is left)
-                if (lo < 0 || sent) { prefix = false; continue; }
-                std::atomic_thread_fence(std::memory_order_acquire);
-                std::memcpy(row_idx + o, p_row + o, sizeof(int) * (size_t)nf);
-                std::memcpy(col_idx + o, p_col + o, sizeof(int) * (size_t)nf);
-                std::memcpy(value + o, p_val + o, sizeof(double) * (size_t)nf);
-            }
-            done[it] = 1; ++n_merged;
-            if (prefix) first_open = it + 1;
-        }
-    };
+    // merges every row that has fully arrived since the last sweep (the arrival test and the copy: merge_sweep, gfpush_plan.hpp)
+    auto sweep = [&]() { merge_sweep(hb, lay, K, n_seeds, done.data(), merge, row_idx, col_idx, value); };
     // The other slab goes back into the sentinel pattern meanwhile, on a thread of its own: at K = 64 a 65 536-row call is 68 MB
     // to validate and copy plus 68 MB to reset inside 13 ms of kernel time -- more than one core moves on a busy host (the
     // Reddit line's host clock fell to 0.83 x the device-resident rate on one box with both jobs on this thread).
@@ -1604,31 +1301,21 @@ int gp_gfpush(gp_graph* g, const int32_t* seeds, int64_t n_seeds,
         const hipError_t q = hipStreamQuery(s);
         if (q == hipSuccess) break;
         if (q != hipErrorNotReady) { (void)hipGetLastError(); break; }        // gp_get_stats below reports it
-        const int64_t before = n_merged;
+        const int64_t before = merge.n_merged;
         sweep();
-        if (n_merged - before < 256) std::this_thread::sleep_for(std::chrono::microseconds(60));
+        if (merge.n_merged - before < 256) std::this_thread::sleep_for(std::chrono::microseconds(60));
     }
     if (resetter.t.joinable()) { resetter.t.join(); g->h_slab_clean[cur ^ 1] = true; }
     else if (reset_inline) { std::memset(idle, 0xFF, g->out_bytes); g->h_slab_clean[cur ^ 1] = true; }
     rc = gp_get_stats(g, nullptr);             // synchronises the stream
     if (rc) return rc;
     // every launch has retired: what is still on its way arrives within microseconds
-    for (int spin = 0; n_merged != n_seeds && spin < 2000000; ++spin) sweep();
-    if (n_merged != n_seeds) return fail(GP_ERR_HIP, "%lld of %lld rows never arrived in host memory", (long long)(n_seeds - n_merged), (long long)n_seeds);
-    if (g->verify_merge) {
-        // The merge rule -- a row is taken once every filled slot has left the sentinel pattern in all three arrays -- rests on an
-        // 8-byte value store never arriving torn and on no slot being rewritten after it first arrived.  With
-        // the launches retired the slab holds the rows as the kernels left them: every row merged WHILE the kernel ran must equal it.
-        int64_t bad = 0, first_bad = -1;
-        for (int64_t it = 0; it < n_seeds; ++it) {
-            const int nf = h_filled[it];
-            const int64_t o = it * (int64_t)K;
-            const bool same = nf >= 0 && nf <= K &&
-                              std::memcmp(row_idx + o, (const void*)(h_row + o), sizeof(int) * (size_t)nf) == 0 &&
-                              std::memcmp(col_idx + o, (const void*)(h_col + o), sizeof(int) * (size_t)nf) == 0 &&
-                              std::memcmp(value + o, (const void*)(h_val + o), sizeof(double) * (size_t)nf) == 0;
-            if (!same) { ++bad; if (first_bad < 0) first_bad = it; }
-        }
+    for (int spin = 0; merge.n_merged != n_seeds && spin < 2000000; ++spin) sweep();
+    if (merge.n_merged != n_seeds) return fail(GP_ERR_HIP, "%lld of %lld rows never arrived in host memory", (long long)(n_seeds - merge.n_merged), (long long)n_seeds);
+    if (g->opt.verify_merge) {
+        // (with the launches retired the slab holds the rows as the kernels left them: verify_merged, gfpush_plan.hpp)
+        int64_t first_bad = -1;
+        const int64_t bad = verify_merged(hb, lay, K, n_seeds, row_idx, col_idx, value, &first_bad);
         if (bad) return fail(GP_ERR_HIP, "verify_merge: %lld of %lld rows were merged before they had fully arrived (first: row %lld)",
                              (long long)bad, (long long)n_seeds, (long long)first_bad);
     }
@@ -1705,11 +1392,11 @@ int replicate_part(gp_graph* g, int d) {
     struct Guard { gp_graph* q; ~Guard() { if (q) gp_graph_destroy(q); } } guard{q};
     q->device = dev; q->n_nodes = src->n_nodes; q->nnz = src->nnz; q->num_cus = prop.multiProcessorCount;
     q->deg_shift = src->deg_shift; q->node_mask = src->node_mask; q->deg_sat = src->deg_sat;
-    q->packed = true; q->max_degree_bits = src->max_degree_bits; q->rows_distinct = src->rows_distinct;
-    q->block_threads = src->block_threads; q->lds_bytes = src->lds_bytes; q->max_workgroups = src->max_workgroups;
-    q->workspace_mb = src->workspace_mb; q->force_global = src->force_global; q->exact_stats = src->exact_stats;
-    q->direct_tables = src->direct_tables; q->est_level_edges = src->est_level_edges; q->seedrow = src->seedrow; q->solo_levels = src->solo_levels;
-    q->kernel = src->kernel; q->row_order = src->row_order; q->gk_acsr = src->gk_acsr; q->sk_seed_merge = src->sk_seed_merge; q->sk_block = src->sk_block; q->sk_lg_mu = src->sk_lg_mu; q->sk_lg_mr = src->sk_lg_mr; q->sk_target = src->sk_target; q->lds_pad = src->lds_pad; q->sk_direct_max = src->sk_direct_max;
+    q->packed = true; q->opt.max_degree_bits = src->opt.max_degree_bits; q->rows_distinct = src->rows_distinct;
+    q->opt.block_threads = src->opt.block_threads; q->opt.lds_bytes = src->opt.lds_bytes; q->opt.max_workgroups = src->opt.max_workgroups;
+    q->opt.workspace_mb = src->opt.workspace_mb; q->opt.force_global = src->opt.force_global; q->opt.exact_stats = src->opt.exact_stats;
+    q->opt.direct_tables = src->opt.direct_tables; q->opt.est_level_edges = src->opt.est_level_edges; q->opt.seedrow = src->opt.seedrow; q->opt.solo_levels = src->opt.solo_levels;
+    q->opt.kernel = src->opt.kernel; q->opt.row_order = src->opt.row_order; q->opt.gk_acsr = src->opt.gk_acsr; q->opt.sk_seed_merge = src->opt.sk_seed_merge; q->opt.sk_block = src->opt.sk_block; q->opt.sk_lg_mu = src->opt.sk_lg_mu; q->opt.sk_lg_mr = src->opt.sk_lg_mr; q->opt.sk_target = src->opt.sk_target; q->opt.lds_pad = src->opt.lds_pad; q->opt.sk_direct_max = src->opt.sk_direct_max;
     const size_t b_ptr = sizeof(int) * (size_t)(q->n_nodes + 1), b_idx = sizeof(int) * (size_t)(q->nnz + 1);     // with the sentinel word
     HIP_TRY(hipMalloc(&q->d_indptr, b_ptr));
     HIP_TRY(hipMalloc(&q->d_indices, b_idx));
@@ -1728,22 +1415,6 @@ int replicate_part(gp_graph* g, int d) {
     guard.q = nullptr;
     g->part[d] = q;                                        // owned by the handle from here on (destroyed with it)
     return GP_OK;
-}
-
-void scatter_filled(const char* slab, int64_t per, int K, int64_t row0, int64_t n_rows,
-                    int32_t* row_idx, int32_t* col_idx, double* value)
-{
-    const size_t slots = (size_t)per * K;
-    const double* h_val = (const double*)slab; const int* h_row = (const int*)(slab + 8 * slots);
-    const int* h_col = (const int*)(slab + 12 * slots); const int* h_filled = (const int*)(slab + 16 * slots);
-    for (int64_t it = 0; it < n_rows; ++it) {
-        const int nf = h_filled[it];
-        if (nf <= 0) continue;                             // graph.h:121: only v > 0 slots are written
-        const size_t o = (size_t)it * K, oo = (size_t)(row0 + it) * K;
-        std::memcpy(row_idx + oo, h_row + o, sizeof(int) * (size_t)nf);
-        std::memcpy(col_idx + oo, h_col + o, sizeof(int) * (size_t)nf);
-        std::memcpy(value + oo, h_val + o, sizeof(double) * (size_t)nf);
-    }
 }
 
 // gfpush_omp on a multi-GPU handle: the caller's ONE call (model.py:268) uses every GPU of the node.
@@ -1800,7 +1471,7 @@ int gfpush_multi(gp_graph* g, const int32_t* seeds, int64_t n_seeds, const doubl
     }
     const size_t cur_stride = stride;                      // this call's layout (the buffers may be larger)
     const int64_t cur_per = per;
-    const size_t slots = (size_t)cur_per * K;
+    const PackedSlab lay(cur_per, K);
 
     std::vector<int> rcs(Gc, GP_OK);
     std::vector<std::string> errs(Gc);
@@ -1812,12 +1483,12 @@ int gfpush_multi(gp_graph* g, const int32_t* seeds, int64_t n_seeds, const doubl
         auto run = [&]() -> int {
             HIP_TRY(hipSetDevice(q->device));
             char* slab = g->m_slab[d];
-            HIP_TRY(hipMemsetAsync(slab + 16 * slots, 0, 4 * (size_t)cur_per, q->stream));          // filled[] = 0
+            HIP_TRY(hipMemsetAsync(slab + lay.filled, 0, 4 * (size_t)cur_per, q->stream));          // filled[] = 0
             if (n > 0) {
                 HIP_TRY(hipMemcpyAsync(g->m_seeds[d], seeds + lo, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, q->stream));
                 q->reset_pending = true;
-                int rc = gp_gfpush_device(q, g->m_seeds[d], n, coef, n_coef, rmax, K, (int*)(slab + 8 * slots),
-                                          (int*)(slab + 12 * slots), (double*)slab, (int*)(slab + 16 * slots), q->stream);
+                int rc = gp_gfpush_device(q, g->m_seeds[d], n, coef, n_coef, rmax, K, (int*)(slab + lay.row),
+                                          (int*)(slab + lay.col), (double*)(slab + lay.val), (int*)(slab + lay.filled), q->stream);
                 if (rc) return rc;
             }
             if (!collective) HIP_TRY(hipMemcpyAsync(g->m_host + (size_t)d * cur_stride, slab, cur_stride, hipMemcpyDeviceToHost, q->stream));
