@@ -49,6 +49,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gfpush_hash.hpp"
+
 namespace gp {
 
 typedef unsigned long long u64;
@@ -121,9 +123,7 @@ constexpr u32    kBucketMin  = GP_BUCKET_MIN;       // levels needing at least t
                                         // instead of re-reading and hash-filtering every CSR range once per partition
 constexpr u32    kSkUnitShift = 5;      // sketch kernel: its self-addressed CSR starts every row at a unit of 32 column words (128 bytes)
 constexpr u32    kSkMaxPushers = 65536; // ... and numbers the pushers of a row with 16 bits in its log
-constexpr u32    kMaxProbe   = 24;      // an LDS insert that probes this many slots reports overflow
-constexpr u32    kProbeSpan  = kMaxProbe * (kMaxProbe + 1) / 2;   // furthest a triangular probe sequence can walk (300 slots)
-                                        // (recoverable: the level / aggregation is redone in more partitions)
+// (kMaxProbe / kProbeSpan -- the probe limit of every LDS table -- live in gfpush_hash.hpp with the hashes)
 
 // Push list of a level: one entry per pushing node, in the order of `off`.  The level's edges are numbered 0 .. E-1 in list
 // order; entry i covers edges [off_i, off_{i+1}) and edge q of it is column word rel + q of the CSR (rel = CSR start - off,
@@ -237,6 +237,18 @@ enum Counter { kQueue = 0, kQueueRetry, kRetryRows,          // zeroed at every 
                                                     //   k = 0 expand ticks, 1 scan ticks, 2 edges, 3 frontier nodes, 4 push entries, 5 table passes
                kNumCounters };
 
+// Overflow recoveries of the LDS hash tables, counted in the product build in diag_sub slots neither kernel uses there (the sketch
+// kernel: 1..7, why rows left).  Each increment sits on the branch that already handles the overflow -- one thread, one global
+// atomic, nothing on the common path.  The instrumented builds use all sixteen slots for their ticks and count nothing here.
+enum OvfCount { kOvfLevel = 8,      // a level table that overflowed was wiped and the level re-streamed / split in two (both kernels)
+                kOvfSolo = 9,       // a one-wave level undid its claims (both kernels)
+                kOvfTopk = 10 };    // the sketch kernel's TOP-K aggregation table overflowed: once per doubling of its partitions
+#if !defined(GP_DIAG) && !defined(GP_SK_TIMING)
+#define GP_OVF_COUNT(p, which) __hip_atomic_fetch_add(&(p).counters[kDiag0 + (which)], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+#else
+#define GP_OVF_COUNT(p, which) do { } while (0)
+#endif
+
 // Phase stamps exist only in the diagnostic build (-DGP_DIAG): thread 0 reads the constant
 // 100 MHz clock at phase boundaries.  The product build compiles them to nothing.
 // Workgroup barrier.  The diagnostic build measures what the waves spend waiting at it (shader cycles).
@@ -340,21 +352,8 @@ __device__ __forceinline__ void csr_row(KP p, u32 key, int& ds, int& de) {
 }
 
 // ---------------------------------------------------------------- small helpers
-// Multiplicative (Fibonacci-style) hashes; slot_of() consumes the HIGH bits.
-__device__ __forceinline__ u32 hash_a(u32 k) {            // residue / aggregation tables
-    k *= 0x9E3779B1u; k ^= k >> 15; k *= 0x85EBCA77u;
-    return k;
-}
-__device__ __forceinline__ u32 hash_b(u32 k) {            // partition choice (independent of hash_a)
-    k *= 0x7FEB352Du; k ^= k >> 16; k *= 0x846CA68Bu;
-    return k;
-}
-__device__ __forceinline__ u32 slot_of(u32 h, u32 cap) { return (u32)(((u64)h * cap) >> 32); }
-// Home slot in an LDS table of `cap` slots.  Homes lie in [0, cap - kProbeSpan): a probe sequence then
-// never leaves [0, cap), so the probing loops need no wrap-around (4 VALU per probe); 2 % of a full
-// table is the price.  Every LDS table has cap >= kMinCap > kProbeSpan.
+// hash_a / hash_b / slot_of / home_lds: gfpush_hash.hpp (HIP-free, checked on the CPU).
 static_assert(kMinCap > 2 * kProbeSpan, "every LDS table must be much larger than the probe span");
-__device__ __forceinline__ u32 home_lds(u32 k, u32 cap) { return slot_of(hash_a(k), cap - kProbeSpan); }
 
 // L2-coherent (L1-bypassing) accesses for tables that are also touched by atomics.
 template <class T> __device__ __forceinline__ T ld_l2(const T* p) {
@@ -2125,7 +2124,7 @@ __device__ GP_PHASE_NOINLINE u32 phase_bucketed_level(u32 lds0, u32 cap, u32 P, 
             if (ctl->ovf) {
                 wipe_table<BLOCK>(lkeys, lvals, w.C);
                 GP_SYNC();
-                if (tid == 0) ctl->ovf = 0;
+                if (tid == 0) { ctl->ovf = 0; GP_OVF_COUNT(p, kOvfLevel); }
                 if (Q < (1u << 20)) { q *= 2; Q *= 2; GP_SYNC(); continue; }
                 if (tid == 0) ctl->fail = 1;
                 GP_SYNC();
@@ -2447,7 +2446,7 @@ __device__ __forceinline__ void gfpush_rows()
                 GP_SYNC();
                 GP_STAMP(t2); GP_ACCUM(tk_scan, t0, t2);
                 if (!uni(ctl->ovf)) solo_done = true;
-                else { GP_SYNC(); if (tid == 0) ctl->ovf = 0; GP_SYNC(); }      // (undone by the wave: the general path takes the level)
+                else { GP_SYNC(); if (tid == 0) { ctl->ovf = 0; GP_OVF_COUNT(p, kOvfSolo); } GP_SYNC(); }      // (undone by the wave: the general path takes the level)
             }
             if (!solo_done && !use_buckets && !uni(ctl->fail)) {
                 {
@@ -2486,7 +2485,7 @@ __device__ __forceinline__ void gfpush_rows()
                             // this partition did not fit: wipe the table and split it in two
                             wipe_table<BLOCK>(lkeys, lvals, C);
                             GP_SYNC();
-                            if (tid == 0) ctl->ovf = 0;
+                            if (tid == 0) { ctl->ovf = 0; GP_OVF_COUNT(p, kOvfLevel); }
                             if (in_lds && !direct) cap = C;      // (a single-pass table sized from the estimate may have been smaller)
                             if (np < 0x20000000u) { part *= 2; np *= 2; GP_SYNC(); continue; }
                             if (tid == 0) ctl->fail = 1;

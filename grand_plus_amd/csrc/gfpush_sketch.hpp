@@ -61,7 +61,6 @@ namespace gp {
 #endif
 constexpr int kSkMaxCoef = 40;            // levels the control block has room for (longer recipes: general kernel)
 constexpr u32 kSkTie     = 256;           // the select ranks at most this many candidates by comparison
-constexpr u32 kSkMul24   = 0x9E3779u;     // sketch hash: cell = top bits of (low 24 bits of the key) * kSkMul24 -- a FULL-RATE multiply (sk_cell)
 
 struct CtlS {
     long long row;
@@ -148,16 +147,7 @@ __device__ __forceinline__ SkView sk_view(KP p, u32 lds0) {
     w.arch    = p.arch + (u64)wg * (u32)p.arch_cap;
     return w;
 }
-// The sketch-cell hash of a key (cells are indexed by its top bits).  v_mul_u32_u24, not v_mul_lo_u32: the full 32 x 32-bit
-// multiply issues at a quarter of the rate, and this hash is computed per edge in STREAM and per record in FILTER and in TOP-K's sweep.
-// (Which nodes share a cell is irrelevant for a bound that only ever adds; the low 24 bits of a key are its unit number on every
-// graph of up to 2^24 units.)
-__device__ __forceinline__ u32 sk_cell(u32 key) { return __umul24(key, kSkMul24); }
-// Home slot of a key in this kernel's LDS tables: the C++ twin of GP_IW4_HASHES (gfpush_kernels.hpp), full-rate multiplies only.
-__device__ __forceinline__ u32 sk_home(u32 k, u32 cap) {
-    u32 h = __umul24(k, 0x9E3779u); h ^= h >> 15; h = __umul24(h, 0x85EBCBu);
-    return __umul24(h >> 16, cap - kProbeSpan) >> 16;
-}
+// sk_cell / sk_home (this kernel's cell and home-slot hashes, full-rate 24-bit multiplies) and kSkMul24: gfpush_hash.hpp.
 __device__ __forceinline__ bool sk_res_add_lds(int* keys, double* vals, u32 cap, int k, double v) {      // res_add_lds with this kernel's hash
     u32 slot = sk_home((u32)k, cap);
     const int seen = probe_cas_asm(keys, slot, k);
@@ -764,6 +754,7 @@ __device__ GP_PHASE_NOINLINE void phase_sk_solo(u32 lds0, u32 cur, u32 n_ent, u3
     asm volatile("" ::: "memory");
     if (uni(ctl->ovf)) {                      // undo: the claimed slots are all there is
         for (u32 j = lane; j < n_list; j += 64u) { const u32 sl = list[j]; lkeys[sl] = kEmpty; lvals[sl] = 0.0; }
+        if (lane == 0) GP_OVF_COUNT(p, kOvfSolo);
         return;
     }
     // ---- SCAN over the claimed slots
@@ -1060,7 +1051,14 @@ __device__ GP_PHASE_NOINLINE void phase_sk_topk(u32 lds0, u32 row_lo, u32 row_hi
                     GP_SYNC();
                 }
                 table_ready = false;
-                if (mine.key != kEmpty && !sk_res_add_lds(t.akeys, t.avals, t.CA, mine.key, __longlong_as_double((long long)mine.bits))) ctl->ovf = 1;
+                // The running list goes back into the (wiped) table so that the select sees it -- at the table's LAST slots, not
+                // through the hash: its keys belong to earlier partitions, no record of this one looks them up, and K best that
+                // share a home slot (25 of them exhaust a probe sequence) used to overflow every partition of every P until the
+                // row left with fail = 4.  To this partition's inserts they are occupied slots like any other.
+                if (n_run != 0u) {
+                    if (mine.key != kEmpty) { t.akeys[t.CA - 1u - (u32)tid] = mine.key; t.avals[t.CA - 1u - (u32)tid] = __longlong_as_double((long long)mine.bits); }
+                    GP_SYNC();
+                }
                 auto tabled = [&](const int (&k)[4], const u32 (&pu)[4], auto all_valid) {
                     constexpr bool kAll = decltype(all_valid)::value;                 // every record of the group is one: no guards
                     u32 cell[4]; double cv[4];
@@ -1088,7 +1086,7 @@ __device__ GP_PHASE_NOINLINE void phase_sk_topk(u32 lds0, u32 row_lo, u32 row_hi
             }
             if (!ovf) break;
             GP_SYNC();
-            if (tid == 0) ctl->ovf = 0;
+            if (tid == 0) { ctl->ovf = 0; GP_OVF_COUNT(p, kOvfTopk); }
             P *= 2; need = 0;
             if (P > 64u) { if (tid == 0) ctl->fail = 4; GP_SYNC(); return; }          // (4: tens of thousands of nodes around the K-th value)
             GP_SYNC();
@@ -1218,7 +1216,11 @@ __device__ GP_PHASE_NOINLINE u32 phase_sk_seed(u32 lds0, int seed)
 
 // One level l = 1..L of a row (graph.h:83-110).  Returns 0 when the row's levels are done (last level, dead frontier, or the row
 // leaves: ctl->fail), 1 to go on.  Every path out has passed the level's last barrier or has touched nothing shared.
-template <int BLOCK>
+// REDO: level 1 once more, after wave 0 ran it behind level 0 (phase_sk_seed) and an insert hit the probe limit.  That attempt has
+// written the level's log records, its reserve-sketch adds and its count in zLevels, and has undone its claims; ctl->ovf is still
+// set.  So no second one-wave attempt and no stream that writes records: the level goes straight to the wipe and the partition
+// walk, as a one-wave level that overflows inside this function does.
+template <int BLOCK, bool REDO = false>
 __device__ __forceinline__ u32 phase_sk_level(u32 lds0, u32 lvl, u32 L)
 {
     KP p = kparams();
@@ -1252,7 +1254,7 @@ __device__ __forceinline__ u32 phase_sk_level(u32 lds0, u32 lvl, u32 L)
         ctl->tot_pu = pu_next; ctl->tot_log = log_pos + n_rec; ctl->max_e = max(ctl->max_e, e_cur);
         ctl->lv_has_dang = has_dang_cur ? 1u : 0u; ctl->lv_dang = dang_cur;
         if (has_dang_cur) w.arch[pu_cur + n_ent_cur] = uni(c_) * dang_cur;        // graph.h:92: the record of the mass returned to the seed
-        zstat(ctl, zLevels, 1);
+        if (!REDO) zstat(ctl, zLevels, 1);
     }
     const double cs = uni(c_) * uni(krs_);                                        // reserve-sketch units per unit of share
     const double cnext = last ? 0.0 : uni(c1_);
@@ -1284,9 +1286,11 @@ __device__ __forceinline__ u32 phase_sk_level(u32 lds0, u32 lvl, u32 L)
     // (a one-wave level must not be able to hit a workspace bound other than through its own checks: the boundary table must
     //  hold the largest level any frontier can produce -- degrees pushed in one level sum to <= 1/rmax)
     //  -- that part of the test does not change during a launch: k_solo_ok)
-    const bool solo = uni(kso_) && direct && e_cur <= kSkSoloEdges && n_ent_cur >= 1u && n_ent_cur <= 64u &&
+    const bool solo = !REDO && uni(kso_) && direct && e_cur <= kSkSoloEdges && n_ent_cur >= 1u && n_ent_cur <= 64u &&
                       (u64)pu_next + kSkSoloEdges + 4u <= pu_cap;
-    if (solo) {
+    if (REDO) {
+        // (nothing to stream: see above)
+    } else if (solo) {
         if (wave_id() == 0)
             phase_sk_solo<BLOCK>(lds0, cur, n_ent_cur, e_cur, seg_base, cs, has_dang_cur ? 1u : 0u, dang_cur, seed_key, lvl & 1u, pu_cur, pu_next, cnext);
         GP_SYNC();
@@ -1312,6 +1316,7 @@ __device__ __forceinline__ u32 phase_sk_level(u32 lds0, u32 lvl, u32 L)
         if (!uni(ctl->ovf)) level_done = true;                                    // (the wave wrote the next push list and lc[lvl & 1] itself)
         else { capx = CX; }                                                       // undone: re-stream the level (first pass below sees ctl->ovf)
     }
+    if (REDO) capx = CX;
     if (!level_done)
     for (;;) {
         if (!(first && direct && P0 == 1u)) {
@@ -1327,7 +1332,7 @@ __device__ __forceinline__ u32 phase_sk_level(u32 lds0, u32 lvl, u32 L)
         if (uni(ctl->ovf)) {
             phase_sk_wipe<BLOCK>(lds0, 2u, by_log ? cap0 : CX, 0u);                              // (a sketch level's share table lives behind slot cap0)
             GP_SYNC();
-            if (tid == 0) ctl->ovf = 0;
+            if (tid == 0) { ctl->ovf = 0; GP_OVF_COUNT(p, kOvfLevel); }
             if (!by_log) capx = CX;
             if (np < 0x10000u) { part *= 2; np *= 2; GP_SYNC(); continue; }
             if (tid == 0) ctl->fail = 5;                                          // (5: a level's candidates in > 65 536 partitions)
@@ -1359,6 +1364,10 @@ __device__ __forceinline__ u32 phase_sk_level(u32 lds0, u32 lvl, u32 L)
     }
     return 1u;
 }
+
+// (its own function with its own register allocation: inlined into the row loop beside the ordinary level it grew the loop's code by a third)
+template <int BLOCK>
+__device__ GP_PHASE_NOINLINE u32 phase_sk_level1_redo(u32 lds0, u32 L) { return phase_sk_level<BLOCK, true>(lds0, 1u, L); }
 
 template <int BLOCK>
 __device__ __forceinline__ void gfpush_sk_rows()
@@ -1414,7 +1423,11 @@ __device__ __forceinline__ void gfpush_sk_rows()
         u32 lvl = 1u + uni(phase_sk_seed<BLOCK>(lds0, seed));                     // (2: wave 0 has done level 1 as well)
         GP_SYNC();
         SKT(ctl, 0); SKT_COUNT(ctl, 15, 1);
-        if (lvl == 2u) { SKT_COUNT(ctl, 13, 1); if (uni(ctl->ovf)) lvl = 1u; }   // (an insert at the probe limit: the claims are undone, level 1 takes the general path)
+        if (lvl == 2u) {
+            SKT_COUNT(ctl, 13, 1);
+            // (an insert at the probe limit: the claims are undone, level 1 is walked in partitions -- L >= 2 here)
+            if (uni(ctl->ovf)) lvl = uni(phase_sk_level1_redo<BLOCK>(lds0, L)) ? 2u : L + 1u;
+        }
         for (; lvl <= L; ++lvl)
             if (!uni(phase_sk_level<BLOCK>(lds0, lvl, L))) break;
         GP_SYNC();

@@ -65,6 +65,10 @@ typedef struct gp_stats {
     int64_t diag_ticks_scan, diag_ticks_expand, diag_ticks_topk, diag_ticks_total;
     int64_t diag_ticks_scan_hbm, diag_ticks_expand_hbm;   /* the part of scan/expand spent on HBM-table levels */
     int64_t diag_sub[16];    /* free-form sub-phase ticks / counts of the diagnostic build          */
+    /* In the product library the slots count what is rare instead: [1..7] rows the sketch kernel handed back, by reason;
+     * [8] LDS level tables that overflowed (an insert probed 24 slots) and were wiped and re-streamed / split in two -- both
+     * kernels; [9] one-wave levels that undid their claims -- both kernels; [10] doublings of the partitions of the sketch
+     * kernel's TOP-K aggregation after an overflow.  [0], [11..15] stay 0.  Each is counted on the branch that recovers. */
     /* ABI 2: workspace policy.  Every workgroup's scratch slab is sized from an estimate; rows that outgrow it are
      * re-run by a second launch on a few workgroups whose slabs are sized from the rigorous 1/rmax bounds. */
     int64_t retried_rows;    /* rows that took that second launch (they are complete and exact, just slower) */

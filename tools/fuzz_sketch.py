@@ -2,7 +2,9 @@
 """Time-bounded randomised differential test of the sketch kernel against the CPU oracle on graphs large enough for sketch
 levels, partition walks and partitioned TOP-K rounds: random power-law graphs (65 k - 400 k nodes, average degree 4 - 40),
 random recipes (levels, coefficients, rmax 5e-6 .. 2e-4, K 1 .. 128), random sketch geometries, duplicate and hub seeds.
-Rows tie-aware identical, pushes / edges / filled exactly the oracle's.   Usage: python tools/fuzz_sketch.py [seconds] [first case]   (FUZZ_KERNEL=1: the general kernel under its launch shapes, rmax down to 1e-6)"""
+Rows tie-aware identical, pushes / edges / filled exactly the oracle's.   Usage: python tools/fuzz_sketch.py [--adversarial] [seconds] [first case]   (FUZZ_KERNEL=1: the general kernel under its launch shapes, rmax down to 1e-6)
+--adversarial: the graph of tests/collision_cases.py instead, its seeds' rows -- 64 targets with ONE home slot at every table
+capacity, and their controls -- among the random seeds: every case overflows tables (gp_stats.diag_sub[8..10] are printed)."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -10,13 +12,19 @@ import numpy as np
 from grand_plus_amd import synth
 from test_gpu_parity import _assert_parity, _oracle, _run_gpu
 
-budget = float(sys.argv[1]) if len(sys.argv) > 1 else 300.0
-case = int(sys.argv[2]) if len(sys.argv) > 2 else 0
+adversarial = "--adversarial" in sys.argv[1:]
+args = [a for a in sys.argv[1:] if a != "--adversarial"]
+budget = float(args[0]) if len(args) > 0 else 300.0
+case = int(args[1]) if len(args) > 1 else 0
+if adversarial:
+    import collision_cases
+    adv = collision_cases.cases()
 t0 = time.time(); done = 0; kinds = {}
 while time.time() - t0 < budget:
     rng = np.random.default_rng(77000 + case)
     n = int(rng.integers(65536, 400000))
-    indptr, indices = synth.powerlaw_csr(n, int(n * rng.uniform(2, 20)), seed=int(rng.integers(1, 1 << 30)), offset=int(rng.integers(2, 30)))
+    if adversarial: n, indptr, indices = adv.n, adv.indptr, adv.indices
+    else: indptr, indices = synth.powerlaw_csr(n, int(n * rng.uniform(2, 20)), seed=int(rng.integers(1, 1 << 30)), offset=int(rng.integers(2, 30)))
     L = int(rng.integers(2, 11))
     mode = rng.choice(["ppr", "avg", "rand"])
     if mode == "ppr":
@@ -49,6 +57,11 @@ while time.time() - t0 < budget:
     if g == 4: opts.update(sk_direct_max=int(rng.choice([1, 64, 100000])))
     if g == 5: opts.update(sk_lg_mu=9, sk_lg_mr=8)
     if case % 5 == 4: opts.update(sk_seed_merge=0) if opts["kernel"] == 2 else opts.update(gk_acsr=0)    # (round 6) the paths the new defaults replace
+    if adversarial:                                        # the seeds whose rows collide under the hash of the kernel that runs, and their controls
+        fam = "sk" if opts["kernel"] == 2 else ("gp" if opts.get("gk_acsr") == 0 else "ga")
+        if fam != "sk": opts.update(block_threads=512, lds_bytes=53248)        # (the table size the general kernel's sets are worked out for)
+        seeds[16:22] = np.concatenate([adv.seeds(fam, "adv"), adv.seeds(fam, "ctl")])
+        rmax = min(rmax, 1.0 / (collision_cases.HUB_LEN * 4))                  # every member of a set pushes
     if case % 2: opts.update(max_workgroups=int(rng.choice([3, 8, 64])))       # a workgroup takes MANY rows one after the other (round 5: state left behind by a row)
     label = f"fuzz {case}: n {n} nnz {len(indices)} {mode} L{L} rmax {rmax:.2e} K{K} {opts}"
     got, st = _run_gpu(indptr, indices, seeds, coef, rmax, K, options=opts)
@@ -57,6 +70,6 @@ while time.time() - t0 < budget:
     assert (st["pushes"], st["edges"], st["filled"]) == (ost["pushes"], ost["edges"], ost["filled"]), (label, st, ost)
     assert st["failed_rows"] == 0, label
     kinds[st["kernel"]] = kinds.get(st["kernel"], 0) + 1
-    print(f"ok {label}: kernel {st['kernel']} retried {st['retried_rows']} cand {st['sketch_candidate_edges']} sweeps2 {st['sketch_second_sweeps']} edges/row {st['edges'] / S:.0f}", flush=True)
+    print(f"ok {label}: kernel {st['kernel']} retried {st['retried_rows']} cand {st['sketch_candidate_edges']} sweeps2 {st['sketch_second_sweeps']} overflows {st['diag_sub'][8:11]} edges/row {st['edges'] / S:.0f}", flush=True)
     done += 1; case += 1
 print(f"fuzz_sketch: {done} cases passed in {time.time() - t0:.0f} s; kernels used {kinds}")
