@@ -15,6 +15,7 @@ _GOLDEN = 0x9E3779B97F4A7C15
 _LAYER_MUL = 0xA0761D6478BD642F
 _SLOT_MUL = 0xE7037ED1A0B428DB
 _STEP_MUL = 0x8CB92BA72F3D8DD7
+_FIT_ROUND_MUL, _FIT_EPOCH_MUL, _FIT_UNLABEL_MUL = 0xC2B2AE3D27D4EB4F, 0x165667B19E3779F9, 0x27D4EB2F165667C5   # csrc/fit_perm.hpp
 
 _seed_counter = itertools.count(0x5EED)
 
@@ -49,6 +50,24 @@ def mag_slot_seed(seed: int, s: int, e: int) -> int:
 def step_seed(base: int, t: int) -> int:
     """Seed of step t >= 1 of a training run with `base` (gp_step_state.seed of grandplus_step.h): mix(base ^ t * GP_STEP_MUL)."""
     return _mix((base & _M64) ^ ((t * _STEP_MUL) & _M64))
+
+
+def perm_index(key: int, n: int, i: int) -> int:
+    """The image of i < n under the keyed permutation of [0, n) of csrc/fit_perm.hpp, 1 <= n < 2**31: a 4-round
+    Feistel network over an even number of bits, walked along its cycle until it lands below n."""
+    if not 1 <= n < 2**31 or not 0 <= i < n:
+        raise ValueError(f"perm_index needs 1 <= n < 2**31 and 0 <= i < n, got n={n}, i={i}")
+    h = (max((n - 1).bit_length(), 2) + 1) // 2
+    mask = (1 << h) - 1
+    key &= _M64
+    x = i
+    while True:
+        L, R = x >> h, x & mask
+        for r in range(4):
+            L, R = R, L ^ (_mix(key ^ (((r + 1) * _FIT_ROUND_MUL) & _M64) ^ R) & mask)
+        x = (L << h) | R
+        if x < n:
+            return x
 
 
 def _check(t, dtype, name):

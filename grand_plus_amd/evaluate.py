@@ -187,7 +187,25 @@ def valid(model, rows, features, idx_val, labels, batch_size=10000, dropnode_rat
 
     model: a GrandPlusMLP, or a MagMLP with `features` = the [N, H] embedding the caller computed in eval mode
     (`model.emb_csr(...)` over all nodes): the MLP is then applied to the propagated embedding, as model_mag.py does."""
-    from .augment import random_prop_rows
+    loss, acc, counts = valid_pass(valid_plan(model, rows, features, idx_val, labels, batch_size), dropnode_rate)
+    return (loss, acc, counts) if return_counts else (loss, acc)
+
+
+class ValidPlan(NamedTuple):
+    """What `valid` prepares once for a validation set: its arguments as checked, the node ids on the device, their
+    positions in `rows` and the evaluation buffers.  `valid_pass` runs over it any number of times (the fit loop)."""
+    model: torch.nn.Module
+    rows: object
+    features: torch.Tensor
+    labels: torch.Tensor
+    idx: torch.Tensor
+    pos: torch.Tensor
+    buf: EvalBuffers
+    batch_size: int
+
+
+def valid_plan(model, rows, features, idx_val, labels, batch_size=10000):
+    """The checks, the one position lookup (KeyError for a node that is no seed) and the buffers of `valid`."""
     from .rows import RowMatrix
     if not isinstance(rows, RowMatrix):
         raise TypeError("rows must be a RowMatrix")
@@ -201,15 +219,20 @@ def valid(model, rows, features, idx_val, labels, batch_size=10000, dropnode_rat
     idx = _node_ids(idx_val, "idx_val", dev)
     n = idx.numel()
     pos = rows.batch_positions(idx, check=True) if n else None
-    buf = eval_buffers(n, dev)
+    return ValidPlan(model, rows, features, labels, idx, pos, eval_buffers(n, dev), batch_size)
+
+
+def valid_pass(plan, dropnode_rate=0.5):
+    """One validation pass over a ValidPlan: (loss, acc, counts) as device tensors.  Nothing synchronises."""
+    from .augment import random_prop_rows
+    model, rows, features, labels, idx, pos, buf, batch_size = plan
     with _NoSync(model):
-        for start in range(0, n, batch_size):
-            end = min(start + batch_size, n)
+        for start in range(0, idx.numel(), batch_size):
+            end = min(start + batch_size, idx.numel())
             aug = random_prop_rows(features, rows.col, rows.val, rows.filled, rows.K, batch_rows=pos[start:end],
                                    dropnode_rate=dropnode_rate, training=False)
             eval_head(model(aug), labels, label_rows=idx[start:end], out=buf, offset=start)
-        loss, acc, counts = eval_reduce(buf)
-    return (loss, acc, counts) if return_counts else (loss, acc)
+        return eval_reduce(buf)
 
 
 def local_logits(model, attr_mat, batch_size=10000, out=None, fused=False):

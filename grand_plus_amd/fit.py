@@ -1,0 +1,320 @@
+"""The training loop around a GRAND+ step without a host round trip per step (reference model.py:302-368).
+
+`TrainStep` replays a whole step from a captured graph, but its caller still drew the batch on the host every step and
+synchronised at every validation.  Here
+
+  * `Sampler` states which nodes step t trains on: the labelled batches of an epoch are consecutive slices of one keyed
+    permutation of the labelled pool, the unlabelled batch is the head of a fresh permutation every step.  `gp_fit_select`
+    evaluates that on the device from the tick and the seed in the step state (`TrainStep.step_sampled`), inside the
+    captured graph; `Sampler.selection` is its numpy mirror.  The selection is ours, not numpy's shuffle stream.
+  * `BestTracker` keeps the reference's early-stop rule (model.py:344-355) and the best weights on the device: one
+    launch decides, a second copies the model's tensors into their snapshot when the first said so.  `read()` is the one
+    place the host waits.
+  * `fit` is the loop: step, validate every `eval_batch` steps, poll the tracker every `poll_every` validations, restore
+    the best weights at the end.
+
+The entry points are extern "C" symbols of libgrandplus.so declared in csrc/fit_abi.hpp; they are not part of C ABI 4,
+so their binding (ABI below), constants and struct mirrors live here and not in `_native`.
+
+Left out: MagMLP, several steps in one graph, numpy's own shuffle stream, a checkpoint on disk
+(`tracker.restore()` then `torch.save` is the caller's line).
+"""
+from __future__ import annotations
+
+import collections
+import ctypes
+import sys
+import types
+
+import numpy as np
+import torch
+
+from . import _native
+from ._common import _FIT_EPOCH_MUL, _FIT_UNLABEL_MUL, _M64, _mix, _stream, perm_index
+
+__all__ = ["Sampler", "BestTracker", "FitLoop", "FitResult", "fit", "early_stop_rule"]
+
+GP_FIT_STOP_ACC, GP_FIT_STOP_BOTH = 0, 1
+GP_FIT_MAX_COPIES = 32
+STOP_MODES = {"acc": GP_FIT_STOP_ACC, "both": GP_FIT_STOP_BOTH}
+_MAX_SIZE = 2 ** 31
+
+
+class GpFitTrack(ctypes.Structure):
+    """gp_fit_track of csrc/fit_abi.hpp: the image of the device struct."""
+    _fields_ = [("best_loss", ctypes.c_float), ("best_acc", ctypes.c_float), ("best_tick", ctypes.c_uint64),
+                ("stop_tick", ctypes.c_uint64), ("bad_counter", ctypes.c_int32), ("n_evals", ctypes.c_int32),
+                ("copy_now", ctypes.c_int32), ("stopped", ctypes.c_int32)]
+
+
+class GpFitCopy(ctypes.Structure):
+    """gp_fit_copy of csrc/fit_abi.hpp: device pointers as integers, 4-byte words."""
+    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("n_words", ctypes.c_int64)]
+
+
+# name -> (restype, argtypes), under the convention stated above _native.ABI; tests/test_host_fit.py holds it against fit_abi.hpp
+_int, _i32, _i64, _u64, _vp = ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_void_p
+ABI = {
+    "gp_fit_select": (_int, [_int, _vp, _u64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "gp_fit_track_update": (_int, [_int, _vp, _vp, _vp, _i32, _i32, _vp]),
+    "gp_fit_snapshot": (_int, [_int, _vp, ctypes.POINTER(GpFitCopy), _i32, _vp]),
+}
+_BOUND = False
+
+
+def lib():
+    """_native.lib() with the fit entry points declared on it.  A library without them is an error, not a fallback."""
+    global _BOUND
+    L = _native.lib()
+    if not _BOUND:
+        for name, (restype, argtypes) in ABI.items():
+            if not hasattr(L, name):
+                raise RuntimeError(f"{_native.LIB_PATH} does not export {name} (an older build?): rebuild the library")
+            f = getattr(L, name)
+            f.restype, f.argtypes = restype, argtypes
+        _BOUND = True
+    return L
+
+
+def _size(v, name):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= int(v) < _MAX_SIZE:
+        raise ValueError(f"{name} must be an int in [1, 2**31), got {v!r}")
+    return int(v)
+
+
+class Sampler:
+    """Which nodes step t >= 1 trains on, on the host: the shapes a capture needs and the numpy mirror of gp_fit_select.
+
+    n_train / n_unlabel: the sizes of the two pools; batch_size: labelled nodes per step (the last batch of an epoch is
+    short, as iterate_minibatches_listinputs leaves it); unlabel_batch: unlabelled nodes per step, at most the pool
+    (sample_unlabel); base_seed: keys the labelled permutations.  The unlabelled one is keyed by the step's own seed."""
+
+    def __init__(self, n_train, n_unlabel, batch_size, unlabel_batch, base_seed=0):
+        self.n_train, self.n_unlabel = _size(n_train, "n_train"), _size(n_unlabel, "n_unlabel")
+        self.batch_size, self.unlabel_batch = _size(batch_size, "batch_size"), _size(unlabel_batch, "unlabel_batch")
+        self.base_seed = int(base_seed) & _M64
+        self.n_batches = -(-self.n_train // self.batch_size)             # steps of an epoch
+        self.u = min(self.unlabel_batch, self.n_unlabel)
+
+    def _slice(self, t):
+        t = int(t)
+        if t < 1:
+            raise ValueError(f"steps count from 1, got t={t}")
+        epoch, j = divmod(t - 1, self.n_batches)
+        lo = j * self.batch_size
+        return epoch, lo, min(self.batch_size, self.n_train - lo)
+
+    def shape(self, t):
+        """(n_labeled, u) of step t."""
+        return self._slice(t)[2], self.u
+
+    def labelled(self, t):
+        """The labelled batch of step t: a slice of the epoch's permutation of the labelled pool."""
+        epoch, lo, n_l = self._slice(t)
+        key = _mix(self.base_seed ^ (((epoch + 1) * _FIT_EPOCH_MUL) & _M64))
+        return np.array([perm_index(key, self.n_train, lo + i) for i in range(n_l)], dtype=np.int64)
+
+    def unlabelled(self, seed):
+        """The unlabelled batch of the step with `seed`: the head of a fresh permutation of the unlabelled pool."""
+        key = _mix((int(seed) & _M64) ^ _FIT_UNLABEL_MUL)
+        return np.array([perm_index(key, self.n_unlabel, i) for i in range(self.u)], dtype=np.int64)
+
+    def selection(self, t, seed):
+        """(train_sel, unlabel_sel) of step t, int64 selections into the two pools as TrainStep.step takes them; seed: the
+        step's seed, step_seed(base of the StepState, t)."""
+        return self.labelled(t), self.unlabelled(seed)
+
+
+def fit_select(state, sampler, n_labeled, sel, flag):
+    """gp_fit_select on the current stream: the selection of the step `state` is at, into sel (int64 CUDA [n_labeled + u]);
+    bit 0 of flag (int32 CUDA [1]) is set when n_labeled is not the step's."""
+    rc = lib().gp_fit_select(state.device.index, state.buf.data_ptr(), ctypes.c_uint64(sampler.base_seed), sampler.n_train,
+                             sampler.n_unlabel, sampler.batch_size, sampler.unlabel_batch, n_labeled, sel.data_ptr(),
+                             flag.data_ptr(), _stream(state.buf))
+    _native.raise_for_status(rc)
+
+
+def early_stop_rule(track, loss, acc, tick, stop_mode, patience):
+    """The rule of gp_fit_track_update on the host, over a dict with the fields of gp_fit_track (updated in place): the
+    model the GPU tests hold the kernel to, itself held to a transcription of model.py:344-359.  loss, acc: float32."""
+    if track["stopped"]:
+        track["copy_now"] = 0
+        return track
+    loss, acc = np.float32(loss), np.float32(acc)
+    track["n_evals"] += 1
+    track["copy_now"] = 0
+    if acc >= track["best_acc"]:
+        if stop_mode == "acc" or (stop_mode == "both" and loss <= track["best_loss"]):
+            track.update(best_loss=loss, best_acc=acc, best_tick=tick, bad_counter=0, copy_now=1)
+    else:
+        track["bad_counter"] += 1
+    if track["bad_counter"] >= patience:
+        track.update(stopped=1, stop_tick=tick)
+    return track
+
+
+def new_track():
+    """The initial image of gp_fit_track as the dict early_stop_rule takes."""
+    return dict(best_loss=np.float32(np.inf), best_acc=np.float32(0), best_tick=0, stop_tick=0, bad_counter=0, n_evals=0,
+                copy_now=0, stopped=0)
+
+
+TrackImage = collections.namedtuple("TrackImage", [n for n, _ in GpFitTrack._fields_])
+
+
+class BestTracker:
+    """Early stopping and the best weights on the device.
+
+    Owns one gp_fit_track, one snapshot buffer per tensor of model.state_dict() (parameters, BatchNorm running statistics
+    and num_batches_tracked alike) and the copy table.  `update(loss, acc, state)` enqueues the decision and the copy;
+    `read()` is one device-to-host copy of the struct; `restore()` copies the snapshot back into the model."""
+
+    def __init__(self, model, device, stop_mode="both", patience=100):
+        if stop_mode not in STOP_MODES:
+            raise ValueError(f"stop_mode must be 'acc' or 'both', got {stop_mode!r}")
+        if isinstance(patience, bool) or not isinstance(patience, (int, np.integer)) or not 1 <= int(patience) < _MAX_SIZE:
+            raise ValueError(f"patience must be an int in [1, 2**31), got {patience!r}")
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise ValueError("BestTracker lives in GPU memory: device must be a CUDA device (no CPU fallback)")
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        self.device, self.stop_mode, self.patience = device, stop_mode, int(patience)
+        self.tensors = []
+        for name, t in model.state_dict().items():
+            if t.device != device:
+                raise ValueError(f"{name} is on {t.device}, the tracker on {device}")
+            if not (t.dtype.is_floating_point or t.dtype in (torch.int8, torch.uint8, torch.int16, torch.int32, torch.int64)):
+                raise ValueError(f"{name} has dtype {t.dtype}: the snapshot holds floating-point and integer tensors")
+            if not t.is_contiguous() or (t.numel() * t.element_size()) % 4 or t.data_ptr() % 4:
+                raise ValueError(f"{name} must be contiguous, 4-byte aligned and a whole number of 4-byte words")
+            self.tensors.append(t)
+        self.snapshot = [torch.zeros_like(t) for t in self.tensors]
+        self._copies = (GpFitCopy * max(len(self.tensors), 1))(*[
+            GpFitCopy(src=t.data_ptr(), dst=s.data_ptr(), n_words=t.numel() * t.element_size() // 4)
+            for t, s in zip(self.tensors, self.snapshot)])
+        init = GpFitTrack(best_loss=float("inf"))
+        self.buf = torch.frombuffer(bytearray(bytes(init)), dtype=torch.int64).to(device)
+        self._val = torch.zeros(2, dtype=torch.float32, device=device)
+
+    def update(self, loss, acc, state):
+        """The rule on (loss, acc) -- 0-dim float32 device tensors, as `valid` returns them -- at state's tick, then the
+        snapshot if the rule took a new best: two launches (more past 32 tensors) on the current stream, nothing read back."""
+        for t, name in ((loss, "loss"), (acc, "acc")):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.numel() != 1 or t.device != self.device:
+                raise TypeError(f"{name} must be a float32 tensor of one element on {self.device}")
+        if acc.data_ptr() == loss.data_ptr() + 4:                        # the two floats eval_reduce writes side by side
+            val = loss
+        else:
+            val = self._val
+            val[0].copy_(loss.reshape(()))
+            val[1].copy_(acc.reshape(()))
+        L = lib()
+        rc = L.gp_fit_track_update(self.device.index, self.buf.data_ptr(), val.data_ptr(), state.buf.data_ptr(),
+                                   STOP_MODES[self.stop_mode], self.patience, _stream(self.buf))
+        _native.raise_for_status(rc)
+        rc = L.gp_fit_snapshot(self.device.index, self.buf.data_ptr(), self._copies, len(self.tensors), _stream(self.buf))
+        _native.raise_for_status(rc)
+
+    def read(self):
+        """The struct on the host (one device-to-host copy): best_loss, best_acc, best_tick, stop_tick, bad_counter,
+        n_evals, copy_now, stopped."""
+        s = GpFitTrack.from_buffer_copy(self.buf.cpu().numpy().tobytes())
+        return TrackImage(np.float32(s.best_loss), np.float32(s.best_acc), int(s.best_tick), int(s.stop_tick), int(s.bad_counter),
+                          int(s.n_evals), int(s.copy_now), int(s.stopped))
+
+    def restore(self):
+        """Copies the best weights back into the model (model.py:368) and returns the struct; with no best yet
+        (best_tick == 0) the model is left as it is."""
+        image = self.read()
+        if image.best_tick:
+            with torch.no_grad():
+                for t, s in zip(self.tensors, self.snapshot):
+                    t.copy_(s)
+        return image
+
+
+FitResult = collections.namedtuple("FitResult", ["steps", "best_tick", "stop_tick", "best_loss", "best_acc"])
+
+
+class FitLoop:
+    """The state of one `fit` run: everything looked up and allocated once, then `advance()` per step.
+
+    advance() runs the next step (`TrainStep.step_sampled`) and, when (t - 1) % eval_batch == 0, the validation pass and
+    `tracker.update`; it returns whether it validated.  Nothing in it waits for the GPU.  `poll()` reads the tracker (the one
+    synchronisation of the steady state) and raises if a step ran with the wrong batch shape; `finish()` restores the best
+    weights and returns the FitResult."""
+
+    def __init__(self, step, sampler, idx_val, *, eval_batch=10, stop_mode="both", patience=100):
+        from .evaluate import valid_plan
+        from .step import TrainStep
+        if not isinstance(step, TrainStep) or not isinstance(sampler, Sampler):
+            raise TypeError("fit takes a TrainStep and a Sampler")
+        step.check_sampler(sampler)
+        if isinstance(eval_batch, bool) or not isinstance(eval_batch, (int, np.integer)) or eval_batch < 1:
+            raise ValueError(f"eval_batch must be an int >= 1, got {eval_batch!r}")
+        self.step, self.sampler, self.eval_batch = step, sampler, int(eval_batch)
+        # the reference validates in batches of the training batch size (model.py:337)
+        self.plan = valid_plan(step.model, step.rows, step.features, idx_val, step.labels, sampler.batch_size)
+        self.tracker = BestTracker(step.model, step.features.device, stop_mode, patience)
+        self.t = step.state.read().tick                                  # the one read of the tick
+        self.steps = self.evals = 0
+        self.last = None                                                 # the StepResult of the last step
+
+    def advance(self):
+        from .evaluate import valid_pass
+        self.t += 1
+        self.last = self.step.step_sampled(self.sampler, self.t)
+        self.steps += 1
+        if (self.t - 1) % self.eval_batch:
+            return False
+        loss, acc, _counts = valid_pass(self.plan, self.step.dropnode_rate)
+        self.tracker.update(loss, acc, self.step.state)
+        self.evals += 1
+        return True
+
+    def poll(self):
+        image = self.tracker.read()
+        self.step.check_selection_flag()
+        return image
+
+    def finish(self):
+        image = self.tracker.restore()
+        self.step.check_selection_flag()
+        return FitResult(self.steps, image.best_tick or None, image.stop_tick if image.stopped else None,
+                         float(image.best_loss), float(image.best_acc))
+
+
+def fit(step, sampler, idx_val, *, epochs, eval_batch=10, stop_mode="both", patience=100, poll_every=1, max_steps=None):
+    """The reference's training loop (model.py:302-368) over a TrainStep: returns FitResult(steps, best_tick, stop_tick,
+    best_loss, best_acc) with the best weights restored into the model.
+
+    step: the TrainStep (model in train mode); sampler: the Sampler over its two pools; idx_val: the validation node ids.
+    Runs the steps after the state's tick (read once here) up to step epochs * sampler.n_batches, at most max_steps of
+    them.  Step t validates when (t - 1) % eval_batch == 0 (num_batch % eval_batch of the reference) and feeds the
+    tracker; every poll_every-th validation the host reads the tracker and stops if the rule has.  With poll_every=1
+    that is the reference's step; a larger value may run further steps, whose validations the stopped tracker ignores,
+    so the restored weights are the same.  Between polls nothing synchronises.  best_tick is None when no validation
+    took a best (the model is then left as trained), stop_tick None when the rule never stopped the run."""
+    for v, name in ((epochs, "epochs"), (poll_every, "poll_every")):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+            raise ValueError(f"{name} must be an int >= 1, got {v!r}")
+    if max_steps is not None and (isinstance(max_steps, bool) or not isinstance(max_steps, (int, np.integer)) or max_steps < 0):
+        raise ValueError(f"max_steps must be None or an int >= 0, got {max_steps!r}")
+    loop = FitLoop(step, sampler, idx_val, eval_batch=eval_batch, stop_mode=stop_mode, patience=patience)
+    last = int(epochs) * sampler.n_batches
+    while loop.t < last and (max_steps is None or loop.steps < max_steps):
+        if loop.advance() and loop.evals % poll_every == 0 and loop.poll().stopped:
+            break
+    return loop.finish()
+
+
+class _FitModule(types.ModuleType):
+    """Importing this module binds the package's attribute `fit` to it, whatever `grand_plus_amd.__getattr__` returned
+    before; calling the module is calling `fit`, so `grand_plus_amd.fit(...)` means the same before and after."""
+
+    def __call__(self, *args, **kwargs):
+        return fit(*args, **kwargs)
+
+
+sys.modules[__name__].__class__ = _FitModule

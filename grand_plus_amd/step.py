@@ -9,7 +9,9 @@ MLP's dropout seed, the consistency weight min(lam, lam * num_batch / warmup) (m
   * `TrainStep` is the step of model.py:305-334 over it: advance, gather the batch, write the step's dropout masks from the
     seed on the device (`gp_step_masks`), then the existing kernels fed those masks, the loss weighted by the state's
     weight, backward, `ClipAdam(capturable=True)`.  With capture=True the body of each batch shape is captured once with
-    `torch.cuda.graph` and replayed; with capture=False the same body runs eagerly every call.
+    `torch.cuda.graph` and replayed; with capture=False the same body runs eagerly every call.  `step()` takes the
+    batch from the host; `step_sampled()` has `gp_fit_select` draw it on the device right after the advance, so a replay
+    takes no host input (`fit.py`).
 
 Left out: MagMLP / mag_prop_rows, several optimisers, `validate=True` of the loss, and schedulers that change
 `lr` between replays -- `lr` is a value of the capture; rebuild the TrainStep after changing it.
@@ -214,16 +216,23 @@ class TrainStep:
         self._node_keep = torch.zeros((samples, rows.col.numel()), dtype=torch.uint8, device=dev) \
             if self.dropnode_rate > 0 else None
         self._shapes = {}              # (B, n_labeled) -> None after the eager call, then its _Graph
+        self._sampled = {}             # the same for step_sampled, keyed by what its capture freezes
+        self.labels = labels
+        self._sel_flag = torch.zeros(1, dtype=torch.int32, device=dev)      # bit 0: a step_sampled ran with a wrong shape
         self._where = None
 
     # ---- one step's launches: what a graph captures
-    def _body(self, sel, n_l):
+    def _body(self, sel, n_l, sampler=None):
         m, S, st = self.model, self.samples, self.state
         layers = m._layers()
         self._where = "optimizer.zero_grad"
         self.optimizer.zero_grad(set_to_none=True)
         self._where = "gp_step_advance"
         st.advance(self.optimizer)
+        if sampler is not None:                                      # step_sampled: the device draws the new tick's selection
+            self._where = "gp_fit_select"
+            from .fit import fit_select
+            fit_select(st, sampler, n_l, sel, self._sel_flag)
         self._where = "index_select"
         batch_rows = self._pos.index_select(0, sel)
         y = self._pool_labels.index_select(0, sel[:n_l]) if n_l else None
@@ -280,13 +289,47 @@ class TrainStep:
         graph.replay()
         return result
 
-    def _capture(self, B, n_l):
+    # ---- the step with the selection drawn on the device
+    def check_sampler(self, sampler):
+        if (sampler.n_train, sampler.n_unlabel) != (self.n_train, self.n_unlabel):
+            raise ValueError(f"the sampler draws from pools of {sampler.n_train} and {sampler.n_unlabel} nodes, "
+                             f"the step holds {self.n_train} and {self.n_unlabel}")
+
+    def check_selection_flag(self):
+        """Raises if a step_sampled ran with a batch shape that was not its step's (one device-to-host copy)."""
+        if int(self._sel_flag.item()) & 1:
+            raise RuntimeError("a step_sampled(sampler, t) ran with the batch shape of another step: t was not the tick of "
+                               "the step state (the selection stayed inside the pools, but the labelled batch was not the step's)")
+
+    def step_sampled(self, sampler, t):
+        """step() with the selection of fit.Sampler drawn on the device: advance -> gp_fit_select -> the rest of the body.
+        t: the step this call runs, the state's tick + 1; the host needs it for the batch shape alone, `sampler.shape(t)`.
+        Bitwise `step(*sampler.selection(t, step_seed(base, t)))`; a replay takes no host input at all.  Graphs are kept per
+        shape under the same MAX_GRAPHS limit as step()'s, apart from them."""
+        if not self.model.training:
+            raise RuntimeError("TrainStep.step_sampled() needs the model in train mode: call model.train() (eval / train are the caller's)")
+        self.check_sampler(sampler)
+        n_l, u = sampler.shape(t)
+        B = n_l + u
+        key = (B, n_l, sampler.batch_size, sampler.unlabel_batch, sampler.base_seed)    # the values a capture freezes
+        if not self.capture or (key not in self._sampled and len(self._sampled) >= MAX_GRAPHS):
+            return self._body(torch.empty(B, dtype=torch.int64, device=self.features.device), n_l, sampler)
+        if key not in self._sampled:                                 # the first call of a shape: a real, eager step
+            self._sampled[key] = None
+            return self._body(torch.empty(B, dtype=torch.int64, device=self.features.device), n_l, sampler)
+        if self._sampled[key] is None:
+            self._sampled[key] = self._capture(B, n_l, sampler)
+        _sel, graph, result = self._sampled[key]
+        graph.replay()
+        return result
+
+    def _capture(self, B, n_l, sampler=None):
         dev = self.features.device
         sel = torch.zeros(B, dtype=torch.int64, device=dev)         # static: a replay reads the selection from here
         graph = torch.cuda.CUDAGraph()
         try:
             with torch.cuda.graph(graph):                            # one side stream; nothing runs until the replay
-                result = self._body(sel, n_l)
+                result = self._body(sel, n_l, sampler)
         except Exception as e:
             where, self._where = self._where, None
             raise RuntimeError(f"capturing the training step broke in {where}: {e}") from e
