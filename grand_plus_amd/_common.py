@@ -91,6 +91,16 @@ def _dev_index(t):
     return t.device.index
 
 
+def _cuda_device(device, owner):
+    """`device` as a torch.device with its index filled in; `owner` names the class whose memory it is, for the message."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise ValueError(f"{owner} lives in GPU memory: device must be a CUDA device (no CPU fallback)")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    return device
+
+
 def _stream(t, stream=None):
     """The stream argument of a native call: the caller's raw stream handle, or the current stream of t's device."""
     return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream if stream is None else stream)

@@ -73,6 +73,22 @@ class GpStepSegment(ctypes.Structure):
                 ("p", ctypes.c_float), ("pad", ctypes.c_int32)]
 
 
+GP_FIT_STOP_ACC, GP_FIT_STOP_BOTH = 0, 1
+GP_FIT_MAX_COPIES = 32
+
+
+class GpFitTrack(ctypes.Structure):
+    """gp_fit_track of grandplus_fit.h: the image of the device struct (BestTracker.read copies it to the host)."""
+    _fields_ = [("best_loss", ctypes.c_float), ("best_acc", ctypes.c_float), ("best_tick", ctypes.c_uint64),
+                ("stop_tick", ctypes.c_uint64), ("bad_counter", ctypes.c_int32), ("n_evals", ctypes.c_int32),
+                ("copy_now", ctypes.c_int32), ("stopped", ctypes.c_int32)]
+
+
+class GpFitCopy(ctypes.Structure):
+    """gp_fit_copy of grandplus_fit.h: device pointers as integers, 4-byte words."""
+    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("n_words", ctypes.c_int64)]
+
+
 class GpOptimTensor(ctypes.Structure):
     """gp_optim_tensor of grandplus.h: device pointers as integers."""
     _fields_ = [("param", ctypes.c_void_p), ("grad", ctypes.c_void_p), ("exp_avg", ctypes.c_void_p),
@@ -144,8 +160,8 @@ class GpStats(ctypes.Structure):
 #     memory, a stream), gp_graph* and gp_step_state*;
 #   * T** is POINTER(c_void_p);
 #   * const char* is c_char_p;
-#   * every other T* is a host array and travels as POINTER(T), with gp_stats, gp_optim_tensor and gp_step_segment mapping to
-#     their Structure classes;
+#   * every other T* is a host array and travels as POINTER(T), with gp_stats, gp_optim_tensor, gp_step_segment and gp_fit_copy
+#     mapping to their Structure classes;
 #   * scalars map one to one.
 # A name that is not required may be missing from an older build selected with GRANDPLUS_LIB (an A/B run): calling it there
 # raises a clear error.  A missing required name fails at load.  (gp_internal_graph_csr, gp_internal_multi_plan and
@@ -245,6 +261,11 @@ ABI = {
         "gp_step_masks": (_int, [_int, _vp, ctypes.POINTER(GpStepSegment), _i32, _vp], False),
         "gp_clip_adam_step_dev": (_int, [_int, ctypes.POINTER(GpOptimTensor), _i32, _int, _f32, _f32, _f64, _f64, _f32, _f32, _vp, _vp,
                                          _vp, _vp, _vp], False),
+    },
+    "grandplus_fit.h": {
+        "gp_fit_select": (_int, [_int, _vp, _u64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp], False),
+        "gp_fit_track_update": (_int, [_int, _vp, _vp, _vp, _i32, _i32, _vp], False),
+        "gp_fit_snapshot": (_int, [_int, _vp, ctypes.POINTER(GpFitCopy), _i32, _vp], False),
     },
 }
 

@@ -1,4 +1,4 @@
-// fit.hip -- what the fit loop adds to a training step on the device (fit_abi.hpp):
+// fit.hip -- what the fit loop adds to a training step on the device (grandplus_fit.h):
 //   fit_select_kernel    the step's selection into the two pools, from the tick and the seed in the step state: one thread
 //                        per index, each a random access into a keyed permutation (fit_perm.hpp), so a replay needs no host input;
 //   fit_track_kernel     one thread: the reference's early-stop rule (model.py:344-355) on the two floats of `valid`;
@@ -8,7 +8,6 @@
 // no atomics.
 #include "gp_common.hpp"
 
-#include "fit_abi.hpp"
 #include "fit_perm.hpp"
 
 namespace {

@@ -13,8 +13,8 @@ synchronised at every validation.  Here
   * `fit` is the loop: step, validate every `eval_batch` steps, poll the tracker every `poll_every` validations, restore
     the best weights at the end.
 
-The entry points are extern "C" symbols of libgrandplus.so declared in csrc/fit_abi.hpp; they are not part of C ABI 4,
-so their binding (ABI below), constants and struct mirrors live here and not in `_native`.
+The three entry points are part of the C ABI (include/grandplus_fit.h): `_native.ABI` binds them, and `_native` holds
+the GP_FIT_* constants and the two struct mirrors.  They are imported here so that `fit.GpFitTrack` and the like resolve.
 
 Left out: MagMLP, several steps in one graph, numpy's own shuffle stream, a checkpoint on disk
 (`tracker.restore()` then `torch.save` is the caller's line).
@@ -30,56 +30,25 @@ import numpy as np
 import torch
 
 from . import _native
-from ._common import _FIT_EPOCH_MUL, _FIT_UNLABEL_MUL, _M64, _mix, _stream, perm_index
+from ._common import _FIT_EPOCH_MUL, _FIT_UNLABEL_MUL, _M64, _cuda_device, _mix, _stream, perm_index
+from ._native import GP_FIT_MAX_COPIES, GP_FIT_STOP_ACC, GP_FIT_STOP_BOTH, GpFitCopy, GpFitTrack  # noqa: F401
 
 __all__ = ["Sampler", "BestTracker", "FitLoop", "FitResult", "fit", "early_stop_rule"]
 
-GP_FIT_STOP_ACC, GP_FIT_STOP_BOTH = 0, 1
-GP_FIT_MAX_COPIES = 32
 STOP_MODES = {"acc": GP_FIT_STOP_ACC, "both": GP_FIT_STOP_BOTH}
 _MAX_SIZE = 2 ** 31
 
 
-class GpFitTrack(ctypes.Structure):
-    """gp_fit_track of csrc/fit_abi.hpp: the image of the device struct."""
-    _fields_ = [("best_loss", ctypes.c_float), ("best_acc", ctypes.c_float), ("best_tick", ctypes.c_uint64),
-                ("stop_tick", ctypes.c_uint64), ("bad_counter", ctypes.c_int32), ("n_evals", ctypes.c_int32),
-                ("copy_now", ctypes.c_int32), ("stopped", ctypes.c_int32)]
-
-
-class GpFitCopy(ctypes.Structure):
-    """gp_fit_copy of csrc/fit_abi.hpp: device pointers as integers, 4-byte words."""
-    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("n_words", ctypes.c_int64)]
-
-
-# name -> (restype, argtypes), under the convention stated above _native.ABI; tests/test_host_fit.py holds it against fit_abi.hpp
-_int, _i32, _i64, _u64, _vp = ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_void_p
-ABI = {
-    "gp_fit_select": (_int, [_int, _vp, _u64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
-    "gp_fit_track_update": (_int, [_int, _vp, _vp, _vp, _i32, _i32, _vp]),
-    "gp_fit_snapshot": (_int, [_int, _vp, ctypes.POINTER(GpFitCopy), _i32, _vp]),
-}
-_BOUND = False
-
-
-def lib():
-    """_native.lib() with the fit entry points declared on it.  A library without them is an error, not a fallback."""
-    global _BOUND
-    L = _native.lib()
-    if not _BOUND:
-        for name, (restype, argtypes) in ABI.items():
-            if not hasattr(L, name):
-                raise RuntimeError(f"{_native.LIB_PATH} does not export {name} (an older build?): rebuild the library")
-            f = getattr(L, name)
-            f.restype, f.argtypes = restype, argtypes
-        _BOUND = True
-    return L
+def _int_in(v, name, lo, hi=None, what="an int"):
+    """int(v) of an int (no bool) in [lo, hi), hi a power of two, or >= lo without hi; `what` words the kind in the message."""
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo or (hi is not None and v >= hi):
+        bounds = f">= {lo}" if hi is None else f"in [{lo}, 2**{hi.bit_length() - 1})"
+        raise ValueError(f"{name} must be {what} {bounds}, got {v!r}")
+    return int(v)
 
 
 def _size(v, name):
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= int(v) < _MAX_SIZE:
-        raise ValueError(f"{name} must be an int in [1, 2**31), got {v!r}")
-    return int(v)
+    return _int_in(v, name, 1, _MAX_SIZE)
 
 
 class Sampler:
@@ -128,9 +97,9 @@ class Sampler:
 def fit_select(state, sampler, n_labeled, sel, flag):
     """gp_fit_select on the current stream: the selection of the step `state` is at, into sel (int64 CUDA [n_labeled + u]);
     bit 0 of flag (int32 CUDA [1]) is set when n_labeled is not the step's."""
-    rc = lib().gp_fit_select(state.device.index, state.buf.data_ptr(), ctypes.c_uint64(sampler.base_seed), sampler.n_train,
-                             sampler.n_unlabel, sampler.batch_size, sampler.unlabel_batch, n_labeled, sel.data_ptr(),
-                             flag.data_ptr(), _stream(state.buf))
+    rc = _native.lib().gp_fit_select(state.device.index, state.buf.data_ptr(), ctypes.c_uint64(sampler.base_seed),
+                                     sampler.n_train, sampler.n_unlabel, sampler.batch_size, sampler.unlabel_batch, n_labeled,
+                                     sel.data_ptr(), flag.data_ptr(), _stream(state.buf))
     _native.raise_for_status(rc)
 
 
@@ -172,14 +141,9 @@ class BestTracker:
     def __init__(self, model, device, stop_mode="both", patience=100):
         if stop_mode not in STOP_MODES:
             raise ValueError(f"stop_mode must be 'acc' or 'both', got {stop_mode!r}")
-        if isinstance(patience, bool) or not isinstance(patience, (int, np.integer)) or not 1 <= int(patience) < _MAX_SIZE:
-            raise ValueError(f"patience must be an int in [1, 2**31), got {patience!r}")
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise ValueError("BestTracker lives in GPU memory: device must be a CUDA device (no CPU fallback)")
-        if device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        self.device, self.stop_mode, self.patience = device, stop_mode, int(patience)
+        self.patience = _size(patience, "patience")
+        self.device = device = _cuda_device(device, "BestTracker")
+        self.stop_mode = stop_mode
         self.tensors = []
         for name, t in model.state_dict().items():
             if t.device != device:
@@ -209,7 +173,7 @@ class BestTracker:
             val = self._val
             val[0].copy_(loss.reshape(()))
             val[1].copy_(acc.reshape(()))
-        L = lib()
+        L = _native.lib()
         rc = L.gp_fit_track_update(self.device.index, self.buf.data_ptr(), val.data_ptr(), state.buf.data_ptr(),
                                    STOP_MODES[self.stop_mode], self.patience, _stream(self.buf))
         _native.raise_for_status(rc)
@@ -251,9 +215,7 @@ class FitLoop:
         if not isinstance(step, TrainStep) or not isinstance(sampler, Sampler):
             raise TypeError("fit takes a TrainStep and a Sampler")
         step.check_sampler(sampler)
-        if isinstance(eval_batch, bool) or not isinstance(eval_batch, (int, np.integer)) or eval_batch < 1:
-            raise ValueError(f"eval_batch must be an int >= 1, got {eval_batch!r}")
-        self.step, self.sampler, self.eval_batch = step, sampler, int(eval_batch)
+        self.step, self.sampler, self.eval_batch = step, sampler, _int_in(eval_batch, "eval_batch", 1)
         # the reference validates in batches of the training batch size (model.py:337)
         self.plan = valid_plan(step.model, step.rows, step.features, idx_val, step.labels, sampler.batch_size)
         self.tracker = BestTracker(step.model, step.features.device, stop_mode, patience)
@@ -296,13 +258,11 @@ def fit(step, sampler, idx_val, *, epochs, eval_batch=10, stop_mode="both", pati
     that is the reference's step; a larger value may run further steps, whose validations the stopped tracker ignores,
     so the restored weights are the same.  Between polls nothing synchronises.  best_tick is None when no validation
     took a best (the model is then left as trained), stop_tick None when the rule never stopped the run."""
-    for v, name in ((epochs, "epochs"), (poll_every, "poll_every")):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
-            raise ValueError(f"{name} must be an int >= 1, got {v!r}")
-    if max_steps is not None and (isinstance(max_steps, bool) or not isinstance(max_steps, (int, np.integer)) or max_steps < 0):
-        raise ValueError(f"max_steps must be None or an int >= 0, got {max_steps!r}")
+    epochs, poll_every = _int_in(epochs, "epochs", 1), _int_in(poll_every, "poll_every", 1)
+    if max_steps is not None:
+        _int_in(max_steps, "max_steps", 0, what="None or an int")
     loop = FitLoop(step, sampler, idx_val, eval_batch=eval_batch, stop_mode=stop_mode, patience=patience)
-    last = int(epochs) * sampler.n_batches
+    last = epochs * sampler.n_batches
     while loop.t < last and (max_steps is None or loop.steps < max_steps):
         if loop.advance() and loop.evals % poll_every == 0 and loop.poll().stopped:
             break

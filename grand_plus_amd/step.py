@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from . import _native
-from ._common import _M64, _stream, step_seed  # noqa: F401  (step_seed: public here)
+from ._common import _M64, _cuda_device, _stream, step_seed  # noqa: F401  (step_seed: public here)
 
 __all__ = ["StepState", "TrainStep", "StepResult", "trained_parameters", "step_seed", "step_weight"]
 
@@ -59,12 +59,7 @@ class StepState:
     the struct's weight, for use in the loss.  `read()` copies the struct to the host (tests and checkpoints only)."""
 
     def __init__(self, device, base_seed=0, lam=0.0, warmup=1.0):
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise ValueError("StepState lives in GPU memory: device must be a CUDA device (no CPU fallback)")
-        if device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        self.device = device
+        self.device = device = _cuda_device(device, "StepState")
         self.configure(base_seed, lam, warmup)
         self.buf = torch.zeros(ctypes.sizeof(_S) // 8, dtype=torch.int64, device=device)
         self.weight = self.buf.view(torch.float32)[_S.weight.offset // 4]

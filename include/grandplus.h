@@ -549,6 +549,11 @@ int gp_clip_adam_step(int device, const gp_optim_tensor* tensors, int32_t n_tens
  * a header of their own, part of this ABI. */
 #include "grandplus_step.h"
 
+/* The fit loop around that step (the step's batch selection drawn on the device from the step state, the
+ * early-stop rule over gp_fit_track, and the snapshot of the best weights): declared in a header of their own, part of
+ * this ABI. */
+#include "grandplus_fit.h"
+
 /* ------------------------------------------------------------------------------------------
  * exact full-graph feature propagation of the inference path, reference
  * predict() (model.py:181-224), lines 186-210.  mode 0 = ppr, 1 = avg, 2 = single (args.prop_mode);

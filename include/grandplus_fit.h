@@ -1,19 +1,18 @@
 /*
- * fit_abi.hpp -- the entry points of the sync-free fit loop (implemented by csrc/fit.hip).
+ * grandplus_fit.h -- the entry points of the sync-free fit loop (implemented by grand_plus_amd/csrc/fit.hip).
  *
- * NOT part of C ABI 4: these are extern "C" symbols of libgrandplus.so that no public header declares.  The one caller
- * is grand_plus_amd/fit.py, which binds them through its own table (fit.ABI) under the convention of _native.ABI: d_* and
- * void* travel as c_void_p, every other T* is a host array.  tests/test_host_fit.py holds that table and the struct mirrors
- * against this file.  Promoting them to a public header is a later change, together with the ABI test.
+ * Part of the ABI that grandplus.h describes (GP_ABI_VERSION and the status codes are defined there, gp_step_state in
+ * grandplus_step.h): grandplus.h includes this file after grandplus_step.h, so callers include grandplus.h alone.  The
+ * ctypes binding declares the entry points under this file's name in _native.ABI and mirrors the two structs, and
+ * tests/test_host_abi.py holds both against this file type by type.
  *
  * Common contract: arguments are checked before the device is touched; no atomics; nothing on a call path allocates,
  * copies or synchronises; every argument travels by value in the kernel arguments, so each launch can be captured.
  */
-#pragma once
+#ifndef GRANDPLUS_FIT_H
+#define GRANDPLUS_FIT_H
 
 #include <stdint.h>
-
-#include "grandplus.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -87,3 +86,4 @@ int gp_fit_snapshot(int device, const gp_fit_track* d_track, const gp_fit_copy* 
 #ifdef __cplusplus
 }
 #endif
+#endif /* GRANDPLUS_FIT_H */

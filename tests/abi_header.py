@@ -39,7 +39,8 @@ def prototypes(header):
 
 SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint8_t": ctypes.c_uint8,
            "uint32_t": ctypes.c_uint32, "uint64_t": ctypes.c_uint64, "float": ctypes.c_float, "double": ctypes.c_double}
-STRUCTS = {"gp_stats": _native.GpStats, "gp_optim_tensor": _native.GpOptimTensor, "gp_step_segment": _native.GpStepSegment}
+STRUCTS = {"gp_stats": _native.GpStats, "gp_optim_tensor": _native.GpOptimTensor, "gp_step_segment": _native.GpStepSegment,
+           "gp_fit_copy": _native.GpFitCopy}
 # host arrays that the binding declares c_void_p all the same (the comment on the entry in _native.ABI says why)
 HOST_AS_VOID = {("gp_internal_graph_acsr", "h_acsr"), ("gp_internal_graph_acsr", "h_node_pos"), ("gp_internal_graph_acsr", "h_unit_info")}
 

@@ -73,7 +73,7 @@ class Arena:
     """33 sources and 33 guarded destinations in two int32 arenas; source 7 is an int64 tensor of 2049 elements."""
 
     def __init__(self):
-        from grand_plus_amd.fit import GpFitCopy
+        from grand_plus_amd._native import GpFitCopy
         self.words = [WORDS[i % len(WORDS)] for i in range(33)]
         self.words[7] = 2 * 2049
         self.src_at = np.concatenate([[0], np.cumsum(self.words)]).astype(np.int64)
@@ -96,8 +96,7 @@ class Arena:
 
     def snapshot(self, track_buf):
         from grand_plus_amd import _native
-        from grand_plus_amd.fit import lib
-        rc = lib().gp_fit_snapshot(0, track_buf.data_ptr(), self.table, 33, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+        rc = _native.lib().gp_fit_snapshot(0, track_buf.data_ptr(), self.table, 33, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
         _native.raise_for_status(rc)
 
     def check(self, want):

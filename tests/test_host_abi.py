@@ -18,16 +18,17 @@ UNITS = {"grandplus.h": ("gfpush.hip", "augment.hip", "propagate.hip", "objectiv
          "grandplus_eval.h": ("evaluate.hip",), "grandplus_scatter.h": ("scatter_det.hip",),
          "grandplus_infer.h": ("mlp_infer.hip",), "grandplus_infer_chain.h": ("mlp_chain.hip",),
          "grandplus_mag.h": ("mag_prop.hip",), "grandplus_order.h": ("gfpush.hip",),
-         "grandplus_step.h": ("step_state.hip", "optim.hip")}
+         "grandplus_step.h": ("step_state.hip", "optim.hip"), "grandplus_fit.h": ("fit.hip",)}
 N_MAIN = 42                                                           # prototypes of grandplus.h itself
 NAMES = {"grandplus_eval.h": ["gp_eval_head", "gp_eval_reduce"],
          "grandplus_scatter.h": ["gp_embedding_bag_backward_det", "gp_random_prop_rows_backward_det"],
          "grandplus_infer.h": ["gp_mlp_infer_block"], "grandplus_infer_chain.h": ["gp_mlp_infer_chain2"],
          "grandplus_mag.h": ["gp_mag_prop_rows", "gp_mag_prop_rows_backward"],
          "grandplus_order.h": ["gp_internal_row_order", "gp_internal_wg_log"],
-         "grandplus_step.h": ["gp_clip_adam_step_dev", "gp_step_advance", "gp_step_masks"]}
+         "grandplus_step.h": ["gp_clip_adam_step_dev", "gp_step_advance", "gp_step_masks"],
+         "grandplus_fit.h": ["gp_fit_select", "gp_fit_snapshot", "gp_fit_track_update"]}
 N_PARAMS = {"gp_mlp_infer_block": 16, "gp_mlp_infer_chain2": 25, "gp_mag_prop_rows": 25, "gp_mag_prop_rows_backward": 24,
-            "gp_clip_adam_step": 15, "gp_clip_adam_step_dev": 15}
+            "gp_clip_adam_step": 15, "gp_clip_adam_step_dev": 15, "gp_fit_select": 11}
 
 
 def test_the_table_lists_the_headers_as_the_main_header_includes_them():
@@ -120,6 +121,7 @@ SIZES = {"optim_workspace_bytes": ("GP_OPTIM_WORKSPACE_BYTES", [()]),
 
 
 PINNED = {"GP_MAX_K": 1024, "GP_STEP_MAX_GROUPS": 8, "GP_STEP_MAX_LAYERS": 8, "GP_STEP_SEG_ROWS": 0, "GP_STEP_SEG_LAYER": 1,
+          "GP_FIT_STOP_ACC": 0, "GP_FIT_STOP_BOTH": 1, "GP_FIT_MAX_COPIES": 32,
           "GP_MLP_CHAIN_MAX_HIDDEN": 1024, "GP_MLP_CHAIN_MAX_OUT": 64, "GP_SCATTER_ROWS_WORKSPACE_BYTES(3, 7)": 4 * 3 * 7,
           "GP_SCATTER_BAG_WORKSPACE_BYTES(9)": 36, "GP_MLP_SAVED_FLOATS(2, 250, 602)": 2 * 250 + 4 * 2 * 602,
           "GP_MLP_FORWARD_WORKSPACE_BYTES(3)": 3 * 2097152,
@@ -134,7 +136,7 @@ def test_the_mirrors_equal_the_macros_as_the_c_compiler_evaluates_them():
     constants = [n for n, v in vars(_native).items() if re.fullmatch(r"GP_[A-Z0-9_]+", n) and isinstance(v, int) and n not in NO_MACRO]
     assert {"GP_OK", "GP_ERR_OVERFLOW", "GP_MAX_K", "GP_LOSS_L2", "GP_MLP_TRAINING", "GP_OPTIM_MAX_TENSORS", "GP_OPTIM_NORM_READY",
             "GP_EVAL_BAD", "GP_STEP_MAX_GROUPS", "GP_STEP_MAX_LAYERS", "GP_STEP_SEG_ROWS", "GP_STEP_SEG_LAYER",
-            "GP_MLP_CHAIN_MAX_HIDDEN", "GP_MLP_CHAIN_MAX_OUT"} <= set(constants)
+            "GP_MLP_CHAIN_MAX_HIDDEN", "GP_MLP_CHAIN_MAX_OUT", "GP_FIT_STOP_ACC", "GP_FIT_STOP_BOTH", "GP_FIT_MAX_COPIES"} <= set(constants)
     # ... and every macro and status code of the headers has its mirror, but for the version and the step seed's multiplier
     code = "".join(ah.read(h)[1] for h in HEADERS)
     declared = set(re.findall(r"#define (GP_\w+)", code)) | set(re.findall(r"\b(GP_OK|GP_ERR_\w+)\s*=", code))
@@ -156,6 +158,7 @@ def test_the_mirrors_equal_the_macros_as_the_c_compiler_evaluates_them():
     assert got["GP_OPTIM_WORKSPACE_BYTES"] <= 1024 * 8
     assert got["GP_OPTIM_MAX_TENSORS"] == oc.MAX_TENSORS == 32
     assert oc.MAX_TENSORS * 48 + 8 < 4096                             # the by-value table fits the kernel arguments
+    assert got["GP_FIT_MAX_COPIES"] * 24 + 8 <= 1024                  # and so does the snapshot's, of 24-byte gp_fit_copy entries
     for n_rows, f_in in INFER:
         size = got[_macro("GP_MLP_INFER_WORKSPACE_BYTES", (n_rows, f_in))]
         assert size % 16 == 0 and 0 <= size - 4 * (n_rows + 2 * f_in) < 16
@@ -165,9 +168,13 @@ def test_the_mirrors_equal_the_macros_as_the_c_compiler_evaluates_them():
 
 
 # ---- the mirrors of the structs
+PINNED_SIZEOF = {"gp_optim_tensor": 40, "gp_fit_track": 40, "gp_fit_copy": 24}
+
+
 @pytest.mark.parametrize("header,struct,mirror", [
     ("grandplus.h", "gp_stats", _native.GpStats), ("grandplus.h", "gp_optim_tensor", _native.GpOptimTensor),
-    ("grandplus_step.h", "gp_step_state", _native.GpStepState), ("grandplus_step.h", "gp_step_segment", _native.GpStepSegment)])
+    ("grandplus_step.h", "gp_step_state", _native.GpStepState), ("grandplus_step.h", "gp_step_segment", _native.GpStepSegment),
+    ("grandplus_fit.h", "gp_fit_track", _native.GpFitTrack), ("grandplus_fit.h", "gp_fit_copy", _native.GpFitCopy)])
 def test_the_struct_mirrors_have_the_headers_fields_size_and_offsets(header, struct, mirror):
     """Field by field against the header's text, then sizeof and every offsetof as the C compiler lays the struct out."""
     _, code = ah.read(header)
@@ -189,5 +196,5 @@ def test_the_struct_mirrors_have_the_headers_fields_size_and_offsets(header, str
     assert got == [ctypes.sizeof(mirror)] + [getattr(mirror, n).offset for n in names]
     if struct == "gp_step_state":
         assert got == [88, 0, 8, 16, 20, 52]
-    if struct == "gp_optim_tensor":
-        assert got[0] == 40
+    if struct in PINNED_SIZEOF:
+        assert got[0] == PINNED_SIZEOF[struct]

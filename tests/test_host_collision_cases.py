@@ -3,32 +3,25 @@ to the header itself (tests/native/gfpush_hash_check.cpp, built with the address
 case's precondition -- a set that shares one home slot at every capacity its table can have, a control that shares none -- is
 asserted from the mirror alone, against the sets pinned in tests/golden/collision_sets.json.  No GPU."""
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
 import collision_cases as cc
+import native_check
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def checker(tmp_path_factory):
-    if shutil.which("g++") is None:
-        pytest.fail("g++ is needed to build tests/native/gfpush_hash_check.cpp")
-    exe = str(tmp_path_factory.mktemp("hash_check") / "gfpush_hash_check")
-    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-I" + os.path.join(ROOT, "grand_plus_amd", "csrc"), "-o", exe,
-                    os.path.join(ROOT, "tests", "native", "gfpush_hash_check.cpp")], check=True, timeout=300)
-    return exe
+    """The path of the check program (test_checker_rejects_what_it_cannot_answer runs it for its exit status)."""
+    return native_check.build(tmp_path_factory, "gfpush_hash_check")
 
 
 def _ask(exe, lines):
-    r = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stderr
-    return [[int(x) for x in ln.split()] for ln in r.stdout.splitlines()]
+    return native_check.ints(native_check.run(exe, lines))
 
 
 def test_the_hash_header_needs_nothing_but_the_standard_library(tmp_path):

@@ -1,18 +1,16 @@
 """CPU tests of the fit loop: the keyed permutation's Python mirror against csrc/fit_perm.hpp itself
-(tests/native/fit_perm_check.cpp, built with the address and undefined-behaviour sanitizers), the binding of csrc/fit_abi.hpp
-(fit.ABI and the struct mirrors) against that header and the C compiler, the entry points' error codes before any GPU
-work, and the host rules: the sampler's shapes and the early-stop rule against a transcription of model.py:344-359."""
+(tests/native/fit_perm_check.cpp, built with the address and undefined-behaviour sanitizers), the entry points' error
+codes before any GPU work, and the host rules: the sampler's shapes and the early-stop rule against a transcription of model.py:344-359."""
 import ctypes
 import glob
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
-import abi_header as ah
+import native_check
 from fit_cases import RULE_CASES, SCRIPTS, bits as _bits, run_rule
 from grand_plus_amd import _common, _native
 from grand_plus_amd import fit as gf
@@ -28,17 +26,8 @@ P = ctypes.c_void_p(16)
 @pytest.fixture(scope="module")
 def checker(tmp_path_factory):
     """ask(lines) -> one list of ints per line.  Nothing is preloaded: the sanitizers are linked into the program itself."""
-    if shutil.which("g++") is None:
-        pytest.fail("g++ is needed to build tests/native/fit_perm_check.cpp")
-    exe = str(tmp_path_factory.mktemp("fit_perm") / "fit_perm_check")
-    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I" + CSRC,
-                    "-o", exe, os.path.join(ROOT, "tests", "native", "fit_perm_check.cpp")], check=True, timeout=300)
-
-    def ask(lines):
-        r = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, timeout=120)
-        assert r.returncode == 0 and not r.stderr, (r.returncode, r.stderr[-4000:])          # (a sanitizer report ends the program)
-        return [[int(x) for x in ln.split()] for ln in r.stdout.splitlines()]
-    return ask
+    exe = native_check.build(tmp_path_factory, "fit_perm_check")
+    return lambda lines: native_check.ints(native_check.run(exe, lines))
 
 
 # ---- 1. the permutation
@@ -156,79 +145,9 @@ def test_sampler_selection_follows_its_definition(checker):
     assert sorted(whole.tolist()) == list(range(5))
 
 
-# ---- 3. the binding
-def _header():
-    text = open(os.path.join(CSRC, "fit_abi.hpp")).read()
-    return text, re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
-
-
-def _prototypes():
-    """name -> (return type, parameters) of fit_abi.hpp, parsed as abi_header.prototypes parses a public header."""
-    _, code = _header()
-    protos = {}
-    for ret, name, params in re.findall(r"\b((?:const\s+)?\w+\s*\**)\s*\b(gp_[a-z_0-9]+)\s*\(([^)]*)\)\s*;", code):
-        assert name not in protos
-        params = [re.fullmatch(r"(.*?)(\w+)", p.strip(), flags=re.S).groups() for p in params.split(",")]
-        protos[name] = (ah._ctype(ret), [ah._ctype(decl) + (pname,) for decl, pname in params])
-    assert sorted(re.findall(r"\b(gp_[a-z_0-9]+)\s*\(", code)) == sorted(protos)
-    return protos
-
-
-def _expected(name, base, stars, param=None):
-    if base == "gp_fit_copy" and stars == 1 and not (param or "").startswith("d_"):
-        return ctypes.POINTER(gf.GpFitCopy)                                  # a host array of the table's struct
-    return ah.expected_ctype(name, base, stars, param)
-
-
-def test_the_table_is_the_headers_prototypes_position_by_position():
-    protos = _prototypes()
-    assert sorted(protos) == sorted(gf.ABI) == ["gp_fit_select", "gp_fit_snapshot", "gp_fit_track_update"]
-    built = ctypes.CDLL(_native.LIB_PATH)
-    for name, (ret, params) in protos.items():
-        restype, argtypes = gf.ABI[name]
-        assert restype is _expected(name, *ret)
-        assert len(argtypes) == len(params), name
-        for i, (got, want) in enumerate(zip(argtypes, params)):
-            assert got is _expected(name, *want), f"{name}: argument {i} is {got} for {want}"
-        assert hasattr(built, name), f"libgrandplus.so does not export {name}"
-        f = getattr(gf.lib(), name)
-        assert f.argtypes == argtypes and f.restype is restype
-    assert len(gf.ABI["gp_fit_select"][1]) == 11
-
-
-def test_the_entry_points_stay_outside_c_abi_4():
-    import __graft_entry__ as entry
-    assert entry.LIB_UNITS[-1] == "fit.hip" and os.path.join(CSRC, "fit_abi.hpp") in entry.lib_sources()
-    names = {n for entries in _native.ABI.values() for n in entries}
-    assert not names & set(gf.ABI)
-    public = "".join(open(p).read() for p in glob.glob(os.path.join(ROOT, "include", "*.h")))
-    assert "gp_fit" not in public and "GP_FIT" not in public
-    assert not [n for n in vars(_native) if "FIT" in n.upper()]
-    assert _native.lib().gp_abi_version() == 4
-
-
-def test_the_struct_mirrors_and_constants_equal_what_the_c_compiler_sees(tmp_path):
-    _, code = _header()
-    exprs = []
-    for struct, mirror in (("gp_fit_track", gf.GpFitTrack), ("gp_fit_copy", gf.GpFitCopy)):
-        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (struct, struct), code, flags=re.S).group(1)
-        fields = []
-        for decl in filter(None, (d.strip() for d in body.split(";"))):
-            base, star, name = re.fullmatch(r"(?:const\s+)?(\w+)\s*(\*?)\s*(\w+)", decl).groups()
-            fields.append((name, ctypes.c_void_p if star else ah.SCALARS[base]))
-        assert [(n, t) for n, t in mirror._fields_] == fields
-        exprs += [(f"sizeof({struct})", ctypes.sizeof(mirror))] + [(f"offsetof({struct}, {n})", getattr(mirror, n).offset) for n, _ in fields]
-    exprs += [(n, getattr(gf, n)) for n in ("GP_FIT_STOP_ACC", "GP_FIT_STOP_BOTH", "GP_FIT_MAX_COPIES")]
-    assert sorted(re.findall(r"#define (GP_FIT_\w+)", code)) == sorted(n for n in vars(gf) if n.startswith("GP_FIT_"))
-    src, exe = tmp_path / "values.cpp", tmp_path / "values"
-    src.write_text('#include <cstdio>\n#include <cstddef>\n#include "fit_abi.hpp"\nint main() {\n' +
-                   "".join(f'  std::printf("%lld\\n", (long long)({e}));\n' for e, _ in exprs) + "  return 0;\n}\n")
-    subprocess.run(["g++", "-std=c++17", "-I" + ah.INC, "-I" + CSRC, "-o", str(exe), str(src)], check=True, timeout=120)
-    got = [int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    assert got == [v for _, v in exprs], list(zip(exprs, got))
-    assert got[0] == 40 and ctypes.sizeof(gf.GpFitCopy) == 24
-    assert gf.GP_FIT_MAX_COPIES * 24 + 8 <= 1024                                 # the by-value table fits the kernel arguments
-    assert gf.TrackImage._fields == tuple(n for n, _ in gf.GpFitTrack._fields_)
+# ---- 3. the host images of gp_fit_track (the binding itself is held in tests/test_host_abi.py)
+def test_the_track_images_carry_the_structs_fields():
+    assert gf.TrackImage._fields == tuple(n for n, _ in _native.GpFitTrack._fields_)
     init = gf.new_track()
     assert set(init) == set(gf.TrackImage._fields) and init["best_loss"] == np.inf and sum(v for k, v in init.items() if k != "best_loss") == 0
 
@@ -237,7 +156,7 @@ def test_the_struct_mirrors_and_constants_equal_what_the_c_compiler_sees(tmp_pat
 def test_the_entries_return_their_error_codes_before_any_gpu_work():
     """No device pointer here is real: every call has to stop at its argument checks."""
     E, N, OK = _native.GP_ERR_INVALID_ARG, _native.GP_ERR_NULL, _native.GP_OK
-    L = gf.lib()
+    L = _native.lib()
 
     def select(st=P, n_train=7, n_unlabel=9, bs=3, ub=4, n_l=3, sel=P, flag=P):
         return L.gp_fit_select(0, st, 1, n_train, n_unlabel, bs, ub, n_l, sel, flag, None)
@@ -249,7 +168,7 @@ def test_the_entries_return_their_error_codes_before_any_gpu_work():
     assert select(st=None) == N and select(sel=None) == N and select(flag=None) == N
     assert select(st=None, n_train=0) == E                                      # sizes are judged first
 
-    def update(tr=P, val=P, st=P, mode=gf.GP_FIT_STOP_BOTH, patience=3):
+    def update(tr=P, val=P, st=P, mode=_native.GP_FIT_STOP_BOTH, patience=3):
         return L.gp_fit_track_update(0, tr, val, st, mode, patience, None)
 
     assert update(mode=2) == E and update(mode=-1) == E and update(patience=0) == E and update(patience=-5) == E
@@ -257,7 +176,7 @@ def test_the_entries_return_their_error_codes_before_any_gpu_work():
     assert update(tr=None) == N and update(val=None) == N and update(st=None) == N
 
     def snap(entries, tr=P, n=None, null=False):
-        tab = (gf.GpFitCopy * max(len(entries), 1))(*[gf.GpFitCopy(*e) for e in entries])
+        tab = (_native.GpFitCopy * max(len(entries), 1))(*[_native.GpFitCopy(*e) for e in entries])
         return L.gp_fit_snapshot(0, tr, None if null else tab, len(entries) if n is None else n, None)
 
     assert snap([(16, 32, 1)], n=-1) == E

@@ -2,11 +2,11 @@
 built stand-alone with the address and undefined-behaviour sanitizers and run as a child process; each decision goes in as a
 line of numbers and comes back as one.  The recorded plans of tests/golden/gfpush_plans.json must come out exactly."""
 import os
-import shutil
 import subprocess
 
 import pytest
 
+import native_check
 import plan_cases
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -22,18 +22,8 @@ CUS = DOC["num_cus"]
 @pytest.fixture(scope="module")
 def checker(tmp_path_factory):
     """run(lines) -> the program's output lines.  Nothing is preloaded: the sanitizers are linked into the program itself."""
-    if shutil.which("g++") is None:
-        pytest.fail("g++ is needed to build tests/native/gfpush_plan_check.cpp")
-    exe = str(tmp_path_factory.mktemp("plan_check") / "gfpush_plan_check")
-    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-I" + os.path.join(ROOT, "grand_plus_amd", "csrc"), "-o", exe,
-                    os.path.join(ROOT, "tests", "native", "gfpush_plan_check.cpp")], check=True, timeout=300)
-
-    def run(lines):
-        r = subprocess.run([exe], input="\n".join([CONSTS] + list(lines)) + "\n", capture_output=True, text=True, timeout=60)
-        assert r.returncode == 0 and not r.stderr, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])     # (a sanitizer report ends the program)
-        return r.stdout.splitlines()
-    return run
+    exe = native_check.build(tmp_path_factory, "gfpush_plan_check")
+    return lambda lines: native_check.run(exe, [CONSTS] + list(lines))
 
 
 def handle(graph, options=None, acsr_ok=1):

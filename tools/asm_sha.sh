@@ -2,6 +2,7 @@
 # SHA-256 of each translation unit's gfx950 device assembly, compiled with the library's flags, less what follows the source
 # text and not the code (comment lines, .file, .ident, the __hip_cuid_ symbol).  Equal hashes = equal device code.
 # SRC=<dir> hashes another revision's sources: git archive REV grand_plus_amd/csrc | tar -x -C <tmp>, SRC=<tmp>/grand_plus_amd/csrc
+# (they compile against THIS tree's include/; for a revision whose public headers differ, archive the whole tree and run its own copy)
 cd "$(dirname "$0")/.."
 for u in $(python -c 'import __graft_entry__ as g; print(*g.LIB_UNITS)'); do
   python -c 'import sys, subprocess, __graft_entry__ as g
