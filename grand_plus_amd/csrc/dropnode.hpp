@@ -1,5 +1,5 @@
 // dropnode.hpp -- the DropNode weight, the embedding bag's layout and the two denominators of the training step's front
-// end, defined once for augment.hip (§7d, §7e), scatter_det.hip (§7i) and mag_prop.hip (§7k).  The three promise each
+// end, defined once for augment.hip (§7d, §7e), scatter_det.hip (§7i), mag_prop.hip (§7k) and mag_det.hip (§7o).  They promise each
 // other's bits; they keep the promise by calling the same lines:
 //     scatter_det.hip's deterministic backwards give what augment.hip's atomic backwards give, up to the order of the sum:
 //         the backward must find an entry, its bag, its mask and its denominator exactly as the forward finds them;

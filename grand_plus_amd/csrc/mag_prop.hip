@@ -9,50 +9,18 @@
 //   the waves' sums meet in LDS and are added in wave order (no atomics in the forward).
 // The order contract, the mask formulas and the bounds rules are stated in grandplus_mag.h.  The DropNode weight of
 // (sample s, entry e) is dropnode.hpp's sample_weight, the line gp_random_prop_rows_multi calls: the same mask for the same seed.
-#include "dropnode.hpp"
+#include "mag_stage.hpp"
 
 #include <algorithm>
 
 namespace {
 
-constexpr int kMaxWaves = 16;
-constexpr int kLdsFloats = 65536 / 4;
-constexpr int kGridCap = 8192;                         // workgroups of up to 1 024 threads: 32 per CU on 256 CUs
 constexpr u64 kSlotMul = 0xE7037ED1A0B428DBull;        // GP_MAG_SLOT_SEED's multiplier: no other derivation uses it
 
 // GP_MAG_SLOT_SEED(seed, s, e)
 __device__ __forceinline__ u64 slot_seed(u64 seed, int s, long long e)
 {
     return mix64(sample_seed(seed, s) ^ ((u64)(e + 1) * kSlotMul));
-}
-
-struct MagArgs {
-    long long V; int H;
-    const long long* indptr; const int* indices; const float* data; long long N;
-    const int* col; const double* val; const int* filled; long long n_rows; int K;
-    const int* batch_rows; int B; int S; int nsc;
-    float p_node, p_in; int training; u64 seed;
-    const unsigned char* keep; long long keep_stride;
-};
-
-// Stage the row's columns (first chunk) and the weights of samples s0 .. s0 + ns - 1; a column outside [0, N) makes
-// the slot absent (weight 0).  Called by every thread, between two barriers of the caller.
-__device__ __forceinline__ void stage_row(const MagArgs& A, long long row, int n, int s0, int ns, float scale_node,
-                                          int* s_col, int* s_seen, float* s_w, int* n_bad)
-{
-    for (int k = threadIdx.x; k < n; k += blockDim.x) {
-        const long long e = row * (long long)A.K + k;
-        const float w = (float)A.val[e];                              // model_mag.py:343
-        const int c = A.col[e];
-        const bool c_ok = c >= 0 && c < A.N;
-        if (s0 == 0) {
-            s_col[k] = c;
-            if (s_seen) s_seen[k] = 0;
-            if (!c_ok && n_bad) atomicAdd(n_bad, 1);
-        }
-        for (int s = 0; s < ns; ++s)
-            s_w[s * A.K + k] = c_ok ? sample_weight(w, e, s0 + s, A.p_node, scale_node, A.training, A.seed, A.keep, A.keep_stride) : 0.0f;
-    }
 }
 
 // LDS: s_col[K] s_seen[K] s_inv[16] s_w[nsc][K] s_red[n_waves][nsc][64].  NS >= nsc accumulators per lane.
@@ -255,23 +223,6 @@ mag_prop_rows_backward_kernel(const float* __restrict__ grad_out, MagArgs A, flo
             }
         }
     }
-}
-
-int mag_check(const char* where, int64_t n_vocab, int32_t dim, int64_t n_nodes, int64_t n_rows, int32_t K, int32_t n_batch,
-              int32_t n_samples, float p_node, float p_in, const void* keep, int64_t keep_stride)
-{
-    if (n_samples < 1 || n_samples > kMaxSamples || !(p_node >= 0.0f && p_node <= 1.0f) || !(p_in >= 0.0f && p_in <= 1.0f))
-        return fail(GP_ERR_INVALID_ARG, where, "n_samples outside [1, 16] or a rate outside [0, 1]");
-    if (n_vocab < 1 || dim < 1 || n_nodes < 0 || n_rows < 0 || K < 1 || K > GP_MAX_K || n_batch < 0 || (keep && keep_stride < 1))
-        return fail(GP_ERR_INVALID_ARG, where, "bad size, K outside [1, 1024] or keep_stride < 1 with a mask");
-    return GP_OK;
-}
-
-int waves_for(int K)                                   // min(16, the power of two >= K): a function of K alone
-{
-    int w = 1;
-    while (w < K && w < kMaxWaves) w <<= 1;
-    return w;
 }
 
 // Accumulators per lane of the forward: S rounded up to a power of two, at most 8; more samples take several chunks.

@@ -11,9 +11,13 @@ step runs under `torch.cuda.set_sync_debug_mode("error")` like every other step 
 is keyed (`mag_slot_seed(seed, s, e)`, t*H + h).  out[s] of an S-sample call equals the single-sample call with
 `sample_seed(seed, s)` (or `keep[s]`) bit for bit, and the forward is bitwise the same run to run.
 
-The gradient reaches `weight` only.  The backward adds into a dense dW with fp32 atomics: it is not bitwise reproducible,
-and there is no deterministic variant; asked for one (`deterministic=True`, or torch's deterministic mode), a call that wants
-a gradient raises and names the composed path, which has one.  There is no CPU fallback.
+The gradient reaches `weight` only.  By default the backward adds into a dense dW with fp32 atomics: fast, and not bitwise
+reproducible.  The deterministic backward (mag_det.py) needs a capacity for its key buffer, because the host
+never learns how many entries a batch has: with `max_entries=` given, a call in deterministic mode (`deterministic=True`, or
+torch's deterministic mode) takes it -- keys, `torch.sort(stable=True)`, a sequential sum per table row, no host read, the
+same bits run to run.  Without `max_entries` such a call still raises and names the composed path.  With `max_entries` and
+the mode resolving to non-deterministic the atomic backward runs and `max_entries` is ignored, so a caller may pass it always
+and let torch's flag decide.  The forward is the same in every mode.  There is no CPU fallback.
 """
 from __future__ import annotations
 
@@ -65,33 +69,47 @@ class _MagRowsFn(torch.autograd.Function):
     """mag_prop_rows with the gradient to weight (summed over the samples)."""
 
     @staticmethod
-    def forward(ctx, weight, call, n_bad):
+    def forward(ctx, weight, call, n_bad, det=None):
+        """det: None for the atomic backward, (max_entries, overflow) for the deterministic one (mag_det.backward_det)."""
         ctx.save_for_backward(*call.tensors)
-        ctx.args = (weight.shape, call.scalars)
+        ctx.args = (weight.shape, call.scalars, det)
         return _forward(weight, call, n_bad)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_out):
-        shape, scalars = ctx.args
-        return _backward(shape, grad_out, _Call(ctx.saved_tensors, *scalars)), None, None
+        shape, scalars, det = ctx.args
+        call = _Call(ctx.saved_tensors, *scalars)
+        if det is None:
+            return _backward(shape, grad_out, call), None, None, None
+        from .mag_det import backward_det
+        return backward_det(shape, grad_out, call, *det), None, None, None
 
 
 def mag_prop_rows(weight, attr_indptr, attr_indices, attr_data, col, val, filled, K, batch_rows=None, *, samples=1,
-                  dropnode_rate=0.5, input_droprate=0.0, training=True, seed=None, keep=None, validate=False, deterministic=None):
+                  dropnode_rate=0.5, input_droprate=0.0, training=True, seed=None, keep=None, validate=False, deterministic=None,
+                  max_entries=None, overflow=None):
     """The S augmented embeddings of a batch of resident rows, in one launch.
 
     weight [V, H] float32 (the `nn.Embedding` table); attr_indptr [N + 1] int64, attr_indices [nnz] int32, attr_data [nnz]
     float32 (the node-attribute CSR resident on the GPU); col int32 [S_rows * K], val float64 [S_rows * K], filled int32
     [S_rows] or None (every slot filled) as `Graph.gfpush_device` returns them; batch_rows int32 [B] (None: every row).
     Returns [B, H] float32 for samples = 1 and [S, B, H] otherwise (keep: uint8 [S, S_rows * K], the DropNode mask of
-    `random_prop_rows`).  Differentiable with respect to `weight`: `torch.zeros` and one launch, fp32 atomics.
+    `random_prop_rows`).  Differentiable with respect to `weight`: by default `torch.zeros` and one launch, fp32 atomics.
     A batch row outside [0, S_rows), a column outside [0, N) and an attribute id outside [0, V) are never used as an
     address; they contribute nothing and are counted: validate=True reads the count back (the only host read of this
     function) and raises IndexError.
-    `deterministic`: None follows `torch.are_deterministic_algorithms_enabled()`; when it resolves to True and a gradient
-    is wanted the call raises RuntimeError (this backward has no deterministic variant)."""
+    `deterministic`: None follows `torch.are_deterministic_algorithms_enabled()`.  When it resolves to True and a gradient
+    is wanted, the backward is the deterministic one of DESIGN §7o if `max_entries` (an int >= 1: the capacity of its key
+    buffer, an upper bound of sum over the batch's slots of the slot's bag length) is given; without `max_entries` the call
+    raises RuntimeError.  It never reads the host: `overflow` (an int32 [1] tensor on weight's device; a private one
+    that nobody reads when omitted) gets bit 0 set by the backward if the batch had more entries than `max_entries`, and
+    the gradient then lacks the entries past it.  Input dropout (input_droprate > 0 while training) is not supported by that
+    backward: ValueError.  When the mode resolves to False `max_entries` is ignored."""
     deterministic = _deterministic(deterministic)
+    if max_entries is not None:
+        from .mag_det import check_max_entries
+        check_max_entries(max_entries)
     if not isinstance(samples, int) or not 1 <= samples <= _native.GP_MAX_SAMPLES:
         raise ValueError(f"samples must be an int in [1, {_native.GP_MAX_SAMPLES}], got {samples!r}")
     _check(weight, torch.float32, "weight")
@@ -129,16 +147,27 @@ def mag_prop_rows(weight, attr_indptr, attr_indices, attr_data, col, val, filled
         if t is not None and t.device != weight.device:
             raise TypeError(f"{name} must be on {weight.device}, got {t.device} (no CPU fallback)")
     wants_grad = torch.is_grad_enabled() and weight.requires_grad
-    if deterministic and wants_grad:
+    det = None
+    if deterministic and wants_grad and max_entries is not None:
+        from .mag_det import check_overflow
+        if training and float(input_droprate) > 0.0:
+            raise ValueError("the deterministic backward of mag_prop_rows does not support input dropout (DESIGN §9): "
+                             "input_droprate must be 0 in training")
+        if B * K >= 2 ** 31:
+            raise ValueError(f"the deterministic backward of mag_prop_rows takes fewer than 2**31 slots, got {B} x {K}")
+        if overflow is not None:
+            check_overflow(overflow, weight.device)
+        det = (max_entries, overflow if overflow is not None else torch.zeros(1, dtype=torch.int32, device=weight.device))
+    elif deterministic and wants_grad:
         raise RuntimeError("mag_prop_rows has no deterministic backward (fp32 atomics into dW); for a reproducible gradient use the "
                            "composed path with deterministic=True: flatten_rows -> embedding_bag_csr(nodes=..., deterministic=True) "
-                           "-> random_prop")
+                           "-> random_prop, or pass max_entries= for the deterministic backward of this op (DESIGN §7o)")
     if seed is None:
         seed = _new_seed()
     call = _Call((attr_indptr, attr_indices, attr_data, col, val, filled, batch_rows, keep), S_rows, K, B, samples,
                  float(dropnode_rate), float(input_droprate), bool(training), seed)
     n_bad = torch.zeros(1, dtype=torch.int32, device=weight.device)
-    out = _MagRowsFn.apply(weight, call, n_bad) if wants_grad else _forward(weight, call, n_bad)
+    out = _MagRowsFn.apply(weight, call, n_bad, det) if wants_grad else _forward(weight, call, n_bad)
     if validate:
         bad = int(n_bad.item())
         if bad:

@@ -1,0 +1,99 @@
+"""The deterministic table gradient of `mag_prop_rows`: the binding of csrc/mag_det_abi.hpp and the backward
+built on it.
+
+The atomic backward of mag.py adds one fp32 atomic per (entry, column) into dW: fast, capturable, not reproducible.  The
+composed path has a deterministic backward, but it asks the host how many entries the batch has.  Here the host never
+learns that number: the caller fixes a capacity `max_entries` beforehand, `gp_mag_det_keys` writes the entries' attribute
+ids into a key buffer of that size (sentinel V in the tail, a flag instead of a write past the end), `torch.sort(stable=True)`
+orders them, and `gp_mag_prop_rows_backward_det` sums every table row's contributions in entry order (b, k, t), left to
+right from 0.0f.  Nothing is read back, so the backward runs under `torch.cuda.set_sync_debug_mode("error")` and inside a
+captured graph.
+
+The entry points are extern "C" symbols of libgrandplus.so declared in csrc/mag_det_abi.hpp; they are not part of C ABI 4,
+so their binding (ABI below) lives here and not in `_native`.
+
+Left out: input dropout (the keyed mask would need S values of U per slot), hub segments cut into chunks.
+"""
+from __future__ import annotations
+
+import ctypes
+
+import torch
+
+from . import _native
+from ._common import _dev_index, _ptr, _stream
+
+__all__ = ["backward_det", "check_max_entries", "check_overflow"]
+
+# name -> (restype, argtypes), under the convention stated above _native.ABI; tests/test_host_mag_det.py holds it against
+# mag_det_abi.hpp.  _native._mag: gp_mag_prop_rows' arguments between the table and the outputs.
+_int, _i32, _i64, _vp = ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p
+ABI = {
+    "gp_mag_det_keys": (_int, [_int, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _i32, _i64, _vp, _vp, _vp, _vp]),
+    "gp_mag_prop_rows_backward_det": (_int, [_int, _vp] + _native._mag + [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+}
+_BOUND = False
+_MAX_SLOTS = 2 ** 31
+
+
+def lib():
+    """_native.lib() with the entry points of mag_det_abi.hpp declared on it.  A library without them is an error, not a
+    fallback."""
+    global _BOUND
+    L = _native.lib()
+    if not _BOUND:
+        for name, (restype, argtypes) in ABI.items():
+            if not hasattr(L, name):
+                raise RuntimeError(f"{_native.LIB_PATH} does not export {name} (an older build?): rebuild the library")
+            f = getattr(L, name)
+            f.restype, f.argtypes = restype, argtypes
+        _BOUND = True
+    return L
+
+
+def check_max_entries(max_entries):
+    """`max_entries` as an int >= 1 (ValueError otherwise): the capacity of the key buffer, in entries."""
+    if isinstance(max_entries, bool) or not isinstance(max_entries, int) or max_entries < 1:
+        raise ValueError(f"max_entries must be an int >= 1, got {max_entries!r}")
+    return max_entries
+
+
+def check_overflow(overflow, device):
+    """`overflow` as the int32 [1] tensor on `device` that receives the overflow flag (TypeError otherwise)."""
+    if not isinstance(overflow, torch.Tensor) or overflow.dtype != torch.int32 or overflow.numel() != 1 or \
+            not overflow.is_contiguous() or overflow.device != device:
+        raise TypeError(f"overflow must be a contiguous int32 tensor of one element on {device}")
+    return overflow
+
+
+def backward_det(weight_shape, grad_out, call, max_entries, overflow):
+    """dW [V, H] of mag_prop_rows by the order contract of mag_det_abi.hpp.  call: mag._Call, the forward's operands;
+    overflow: int32 [1], bit 0 is set when the batch has more than max_entries entries (the gradient then lacks the rest).
+    Six launches, torch.sort between the third and the fourth; no host read."""
+    V, H = weight_shape
+    attr_indptr, attr_indices, attr_data, col, val, filled, batch_rows, keep = call.tensors
+    S_rows, K, B, S, p_node, p_in, training, seed = call.scalars
+    if training and p_in > 0.0:
+        raise ValueError("the deterministic backward of mag_prop_rows does not support input dropout (DESIGN §9)")
+    if B * K >= _MAX_SLOTS:
+        raise ValueError(f"the deterministic backward of mag_prop_rows takes fewer than 2**31 slots, got {B} x {K}")
+    g = grad_out.contiguous()
+    dev = g.device
+    dW = torch.zeros((V, H), dtype=torch.float32, device=dev)
+    if B == 0:
+        return dW
+    slot_base = torch.empty(B * K + 1, dtype=torch.int64, device=dev)
+    keys = torch.empty(max_entries, dtype=torch.int64, device=dev)
+    L = lib()
+    rc = L.gp_mag_det_keys(_dev_index(g), V, attr_indptr.data_ptr(), attr_indices.data_ptr(), attr_indptr.numel() - 1,
+                           col.data_ptr(), _ptr(filled), S_rows, K, _ptr(batch_rows), B, max_entries, slot_base.data_ptr(),
+                           keys.data_ptr(), overflow.data_ptr(), _stream(g))
+    _native.raise_for_status(rc)
+    sorted_keys, order = torch.sort(keys, stable=True)
+    U = torch.empty((B * K, H), dtype=torch.float32, device=dev)
+    inv = torch.empty((S, B), dtype=torch.float32, device=dev)
+    rc = L.gp_mag_prop_rows_backward_det(_dev_index(g), g.data_ptr(), V, H, *call.args(), slot_base.data_ptr(), order.data_ptr(),
+                                         sorted_keys.data_ptr(), max_entries, U.data_ptr(), inv.data_ptr(), dW.data_ptr(),
+                                         _stream(g))
+    _native.raise_for_status(rc)
+    return dW

@@ -1,0 +1,111 @@
+"""MAG's training step over device-resident step state, replayable from a captured graph.
+
+`MagTrainStep` is `step.TrainStep` with the front end swapped: where that runs `random_prop_rows` over dense features,
+this runs `MagMLP.emb_rows` (`mag_prop_rows`, §7k) over the node-attribute CSR and trains the embedding table with the
+layers.  The advance, the batch gather, `gp_step_masks` (the DropNode mask is `random_prop_rows`'s layout, which
+`mag_prop_rows` takes), the S-sample MLP, the loss, `ClipAdam(capturable=True)`, `step`, `step_sampled`, the graph per batch
+shape, `MAX_GRAPHS` and the wrapping of a broken capture are inherited.
+
+The table gradient has two modes.  `deterministic=False`: the atomic backward, one launch, not reproducible -- the fast
+mode.  `deterministic=True` (None follows torch's flag): the sort-then-gather backward of mag_det.py, which never asks the
+host for a number, so the whole step is captured and a replay is bitwise the eager step.  Its key buffer holds
+`max_entries` entries per batch row and slot: None means K * Lmax per batch row, Lmax the longest bag among the nodes that
+occur as columns of `rows` (read once here, the constructor's one host read), and then the buffer cannot overflow.
+
+Left out: input dropout (`model.input_droprate` must be 0), `fit` for MAG, several steps in one graph.
+"""
+from __future__ import annotations
+
+import torch
+
+from ._common import _deterministic
+from .step import TrainStep, trained_parameters
+
+__all__ = ["MagTrainStep", "mag_trained_parameters"]
+
+
+def mag_trained_parameters(model):
+    """The parameters of a MagMLP that a training step gives a gradient: the embedding table, then what
+    `trained_parameters` lists for the layers."""
+    return [model.embeds.weight] + trained_parameters(model)
+
+
+def _csr(t, dtype, name):
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.dim() != 1 or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous 1-D tensor of dtype {dtype}")
+
+
+class MagTrainStep(TrainStep):
+    """One MAG training step (model_mag.py's loop body) as one replayable object.
+
+    model: a MagMLP in train mode with input_droprate = 0; optimizer: a ClipAdam(capturable=True, state=StepState(device))
+    over `mag_trained_parameters(model)`; rows: the RowMatrix; attr_indptr int64 [N + 1], attr_indices int32 [nnz],
+    attr_data float32 [nnz]: the node-attribute CSR on the GPU; labels, idx_train, idx_unlabel and the keywords up to
+    `capture` as for TrainStep.  nlayers = 1 (no `fcs`: the embedding is the logits) is accepted.
+
+    deterministic: None follows torch.are_deterministic_algorithms_enabled(), resolved here once.  True: the table gradient is
+    mag_det's (bitwise the same run to run, eager or replayed); False: fp32 atomics.
+    max_entries: the capacity of the deterministic backward's key buffer for the WHOLE batch; None: B * K * Lmax per batch
+    shape, which cannot overflow.  A tighter value may: the step then runs on with a gradient that lacks the entries past
+    it and sets a flag, which `check_entries_flag()` reads.
+
+    With capture=True and the deterministic mode the capture includes `torch.sort`; should a torch build refuse to capture it,
+    the capture fails as every broken capture does here: a RuntimeError naming the call (backward), no retry, no fallback."""
+
+    def __init__(self, model, optimizer, rows, attr_indptr, attr_indices, attr_data, labels, idx_train, idx_unlabel, *, samples,
+                 dropnode_rate, lam, warmup, tem, conf=None, kind="l2", seed, capture=True, deterministic=None, max_entries=None):
+        from .mlp import MagMLP
+        if not isinstance(model, MagMLP):
+            raise ValueError("MagTrainStep takes a MagMLP (a GrandPlusMLP goes to step.TrainStep)")
+        if float(model.input_droprate) != 0.0:
+            raise ValueError("MagTrainStep needs model.input_droprate = 0: input dropout in the step is left out (DESIGN §9), got "
+                             f"{model.input_droprate}")
+        self._check_optimizer_and_rows(optimizer, rows)
+        _csr(attr_indptr, torch.int64, "attr_indptr")
+        _csr(attr_indices, torch.int32, "attr_indices")
+        _csr(attr_data, torch.float32, "attr_data")
+        if attr_indptr.numel() != rows.n_nodes + 1 or attr_data.numel() != attr_indices.numel():
+            raise ValueError(f"attr_indptr needs one entry per node ({rows.n_nodes}) plus one; attr_indices and attr_data the same length")
+        self._check_hyperparameters(model, optimizer, samples, dropnode_rate, kind, tem)
+        self.deterministic = _deterministic(deterministic)
+        if max_entries is not None:
+            from .mag_det import check_max_entries
+            check_max_entries(max_entries)
+        if not attr_indptr.is_cuda:
+            raise ValueError("the step runs on the GPU only: the attribute CSR must be CUDA tensors (no CPU fallback)")
+        dev = attr_indptr.device
+        for name, t in (("attr_indices", attr_indices), ("attr_data", attr_data), ("rows.col", rows.col),
+                        ("model.embeds.weight", model.embeds.weight)):
+            if t.device != dev:
+                raise ValueError(f"{name} must be on the device of attr_indptr ({dev}), got {t.device}")
+        if not isinstance(labels, torch.Tensor) or labels.dtype != torch.int64 or labels.device != dev:
+            raise ValueError("labels must be an int64 tensor on the device of the attribute CSR")
+        self.attr = (attr_indptr, attr_indices, attr_data)
+        self.max_entries = max_entries
+        self._setup(model, optimizer, rows, labels, idx_train, idx_unlabel, dev, samples=samples, dropnode_rate=dropnode_rate,
+                    lam=lam, warmup=warmup, tem=tem, conf=conf, kind=kind, seed=seed, capture=capture)
+        self._entries_flag = torch.zeros(1, dtype=torch.int32, device=dev)   # bit 0: a backward had more entries than its buffer
+        # the longest bag among the nodes that occur as columns of rows: the one host read, and only here
+        lens = attr_indptr[1:] - attr_indptr[:-1]
+        cols = rows.col.long()
+        cols = cols[(cols >= 0) & (cols < rows.n_nodes)]
+        self.longest_bag = int(lens[cols].max().item()) if cols.numel() else 0
+
+    def _max_entries(self, B):
+        if self.max_entries is not None:
+            return self.max_entries
+        return max(1, B * self.rows.K * self.longest_bag)
+
+    def _front(self, batch_rows):
+        self._where = "mag_prop_rows"
+        S = self.samples
+        X = self.model.emb_rows(*self.attr, self.rows, batch_rows=batch_rows, samples=S, dropnode_rate=self.dropnode_rate, seed=0,
+                                keep=self._node_keep, deterministic=self.deterministic,
+                                max_entries=self._max_entries(batch_rows.numel()), overflow=self._entries_flag)
+        return X[None] if S == 1 else X
+
+    def check_entries_flag(self):
+        """Raises if a deterministic backward had more entries than `max_entries` (one device-to-host copy)."""
+        if int(self._entries_flag.item()) & 1:
+            raise RuntimeError(f"a step's batch had more entries than max_entries = {self.max_entries}: the table gradient of that "
+                               "step lacks the entries past it (pass a larger max_entries, or None for B * K * Lmax)")

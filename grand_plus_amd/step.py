@@ -13,7 +13,11 @@ MLP's dropout seed, the consistency weight min(lam, lam * num_batch / warmup) (m
     batch from the host; `step_sampled()` has `gp_fit_select` draw it on the device right after the advance, so a replay
     takes no host input (`fit.py`).
 
-Left out: MagMLP / mag_prop_rows, several optimisers, `validate=True` of the loss, and schedulers that change
+`TrainStep` takes a GrandPlusMLP over dense features.  MAG's step (a MagMLP, whose front end is `mag_prop_rows` and whose
+embedding table is trained) is `mag_step.MagTrainStep`, a subclass that swaps the front end of the body (`_front`) and
+inherits the rest.
+
+Left out: several optimisers, `validate=True` of the loss, and schedulers that change
 `lr` between replays -- `lr` is a value of the capture; rebuild the TrainStep after changing it.
 """
 from __future__ import annotations
@@ -163,19 +167,38 @@ class TrainStep:
     def __init__(self, model, optimizer, rows, features, labels, idx_train, idx_unlabel, *, samples, dropnode_rate, lam,
                  warmup, tem, conf=None, kind="l2", seed, capture=True):
         from .mlp import GrandPlusMLP
-        from .optim import ClipAdam
-        from .rows import RowMatrix
         if not isinstance(model, GrandPlusMLP):
-            raise ValueError("TrainStep takes a GrandPlusMLP (MagMLP / mag_prop_rows are left out: DESIGN §9)")
-        if not isinstance(optimizer, ClipAdam) or not optimizer.capturable:
-            raise ValueError("TrainStep takes a ClipAdam(capturable=True)")
-        if not isinstance(rows, RowMatrix):
-            raise ValueError("rows must be a RowMatrix")
+            raise ValueError("TrainStep takes a GrandPlusMLP (a MagMLP goes to mag_step.MagTrainStep: DESIGN §7o)")
+        self._check_optimizer_and_rows(optimizer, rows)
         if not isinstance(features, torch.Tensor) or features.dtype != torch.float32 or features.dim() != 2 or \
                 not features.is_contiguous():
             raise ValueError("features must be a contiguous float32 [N, F] tensor")
         if features.requires_grad:
             raise ValueError("features must not require grad: the step trains the MLP alone (model.py:322 detaches)")
+        self._check_hyperparameters(model, optimizer, samples, dropnode_rate, kind, tem)
+        if not features.is_cuda:
+            raise ValueError("the step runs on the GPU only: features must be a CUDA tensor (no CPU fallback)")
+        if not isinstance(labels, torch.Tensor) or labels.dtype != torch.int64 or labels.device != features.device:
+            raise ValueError("labels must be an int64 tensor on the device of features")
+        dev = features.device
+        if features.shape[0] != rows.n_nodes or rows.col.device != dev:
+            raise ValueError(f"features must have one row per node ({rows.n_nodes}) on the device of rows ({rows.col.device})")
+        self.features = features
+        self._setup(model, optimizer, rows, labels, idx_train, idx_unlabel, dev, samples=samples, dropnode_rate=dropnode_rate,
+                    lam=lam, warmup=warmup, tem=tem, conf=conf, kind=kind, seed=seed, capture=capture)
+
+    # ---- the refusals and the state that every step shares (mag_step.MagTrainStep calls them too)
+    @staticmethod
+    def _check_optimizer_and_rows(optimizer, rows):
+        from .optim import ClipAdam
+        from .rows import RowMatrix
+        if not isinstance(optimizer, ClipAdam) or not optimizer.capturable:
+            raise ValueError("TrainStep takes a ClipAdam(capturable=True)")
+        if not isinstance(rows, RowMatrix):
+            raise ValueError("rows must be a RowMatrix")
+
+    @staticmethod
+    def _check_hyperparameters(model, optimizer, samples, dropnode_rate, kind, tem):
         if not isinstance(samples, int) or not 1 <= samples <= _native.GP_MAX_SAMPLES:
             raise ValueError(f"samples must be an int in [1, {_native.GP_MAX_SAMPLES}], got {samples!r}")
         if not 0.0 <= float(dropnode_rate) <= 1.0:
@@ -188,14 +211,10 @@ class TrainStep:
             raise ValueError(f"at most {_native.GP_STEP_MAX_LAYERS} layers, got {len(model._layers())}")
         if len(optimizer.param_groups) > _native.GP_STEP_MAX_GROUPS:
             raise ValueError(f"at most {_native.GP_STEP_MAX_GROUPS} parameter groups, got {len(optimizer.param_groups)}")
-        if not features.is_cuda:
-            raise ValueError("the step runs on the GPU only: features must be a CUDA tensor (no CPU fallback)")
-        if not isinstance(labels, torch.Tensor) or labels.dtype != torch.int64 or labels.device != features.device:
-            raise ValueError("labels must be an int64 tensor on the device of features")
-        dev = features.device
-        if features.shape[0] != rows.n_nodes or rows.col.device != dev:
-            raise ValueError(f"features must have one row per node ({rows.n_nodes}) on the device of rows ({rows.col.device})")
-        self.model, self.optimizer, self.rows, self.features = model, optimizer, rows, features
+
+    def _setup(self, model, optimizer, rows, labels, idx_train, idx_unlabel, dev, *, samples, dropnode_rate, lam, warmup, tem,
+               conf, kind, seed, capture):
+        self.model, self.optimizer, self.rows, self.device = model, optimizer, rows, dev
         self.samples, self.dropnode_rate, self.tem, self.conf, self.kind = samples, float(dropnode_rate), float(tem), conf, kind
         self.capture = bool(capture)
         idx_train = torch.as_tensor(np.asarray(idx_train).reshape(-1), dtype=torch.int64)
@@ -206,7 +225,7 @@ class TrainStep:
         self._pool_labels = labels[idx_train.to(dev)].contiguous()
         self.state = optimizer.step_state                          # the optimiser's: its tick is Adam's step count
         if self.state.device != dev:
-            raise ValueError(f"the optimiser's StepState is on {self.state.device}, features on {dev}")
+            raise ValueError(f"the optimiser's StepState is on {self.state.device}, the step's tensors on {dev}")
         self.state.configure(seed, lam, warmup)
         self._node_keep = torch.zeros((samples, rows.col.numel()), dtype=torch.uint8, device=dev) \
             if self.dropnode_rate > 0 else None
@@ -242,13 +261,8 @@ class TrainStep:
             if keeps[-1] is not None:
                 segments.append(layer_segment(keeps[-1], l, p))
         step_masks(st, segments)
-        self._where = "random_prop_rows"
-        from .augment import random_prop_rows
+        X = self._front(batch_rows)
         from .objective import grand_plus_loss
-        X = random_prop_rows(self.features, self.rows.col, self.rows.val, self.rows.filled, self.rows.K, batch_rows=batch_rows,
-                             dropnode_rate=self.dropnode_rate, training=True, seed=0, keep=self._node_keep, samples=S)
-        if S == 1:
-            X = X[None]
         self._where = "model"
         z = m(X, seed=0, keep=keeps)
         self._where = "grand_plus_loss"
@@ -261,6 +275,15 @@ class TrainStep:
         self._where = None
         return StepResult(loss.detach(), parts["sup"].detach(), parts["con"].detach(), parts["n_conf"], parts["n_correct"], norm)
 
+    def _front(self, batch_rows):
+        """The front end of the body: the S augmented inputs [S, B, F] of the batch, under the DropNode mask that
+        gp_step_masks has just written.  The one part of the body a subclass swaps."""
+        self._where = "random_prop_rows"
+        from .augment import random_prop_rows
+        X = random_prop_rows(self.features, self.rows.col, self.rows.val, self.rows.filled, self.rows.K, batch_rows=batch_rows,
+                             dropnode_rate=self.dropnode_rate, training=True, seed=0, keep=self._node_keep, samples=self.samples)
+        return X[None] if self.samples == 1 else X
+
     def step(self, train_sel, unlabel_sel):
         if not self.model.training:
             raise RuntimeError("TrainStep.step() needs the model in train mode: call model.train() (eval / train are the caller's)")
@@ -272,10 +295,10 @@ class TrainStep:
         host = torch.from_numpy(np.concatenate([a, b + self.n_train]))
         key = (B, n_l)
         if not self.capture or (key not in self._shapes and len(self._shapes) >= MAX_GRAPHS):
-            return self._body(host.pin_memory().to(self.features.device, non_blocking=True), n_l)
+            return self._body(host.pin_memory().to(self.device, non_blocking=True), n_l)
         if key not in self._shapes:                                  # the first call of a shape: a real, eager step
             self._shapes[key] = None
-            return self._body(host.pin_memory().to(self.features.device, non_blocking=True), n_l)
+            return self._body(host.pin_memory().to(self.device, non_blocking=True), n_l)
         if self._shapes[key] is None:
             self._shapes[key] = self._capture(B, n_l)
         sel, graph, result = self._shapes[key]
@@ -308,10 +331,10 @@ class TrainStep:
         B = n_l + u
         key = (B, n_l, sampler.batch_size, sampler.unlabel_batch, sampler.base_seed)    # the values a capture freezes
         if not self.capture or (key not in self._sampled and len(self._sampled) >= MAX_GRAPHS):
-            return self._body(torch.empty(B, dtype=torch.int64, device=self.features.device), n_l, sampler)
+            return self._body(torch.empty(B, dtype=torch.int64, device=self.device), n_l, sampler)
         if key not in self._sampled:                                 # the first call of a shape: a real, eager step
             self._sampled[key] = None
-            return self._body(torch.empty(B, dtype=torch.int64, device=self.features.device), n_l, sampler)
+            return self._body(torch.empty(B, dtype=torch.int64, device=self.device), n_l, sampler)
         if self._sampled[key] is None:
             self._sampled[key] = self._capture(B, n_l, sampler)
         _sel, graph, result = self._sampled[key]
@@ -319,7 +342,7 @@ class TrainStep:
         return result
 
     def _capture(self, B, n_l, sampler=None):
-        dev = self.features.device
+        dev = self.device
         sel = torch.zeros(B, dtype=torch.int64, device=dev)         # static: a replay reads the selection from here
         graph = torch.cuda.CUDAGraph()
         try:
