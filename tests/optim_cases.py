@@ -12,6 +12,7 @@ import torch
 
 CHUNK = 4096          # kChunk of csrc/optim.hip: elements of one tensor per unit of work
 MAX_TENSORS = 32      # GP_OPTIM_MAX_TENSORS
+GRID_CAP = 1024       # kMaxGrid = kSlots = GP_OPTIM_WORKSPACE_BYTES / 8: workgroups of one launch
 STEPS = 5
 BETAS, EPS = (0.9, 0.999), 1e-8
 
@@ -22,7 +23,21 @@ SETS = {
     "views": [(5,), (3, 7), (CHUNK + 3,), (66,)],                    # views of one flat buffer, none 16-byte aligned
     "many": [(n,) for n in range(1, 41)],                             # over the table capacity: two groups
     "holes": [(64, 1433), (64,), (7, 64), (7,)],                      # cora with .grad = None on two of them
+    # past the grid cap of GRID_CAP workgroups (tests/test_gpu_second_trip.py): 1 028 chunks, so workgroups 0 .. 3 take a
+    # second chunk each -- two whole chunks of the second tensor, its 5-element tail and the whole third tensor
+    "stride": [(5,), ((GRID_CAP + 1) * CHUNK + 5,), (7,)],
+    # two table groups, the second with more chunks (42) than the first (32): the first norm launch owns slots it has no
+    # chunk for, and the second launch adds into them
+    "late_big": [(1,)] * MAX_TENSORS + [(40 * CHUNK + 3,), (3,)],
+    "solo": [(1,)],                                                   # one element: one workgroup, every other slot zeroed
 }
+# Sets that tests/test_gpu_second_trip.py runs, outside the 5-step grid of test_gpu_optim.py.  "stride" is too large for
+# 15 cases of 5 steps and takes STRIDE_STEPS.  "solo" is stepped once, after "stride", for its norm: the grid's rule
+# measures ours by the maximum of torch's float32 error over all elements, which one element does not give (on its five
+# gradients exp_avg = 4.7e-3 is what is left of terms of 1e-2; the kernel's documented arithmetic, walked in numpy
+# float32, is 2.59e-9 off float64, torch's lerp form 2.1e-10 by luck, the bound from it 1.4e-9).
+OWN_TESTS = ("stride", "solo")
+STRIDE_STEPS = 2
 VIEW_OFFSETS = (1, 2, 3, 5)       # element offset of each view past a 64-element boundary of the flat buffer
 HOLES = (1, 2)                    # indices of "holes" without a gradient
 
@@ -34,6 +49,8 @@ HYPERS = [
 ]
 
 assert len(SETS["many"]) > MAX_TENSORS and (CHUNK + 1,) in SETS["odd"]
+SEED_ORDER = ("cora", "holes", "many", "odd", "views", "stride", "late_big", "solo")   # a set's place seeds its inputs: append only
+assert sorted(SEED_ORDER) == sorted(SETS)
 
 
 def numel(shape):
@@ -46,7 +63,7 @@ def numel(shape):
 @functools.lru_cache(maxsize=None)
 def inputs(name, hi, steps=STEPS):
     """(initial parameters, gradient sequence) of a case as float32 CPU tensors; a gradient of "holes" may be None."""
-    g = torch.Generator().manual_seed(1000 * hi + sorted(SETS).index(name))
+    g = torch.Generator().manual_seed(1000 * hi + SEED_ORDER.index(name))
     init = [torch.randn(s, generator=g) * 0.1 for s in SETS[name]]
     scale = HYPERS[hi]["gscale"]
     seq = []
@@ -86,9 +103,9 @@ def torch_run(init, seq, hyper, dtype, betas=BETAS, eps=EPS):
 
 
 @functools.lru_cache(maxsize=None)
-def reference(name, hi):
-    """(float64 run, float32 run) of torch on the CPU over the STEPS gradients of the case; computed once."""
-    init, seq = inputs(name, hi)
+def reference(name, hi, steps=STEPS):
+    """(float64 run, float32 run) of torch on the CPU over the `steps` gradients of the case; computed once."""
+    init, seq = inputs(name, hi, steps)
     return torch_run(init, seq, HYPERS[hi], torch.float64), torch_run(init, seq, HYPERS[hi], torch.float32)
 
 

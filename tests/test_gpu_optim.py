@@ -13,7 +13,7 @@ import optim_cases as oc
 
 pytestmark = pytest.mark.gpu
 
-CASES = [(name, hi) for name in oc.SETS for hi in range(len(oc.HYPERS))]
+CASES = [(name, hi) for name in oc.SETS if name not in oc.OWN_TESTS for hi in range(len(oc.HYPERS))]
 IDS = [f"{name}-h{hi}" for name, hi in CASES]
 
 
