@@ -392,3 +392,83 @@ def bags_as_csr(c):
     pos = torch.cat([torch.arange(int(indptr[n]), int(indptr[n + 1])) for n in nodes.tolist()])
     node_idx = torch.repeat_interleave(torch.arange(nodes.numel()), lens[nodes])
     return indptr, c.attr_idx.to(torch.int32), c.attr_data, nodes, c.attr_idx[pos], node_idx, c.attr_data[pos]
+
+
+# ---- the two operations written out, and one deliberate mistake (tests/test_host_mutants.py)
+MUTANTS = ("den_no_eps", "den_eps_swapped", "den_max", "keep_scale_missing", "sample0_mask_for_all", "bag_not_normalised")
+TINY_BAG, TINY_WEIGHT = 8, 1e-11           # edge_bags' bag of 9 entries; 9 weights of 1e-11 sum to the 1e-10 beside them
+TINY_BAG_H = (12, 65)
+
+
+def divide(num, den, eps, other, mut):
+    """num / (den + eps), or what a mistaken denominator gives: none, the other operation's epsilon, max(den, eps)."""
+    if mut == "den_no_eps":
+        return num / den
+    if mut == "den_eps_swapped":
+        return num / (den + other)
+    if mut == "den_max":
+        return num / den.clamp(min=eps)
+    return num / (den + eps)
+
+
+def coo_manual64(c, training, mut=None):
+    """coo_reference's first result from explicit formulas (mut None), or with one of MUTANTS built in."""
+    out = torch.zeros((c.S, c.n_out, c.F), dtype=torch.float64)
+    f, sc = c.feats.double(), c.scores.double()
+    scale = 1.0 if mut == "keep_scale_missing" and c.p < 1.0 else (1.0 / (1.0 - c.p) if c.p < 1.0 else 0.0)
+    for s in range(c.S if c.idx.numel() else 0):
+        w = sc * c.keep[0 if mut == "sample0_mask_for_all" else s].double() * scale if training else sc
+        num = torch.zeros((c.n_out, c.F), dtype=torch.float64).index_add_(0, c.idx, f * w[:, None])
+        den = torch.zeros((c.n_out, 1), dtype=torch.float64).index_add_(0, c.idx, w[:, None])
+        out[s] = num if mut == "bag_not_normalised" else divide(num, den, 1e-12, 1e-10, mut)
+    return out
+
+
+def bag_manual64(c, training, mut=None):
+    """bag_reference's first result from explicit formulas (mut None), or with one of MUTANTS built in."""
+    fe = c.W.double()[c.attr_idx]
+    if training:
+        scale = 1.0 if mut == "keep_scale_missing" and c.p < 1.0 else (1.0 / (1.0 - c.p) if c.p < 1.0 else 0.0)
+        fe = fe * c.keep.double() * scale
+    d = c.attr_data.double()[:, None]
+    num = torch.zeros((c.n_out, c.H), dtype=torch.float64).index_add_(0, c.node_idx, fe * d)
+    den = torch.zeros((c.n_out, 1), dtype=torch.float64).index_add_(0, c.node_idx, d)
+    return num if mut == "bag_not_normalised" else divide(num, den, 1e-10, 1e-12, mut)
+
+
+def finite_ratio(got, ref, terms):
+    """(`ratio` over the elements where `got` is finite, whether some element is not)."""
+    got = torch.as_tensor(got).double()
+    ok = torch.isfinite(got)
+    r = ((got - ref.double()).abs() / bound(terms))[ok]
+    return (float(r.max()) if r.numel() else 0.0), not bool(ok.all())
+
+
+def tiny_bags(H):
+    """edge_bags(H) with the 9 weights of bag TINY_BAG at 1e-11: its denominator is of the size of the bag's 1e-10."""
+    c = edge_bags(H, seed=H)
+    assert int(c.lens[TINY_BAG]) == 9
+    e = c.node_idx == TINY_BAG
+    c.attr_data[e] = TINY_WEIGHT
+    c.sent = c.sent & ~e
+    return c
+
+
+def drawn_forward():
+    """The forward cases tests/test_gpu_augment_edges.py holds to float64, as (name, kind, case, training), kind "coo" (a COO
+    case or the COO view of a rows case) or "bag": groups A (K up to 257), C, E, F and G with the file's own parameters and
+    seeds, and the bags at the epsilon's scale."""
+    for training in (False, True):
+        for S in (1, 2):
+            for K in (k for k in A_K if k <= 257):
+                for F in (12, 65):
+                    yield f"A K={K} F={F} S={S} training={training}", "coo", coo_view(edge_rows(K, F, S, seed=K + F + S)), training
+            yield f"E S={S} training={training}", "coo", edge_coo(6, S, seed=40 + S), training
+            yield f"F S={S} training={training}", "coo", coo_view(score_rows(S)), training
+        for S in (1, 3):
+            for F in C_F:
+                yield f"C F={F} S={S} training={training}", "coo", coo_view(edge_rows(9, F, S, seed=F + S)), training
+        for H in G_H:
+            yield f"G H={H} training={training}", "bag", edge_bags(H, seed=H), training
+        for H in TINY_BAG_H:
+            yield f"tiny bag H={H} training={training}", "bag", tiny_bags(H), training

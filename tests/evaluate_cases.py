@@ -54,6 +54,112 @@ def assert_loss(ours, torch32, ref64, what):
     assert e_ours <= 4.0 * e_t + 2.0 ** -23 * abs(ref64), (what, ours, torch32, ref64)
 
 
+def ties_case():
+    """(z [8, 349], y): ties across lanes and passes, NaNs, a row of -inf and one +inf; labels ignored but for four rows."""
+    C = 349
+    z = torch.randn((8, C), generator=torch.Generator().manual_seed(5))
+    z[0, [0, 63, 64]] = 9.0                                  # lanes 0 / 63 and the second pass of lane 0
+    z[1, [63, 64]] = 9.0
+    z[2, [64, 128, 320]] = 9.0                               # the same lane, three passes
+    z[3, [348, 100]] = 9.0
+    z[4, 70] = float("nan"); z[4, 5] = float("nan")          # the first NaN wins
+    z[5, 64] = float("nan"); z[5, 3] = 50.0                  # a NaN beats every number
+    z[6, :] = float("-inf")                                  # all equal: index 0
+    z[7, 10] = float("inf")
+    y = torch.full((8,), -100, dtype=torch.int64)            # ignored: the loss of a NaN row is not the subject here
+    y[:4] = torch.tensor([0, 63, 64, 100])
+    return z, y
+
+
+def ignored_case():
+    """(z [300, 7], clean labels, labels with ignored and bad entries, rows, label_rows, ignored positions, bad positions)."""
+    n, C = 300, 7
+    z, y, _ = head_case(4097, C)
+    z, y = z[:n].clone(), y[:n].clone()
+    y2 = y.clone()
+    y2[[3, 77]] = -100                                       # ignore_index
+    y2[[5, 100]] = torch.tensor([C, -1])                     # labels outside [0, C)
+    y2[200] = 2 ** 40
+    rows, lrows = torch.arange(n), torch.arange(n)
+    rows[[9, 10]] = torch.tensor([n, -1])                    # a logits row outside the array
+    lrows[[11, 12]] = torch.tensor([n, -(2 ** 50)])          # a label index outside the array
+    return z, y, y2, rows, lrows, [3, 77], [5, 100, 200, 9, 10, 11, 12]
+
+
+# ---- the head written out in float64, and one deliberate mistake (tests/test_host_mutants.py)
+MUTANTS = ("acc_over_valid", "loss_over_rows", "tie_last_index", "nan_not_max", "ignored_in_loss")
+
+
+def head64(z, y, rows=None, label_rows=None, ignore_index=-100, mut=None):
+    """What eval_head + eval_reduce must give, on the CPU in float64: {"pred", "flag", "counts", "acc", "loss"}; mut None, or
+    one of MUTANTS built in.  A row whose logits row, label index or label is outside its array is BAD (pred -1 without a
+    logits row); a label equal to ignore_index is IGNORED; acc is over all rows, the loss over the others alone."""
+    z, y = z.double(), y.long()
+    n = rows.numel() if rows is not None else label_rows.numel() if label_rows is not None else z.shape[0]
+    C = z.shape[1]
+    rows = torch.arange(n) if rows is None else rows.long()
+    lrows = torch.arange(n) if label_rows is None else label_rows.long()
+    pred, flag = torch.full((n,), -1, dtype=torch.int64), torch.full((n,), BAD, dtype=torch.uint8)
+    total, n_valid = 0.0, 0
+    for i in range(n):
+        r, l = int(rows[i]), int(lrows[i])
+        if not 0 <= r < z.shape[0]:
+            continue
+        row = z[r]
+        nan = torch.isnan(row)
+        if bool(nan.any()) and mut != "nan_not_max":
+            pred[i] = int(nan.nonzero()[0])                  # the first NaN, as torch.argmax and numpy
+        else:
+            v = torch.where(nan, torch.full_like(row, float("-inf")), row)
+            hits = (v == v.max()).nonzero()[:, 0]
+            pred[i] = int(hits[-1] if mut == "tie_last_index" else hits[0])
+        if not 0 <= l < y.numel():
+            continue
+        label = int(y[l])
+        if label == ignore_index:
+            flag[i] = IGNORED
+            if mut == "ignored_in_loss":                      # a head that gathers before it tests the label: class 0
+                total, n_valid = total - float(torch.log_softmax(row, dim=0)[0]), n_valid + 1
+            continue
+        if not 0 <= label < C:
+            continue
+        flag[i] = CORRECT if int(pred[i]) == label else WRONG
+        total -= float(torch.log_softmax(row, dim=0)[label])
+    counts = [int((flag <= CORRECT).sum()), int((flag == CORRECT).sum()), int((flag == IGNORED).sum()), int((flag == BAD).sum())]
+    n_valid += counts[0]
+    den_loss = n if mut == "loss_over_rows" else n_valid
+    den_acc = counts[0] if mut == "acc_over_valid" else n
+    return {"pred": pred, "flag": flag, "counts": counts, "acc": counts[1] / den_acc if den_acc else float("nan"),
+            "loss": total / den_loss if den_loss else float("nan")}
+
+
+def head_share(got, ref, loss32, loss_held=True):
+    """How far `got` (a head64 result) is from `ref` under the GPU file's assertions: infinite when a quantity the file
+    holds exactly differs (pred, flag, counts, acc, a NaN loss), otherwise |loss - loss64| over assert_loss's bound, or 0
+    where the file does not look at the loss (`loss_held`)."""
+    same = lambda a, b: a == b or (a != a and b != b)  # noqa: E731
+    if not (torch.equal(got["pred"], ref["pred"]) and torch.equal(got["flag"], ref["flag"]) and got["counts"] == ref["counts"]
+            and same(got["acc"], ref["acc"])):
+        return float("inf")
+    if not loss_held:
+        return 0.0
+    if ref["loss"] != ref["loss"] or got["loss"] != got["loss"] or got["loss"] == ref["loss"]:
+        return 0.0 if same(got["loss"], ref["loss"]) else float("inf")
+    return abs(got["loss"] - ref["loss"]) / (4.0 * abs(loss32 - ref["loss"]) + 2.0 ** -23 * abs(ref["loss"]))
+
+
+def head_drawn():
+    """The head's inputs that tests/test_gpu_evaluate.py draws, up to 65 rows of the grid (the reference walks row by row):
+    (name, z, y, {rows, label_rows, ignore_index}, whether the file holds the loss there)."""
+    out = [(f"head C={C} n={n}", *head_case(n, C)[:2], {}, True) for C in HEAD_C for n in HEAD_N if n <= 65]
+    z, y = ties_case()
+    out.append(("ties", z, y, {}, False))
+    z, _, y2, rows, lrows, _, _ = ignored_case()
+    out.append(("ignored", z, y2, dict(rows=rows, label_rows=lrows), True))
+    out.append(("all ignored", z, torch.full((z.shape[0],), 3), dict(ignore_index=3), True))
+    return out
+
+
 def reduce_case(n, seed=0):
     """Synthetic filled buffers (nll float32, flag uint8) and what the reduce must give: (nll, flag, loss64, counts)."""
     rng = np.random.default_rng(seed + n)
@@ -76,8 +182,9 @@ def node_labels(n_nodes, seed=4):
     return torch.randint(0, CLASSES, (n_nodes,), generator=torch.Generator().manual_seed(seed))
 
 
-def model_pair(name, seed=11, f_in=F_IN):
-    """(GrandPlusMLP on the CPU, its float64 restatement), equal parameters, non-trivial BatchNorm state."""
+def model_pair(name, seed=11, f_in=F_IN, small=False):
+    """(GrandPlusMLP on the CPU, its float64 restatement), equal parameters, non-trivial BatchNorm state; with `small`,
+    infer_cases.small_var's running variances and per-layer epsilons."""
     from grand_plus_amd.mlp import GrandPlusMLP
     use_bn, norm = MODELS[name]
     torch.manual_seed(seed)
@@ -92,6 +199,9 @@ def model_pair(name, seed=11, f_in=F_IN):
     ours.fcs[-1].weight.data *= LAST_SCALE
     ref = RefMLP(f_in, CLASSES, HIDDEN, LAYERS, use_bn, 0.5, 0.7, norm)
     ref.load_state_dict(ours.state_dict())
+    if small:
+        from infer_cases import small_var
+        small_var(ours, ref)
     return ours, ref.double().eval()
 
 

@@ -43,6 +43,109 @@ EDGE_SHAPES = sorted({(fi, fo) for fi in (1, 3, 15, 16, 17, 31, 32, 33, 63, 64, 
                      {(fi, fo) for fo in (1, 47, 48, 49, 63, 64, 65, 127, 128, 129, 200) for fi in (17, 96)})
 
 
+# ---- eval BatchNorm where its epsilon decides (tests/test_host_mutants.py): running variances from 0 to 1e-3 in every third
+# column, those columns' running means scaled down by 1e-3 (a mean of 0.1 over sqrt(1e-7) would be all the column holds), and
+# one epsilon per layer.  The first rows of the inputs are special too, see `inputs`.
+SMALL_VARS = (0.0, 1e-7, 1e-6, 1e-5, 1e-4, 1e-3)
+SMALL_EPS = (1e-3, 1e-5, 1e-7)
+SMALL_ROWS = 129
+SMALL_VAR = [
+    ("deep", "model", 7, 100, 5, 3, True, True),
+    ("mag_bn", "mag", 64, 64, 8, 3, True, True),
+    ("17-130-5", "model", 17, 130, 5, 2, True, True),
+]
+SMALL_VAR_TILE32 = (("17-1024-5", "model", 17, 1024, 5, 2, True, True), 33)      # the chain's 32-row tile, B = 33
+SMALL_DRAWN = [(c, SMALL_ROWS) for c in SMALL_VAR] + [SMALL_VAR_TILE32]
+# what tests/test_gpu_infer.py holds to the float64 rule: (case, rows, with small variances)
+DRAWN = [(c, B, False) for c in CASES for B in CASE_ROWS] + [(c, B, True) for c, B in SMALL_DRAWN]
+SMALL_VAR_BITWISE =[c for c in SMALL_VAR if max(c[2] if c[1] == "model" else c[3], c[3]) <= 64]    # f_in <= 64 in every layer
+
+
+def small_var(*models):
+    """Gives the BatchNorms of `models` (built alike) the small running variances and the per-layer epsilons, in place."""
+    for m in models:
+        for i, b in enumerate(m.bns):
+            cols = torch.arange(0, b.running_var.numel(), 3)
+            var = torch.tensor(SMALL_VARS, dtype=torch.float32)[torch.arange(cols.numel()) % len(SMALL_VARS)]
+            b.running_var.data[cols] = var.to(b.running_var.dtype)                     # float32 values in the float64 twin too
+            b.running_mean.data[cols] = (b.running_mean.data[cols].float() * 1e-3).to(b.running_mean.dtype)
+            b.eps = SMALL_EPS[i]
+    return models
+
+
+def small_pair(case, seed=0):
+    ours, ref = pair(case, seed)
+    small_var(ours, ref)
+    return ours, ref
+
+
+def small_inputs(case, B, seed=7):
+    """`inputs`, but row 1 has a norm of 1e-12, the epsilon of node_norm: 1 / (1e-12 + L) is half of 1 / max(L, 1e-12)."""
+    X = inputs(case, B, seed)
+    if B > 1:
+        X[1] *= 1e-12 / float(X[1].double().norm())
+        if case[1] != "model":
+            X[1] = X[1].abs()                                # the MAG layout's first block begins with ReLU
+    return X
+
+
+# ---- the eval MLP written out in float64, and one deliberate mistake
+MUTANTS = ("eps_x2", "eps_default", "eps_outside_sqrt", "eps_swapped", "norm_max", "bn_before_norm", "relu_after_norm", "mean_sign")
+
+
+def manual64(ref, X, mut=None, dtype=torch.float64):
+    """(logits, the last Linear's input) of the restatement `ref` (RefMLP or RefMagMLP, eval mode) on X from explicit
+    formulas (mut None), or with one of MUTANTS built in.  In float32 it is the kernels' documented arithmetic (DESIGN
+    §7j): r = 1 / (1e-12 + |relu?(x)|), mul = gamma * is, add = beta - mean * mul, a = (relu?(x) * r) * mul + add."""
+    mag = isinstance(ref, RefMagMLP)
+    f32 = dtype == torch.float32
+    eps = [b.eps for b in ref.bns]
+    if mut == "eps_swapped" and len(eps) >= 2:
+        eps[-1], eps[-2] = eps[-2], eps[-1]
+    h = X.to(dtype)
+    a = None
+    with torch.no_grad():
+        for i, (fc, bn) in enumerate(zip(ref.fcs, ref.bns)):
+            relu = mag or i > 0
+
+            def norm(v):
+                L = v.norm(dim=-1, keepdim=True)
+                return v * (1.0 / L.clamp(min=1e-12) if mut == "norm_max" else 1.0 / (1e-12 + L))
+
+            def bnorm(v):
+                e = {"eps_x2": 2 * eps[i], "eps_default": 1e-5}.get(mut, eps[i])
+                var, mean = bn.running_var.to(dtype), bn.running_mean.to(dtype)
+                istd = 1.0 / (var.sqrt() + e) if mut == "eps_outside_sqrt" else 1.0 / (var + e).sqrt()
+                gamma, beta = bn.weight.to(dtype), bn.bias.to(dtype)
+                if f32:
+                    mul = gamma * istd
+                    return v * mul + (beta - mean * mul)
+                return (v + mean if mut == "mean_sign" else v - mean) * istd * gamma + beta
+
+            steps = []
+            if relu and mut != "relu_after_norm":
+                steps.append(torch.relu)
+            if ref.node_norm:
+                steps.append(norm)
+            if relu and mut == "relu_after_norm":
+                steps.append(torch.relu)
+            if ref.use_bn:
+                steps.append(bnorm)
+            if mut == "bn_before_norm" and ref.use_bn and ref.node_norm:
+                steps[-1], steps[-2] = steps[-2], steps[-1]
+            for f in steps:
+                h = f(h)
+            a = h
+            h = a @ fc.weight.to(dtype).t() + fc.bias.to(dtype)
+    return h, a
+
+
+def share(got, want, bound):
+    """max |got - want| / bound of the rule; a non-finite entry counts as infinite."""
+    r = ((got.double() - want).abs() / bound).max()
+    return float(r) if bool(torch.isfinite(r)) else float("inf")
+
+
 def pair(case, seed=0):
     """(ours on the CPU, the float64 restatement on the CPU in eval mode), same parameters and running statistics."""
     from grand_plus_amd.mlp import GrandPlusMLP, MagMLP

@@ -90,6 +90,16 @@ def problem(H, K, bags=BAGS, S_rows=6, V=50, filled="ragged", seed=0):
                    S_rows=S_rows, longest=int(lens.max()))
 
 
+def at_eps_scale(P):
+    """Row 2's scores become 1e-13, so that the sum of the kept ones is of the size of the 1e-12 beside it, and the one
+    attribute of node 1, which row 3 names in slot 1, gets the weight 5e-11, half of the 1e-10 beside it: there
+    1 / (den + eps), 1 / den, 1 / max(den, eps) and the other formula's epsilon all differ by tens of per cent."""
+    P.val[2, :] = 1e-13
+    P.col[3, 1] = 1
+    assert int(P.indptr[2] - P.indptr[1]) == 1
+    P.data[int(P.indptr[1])] = 5e-11
+
+
 def _entries(P, batch):
     """The filled slots of the batch, row after row: (idx = batch position, e = r * K + k, node)."""
     rows = P.rows(batch)
@@ -129,6 +139,52 @@ def chain64(P, W, batch, S, p_node, p_in, training, keep, seed):
             o = torch.cat([r, o[r.shape[0]:]])                                    # trailing empty rows
         outs.append(o)
     return torch.stack(outs)
+
+
+# ---- the two formulas written out, and one deliberate mistake (tests/test_host_mutants.py)
+MUTANTS = ("den_no_eps", "den_eps_swapped", "den_max", "keep_scale_missing", "sample0_mask_for_all", "bag_not_normalised")
+
+
+def divide(num, den, eps, other, mut):
+    """num / (den + eps), or what a mistaken denominator gives: none, the other formula's epsilon, max(den, eps)."""
+    if mut == "den_no_eps":
+        return num / den
+    if mut == "den_eps_swapped":
+        return num / (den + other)
+    if mut == "den_max":
+        return num / den.clamp(min=eps)
+    return num / (den + eps)
+
+
+def manual64(P, batch, S, p_node, p_in, training, keep, seed, mut=None):
+    """chain64 on P.W from explicit formulas (mut None), or with one of MUTANTS built in: out [S, B, H]."""
+    idx, e, nodes, B = _entries(P, batch)
+    M, H = e.numel(), P.H
+    lens = P.indptr[nodes + 1] - P.indptr[nodes]
+    occ = torch.repeat_interleave(torch.arange(M), lens)
+    first = torch.cumsum(lens, 0) - lens
+    pos = P.indptr[nodes][occ] + torch.arange(int(lens.sum())) - first[occ]
+    a, d = P.indices[pos].long(), P.data[pos].double()
+    scores = P.val.reshape(-1)[e].float().double()
+    W = P.W.double()
+    scaled = mut != "keep_scale_missing"
+    scale_in = (1.0 / (1.0 - p_in) if p_in < 1.0 else 0.0) if scaled or p_in >= 1.0 else 1.0
+    scale_node = (1.0 / (1.0 - p_node) if p_node < 1.0 else 0.0) if scaled or p_node >= 1.0 else 1.0
+    out = torch.zeros((S, B, H), dtype=torch.float64)
+    for s in range(S):
+        sm = 0 if mut == "sample0_mask_for_all" else s
+        fe = W[a]
+        if training and p_in > 0.0:
+            m = np.concatenate([input_keep(seed, sm, e[j], int(lens[j]), H, p_in) for j in range(M)] + [np.zeros((0, H), bool)])
+            fe = fe * torch.from_numpy(m).double() * scale_in
+        num = torch.zeros((M, H), dtype=torch.float64).index_add_(0, occ, fe * d[:, None])
+        den = torch.zeros((M, 1), dtype=torch.float64).index_add_(0, occ, d[:, None])
+        emb = num if mut == "bag_not_normalised" else divide(num, den, 1e-10, 1e-12, mut)
+        w = scores * keep[sm].reshape(-1)[e].double() * scale_node if training else scores
+        num2 = torch.zeros((B, H), dtype=torch.float64).index_add_(0, idx, emb * w[:, None])
+        den2 = torch.zeros((B, 1), dtype=torch.float64).index_add_(0, idx, w[:, None])
+        out[s] = divide(num2, den2, 1e-12, 1e-10, mut)
+    return out
 
 
 def ref64(P, batch, S, p_node, p_in, training, keep, seed, G=None):
@@ -223,6 +279,8 @@ CASES = {
     "pin1":            (7,   5,  2,  "ragged", None,       0.5,   1.0,  True,  BAGS),
     "pin0_pnode0":     (64,  32, 1,  None,     None,       0.0,   0.0,  True,  BAGS[:5]),
     "hub":             (7,   1,  1,  "full",   None,       0.0,   0.0,  True,  (3, 2, 1, 4097)),
+    # both denominators at the scale of their epsilons (see `at_eps_scale`)
+    "eps_scale":       (7,   5,  2,  "full",   None,       0.5,   0.5,  True,  BAGS),
 }
 SEED = 0x5EED0FACADE
 
@@ -234,6 +292,8 @@ def case(name):
     and the number of roundings the tolerance stands for."""
     H, K, S, filled, mode, p_node, p_in, training, bags = CASES[name]
     P = problem(H, K, bags=bags, filled=filled, S_rows=2 if name == "hub" else 6)
+    if name == "eps_scale":
+        at_eps_scale(P)
     roundings = K + P.longest + S + 8
     assert name == "hub" or roundings <= ROUNDINGS, (name, roundings)
     batch = batch_rows(mode, P.S_rows)

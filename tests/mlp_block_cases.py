@@ -35,7 +35,8 @@ RELU, NORM, BN, TRAIN = 1, 2, 4, 8                       # GP_MLP_* of grandplus
 ALL = frozenset(("x", "w", "b", "gamma", "beta"))
 DROP_SEED = 0xDEADBEEF12345
 
-Case = collections.namedtuple("Case", "name S B F N flags p bias affine rg special hashed loose seed")
+Case = collections.namedtuple("Case", "name S B F N flags p bias affine rg special hashed loose seed eps momentum",
+                              defaults=(None, None))      # BatchNorm's eps and momentum; None: torch's defaults
 Built = collections.namedtuple("Built", "case x fc bn keep gy")
 Ref = collections.namedtuple("Ref", "out a gx gw gb gg gbe rm rv nbt")
 
@@ -44,14 +45,14 @@ def flag_name(flags):
     return "".join(ch for ch, bit in zip("RNBT", (RELU, NORM, BN, TRAIN)) if flags & bit) or "0"
 
 
-def case(lst, S, B, F, N, flags, p=None, bias=True, affine=True, rg=ALL, special=None, hashed=False, tag=""):
+def case(lst, S, B, F, N, flags, p=None, bias=True, affine=True, rg=ALL, special=None, hashed=False, tag="", eps=None, momentum=None):
     """p defaults to 0.5 under TRAINING and 0 otherwise."""
     if p is None:
         p = 0.5 if flags & TRAIN else 0.0
     name = f"{lst}-{flag_name(flags)}-S{S}-B{B}-F{F}-N{N}" + (f"-{tag}" if tag else "")
     loose = B == 2 and (flags & (BN | TRAIN)) == (BN | TRAIN)
     return Case(name, S, B, F, N, flags, float(p), bias, affine, frozenset(rg), special, hashed, loose,
-                zlib.crc32(name.encode()))
+                zlib.crc32(name.encode()), eps, momentum)
 
 
 # ---- the lists
@@ -99,8 +100,11 @@ TIGHT = [case("tight", 2, 128, 2048, 128, FULL, tag="fwd"),          # 32 chunks
 GUARD = TIGHT + [case("tight", *FLAGS_SHAPE, FULL, tag="flags_shape"),
                  case("tight", *FLAGS_SHAPE, BN, tag="eval_saved")]  # eval, no NORM: `saved` is unused but for slot 0 of the statistics
 
+# BatchNorm's eps and momentum away from torch's defaults (1e-5, 0.1): forward, backward and the running statistics
+BN_HYPER = [case("bnh", *FLAGS_SHAPE, f, eps=1e-3, momentum=0.3, tag="eps1e-3_mom0.3") for f in (BN | TRAIN, FULL)]
+
 LISTS = {"FLAGS": FLAGS, "SAMPLES": SAMPLES, "GEMM_EDGES": GEMM_EDGES, "BN_EDGES": BN_EDGES, "ROW_EDGES": ROW_EDGES,
-         "OPTIONAL": OPTIONAL, "DROPOUT": DROPOUT}
+         "OPTIONAL": OPTIONAL, "DROPOUT": DROPOUT, "BN_HYPER": BN_HYPER}
 
 
 def ids(cases):
@@ -183,7 +187,7 @@ def build(c):
         fc.bias.data = (torch.rand((c.N,), generator=g) * 2 - 1) * k
     bn = None
     if c.flags & BN:
-        bn = nn.BatchNorm1d(c.F, affine=c.affine)
+        bn = nn.BatchNorm1d(c.F, affine=c.affine, **{k: v for k, v in (("eps", c.eps), ("momentum", c.momentum)) if v is not None})
         if c.affine:
             bn.weight.data = torch.rand((c.F,), generator=g) + 0.5
             bn.bias.data = torch.randn((c.F,), generator=g) * 0.1
@@ -251,7 +255,8 @@ def splits(rows, cols, K):
 
 # ---- the same block with the backward written out, and one deliberate mistake
 MUTANTS = ("relu_ge", "no_mean_dy", "unbiased_norm_var", "biased_running_var", "running_once", "sample0_stats", "no_norm_jacobian",
-           "drop_scale_once", "last_chunk", "last_row", "bias_per_chunk")
+           "drop_scale_once", "last_chunk", "last_row", "bias_per_chunk",
+           "eps_x2", "eps_default", "eps_outside_sqrt", "momentum_default")
 
 
 def _gemm(A, Bm, rows, cols, mut):
@@ -278,7 +283,8 @@ def block_manual64(b, mut=None):
     n = u * r
     rm = rv = nbt = gamma = None
     if b.bn is not None:
-        eps, mom = b.bn.eps, b.bn.momentum
+        eps = {"eps_x2": 2 * b.bn.eps, "eps_default": 1e-5}.get(mut, b.bn.eps)
+        mom = 0.1 if mut == "momentum_default" else b.bn.momentum
         rm, rv = b.bn.running_mean.double().clone(), b.bn.running_var.double().clone()
         gamma = b.bn.weight.detach().double() if b.bn.weight is not None else torch.ones(F, dtype=torch.float64, device=x.device)
         beta = b.bn.bias.detach().double() if b.bn.bias is not None else torch.zeros(F, dtype=torch.float64, device=x.device)
@@ -294,7 +300,7 @@ def block_manual64(b, mut=None):
             nbt = S
         else:
             mu, var, nbt = rm.view(1, 1, F), rv.view(1, 1, F), 0
-        istd = 1.0 / torch.sqrt(var + eps)
+        istd = 1.0 / (torch.sqrt(var) + eps) if mut == "eps_outside_sqrt" else 1.0 / torch.sqrt(var + eps)
         xhat = (n - mu) * istd
         h = xhat * gamma + beta
     else:

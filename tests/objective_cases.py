@@ -169,6 +169,69 @@ def reference_terms(z, labels, n_l, w, tem, conf, kind, log_probs=False, ignore_
     return sup + w * con, sup, con
 
 
+# ---- the same terms written out, and one deliberate mistake (tests/test_host_mutants.py)
+MUTANTS = ("conf_ge", "mean_over_all_rows", "sharp_not_detached", "kl_reversed", "tem_not_inverted", "weight_on_sup",
+           "sup_last_sample_only", "sup_summed_over_samples")
+# `avg_p.max(1) >= conf` differs from `> conf` on a row whose float64 avg_p.max(1) equals conf, and on no other.  The
+# reference's own exp(log_softmax) is not exact there, so which side a tie falls on is not defined by it, and make_case keeps
+# every row away from conf by MARGIN for that reason: no case can see this mistake, and none should.
+INDISTINGUISHABLE = ("conf_ge",)
+
+
+def manual_terms(z, labels, n_l, w, tem, conf, kind, log_probs=False, ignore_index=IGNORE, mut=None):
+    """reference_terms from explicit formulas (mut None), or with one of MUTANTS built in."""
+    S = len(z)
+    lps = [z[s] if log_probs else torch.log_softmax(z[s], dim=-1) for s in range(S)]
+    sup = 0.
+    for s in (range(S - 1, S) if mut == "sup_last_sample_only" else range(S)):
+        sup = sup + Fn.nll_loss(lps[s][:n_l], labels[:n_l], ignore_index=ignore_index)
+    if mut not in ("sup_last_sample_only", "sup_summed_over_samples"):
+        sup = sup / S
+    ps = [torch.exp(lp[n_l:]) for lp in lps]
+    avg_p = sum(ps[1:], ps[0]) / S
+    powered = torch.pow(avg_p, tem if mut == "tem_not_inverted" else 1. / tem)
+    sharp_p = powered / powered.sum(dim=1, keepdim=True)
+    if mut != "sharp_not_detached":
+        sharp_p = sharp_p.detach()
+    top = avg_p.max(1)[0]
+    mask = top >= conf if mut == "conf_ge" else top > conf
+    con = 0.
+    for p in ps:
+        if kind == "kl":
+            row = (-p * torch.log(sharp_p)).sum(1) if mut == "kl_reversed" else (-sharp_p * torch.log(p)).sum(1)
+        else:
+            row = (p - sharp_p).pow(2).sum(1)
+        con = con + (row[mask].sum() / row.numel() if mut == "mean_over_all_rows" else torch.mean(row[mask]))
+    con = con / S
+    return (w * sup + con if mut == "weight_on_sup" else sup + w * con), sup, con
+
+
+def manual_with_upstream(z, labels, n_l, w, tem, conf, kind, coeffs=(1, 0, 0), log_probs=False, mut=None):
+    """reference_with_upstream in float64 over manual_terms."""
+    leaf = z.detach().double().clone().requires_grad_(True)
+    terms = manual_terms(leaf, labels, n_l, w, tem, conf, kind, log_probs, mut=mut)
+    total = combine(terms, coeffs)
+    if total is not None and total.requires_grad:
+        total.backward()
+    grad = leaf.grad if leaf.grad is not None else torch.zeros_like(leaf)
+    loss, sup, con = (float(t.detach()) for t in terms)
+    return {"loss": loss, "sup": sup, "con": con, "grad": grad.detach()}
+
+
+def manual(case, coeffs=(1, 0, 0), mut=None):
+    z, labels, n_l, conf = build(case)
+    return manual_with_upstream(z, labels, n_l, case.w, case.tem, conf, case.kind, coeffs, case.log_probs, mut)
+
+
+def share(got, ref):
+    """The largest |got - ref| / bound over the loss, its parts and the gradient, under assert_matches' rule."""
+    out = grad_error(got["grad"], ref["grad"])[1]
+    for k in ("loss", "sup", "con"):
+        e, b = value_error(got[k], ref[k])
+        out = max(out, e / b if b else (math.inf if e else 0.0))
+    return out
+
+
 def combine(terms, coeffs):
     """a*loss + b*L_sup + c*L_con without the terms whose coefficient is 0 (so that autograd passes None for them);
     None when every coefficient is 0."""

@@ -46,7 +46,17 @@ HYPERS = [
     dict(lr=1e-2, weight_decay=5e-4, clip=0.1, gscale=1.0),          # clipping active: the run scripts' values
     dict(lr=1e-2, weight_decay=0.0, clip=0.0, gscale=1.0),           # no clipping
     dict(lr=1e-3, weight_decay=1e-5, clip=5.0, gscale=1e-3),         # the coefficient clamps to 1
+    # total norms of 1e-8 sqrt(n), 1.1e-6 on "odd": coef = clip / (norm + 1e-6) is about half of clip / norm, so the 1e-6
+    # of the coefficient decides the step (tests/test_host_mutants.py: without it "cora" moves by 3.5e4 bounds)
+    dict(lr=1e-2, weight_decay=5e-4, clip=2e-6, gscale=1e-8),
 ]
+TINY = 3                          # the entry above: gradients at the scale of clip_grad_norm's 1e-6
+# betas and eps away from torch's defaults, on the host-number and on the capturable path: (set, hyper, betas, eps)
+OFF_DEFAULT = [("cora", 0, (0.8, 0.99), 1e-6), ("odd", 0, (0.8, 0.99), 1e-6)]
+
+# what tests/test_gpu_optim.py draws: the 5-step grid at the default betas and eps, then OFF_DEFAULT on both paths
+GRID = [(name, hi) for name in SETS if name not in OWN_TESTS for hi in range(len(HYPERS))]
+DRAWN = [(name, hi, BETAS, EPS) for name, hi in GRID] + OFF_DEFAULT
 
 assert len(SETS["many"]) > MAX_TENSORS and (CHUNK + 1,) in SETS["odd"]
 SEED_ORDER = ("cora", "holes", "many", "odd", "views", "stride", "late_big", "solo")   # a set's place seeds its inputs: append only
@@ -103,10 +113,89 @@ def torch_run(init, seq, hyper, dtype, betas=BETAS, eps=EPS):
 
 
 @functools.lru_cache(maxsize=None)
-def reference(name, hi, steps=STEPS):
+def reference(name, hi, steps=STEPS, betas=BETAS, eps=EPS):
     """(float64 run, float32 run) of torch on the CPU over the `steps` gradients of the case; computed once."""
     init, seq = inputs(name, hi, steps)
-    return torch_run(init, seq, HYPERS[hi], torch.float64), torch_run(init, seq, HYPERS[hi], torch.float32)
+    return torch_run(init, seq, HYPERS[hi], torch.float64, betas, eps), torch_run(init, seq, HYPERS[hi], torch.float32, betas, eps)
+
+
+# ---- the same run written out, and one deliberate mistake (tests/test_host_mutants.py)
+MUTANTS = ("eps_x10", "eps_0", "eps_before_bias_correction", "eps_in_sqrt", "clip_no_1e6", "clip_no_clamp", "wd_before_clip",
+           "wd_decoupled", "bc_step_minus_1", "betas_default", "eps_default", "lr_without_bc1")
+
+
+def manual_run(init, seq, hyper, betas=BETAS, eps=EPS, mut=None, dtype=torch.float64):
+    """torch_run's results from explicit formulas (mut None), or with one of MUTANTS built in.  In float32 it is the kernel's
+    documented arithmetic: the float64 norm rounded once, coef, then per element g = grad coef + wd p,
+    m = b1 m + (1 - b1) g, v = b2 v + (1 - b2) g g, p -= step_size (m / (sqrt(v) rsqrt_bc2 + eps)), the two step numbers
+    formed in double."""
+    lr, wd, clip = hyper["lr"], hyper["weight_decay"], hyper["clip"]
+    if mut == "betas_default":
+        betas = BETAS
+    if mut == "eps_default":
+        eps = EPS
+    eps = {"eps_x10": 10 * eps, "eps_0": 0.0}.get(mut, eps)
+    b1, b2 = betas
+    P = [p.to(dtype).clone() for p in init]
+    M, V = [None] * len(P), [None] * len(P)
+    cast = lambda v: torch.tensor(v, dtype=dtype)  # noqa: E731
+    for t, grads in enumerate(seq, 1):
+        G = [None if g is None else g.to(dtype) for g in grads]
+        if mut == "wd_before_clip":
+            G = [None if g is None else g + cast(wd) * p for g, p in zip(G, P)]
+        if clip > 0:
+            sq = sum(float((g.double() ** 2).sum()) for g in G if g is not None)
+            norm = cast(sq ** 0.5)
+            coef = cast(clip) / (norm if mut == "clip_no_1e6" else norm + cast(1e-6))
+            if mut != "clip_no_clamp":
+                coef = coef.clamp(max=1.0)
+        else:
+            coef = cast(1.0)
+        tb = t - 1 if mut == "bc_step_minus_1" else t
+        bc1, bc2 = 1.0 - b1 ** tb, 1.0 - b2 ** tb
+        with torch.no_grad():
+            for i, g in enumerate(G):
+                if g is None:
+                    continue
+                if M[i] is None:
+                    M[i], V[i] = torch.zeros_like(P[i]), torch.zeros_like(P[i])
+                g = g * coef
+                if mut == "wd_decoupled":
+                    P[i] = P[i] * cast(1.0 - lr * wd)
+                elif mut != "wd_before_clip":
+                    g = g + cast(wd) * P[i]
+                M[i] = cast(b1) * M[i] + cast(1.0 - b1) * g
+                V[i] = cast(b2) * V[i] + cast(1.0 - b2) * g * g
+                if bc1 == 0.0 or bc2 == 0.0:                          # bc_step_minus_1 at the first step: lr / 0
+                    P[i] = P[i] * float("nan")
+                    continue
+                step_size = lr if mut == "lr_without_bc1" else lr / bc1
+                if mut == "eps_before_bias_correction":
+                    denom = (V[i].sqrt() + cast(eps)) * cast(bc2 ** -0.5)
+                elif mut == "eps_in_sqrt":
+                    denom = (V[i] * cast(1.0 / bc2) + cast(eps)).sqrt()
+                else:
+                    denom = V[i].sqrt() * cast(bc2 ** -0.5) + cast(eps)
+                P[i] = P[i] - cast(step_size) * (M[i] / denom)
+    return {"param": P, "exp_avg": M, "exp_avg_sq": V}
+
+
+def rule(ours, t32, r64):
+    """{key: (max|ours - ref64|, max|torch32 - ref64|, the bound)} of error_ratios' rule; nothing asserted but that state is
+    present on both sides or on neither.  A non-finite entry of `ours` counts as an infinite error."""
+    out = {}
+    for key in ("param", "exp_avg", "exp_avg_sq"):
+        e_ours = e_t32 = top = 0.0
+        for o, t, r in zip(ours[key], t32[key], r64[key]):
+            assert (o is None) == (r is None), f"{key}: state present on one side only"
+            if r is None or r.numel() == 0:
+                continue
+            e = float((o.detach().cpu().double() - r).abs().max())
+            e_ours = max(e_ours, e if e == e else float("inf"))
+            e_t32 = max(e_t32, float((t.double() - r).abs().max()))
+            top = max(top, float(r.abs().max()))
+        out[key] = (e_ours, e_t32, 4 * e_t32 + 2.0 ** -23 * top)
+    return out
 
 
 def error_ratios(ours, t32, r64, label=""):
@@ -118,16 +207,7 @@ def error_ratios(ours, t32, r64, label=""):
     the case where torch happens to be exact.  `ours` maps the three keys to lists of tensors (any device; None where
     there is no state).  Prints each figure, then asserts; returns {key: ours / torch32}."""
     out = {}
-    for key in ("param", "exp_avg", "exp_avg_sq"):
-        e_ours = e_t32 = top = 0.0
-        for o, t, r in zip(ours[key], t32[key], r64[key]):
-            assert (o is None) == (r is None), f"{label} {key}: state present on one side only"
-            if r is None or r.numel() == 0:
-                continue
-            e_ours = max(e_ours, float((o.detach().cpu().double() - r).abs().max()))
-            e_t32 = max(e_t32, float((t.double() - r).abs().max()))
-            top = max(top, float(r.abs().max()))
-        bound = 4 * e_t32 + 2.0 ** -23 * top
+    for key, (e_ours, e_t32, bound) in rule(ours, t32, r64).items():
         out[key] = e_ours / e_t32 if e_t32 > 0 else float("inf") if e_ours > 0 else 0.0
         print(f"{label} {key}: ours {e_ours:.3e} torch32 {e_t32:.3e} ratio {out[key]:.3g} bound {bound:.3e}")
         assert e_ours <= bound, f"{label} {key}: max error {e_ours:.3e} over the bound {bound:.3e} (torch32 {e_t32:.3e})"

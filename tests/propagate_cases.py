@@ -98,15 +98,29 @@ def graph(name):
 def edge_weights(name):
     """(float32 [nnz] drawn from uniform(0.5, 2.0), zero_row): the stored values of a weighted adjacency; the weights
     of one short row are all 0.0, so its row sum is 0, max(deg, 1e-12) takes its other branch and the row must come
-    out 0, not NaN."""
+    out 0, not NaN.  The next short row (`tiny_row`) has two weights of 5e-13 and zeros: its row sum is the 1e-12 of
+    max(deg, 1e-12) itself, where deg + 1e-12 would halve the row."""
     indptr, indices = graph(name)
     w = np.random.default_rng(GRAPHS[name]["seed"] + 100).uniform(0.5, 2.0, size=len(indices)).astype(np.float32)
     deg = np.diff(indptr)
     n_hubs = len(GRAPHS[name]["hub_degrees"])
     zero_row = n_hubs + int(np.flatnonzero((deg[n_hubs:] >= 2) & (deg[n_hubs:] <= 12))[0])
     w[indptr[zero_row]:indptr[zero_row + 1]] = 0.0
+    tiny = tiny_row(name)
+    w[indptr[tiny]:indptr[tiny + 1]] = 0.0
+    w[indptr[tiny]:indptr[tiny] + 2] = TINY_WEIGHT
     w.setflags(write=False)
     return w, zero_row
+
+
+TINY_WEIGHT = np.float32(5e-13)
+
+
+def tiny_row(name):
+    """The second row of 2 .. 12 neighbours after the hubs: the first is the zero row."""
+    deg = np.diff(graph(name)[0])
+    n_hubs = len(GRAPHS[name]["hub_degrees"])
+    return n_hubs + int(np.flatnonzero((deg[n_hubs:] >= 2) & (deg[n_hubs:] <= 12))[1])
 
 
 # -- cases: every (graph, F, mode, order, alpha, weights) the GPU tests run ----------------------------------
@@ -159,6 +173,43 @@ def reference(case):
     ref = propagate_ref(_adjacency(indptr, indices, w), X, case.mode, case.order, case.alpha)
     ref.setflags(write=False)
     return ref
+
+
+# -- the reference written out, and one deliberate mistake (tests/test_host_mutants.py) -----------------------------
+MUTANTS = ("deg_plus_eps", "alpha_on_every_term", "avg_over_n", "single_returns_sum", "alpha_missing_on_x0")
+
+
+def propagate_manual64(case, mut=None):
+    """oracle.predict_ref.propagate_ref of a case from explicit formulas (mut None), or with one of MUTANTS built in."""
+    indptr, indices, w, X = inputs(case)
+    adj = _adjacency(indptr, indices, w)
+    deg = np.asarray(adj.sum(1)).reshape(-1)
+    inv = 1.0 / (deg + 1e-12) if mut == "deg_plus_eps" else 1.0 / np.maximum(deg, 1e-12)
+    ppr = case.mode == "ppr"
+    step = ((1.0 - case.alpha) if ppr else 1.0) * inv
+    if ppr and mut == "alpha_on_every_term":
+        step = case.alpha * step
+    x = np.asarray(X, dtype=np.float64)
+    if ppr and mut != "alpha_missing_on_x0":
+        x = case.alpha * x
+    total = x.copy()
+    for _ in range(case.order):
+        x = step[:, None] * adj.dot(x)
+        total += x
+    if case.mode == "single":
+        return total if mut == "single_returns_sum" else x
+    if case.mode == "avg":
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return total / (case.order if mut == "avg_over_n" else case.order + 1)
+    return total
+
+
+def share(got, ref):
+    """max |got - ref| / tolerance; a non-finite entry counts as infinite."""
+    d, tol = np.abs(got - ref), tolerance(ref)
+    if not np.isfinite(d).all() or (d > 0)[tol == 0].any():
+        return float("inf")
+    return float((d[tol > 0] / tol[tol > 0]).max()) if (tol > 0).any() else 0.0
 
 
 def emulate_fp32_storage(indptr, indices, weights, X, mode, order, alpha):

@@ -265,6 +265,24 @@ def test_embedding_bag_lane_groups_and_bag_lengths(H, training):
         assert int((~named).sum()) >= 50 and torch.count_nonzero(W.grad.cpu()[~named]) == 0
 
 
+@pytest.mark.parametrize("H", ac.TINY_BAG_H)
+@pytest.mark.parametrize("training", [False, True])
+def test_embedding_bag_weights_at_the_epsilons_scale(H, training):
+    """A bag of 9 weights of 1e-11: its denominator is of the size of the 1e-10 beside it, so 1 / (den + 1e-10) is about half
+    of 1 / den and a hundredth of what random_prop's 1e-12 would give; forward and W.grad of both backwards."""
+    import torch
+    c = ac.tiny_bags(H)
+    ref, terms, dW, dW_terms = ac.bag_reference(c, training)
+    assert 0.4 < float(c.attr_data[c.node_idx == ac.TINY_BAG].double().sum()) / 1e-10 / 2 < 0.5
+    for det in (False, True):
+        W = c.W.cuda().requires_grad_(True)
+        out = _bag_call(c, W, training, det)
+        close(out, ref, terms)
+        assert torch.count_nonzero(out[ac.TINY_BAG]) > 0
+        out.backward(c.G.cuda())
+        close(W.grad, dW, dW_terms)
+
+
 @pytest.mark.parametrize("H", ac.G_CSR_H)
 def test_embedding_bag_csr_equals_coo_bitwise_at_the_edges(H):
     """G: the CSR form (int32 ids, nodes out of order with one repeat) equals the COO form of the same bags bit for bit."""

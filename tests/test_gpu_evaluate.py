@@ -46,18 +46,7 @@ def test_head_matches_torch(C, n):
 
 
 def test_ties_and_nans_follow_argmax():
-    C = 349
-    z = torch.randn((8, C), generator=torch.Generator().manual_seed(5))
-    z[0, [0, 63, 64]] = 9.0                                  # lanes 0 / 63 and the second pass of lane 0
-    z[1, [63, 64]] = 9.0
-    z[2, [64, 128, 320]] = 9.0                               # the same lane, three passes
-    z[3, [348, 100]] = 9.0
-    z[4, 70] = float("nan"); z[4, 5] = float("nan")          # the first NaN wins
-    z[5, 64] = float("nan"); z[5, 3] = 50.0                  # a NaN beats every number
-    z[6, :] = float("-inf")                                  # all equal: index 0
-    z[7, 10] = float("inf")
-    y = torch.full((8,), -100, dtype=torch.int64)            # ignored: the loss of a NaN row is not the subject here
-    y[:4] = torch.tensor([0, 63, 64, 100])
+    z, y = ec.ties_case()
     buf, loss, acc, counts = _head(z.cuda(), y.cuda())
     expect = torch.argmax(z, dim=1)
     assert expect.tolist() == [0, 63, 64, 100, 5, 64, 0, 10] == np.argmax(z.numpy(), axis=1).tolist()
@@ -90,19 +79,11 @@ def test_row_and_label_indices_are_gathered_on_the_device():
 
 
 def test_ignored_and_bad_rows_are_counted_and_leave_the_others_unchanged():
-    n, C = 300, 7
-    z, y, _ = ec.head_case(4097, C)
-    z, y = z[:n].clone(), y[:n].clone()
+    z, y, y2, rows, lrows, ignored, bad = ec.ignored_case()
+    n, C = z.shape
     clean, *_ = _head(z.cuda(), y.cuda())
-    y2 = y.clone()
-    y2[[3, 77]] = -100                                       # ignore_index
-    y2[[5, 100]] = torch.tensor([C, -1])                     # labels outside [0, C)
-    y2[200] = 2 ** 40
-    rows, lrows = torch.arange(n), torch.arange(n)
-    rows[[9, 10]] = torch.tensor([n, -1])                    # a logits row outside the array
-    lrows[[11, 12]] = torch.tensor([n, -(2 ** 50)])          # a label index outside the array
     buf, loss, acc, counts = _head(z.cuda(), y2.cuda(), rows=rows.cuda(), label_rows=lrows.cuda())
-    ignored, bad = [3, 77], [5, 100, 200, 9, 10, 11, 12]
+    assert (ignored, bad) == ([3, 77], [5, 100, 200, 9, 10, 11, 12])
     keep = torch.ones(n, dtype=torch.bool)
     keep[ignored + bad] = False
     assert buf.flag[ignored].tolist() == [2, 2] and buf.flag[bad].tolist() == [3] * 7
@@ -244,6 +225,23 @@ def test_valid_end_to_end(world, valid_refs, name, batch_size, monkeypatch):
     ec.assert_decided_preds(preds[-1], r64, f"valid {name} B={batch_size}")
     loss2, acc2 = valid(model, world["rm"], world["X"].cuda(), idx, y.cuda(), batch_size=batch_size)
     assert torch.equal(_bits(loss2), _bits(loss)) and torch.equal(_bits(acc2), _bits(acc))
+
+
+def test_valid_at_small_running_variances_and_one_epsilon_per_layer(world):
+    """The bn_norm model with infer_cases.small_var's BatchNorm state (variances from 0 to 1e-3, eps 1e-3 and 1e-5 by layer):
+    valid against the float64 chain, whose bounds scale with the model as before."""
+    from grand_plus_amd import valid
+    ours, ref = ec.model_pair("bn_norm", small=True)
+    idx, y = world["idx_val"], world["y"]
+    pos = world["rm"].batch_positions(idx, check=True).cpu()
+    r64 = ec.valid64(ref, world["X"], *world["host_rows"], ec.K_ROWS, pos, y[idx])
+    ours = ours.cuda().eval()
+    loss, acc, counts = valid(ours, world["rm"], world["X"].cuda(), idx, y.cuda(), batch_size=257, return_counts=True)
+    print(f"[evaluate] valid small_var: |loss-loss64| {abs(float(loss) - r64['loss']):.3e}, bound {r64['loss_bound']:.3e}")
+    assert abs(float(loss) - r64["loss"]) <= r64["loss_bound"]
+    pred = torch.argmax(_composed_logits(ours, world, 257), dim=1)
+    ec.assert_decided_preds(pred, r64, "valid small_var")
+    assert counts.tolist() == [idx.numel(), int((pred.cpu() == y[idx]).sum()), 0, 0]
 
 
 def test_valid_raises_for_a_node_that_is_no_seed(world, valid_refs):

@@ -66,6 +66,20 @@ def test_infer_matches_the_float64_restatement(case, B):
     ic.assert_rule(got, want, bound, f"{case[0]} B={B}")
 
 
+@pytest.mark.parametrize("case,B", ic.SMALL_DRAWN, ids=[c[0] for c, _ in ic.SMALL_DRAWN])
+def test_infer_at_small_running_variances_and_one_epsilon_per_layer(case, B):
+    """Running variances from 0 to 1e-3, bn.eps = 1e-3, 1e-5, 1e-7 by layer and a row whose norm is node_norm's 1e-12: here
+    the epsilons decide the logits (tests/test_host_mutants.py), under the same rule."""
+    ours, ref = ic.small_pair(case)
+    X = ic.small_inputs(case, B).cuda()
+    ours = ours.cuda()
+    got = ours.infer(X)
+    want, bound = ic.ref_out(ref.cuda(), X.double())
+    ic.assert_rule(got, want, bound, f"{case[0]} small_var B={B}")
+    if case in ic.SMALL_VAR_BITWISE:
+        assert _same(got, _block(ours, X))
+
+
 # ------------------------------------------------------------------------------------- 3. tile and reduction edges
 @pytest.mark.parametrize("f_in,f_out", ic.EDGE_SHAPES)
 def test_tile_and_reduction_edges(f_in, f_out):

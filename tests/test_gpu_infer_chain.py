@@ -81,6 +81,18 @@ def test_fused_matches_the_float64_restatement(name):
     ic.assert_rule(got, want, bound, f"fused {name} B={cc.RULE_ROWS}")
 
 
+@pytest.mark.parametrize("case,B", ic.SMALL_DRAWN, ids=[c[0] for c, _ in ic.SMALL_DRAWN])
+def test_fused_at_small_running_variances_and_one_epsilon_per_layer(case, B):
+    """The two fused blocks take their own epsilons (bn1_eps, bn2_eps): unequal ones at variances they decide."""
+    ours, ref = ic.small_pair(case)
+    X = ic.small_inputs(case, B).cuda()
+    ours = ours.cuda()
+    got = ours.infer(X, fused=True)
+    assert _same(got, ours.infer(X))
+    want, bound = ic.ref_out(ref.cuda(), X.double())
+    ic.assert_rule(got, want, bound, f"fused {case[0]} small_var B={B}")
+
+
 # ------------------------------------------------------------------------------------------------------------ 6. rows
 @pytest.fixture(scope="module")
 def chunk():

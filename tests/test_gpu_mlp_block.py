@@ -96,6 +96,13 @@ def test_batchnorm_column_kernel_tails(c):
     _check(c)
 
 
+@pytest.mark.parametrize("c", mc.BN_HYPER, ids=mc.ids(mc.BN_HYPER))
+def test_batchnorm_eps_and_momentum_away_from_the_defaults(c):
+    """eps = 1e-3 and momentum = 0.3 in training: the normalised forward, its backward and both running statistics."""
+    b, bd, _, _ = _check(c)
+    assert bd.bn.eps == 1e-3 and bd.bn.momentum == 0.3 and b.bn.eps == 1e-3
+
+
 @pytest.mark.parametrize("c", mc.ROW_EDGES, ids=mc.ids(mc.ROW_EDGES))
 def test_row_kernel_tails_and_degenerate_rows(c):
     b, bd, got, _ = _check(c)

@@ -13,7 +13,7 @@ import optim_cases as oc
 
 pytestmark = pytest.mark.gpu
 
-CASES = [(name, hi) for name in oc.SETS if name not in oc.OWN_TESTS for hi in range(len(oc.HYPERS))]
+CASES = oc.GRID
 IDS = [f"{name}-h{hi}" for name, hi in CASES]
 
 
@@ -136,6 +136,55 @@ def test_clip_grad_norm_scales_by_the_fp32_coefficient_of_the_returned_norm(name
     clip_grad_norm(params, 1e6)
     for p, g in zip(params, scaled):
         assert _bits_equal(p.grad, g)
+
+
+def test_clip_grad_norm_where_the_1e6_of_the_coefficient_decides():
+    """Gradients of total norm 1.1e-6 (the "odd" set at 1e-8) and max_norm = 2e-6: max_norm / (norm + 1e-6) is about 0.95,
+    max_norm / norm about 1.8 and clamps to 1.  Bitwise against g * coef, after showing that the two coefficients differ."""
+    from grand_plus_amd import clip_grad_norm
+    hi = oc.TINY
+    max_norm = oc.HYPERS[hi]["clip"]
+    init, seq = oc.inputs("odd", hi)
+    params = oc.device_params("odd", init)
+    oc.set_grads(params, seq[0])
+    before = [p.grad.clone() for p in params]
+    norm = clip_grad_norm(params, max_norm)
+    _assert_norm(norm, oc.reference("odd", hi)[0]["norm"][0])
+    one, m = torch.tensor(1.0, dtype=torch.float32), torch.tensor(max_norm, dtype=torch.float32)
+    coef = torch.minimum(m / (norm.cpu() + torch.tensor(1e-6, dtype=torch.float32)), one)
+    without = torch.minimum(m / norm.cpu(), one)
+    assert coef.dtype == torch.float32 and 0.5 < float(coef) < 1.0 and float(without) != float(coef)
+    for p, g in zip(params, before):
+        assert _bits_equal(p.grad, g * coef.cuda())
+        assert g.numel() == 0 or not _bits_equal(p.grad, g * without.cuda())
+
+
+def _off_default_ids():
+    return [f"{name}-h{hi}" for name, hi, _, _ in oc.OFF_DEFAULT]
+
+
+@pytest.mark.parametrize("capturable", [False, True], ids=["host_number", "capturable"])
+@pytest.mark.parametrize("name,hi,betas,eps", oc.OFF_DEFAULT, ids=_off_default_ids())
+def test_betas_and_eps_away_from_the_defaults(name, hi, betas, eps, capturable):
+    """betas = (0.8, 0.99) and eps = 1e-6, five steps: through the host-number ClipAdam, whose step numbers the host forms,
+    and through the capturable one, where step_state.hip forms the bias corrections from the device's tick."""
+    from grand_plus_amd import ClipAdam, StepState
+    h = oc.HYPERS[hi]
+    init, seq = oc.inputs(name, hi)
+    r64, t32 = oc.reference(name, hi, oc.STEPS, betas, eps)
+    params = oc.device_params(name, init)
+    kw = dict(lr=h["lr"], betas=betas, eps=eps, weight_decay=h["weight_decay"], clip_norm=h["clip"])
+    st = StepState("cuda", 1, 1.0, 10) if capturable else None
+    opt = ClipAdam(params, capturable=True, state=st, **kw) if capturable else ClipAdam(params, **kw)
+    norms = []
+    for grads in seq:
+        if capturable:
+            st.advance(opt)
+        oc.set_grads(params, grads)
+        norms.append(opt.step())
+    oc.error_ratios(_state_of(opt, params), t32, r64, f"{name}-h{hi} betas {betas} eps {eps} capturable {capturable}")
+    for got, ref in zip(norms, r64["norm"]):
+        _assert_norm(got, ref)
 
 
 def test_clip_grad_norm_with_max_norm_0_returns_the_norm_and_touches_nothing():

@@ -158,8 +158,12 @@ BOUNDARY_ROWS = {u: f"degree {pc.HUB_DEGREES[u]}" for u in range(pc.N_BOUNDARY_R
 def test_hub_rows_in_every_mode_weighted_and_not(case):
     """Rows of 4096 (main kernel) and 4097 / 4227 / 5999 / 4104 neighbours (long kernel; 4227 = 4096 + 128 + 3 has a tail
     after the 128-neighbour batches), each asserted by name, then the whole matrix.  Weighted: one short row's weights
-    sum to 0, its scale is 1 / 1e-12 and its result 0, not NaN."""
-    got = _check_case(case, rows=BOUNDARY_ROWS).cpu().numpy()
+    sum to 0, its scale is 1 / 1e-12 and its result 0, not NaN; the weights of another sum to 1e-12 itself, where
+    max(deg, 1e-12) and deg + 1e-12 differ by a factor of two."""
+    rows = dict(BOUNDARY_ROWS)
+    if case.weighted:
+        rows[pc.tiny_row(case.graph)] = "weights summing to 1e-12"
+    got = _check_case(case, rows=rows).cpu().numpy()
     if case.weighted:
         zero_row = pc.edge_weights(case.graph)[1]
         assert np.isfinite(got[zero_row]).all()

@@ -43,13 +43,19 @@ def test_hub_graph_is_what_it_promises(name):
 
 
 def test_weighted_variant_has_one_short_row_of_zero_weights():
+    """... and, since the audit of DESIGN §7q, one short row at the epsilon's scale."""
     indptr, indices = pc.graph("hub")
     w, zero_row = pc.edge_weights("hub")
     assert w.dtype == np.float32 and len(w) == len(indices)
     assert zero_row >= len(pc.HUB_DEGREES) and 2 <= indptr[zero_row + 1] - indptr[zero_row] <= 12
     rows = np.repeat(np.arange(len(indptr) - 1), np.diff(indptr))
     assert (w[rows == zero_row] == 0.0).all()
-    assert w[rows != zero_row].min() >= 0.5 and w[rows != zero_row].max() <= 2.0
+    tiny = pc.tiny_row("hub")                          # ... and one whose weights sum to the 1e-12 of max(deg, 1e-12)
+    assert tiny > zero_row and 2 <= indptr[tiny + 1] - indptr[tiny] <= 12
+    assert w[rows == tiny][:2].tolist() == [pc.TINY_WEIGHT] * 2 and (w[rows == tiny][2:] == 0.0).all()
+    assert abs(float(w[rows == tiny].astype(np.float64).sum()) - 1e-12) < 1e-18
+    other = (rows != zero_row) & (rows != tiny)
+    assert w[other].min() >= 0.5 and w[other].max() <= 2.0
     for mode in pc.MODES:                              # scale = numer / 1e-12 times a sum of 0: 0, never NaN
         ref = pc.reference(pc.Case("hub", 12, mode, 1, 0.2, True))
         assert np.isfinite(ref).all()
