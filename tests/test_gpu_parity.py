@@ -647,7 +647,13 @@ def test_sharded_path_with_several_parts_on_one_device(n_seeds, devices):
     """The >= 2-part branch of gp_gfpush on the hardware there is: gp_graph_create_multi_on with a repeated device
     gives the handle several parts on ONE GPU -- replicas (replicate_part), the partition plan, one host thread / stream / workspace
     per part, seed blocks with a ragged last block, one D2H per part and the scatter of the v > 0 slots -- everything an 8-GPU node
-    runs except the RCCL collective (one rank per device).  Rows and exact counters must equal the single-GPU call's."""
+    runs except the RCCL collective (one rank per device).  Rows and exact counters must equal the single-GPU call's.
+
+    Both handles run with measure_choice = 0: `workgroups` is summed over the parts, and a call of 65 537 rows is large enough to
+    time its candidates, so the single-GPU call could measure its way to two workgroups per CU while each part (half the rows)
+    measured its way to one -- 512 against 512, and "every part ran its own launch" failed on a timing.  With kernel and launch
+    shape from the thresholds alone the single call and every part get the same shape, and the sum over parts must exceed the
+    single call's count.  (tests/test_gpu_stress.py covers the calibration.)"""
     from grand_plus_amd import Graph, synth
     from grand_plus_amd.recipes import RECIPES
     indptr, indices = synth.shape_csr("small")
@@ -657,10 +663,11 @@ def test_sharded_path_with_several_parts_on_one_device(n_seeds, devices):
     base = synth.seeds(n, min(n_seeds, n))
     seeds = np.resize(base, n_seeds)                                   # (more seeds than nodes: duplicates are legal)
     fill = (-1, -1, -1.0)
-    single, st1 = _run_gpu(indptr, indices, seeds, r.coef(), r.rmax, K, fill=fill)
+    single, st1 = _run_gpu(indptr, indices, seeds, r.coef(), r.rmax, K, fill=fill, options={"measure_choice": 0})
     g = Graph(indptr, indices, 0, devices=devices)
     assert g.n_gpus == len(devices)
     g.set_option("min_rows_per_gpu", 64)
+    g.set_option("measure_choice", 0)
     with pytest.raises(ValueError):
         g.set_option("gather_host", 0)                                 # parts share a device: no collective
     row = np.full(n_seeds * K, -1, np.int32); col = np.full(n_seeds * K, -1, np.int32); val = np.full(n_seeds * K, -1.0)
@@ -669,6 +676,7 @@ def test_sharded_path_with_several_parts_on_one_device(n_seeds, devices):
     _assert_parity(seeds, K, (row, col, val), single, fill=fill)
     assert st["rows"] == n_seeds and st["failed_rows"] == 0
     assert (st["pushes"], st["edges"], st["filled"]) == (st1["pushes"], st1["edges"], st1["filled"])
+    assert st["choice_ms"] == [0.0, 0.0, 0.0] == st1["choice_ms"]      # nothing was timed: the shapes are the thresholds'
     assert st["workgroups"] > st1["workgroups"]                        # every part ran its own launch
     # a second call on the same handle re-uses replicas and buffers
     row2 = np.full(n_seeds * K, -1, np.int32); col2 = np.full(n_seeds * K, -1, np.int32); val2 = np.full(n_seeds * K, -1.0)
