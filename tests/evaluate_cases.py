@@ -1,4 +1,5 @@
-"""Inputs, references and bounds shared by tests/test_gpu_evaluate.py and tests/test_host_evaluate.py.
+"""Inputs, references and bounds shared by tests/test_gpu_evaluate.py, tests/test_gpu_evaluate_edges.py and the audit of
+tests/test_host_mutants.py.
 
 The references are torch's own `F.nll_loss(F.log_softmax(z))` in float64 on the CPU for the head, and for the end-to-end
 checks the float64 chain of the oracles: `oracle.random_prop_ref` (or `oracle.predict_ref.propagate_ref`) ->
@@ -87,30 +88,60 @@ def ignored_case():
 
 
 # ---- the head written out in float64, and one deliberate mistake (tests/test_host_mutants.py)
-MUTANTS = ("acc_over_valid", "loss_over_rows", "tie_last_index", "nan_not_max", "ignored_in_loss")
+BOOKKEEPING = ("acc_over_valid", "loss_over_rows", "tie_last_index", "nan_not_max", "ignored_in_loss")
+# arithmetic mistakes of the head, judged on EDGE_DRAWN row by row against row_bound64, and of the reduce (reduce64)
+HEAD_ARITHMETIC = ("no_max_subtraction", "lse_first_pass_only", "lse_tail_dropped", "max_first_pass_only", "gather_y_mod_64",
+                   "nll_of_pred", "lse_sign")
+REDUCE_MUTANTS = ("reduce_in_float32", "reduce_last_slice_dropped")
+MUTANTS = BOOKKEEPING + HEAD_ARITHMETIC + REDUCE_MUTANTS
+# A mistake that no drawn case can tell from the correct head would be named here with its reason, as
+# objective_cases.INDISTINGUISHABLE does; every mistake of MUTANTS is seen.
+INDISTINGUISHABLE = ()
+WRITTEN_OUT = "written_out"                                  # no mistake, through the formulas that take the mistakes
+
+
+def _row_nll64(row, label, pred, mut):
+    """-((z_y - m) - log sum exp(z - m)) of one float64 row, written out so that one of HEAD_ARITHMETIC can be built in.
+    m is the maximum that the argmax search found (a NaN where the row holds one, as in the kernel)."""
+    C = row.numel()
+    seen = row[:64] if mut == "max_first_pass_only" else row
+    m = seen.max()                                           # torch.max hands a NaN on
+    if mut == "no_max_subtraction":
+        m = torch.zeros((), dtype=row.dtype)
+    summed = row
+    if mut == "lse_first_pass_only":
+        summed = row[:64]
+    elif mut == "lse_tail_dropped" and C > 64 and C % 64:
+        summed = row[:64 * (C // 64)]
+    lse = torch.log(torch.exp(summed - m).sum())
+    at = label % 64 if mut == "gather_y_mod_64" else pred if mut == "nll_of_pred" else label
+    return float(-((row[at] - m) + lse) if mut == "lse_sign" else -((row[at] - m) - lse))
 
 
 def head64(z, y, rows=None, label_rows=None, ignore_index=-100, mut=None):
-    """What eval_head + eval_reduce must give, on the CPU in float64: {"pred", "flag", "counts", "acc", "loss"}; mut None, or
-    one of MUTANTS built in.  A row whose logits row, label index or label is outside its array is BAD (pred -1 without a
-    logits row); a label equal to ignore_index is IGNORED; acc is over all rows, the loss over the others alone."""
+    """What eval_head + eval_reduce must give, on the CPU in float64: {"pred", "flag", "counts", "acc", "loss", "nll"}; mut
+    None, or one of BOOKKEEPING or HEAD_ARITHMETIC built in.  A row whose logits row, label index or label is outside its
+    array is BAD (pred -1 without a logits row); a label equal to ignore_index is IGNORED; acc is over all rows, the loss
+    over the others alone.  nll [n] holds each row's term of the loss, 0 for a row that is ignored or bad."""
     z, y = z.double(), y.long()
     n = rows.numel() if rows is not None else label_rows.numel() if label_rows is not None else z.shape[0]
     C = z.shape[1]
     rows = torch.arange(n) if rows is None else rows.long()
     lrows = torch.arange(n) if label_rows is None else label_rows.long()
     pred, flag = torch.full((n,), -1, dtype=torch.int64), torch.full((n,), BAD, dtype=torch.uint8)
+    nll = torch.zeros(n, dtype=torch.float64)
     total, n_valid = 0.0, 0
     for i in range(n):
         r, l = int(rows[i]), int(lrows[i])
         if not 0 <= r < z.shape[0]:
             continue
         row = z[r]
-        nan = torch.isnan(row)
+        seen = row[:64] if mut == "max_first_pass_only" else row
+        nan = torch.isnan(seen)
         if bool(nan.any()) and mut != "nan_not_max":
             pred[i] = int(nan.nonzero()[0])                  # the first NaN, as torch.argmax and numpy
         else:
-            v = torch.where(nan, torch.full_like(row, float("-inf")), row)
+            v = torch.where(nan, torch.full_like(seen, float("-inf")), seen)
             hits = (v == v.max()).nonzero()[:, 0]
             pred[i] = int(hits[-1] if mut == "tie_last_index" else hits[0])
         if not 0 <= l < y.numel():
@@ -124,13 +155,17 @@ def head64(z, y, rows=None, label_rows=None, ignore_index=-100, mut=None):
         if not 0 <= label < C:
             continue
         flag[i] = CORRECT if int(pred[i]) == label else WRONG
-        total -= float(torch.log_softmax(row, dim=0)[label])
+        # torch's own log_softmax unless a mistake goes into it; WRITTEN_OUT is _row_nll64 with none, held to torch's
+        # up to the rounding of float64's own sum (tests/test_host_mutants.py)
+        written = mut in HEAD_ARITHMETIC or mut == WRITTEN_OUT
+        nll[i] = _row_nll64(row, label, int(pred[i]), mut) if written else -float(torch.log_softmax(row, dim=0)[label])
+        total += float(nll[i])
     counts = [int((flag <= CORRECT).sum()), int((flag == CORRECT).sum()), int((flag == IGNORED).sum()), int((flag == BAD).sum())]
     n_valid += counts[0]
     den_loss = n if mut == "loss_over_rows" else n_valid
     den_acc = counts[0] if mut == "acc_over_valid" else n
     return {"pred": pred, "flag": flag, "counts": counts, "acc": counts[1] / den_acc if den_acc else float("nan"),
-            "loss": total / den_loss if den_loss else float("nan")}
+            "loss": total / den_loss if den_loss else float("nan"), "nll": nll}
 
 
 def head_share(got, ref, loss32, loss_held=True):
@@ -160,15 +195,235 @@ def head_drawn():
     return out
 
 
-def reduce_case(n, seed=0):
-    """Synthetic filled buffers (nll float32, flag uint8) and what the reduce must give: (nll, flag, loss64, counts)."""
+REDUCE_N = (0, 1, 1023, 1025, 2047, 2049, 1024 * 5 - 1, 1024 * 1023 + 1, 1024 * 1024 + 1, 1024 * 1025 - 1)
+ABSORB_N = 1024 * 5 - 1                                      # the smallest drawn size with more than two slices
+
+
+def reduce_case(n, seed=0, absorb=False):
+    """Synthetic filled buffers (nll float32, flag uint8) and what the reduce must give: (nll, flag, loss64, counts).
+    With `absorb` every 1024th row holds 2^24 and the other valid rows 0.75, less than half a float32 ulp of 2^24: the
+    float64 sum is exact, a float32 accumulator that has taken the large row in takes in none of the small ones."""
     rng = np.random.default_rng(seed + n)
     flag = rng.integers(0, 4, n).astype(np.uint8)
     nll = (rng.random(n) * 5.0).astype(np.float32)
+    if absorb:
+        nll[:] = 0.75
+        nll[::1024] = 2.0 ** 24
+        flag[::1024] = WRONG
     nll[flag >= IGNORED] = 0.0
     counts = [int((flag <= CORRECT).sum()), int((flag == CORRECT).sum()), int((flag == IGNORED).sum()), int((flag == BAD).sum())]
     loss = float(np.sum(nll.astype(np.float64))) / counts[0] if counts[0] else float("nan")
     return torch.from_numpy(nll), torch.from_numpy(flag), loss, counts
+
+
+def reduce_drawn():
+    """What tests/test_gpu_evaluate.py gives the reduce: (name, n, absorb)."""
+    return [(f"reduce n={n}", n, False) for n in REDUCE_N] + [(f"reduce n={ABSORB_N} absorb", ABSORB_N, True)]
+
+
+def reduce64(nll, flag, mut=None):
+    """eval_reduce's result from filled buffers, on the CPU: {"loss", "acc", "counts"}, with the kernel's slices (at least
+    1024 rows each, at most 1024 of them); mut None, or one of REDUCE_MUTANTS built in."""
+    nll, flag = nll.numpy(), flag.numpy()
+    n = len(nll)
+    grid = min(max(-(-n // 1024), 1), 1024)
+    rows = -(-n // grid)                                     # of a slice
+    if mut == "reduce_last_slice_dropped":
+        nll, flag = nll[:(grid - 1) * rows], flag[:(grid - 1) * rows]
+    counts = [int((flag <= CORRECT).sum()), int((flag == CORRECT).sum()), int((flag == IGNORED).sum()), int((flag == BAD).sum())]
+    if mut == "reduce_in_float32":                           # numpy's cumsum adds one by one in the dtype it is given
+        parts = [np.cumsum(nll[s:s + rows], dtype=np.float32)[-1] for s in range(0, len(nll), max(rows, 1))]
+        total = float(np.sum(np.asarray(parts, dtype=np.float64)))
+    else:
+        total = float(np.sum(nll.astype(np.float64)))
+    return {"loss": total / counts[0] if counts[0] else float("nan"), "acc": counts[1] / n if n else float("nan"), "counts": counts}
+
+
+def reduce_share(got, loss64, counts, n):
+    """How far a reduce64 result is from the case under the GPU test's assertions: infinite where the counts, the accuracy
+    or a NaN loss differ, otherwise |loss - loss64| over 2^-23 |loss64|."""
+    acc = counts[1] / n if n else float("nan")
+    same = lambda a, b: a == b or (a != a and b != b)  # noqa: E731
+    if got["counts"] != counts or not same(got["acc"], acc) or (got["loss"] != got["loss"]) != (loss64 != loss64):
+        return float("inf")
+    if loss64 != loss64 or got["loss"] == loss64:
+        return 0.0
+    return abs(got["loss"] - loss64) / (2.0 ** -23 * abs(loss64))
+
+
+# ---- the head at its edges (DESIGN §7h): a bound from the kernel's order of operations, that order walked in float32,
+# and the drawn cases
+U = 2.0 ** -24                                               # half a float32 ulp, relative: one rounding
+EDGE_N = 65                                                  # more than one wave per block, one row past 64
+EDGE_C = (1, 2, 63, 64, 65, 127, 128, 129, 4095, 4096)       # the lane loop's pass edges, and kMaxC
+
+
+def bounds64(z, y):
+    """row_bound64 for every row of z [n, C] (float32 values, taken as given) with labels y [n] in [0, C): (nll [n], bound
+    [n]) in float64.  nll is torch's float64 -log_softmax(z)[y]; the bound is NaN where nll is not finite (such a row is
+    held exactly).  With u = 2^-24, m the row's max, t_c = |z_c - m|, p = softmax(z), lse = log sum exp(z_c - m), following
+    eval_head_kernel step by step:
+
+        u |z_y - m|                the subtraction z_y - m
+      + u sum_c p_c (t_c + 2)      z_c - m rounded (u t_c), then expf (at most 2 ulp = 2u), each by its share of the sum
+      + u (ceil(C / 64) + 6)       a lane's serial adds over its passes and the six steps of wave_sum, each at most u of a
+                                   partial sum that is at most the whole sum
+      + 2u |lse|                   logf, at most 2 ulp of its result
+      + 2u |nll|                   the last subtraction and the store
+
+    The 2 ulp of expf and logf are an assumption about the device's library, not a documented figure (DESIGN §7h says
+    what the run showed).  A class at -inf has p_c = 0 and contributes nothing; a term whose expf underflows errs by at most
+    itself, below 2^-126 of the sum, which the third line covers many times over."""
+    z64, y = z.double(), y.long()
+    C = z64.shape[1]
+    nll = -torch.log_softmax(z64, dim=1).gather(1, y[:, None])[:, 0]
+    m = z64.max(dim=1, keepdim=True).values
+    t = (z64 - m).abs()
+    e = torch.exp(z64 - m)
+    s = e.sum(dim=1, keepdim=True)
+    spread = torch.where(e > 0, e / s * (t + 2.0), torch.zeros_like(e)).sum(dim=1)
+    zy = z64.gather(1, y[:, None])
+    bound = U * ((zy - m).abs()[:, 0] + spread + (-(-C // 64) + 6) + 2.0 * torch.log(s)[:, 0].abs() + 2.0 * nll.abs())
+    return nll, torch.where(torch.isfinite(nll), bound, torch.full_like(bound, float("nan")))
+
+
+def row_bound64(z, y):
+    """(float64 nll, the largest error a correct float32 head may make) of one row z [C] with label y: see bounds64."""
+    nll, bound = bounds64(z[None, :], torch.tensor([int(y)]))
+    return float(nll[0]), float(bound[0])
+
+
+def mean_bound64(nll, bound):
+    """(mean64, its bound) of rows that are all finite: mean_i bound_i + 2^-23 |mean64|, the reduce being a float64 sum
+    of the float32 rows that is rounded once."""
+    mean = float(nll.mean())
+    return mean, float(bound.mean()) + 2.0 ** -23 * abs(mean)
+
+
+def head_walk32(z, y):
+    """eval_head_kernel's order in numpy float32 for the rows of z [n, C] and labels y [n] in [0, C): float32 [n].  Class
+    c goes to lane c % 64 and is added pass by pass into that lane's accumulator, the 64 accumulators go through the xor
+    tree 32 ... 1, then logf and -((z_y - max) - ls).  numpy's float32 exp and log stand in for expf and logf.  The lanes
+    past C add exp(-inf - max) = 0 here, where the kernel adds nothing: the same bits."""
+    z, y = z.numpy().astype(np.float32), y.numpy()
+    n, C = z.shape
+    passes = -(-C // 64)
+    padded = np.full((n, passes * 64), -np.inf, dtype=np.float32)
+    padded[:, :C] = z
+    lane = np.arange(64)
+    with np.errstate(all="ignore"):
+        best = z.max(axis=1)                                 # a NaN in the row is its max, as in the kernel's search
+        e = np.zeros((n, 64), dtype=np.float32)
+        for k in range(passes):
+            e = e + np.exp(padded[:, 64 * k:64 * k + 64] - best[:, None])
+        for o in (32, 16, 8, 4, 2, 1):
+            e = e + e[:, lane ^ o]
+        out = -((z[np.arange(n), y] - best) - np.log(e[:, 0]))
+    assert out.dtype == np.float32
+    return out
+
+
+def _rotation(z):
+    """Labels by a fixed rotation over the rows: 0, C-1, min(63, C-1), min(64, C-1), min(65, C-1), the argmax, the argmin
+    (of the finite classes), so that y >= 64, y = C-1, the correct and the most wrong class all occur.  A label that lands
+    on a -inf class moves one class down (the masked classes are every third one, never class 0)."""
+    n, C = z.shape
+    top = torch.argmax(z, dim=1)
+    low = torch.argmin(torch.where(torch.isfinite(z), z, torch.full_like(z, float("inf"))), dim=1)
+    y = torch.empty(n, dtype=torch.int64)
+    for i in range(n):
+        y[i] = (0, C - 1, min(63, C - 1), min(64, C - 1), min(65, C - 1), int(top[i]), int(low[i]))[i % 7]
+        if z[i, y[i]] == float("-inf"):
+            y[i] -= 1
+    return y
+
+
+def _masked(z):
+    z = z.clone()
+    z[:, 2::3] = float("-inf")
+    return z
+
+
+def _edge_drawn():
+    out = []
+    for ci, C in enumerate(EDGE_C):
+        def g(family):
+            return torch.Generator().manual_seed(7000 + 100 * family + ci)
+        n = EDGE_N
+        wide = torch.randn((n, C), generator=g(0)) * 30.0
+        out.append((f"wide C={C}", wide, _rotation(wide), {}))
+        huge = torch.randn((n, C), generator=g(1)) * 1e4 + 1e6
+        out.append((f"huge C={C}", huge, _rotation(huge), {}))
+        conf = torch.randn((n, C), generator=g(2)) - 30.0
+        y = _rotation(conf)
+        conf[torch.arange(n), y] = 0.0
+        out.append((f"confident C={C}", conf, y, {}))
+        flat = torch.full((n, C), 5.0)
+        out.append((f"flat C={C}", flat, _rotation(flat), {}))
+        zeros = torch.where(torch.rand((n, C), generator=g(3)) < 0.5, -0.0, 0.0)
+        zeros[::2, 0] = -0.0                                 # a -0.0 first, a 0.0 after it: still index 0
+        zeros[::2, C // 2] = 0.0
+        out.append((f"flat signed zeros C={C}", zeros, _rotation(zeros), {}))
+        if C >= 3:
+            masked = _masked(torch.randn((n, C), generator=g(4)) * 3.0)
+            ym = _rotation(masked)
+            out.append((f"masked C={C}", masked, ym, {}))
+        if C >= 65:                                          # class 64 has to exist
+            z, y = masked.clone(), ym.clone()
+            y[5] = C - 1 - (C - 3) % 3                       # the last -inf class: nll = +inf
+            z[17, C - 1], y[17] = float("inf"), 0            # inf - inf: NaN
+            z[40, 64], y[40] = float("nan"), 1               # a NaN is the max: NaN
+            z[64, :], y[64] = float("-inf"), 0               # -inf - -inf: NaN, and pred = label = 0
+            out.append((f"special C={C}", z, y, {}))
+    C, R, n = 4096, 300, 200
+    gen = torch.Generator().manual_seed(7999)
+    z = torch.randn((R, C), generator=gen) * 30.0
+    rows = torch.randint(0, R, (n,), generator=gen)
+    rows[:40] = torch.arange(R - 1, R - 41, -1)              # reverse order
+    rows[40:60] = 17                                         # duplicates
+    lrows = torch.randint(0, R, (n,), generator=gen)         # labels picked by another list
+    out.append(("gathered4096", z, _rotation(z), dict(rows=rows, label_rows=lrows)))
+    return out
+
+
+# (name, z, y, {rows, label_rows}): built once, read by tests/test_gpu_evaluate_edges.py and tests/test_host_mutants.py;
+# nothing that reads them modifies them.  Every label is in [0, C) and every index inside its array.
+EDGE_DRAWN = _edge_drawn()
+EDGE_NAMES = [c[0] for c in EDGE_DRAWN]
+EDGE_SPECIAL_ROWS = (5, 17, 40, 64)                          # of the `special` cases: +inf, NaN, NaN, NaN
+PRINT_ONLY = ("huge", "flat")                                # families where torch's float32 can be exact: §7g's rule is printed
+
+
+def edge_family(name):
+    return name.split(" C=")[0]
+
+
+@functools.lru_cache(maxsize=None)
+def edge_reference(name):
+    """What a case of EDGE_DRAWN must give, from torch on the CPU, computed once: the gathered logits and labels (zz, yy),
+    pred, flag, counts, acc, and nll64 with its bound per row (bounds64)."""
+    _, z, y, kw = EDGE_DRAWN[EDGE_NAMES.index(name)]
+    n = kw["rows"].numel() if "rows" in kw else z.shape[0]
+    zz, yy = z[kw.get("rows", torch.arange(n))], y[kw.get("label_rows", torch.arange(n))]
+    pred = torch.argmax(zz, dim=1)
+    nll, bound = bounds64(zz, yy)
+    n_correct = int((pred == yy).sum())
+    return {"zz": zz, "yy": yy, "pred": pred, "flag": (pred == yy).to(torch.uint8), "counts": [n, n_correct, 0, 0],
+            "acc": float(np.float32(n_correct / n)), "nll": nll, "bound": bound, "mean": float(nll64(zz, yy))}
+
+
+def edge_share(got, ref, bound):
+    """How far `got` (a head64 result) is from `ref` under tests/test_gpu_evaluate_edges.py's assertions: infinite where
+    a quantity held exactly differs (pred, flag, counts, acc, a row that is not finite), otherwise the largest
+    |nll_i - nll64_i| / bound_i."""
+    same = lambda a, b: a == b or (a != a and b != b)  # noqa: E731
+    a, b = got["nll"], ref["nll"]
+    fin = torch.isfinite(b)
+    if not (torch.equal(got["pred"], ref["pred"]) and torch.equal(got["flag"], ref["flag"]) and got["counts"] == ref["counts"]
+            and same(got["acc"], ref["acc"]) and torch.equal(torch.isfinite(a), fin)
+            and torch.equal(torch.nan_to_num(a[~fin], nan=1.0), torch.nan_to_num(b[~fin], nan=1.0))):
+        return float("inf")
+    return float(((a - b).abs()[fin] / bound[fin]).max()) if bool(fin.any()) else 0.0
 
 
 def features(n_nodes, seed=3):

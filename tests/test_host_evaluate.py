@@ -109,6 +109,8 @@ def test_entries_return_their_error_codes_before_any_gpu_work():
     E, N = _native.GP_ERR_INVALID_ARG, _native.GP_ERR_NULL
     assert _head(C=0) == E and _head(C=4097) == E
     assert "gp_eval_head" in _native.lib().gp_last_error().decode()
+    assert _native.GP_MAX_CLASSES == 4096 and _head(C=-1) == E and _head(C=2 ** 31 - 1) == E
+    assert _head(C=4096, n=0, cap=0, nll=None) == _native.GP_OK      # the limit itself passes the checks
     assert _head(n=-1) == E and _head(n_z=-1) == E and _head(n_labels=-1) == E and _head(off=-1) == E
     assert _head(off=1) == E and _head(cap=3) == E and _head(off=2 ** 62, cap=2 ** 62) == E     # past the buffers
     assert _head(n_z=3) == E and _head(n_labels=3) == E                # more rows than the array, no index list

@@ -149,7 +149,7 @@ def test_head_manual_formulas_are_torchs_nll_loss_and_argmax():
     assert ref["counts"][0] == 300 - 9 and ref["counts"][2:] == [2, 7]
 
 
-@pytest.mark.parametrize("mut", ec.MUTANTS)
+@pytest.mark.parametrize("mut", ec.BOOKKEEPING)
 def test_head_each_mistake_is_seen(mut):
     best = (0.0, None)
     for name, z, y, kw, loss_held in ec.head_drawn():
@@ -159,6 +159,120 @@ def test_head_each_mistake_is_seen(mut):
         if s > best[0]:
             best = (s, name)
     _report("evaluate", mut, best)
+
+
+def test_head_mistakes_are_each_judged_or_declared():
+    assert set(ec.MUTANTS) == set(ec.BOOKKEEPING + ec.HEAD_ARITHMETIC + ec.REDUCE_MUTANTS) and len(set(ec.MUTANTS)) == len(ec.MUTANTS)
+    assert set(ec.INDISTINGUISHABLE) <= set(ec.MUTANTS)
+
+
+def test_head_edge_cases_hold_what_their_names_say():
+    """The list the GPU file parametrises over: every family at every class count where it exists, 65 rows, labels inside
+    [0, C) that reach C-1, 64 and beyond, the argmax and the argmin; the four rows of `special` are what they are named."""
+    fams = {}
+    for name, z, y, kw in ec.EDGE_DRAWN:
+        fams.setdefault(ec.edge_family(name), []).append(z.shape[1])
+        assert z.dtype == torch.float32 and y.dtype == torch.int64 and int(y.min()) >= 0 and int(y.max()) < z.shape[1], name
+        if not kw:
+            assert z.shape[0] == y.numel() == ec.EDGE_N, name
+            last = z.shape[1] - 1
+            if ec.edge_family(name) in ("masked", "special") and last % 3 == 2:
+                last -= 1                                    # the last finite class
+            assert int(y[1]) == last and int(y[0]) == 0 and int(y[3]) == min(64, last), name
+        for idx in kw.values():
+            assert int(idx.min()) >= 0 and int(idx.max()) < z.shape[0], name
+    every = list(ec.EDGE_C)
+    assert fams == {"wide": every, "huge": every, "confident": every, "flat": every, "flat signed zeros": every,
+                    "masked": [C for C in every if C >= 3], "special": [C for C in every if C >= 65], "gathered4096": [4096]}
+    for name in ec.EDGE_NAMES:
+        ref, fam = ec.edge_reference(name), ec.edge_family(name)
+        odd = [i for i in range(ref["nll"].numel()) if not math.isfinite(float(ref["nll"][i]))]
+        assert odd == (list(ec.EDGE_SPECIAL_ROWS) if fam == "special" else []), name
+        if fam == "special":
+            assert float(ref["nll"][5]) == math.inf and all(math.isnan(float(ref["nll"][i])) for i in (17, 40, 64)), name
+            assert ref["pred"][[17, 40, 64]].tolist() == [ref["zz"].shape[1] - 1, 64, 0] and int(ref["flag"][64]) == ec.CORRECT
+        if fam in ("masked", "special"):
+            assert bool(torch.isinf(ref["zz"][:, 2::3]).all()), name
+        if fam == "flat":
+            assert float((ref["nll"] - math.log(ref["zz"].shape[1])).abs().max()) < 1e-12 and not bool(ref["pred"].any()), name
+        if fam == "flat signed zeros":
+            z = ref["zz"][::2]                               # the rows with a -0.0 first and a 0.0 after it
+            assert not bool(ref["pred"].any()) and (z.shape[1] == 1 or bool((torch.signbit(z).any(dim=1) & ~torch.signbit(z).all(dim=1)).all())), name
+        if fam == "confident" and ref["zz"].shape[1] > 1:
+            assert 0.0 < float(ref["nll"].min()) and float(ref["nll"].max()) < 1e-8, name
+        if fam in ("wide", "huge") and ref["zz"].shape[1] > 2:
+            assert float(ref["nll"].max()) > (100.0 if fam == "wide" else 1e4), name
+
+
+@functools.lru_cache(maxsize=None)
+def _edge_head64(name):
+    """head64 without a mistake on a case of EDGE_DRAWN, once."""
+    _, z, y, kw = ec.EDGE_DRAWN[ec.EDGE_NAMES.index(name)]
+    return ec.head64(z, y, **kw)
+
+
+def test_head_edge_formulas_are_torchs_nll_loss_and_argmax():
+    for name, z, y, kw in ec.EDGE_DRAWN:
+        got, ref = _edge_head64(name), ec.edge_reference(name)
+        assert torch.equal(got["pred"], ref["pred"]) and torch.equal(got["flag"], ref["flag"]) and got["counts"] == ref["counts"], name
+        assert float(np.float32(got["acc"])) == ref["acc"], name
+        torch.testing.assert_close(got["nll"], ref["nll"], rtol=1e-9, atol=0.0, equal_nan=True, msg=name)
+        want = ref["mean"]
+        assert (math.isnan(want) and math.isnan(got["loss"])) or got["loss"] == want or abs(got["loss"] - want) <= 1e-9 * abs(want), name
+        # the formulas that take the mistakes, with none: a float64 sum of C terms exp(z - m) <= 1 rounds at most C - 1 partial
+        # sums by 2^-53 each, in torch's log_softmax and here, in whatever order each adds; relative to a sum of at least 1
+        # that is an absolute 2^-53 C on the logarithm, and at the `confident` losses of 1e-12 all that separates the two
+        out = ec.head64(z, y, mut=ec.WRITTEN_OUT, **kw)["nll"]
+        torch.testing.assert_close(out, ref["nll"], rtol=1e-9, atol=2.0 ** -53 * (z.shape[1] + 2), equal_nan=True, msg=name)
+        # row_bound64, the one-row form, is the same function
+        i = ref["nll"].numel() - 1
+        one = ec.row_bound64(ref["zz"][i], ref["yy"][i])
+        assert all(a == float(b) or (a != a and float(b) != float(b)) for a, b in zip(one, (ref["nll"][i], ref["bound"][i]))), name
+
+
+@pytest.mark.parametrize("mut", [m for m in ec.HEAD_ARITHMETIC if m not in ec.INDISTINGUISHABLE])
+def test_head_each_arithmetic_mistake_is_seen_at_the_edges(mut):
+    """Either way counts: a quantity the GPU file holds exactly (the first such case is printed), or a row moved by more
+    than SEEN of its row_bound64 (the largest such move)."""
+    best, exact = (0.0, None), None
+    for name, z, y, kw in ec.EDGE_DRAWN:
+        s = ec.edge_share(ec.head64(z, y, mut=mut, **kw), _edge_head64(name), ec.edge_reference(name)["bound"])
+        if math.isinf(s):
+            exact = exact or name
+        elif s > best[0]:
+            best = (s, name)
+    print(f"[mutants] evaluate {mut}: held exactly in {exact}; the largest move of a finite row is {best[0]:.3g} bounds ({best[1]})")
+    _report("evaluate", mut, (math.inf, exact) if exact else best)
+
+
+@pytest.mark.parametrize("mut", [m for m in ec.REDUCE_MUTANTS if m not in ec.INDISTINGUISHABLE])
+def test_reduce_each_mistake_is_seen(mut):
+    best = (0.0, None)
+    for name, n, absorb in ec.reduce_drawn():
+        nll, flag, loss64, counts = ec.reduce_case(n, absorb=absorb)
+        assert ec.reduce_share(ec.reduce64(nll, flag), loss64, counts, n) <= 2.0 ** -29, name     # the float64 sum itself
+        s = ec.reduce_share(ec.reduce64(nll, flag, mut), loss64, counts, n)
+        print(f"[mutants] evaluate {mut}: {name} {s:.3g} bounds")
+        if s > best[0]:
+            best = (s, name)
+    _report("evaluate", mut, best)
+
+
+def test_head_walk_in_float32_stays_inside_the_row_bound():
+    """row_bound64 is a worst-case derivation, so the kernel's order walked in float32 is held to the bound itself; its
+    share is printed per family beside ROOM, which is not asserted (as for §7g's walk)."""
+    worst = {}
+    for name, z, y, kw in ec.EDGE_DRAWN:
+        ref = ec.edge_reference(name)
+        walk = torch.from_numpy(ec.head_walk32(ref["zz"], ref["yy"])).double()
+        fin = torch.isfinite(ref["nll"])
+        assert torch.equal(torch.nan_to_num(walk[~fin], nan=1.0), torch.nan_to_num(ref["nll"][~fin], nan=1.0)), name
+        share = float(((walk - ref["nll"]).abs()[fin] / ref["bound"][fin]).max())
+        assert share <= 1.0, (name, share)
+        fam = ec.edge_family(name)
+        worst[fam] = max(worst.get(fam, (0.0, "")), (share, name))
+    for fam, (share, name) in worst.items():
+        print(f"[mutants] evaluate walk {fam}: the float32 walk uses {share:.3g} of the row bound at most ({name}); ROOM is {ROOM}")
 
 
 # ------------------------------------------------------------------------------------------------------ propagate_features
