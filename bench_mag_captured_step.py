@@ -2,13 +2,17 @@
 """bench_mag_captured_step.py -- a whole MAG training step, eager against captured, one JSON line.
 
 Not the driver's bench (that is bench.py = GFPush rows/s).  At bench_mag_rows.py's mag-train shape (V = 500 000, H = 64,
-B = 40, K = 32, S = 2, synthetic bags of mean 20, 2 000 000 nodes, input_droprate 0), three variants of one step (select a
+B = 40, K = 32, S = 2, synthetic bags of mean 20, 2 000 000 nodes, input_droprate 0), five variants of one step (select a
 batch -> emb_rows -> MagMLP -> loss -> backward -> clip + Adam over the table and the layers), alternated window by window in
 one process:
   eager           what the project offered before MagTrainStep: emb_rows + MagMLP + grand_plus_loss + ClipAdam.step() with
                   host numbers (a host seed, the host weight of model.py:329, ClipAdam's host step count); atomic dW
   replay-atomic   MagTrainStep(capture=True, deterministic=False): one graph replay per step, atomic dW
   replay-det      MagTrainStep(capture=True, deterministic=True): the same with the sort-then-gather dW of mag_det
+  replay-det-exact  replay-det with table_step="exact" (DESIGN §7t): the table stepped from the backward's row list, bit for
+                  bit replay-det's update, without the zero-fill of dW and its two dense reads
+  replay-det-lazy   replay-det with table_step="lazy": the touched rows of the table and its moments alone -- NOT the reference's
+                  dense Adam; the table sits in a parameter group of its own with weight_decay = 0, which lazy mode requires
 Every variant gets a fresh selection per step from the same pre-drawn list and uploads it the same way.
 Per variant: `<v>_us` wall clock per step (a window of --iters steps between two synchronisations, median [min, max] of
 --reps windows) and `<v>_host_us`, the host time per step to enqueue the same window.
@@ -39,7 +43,7 @@ from grand_plus_amd.step import step_weight  # noqa: E402
 S, P_NODE, TEM, C, N_L, N_U = 2, 0.5, 0.5, 8, 20, 20
 LAM, WARMUP, BASE_SEED, N_SELECTIONS = 1.0, 100, 0x5EED, 64
 ADAM = dict(lr=1e-2, weight_decay=5e-4, clip_norm=0.1)
-VARIANTS = ("eager", "replay-atomic", "replay-det")
+VARIANTS = ("eager", "replay-atomic", "replay-det", "replay-det-exact", "replay-det-lazy")
 
 
 def build(a, dev):
@@ -90,13 +94,18 @@ def variants(c, dev, only=None):
             opt.step()
 
         out["eager"] = eager
-    for key, det in (("replay-atomic", False), ("replay-det", True)):
+    for key, det, table_step in (("replay-atomic", False, None), ("replay-det", True, None), ("replay-det-exact", True, "exact"),
+                                 ("replay-det-lazy", True, "lazy")):
         if only not in (None, key):
             continue
         mm = make_model(c, dev)
-        ts = MagTrainStep(mm, ClipAdam(mag_trained_parameters(mm), capturable=True, state=StepState(dev), **ADAM), rm, *attrs,
+        params = mag_trained_parameters(mm)
+        if table_step == "lazy":                                    # lazy mode takes no weight decay on the table
+            params = [dict(params=params[:1], weight_decay=0.0), dict(params=params[1:])]
+        kw = {} if table_step is None else dict(table_step=table_step)
+        ts = MagTrainStep(mm, ClipAdam(params, capturable=True, state=StepState(dev), **ADAM), rm, *attrs,
                           c["labels"], c["idx_train"], c["idx_unlabel"], samples=S, dropnode_rate=P_NODE, lam=LAM, warmup=WARMUP,
-                          tem=TEM, kind="l2", seed=BASE_SEED, capture=True, deterministic=det)
+                          tem=TEM, kind="l2", seed=BASE_SEED, capture=True, deterministic=det, **kw)
         out[key] = lambda i, ts=ts: ts.step(*c["sels"][i % N_SELECTIONS])
         out[key].step = ts
     return out
@@ -140,7 +149,7 @@ def main():
     wall = {k: [] for k in v}
     host = {k: [] for k in v}
     for rep in range(a.reps):
-        for k, fn in v.items():                                     # alternated: a drift of the clocks reaches all three
+        for k, fn in v.items():                                     # alternated: a drift of the clocks reaches every variant
             w, h = window(fn, a.iters, 3 + rep * a.iters)
             wall[k].append(w)
             host[k].append(h)

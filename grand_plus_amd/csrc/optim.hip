@@ -17,9 +17,8 @@
 //                           (gp_clip_adam_step_dev), read once per thread before the same arithmetic.
 // A chunk whose four pointers are 16-byte aligned moves as float4; any other takes a scalar path with the same
 // per-element arithmetic (-ffp-contract=off: no fused multiply-add), so an element's result never depends on where it lies.
-#include "gp_common.hpp"
-
-#include <cmath>
+// AdamArgs, adam_element and the norm / coefficient out of the partials are optim_math.hpp's, shared with optim_rows.hip.
+#include "optim_math.hpp"
 
 namespace {
 
@@ -44,11 +43,6 @@ struct OptimTable {
 };
 
 static_assert(sizeof(OptimTable) <= 2048, "the table travels in the kernel arguments (4 KB)");
-
-struct AdamArgs {
-    float max_norm, beta1, beta2, one_minus_beta1, one_minus_beta2, eps, weight_decay, step_size, rsqrt_bc2;
-    int clip_only;
-};
 
 // the entry of chunk c: the first whose chunk_end exceeds c (entries of 0 elements are never found)
 __device__ __forceinline__ int entry_of(const OptimTable& tab, long long c)
@@ -95,14 +89,6 @@ __global__ __launch_bounds__(kBlock) void optim_sqnorm_kernel(const OptimTable t
         for (int i = gridDim.x + blockIdx.x * kBlock + tid; i < kSlots; i += gridDim.x * kBlock) partials[i] = 0.0;
 }
 
-__device__ __forceinline__ void adam_element(float& p, float g, float& m, float& v, float coef, const AdamArgs& a)
-{
-    g = g * coef + a.weight_decay * p;
-    m = a.beta1 * m + a.one_minus_beta1 * g;
-    v = a.beta2 * v + a.one_minus_beta2 * g * g;
-    p -= a.step_size * (m / (sqrtf(v) * a.rsqrt_bc2 + a.eps));
-}
-
 template <bool kDeviceSteps>
 __global__ __launch_bounds__(kBlock) void optim_clip_adam_kernel(const OptimTable tab, const double* __restrict__ partials,
                                                                   float* __restrict__ norm_out, long long n_chunks, const AdamArgs a_in,
@@ -113,14 +99,8 @@ __global__ __launch_bounds__(kBlock) void optim_clip_adam_kernel(const OptimTabl
     AdamArgs a = a_in;
     if (kDeviceSteps) { a.step_size = *d_step_size; a.rsqrt_bc2 = *d_rsqrt_bc2; }
     const int tid = threadIdx.x;
-    const double* q = partials + tid * 4;
-    const double sum = block_sum<kWaves>(((q[0] + q[1]) + q[2]) + q[3], lds);
-    const float norm = (float)sqrt(sum);
-    float coef = 1.0f;
-    if (a.max_norm > 0.0f) {
-        const float c = a.max_norm / (norm + 1e-6f);
-        coef = c >= 1.0f ? 1.0f : c;                          // torch.clamp(max=1): a NaN stays a NaN
-    }
+    float norm;
+    const float coef = clip_coef<kWaves>(partials, a.max_norm, lds, norm);
     if (norm_out && blockIdx.x == 0 && tid == 0) *norm_out = norm;
 
     for (long long c = blockIdx.x; c < n_chunks; c += gridDim.x) {

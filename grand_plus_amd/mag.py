@@ -70,7 +70,8 @@ class _MagRowsFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, weight, call, n_bad, det=None):
-        """det: None for the atomic backward, (max_entries, overflow) for the deterministic one (mag_det.backward_det)."""
+        """det: None for the atomic backward, (max_entries, overflow, row_grad) for the deterministic one
+        (mag_det.backward_det); with a row_grad the weight's gradient is None and dW goes to the RowGrad."""
         ctx.save_for_backward(*call.tensors)
         ctx.args = (weight.shape, call.scalars, det)
         return _forward(weight, call, n_bad)
@@ -88,7 +89,7 @@ class _MagRowsFn(torch.autograd.Function):
 
 def mag_prop_rows(weight, attr_indptr, attr_indices, attr_data, col, val, filled, K, batch_rows=None, *, samples=1,
                   dropnode_rate=0.5, input_droprate=0.0, training=True, seed=None, keep=None, validate=False, deterministic=None,
-                  max_entries=None, overflow=None):
+                  max_entries=None, overflow=None, row_grad=None):
     """The S augmented embeddings of a batch of resident rows, in one launch.
 
     weight [V, H] float32 (the `nn.Embedding` table); attr_indptr [N + 1] int64, attr_indices [nnz] int32, attr_data [nnz]
@@ -105,7 +106,12 @@ def mag_prop_rows(weight, attr_indptr, attr_indices, attr_data, col, val, filled
     raises RuntimeError.  It never reads the host: `overflow` (an int32 [1] tensor on weight's device; a private one
     that nobody reads when omitted) gets bit 0 set by the backward if the batch had more entries than `max_entries`, and
     the gradient then lacks the entries past it.  Input dropout (input_droprate > 0 while training) is not supported by that
-    backward: ValueError.  When the mode resolves to False `max_entries` is ignored."""
+    backward: ValueError.  When the mode resolves to False `max_entries` is ignored.
+    `row_grad`: an `optim_rows.RowGrad(weight)`.  The deterministic backward then writes dW into its persistent
+    buffer instead of a fresh `torch.zeros`, hands it the sorted key list and returns no gradient for `weight`
+    (`weight.grad` stays None): the table is stepped by `ClipAdam.set_row_grad`.  It needs the deterministic mode and
+    `max_entries` (ValueError with the atomic mode or without a capacity) and must be the RowGrad of this very `weight`
+    (TypeError / ValueError).  The forward is the same."""
     deterministic = _deterministic(deterministic)
     if max_entries is not None:
         from .mag_det import check_max_entries
@@ -115,6 +121,14 @@ def mag_prop_rows(weight, attr_indptr, attr_indices, attr_data, col, val, filled
     _check(weight, torch.float32, "weight")
     if weight.dim() != 2 or weight.shape[0] < 1 or weight.shape[1] < 1:
         raise TypeError("weight must be a 2-D [V, H] table")
+    if row_grad is not None:
+        from .optim_rows import RowGrad
+        if not isinstance(row_grad, RowGrad):
+            raise TypeError(f"row_grad must be an optim_rows.RowGrad, got {type(row_grad).__name__}")
+        if not deterministic or max_entries is None:
+            raise ValueError("row_grad needs the deterministic backward: deterministic=True (or torch's deterministic mode) and "
+                             "max_entries=; the atomic backward keeps no list of the rows it touched (DESIGN §9)")
+        row_grad.check_weight(weight)
     _check(attr_indptr, torch.int64, "attr_indptr")
     _check(attr_indices, torch.int32, "attr_indices")
     _check(attr_data, torch.float32, "attr_data")
@@ -157,7 +171,7 @@ def mag_prop_rows(weight, attr_indptr, attr_indices, attr_data, col, val, filled
             raise ValueError(f"the deterministic backward of mag_prop_rows takes fewer than 2**31 slots, got {B} x {K}")
         if overflow is not None:
             check_overflow(overflow, weight.device)
-        det = (max_entries, overflow if overflow is not None else torch.zeros(1, dtype=torch.int32, device=weight.device))
+        det = (max_entries, overflow if overflow is not None else torch.zeros(1, dtype=torch.int32, device=weight.device), row_grad)
     elif deterministic and wants_grad:
         raise RuntimeError("mag_prop_rows has no deterministic backward (fp32 atomics into dW); for a reproducible gradient use the "
                            "composed path with deterministic=True: flatten_rows -> embedding_bag_csr(nodes=..., deterministic=True) "

@@ -66,10 +66,12 @@ def check_overflow(overflow, device):
     return overflow
 
 
-def backward_det(weight_shape, grad_out, call, max_entries, overflow):
+def backward_det(weight_shape, grad_out, call, max_entries, overflow, row_grad=None):
     """dW [V, H] of mag_prop_rows by the order contract of mag_det_abi.hpp.  call: mag._Call, the forward's operands;
     overflow: int32 [1], bit 0 is set when the batch has more than max_entries entries (the gradient then lacks the rest).
-    Six launches, torch.sort between the third and the fourth; no host read."""
+    Six launches, torch.sort between the third and the fourth; no host read.
+    row_grad: an optim_rows.RowGrad.  The gather then writes the touched rows into `row_grad.values`, which
+    nobody zeroes, the RowGrad takes the sorted key list over, and None is returned in place of dW."""
     V, H = weight_shape
     attr_indptr, attr_indices, attr_data, col, val, filled, batch_rows, keep = call.tensors
     S_rows, K, B, S, p_node, p_in, training, seed = call.scalars
@@ -79,9 +81,12 @@ def backward_det(weight_shape, grad_out, call, max_entries, overflow):
         raise ValueError(f"the deterministic backward of mag_prop_rows takes fewer than 2**31 slots, got {B} x {K}")
     g = grad_out.contiguous()
     dev = g.device
-    dW = torch.zeros((V, H), dtype=torch.float32, device=dev)
+    dW = torch.zeros((V, H), dtype=torch.float32, device=dev) if row_grad is None else row_grad.values
     if B == 0:
-        return dW
+        if row_grad is None:
+            return dW
+        row_grad.fill(torch.full((1,), V, dtype=torch.int64, device=dev))       # the sentinel alone: no row is touched
+        return None
     slot_base = torch.empty(B * K + 1, dtype=torch.int64, device=dev)
     keys = torch.empty(max_entries, dtype=torch.int64, device=dev)
     L = lib()
@@ -96,4 +101,7 @@ def backward_det(weight_shape, grad_out, call, max_entries, overflow):
                                          sorted_keys.data_ptr(), max_entries, U.data_ptr(), inv.data_ptr(), dW.data_ptr(),
                                          _stream(g))
     _native.raise_for_status(rc)
-    return dW
+    if row_grad is None:
+        return dW
+    row_grad.fill(sorted_keys)
+    return None

@@ -12,6 +12,11 @@ host for a number, so the whole step is captured and a replay is bitwise the eag
 `max_entries` entries per batch row and slot: None means K * Lmax per batch row, Lmax the longest bag among the nodes that
 occur as columns of `rows` (read once here, the constructor's one host read), and then the buffer cannot overflow.
 
+`table_step="exact"` or `"lazy"` (deterministic mode only) steps the embedding table from the backward's row list
+instead of a dense gradient: no `torch.zeros` of [V, H] per step, no dense read of dW.  "exact" is bit for bit today's
+step.  "lazy" updates the touched rows alone and is NOT the reference's dense Adam (model_mag.py:312), under which an
+untouched row still moves while its moments decay.
+
 Left out: input dropout (`model.input_droprate` must be 0), `fit` for MAG, several steps in one graph.
 """
 from __future__ import annotations
@@ -49,11 +54,19 @@ class MagTrainStep(TrainStep):
     shape, which cannot overflow.  A tighter value may: the step then runs on with a gradient that lacks the entries past
     it and sets a flag, which `check_entries_flag()` reads.
 
+    table_step: None is the dense table gradient and the dense clip + Adam pass over it.  "exact" / "lazy" need the
+    deterministic mode (ValueError otherwise): one optim_rows.RowGrad, shared by every graph of the step, receives the
+    backward's rows and `optimizer.set_row_grad(weight, row_grad, table_step)` steps the table from them; `weight.grad` stays
+    None.  "exact": every parameter, Adam tensor and loss is bit for bit what None gives (with clipping on, up to the
+    rounding of the norm, whose partial sums are cut differently).  "lazy": only the touched rows of the table and of its
+    moments change -- NOT the reference's trajectory (dense Adam moves an untouched row while its moments decay); the table's
+    group must have weight_decay = 0.
+
     With capture=True and the deterministic mode the capture includes `torch.sort`; should a torch build refuse to capture it,
     the capture fails as every broken capture does here: a RuntimeError naming the call (backward), no retry, no fallback."""
 
     def __init__(self, model, optimizer, rows, attr_indptr, attr_indices, attr_data, labels, idx_train, idx_unlabel, *, samples,
-                 dropnode_rate, lam, warmup, tem, conf=None, kind="l2", seed, capture=True, deterministic=None, max_entries=None):
+                 dropnode_rate, lam, warmup, tem, conf=None, kind="l2", seed, capture=True, deterministic=None, max_entries=None, table_step=None):
         from .mlp import MagMLP
         if not isinstance(model, MagMLP):
             raise ValueError("MagTrainStep takes a MagMLP (a GrandPlusMLP goes to step.TrainStep)")
@@ -71,6 +84,12 @@ class MagTrainStep(TrainStep):
         if max_entries is not None:
             from .mag_det import check_max_entries
             check_max_entries(max_entries)
+        if table_step is not None:
+            from .optim_rows import check_mode
+            check_mode(table_step)
+            if not self.deterministic:
+                raise ValueError(f"table_step={table_step!r} needs the deterministic table gradient: deterministic=True (the atomic "
+                                 "backward keeps no list of the rows it touched, DESIGN §9)")
         if not attr_indptr.is_cuda:
             raise ValueError("the step runs on the GPU only: the attribute CSR must be CUDA tensors (no CPU fallback)")
         dev = attr_indptr.device
@@ -85,6 +104,11 @@ class MagTrainStep(TrainStep):
         self._setup(model, optimizer, rows, labels, idx_train, idx_unlabel, dev, samples=samples, dropnode_rate=dropnode_rate,
                     lam=lam, warmup=warmup, tem=tem, conf=conf, kind=kind, seed=seed, capture=capture)
         self._entries_flag = torch.zeros(1, dtype=torch.int32, device=dev)   # bit 0: a backward had more entries than its buffer
+        self.table_step, self.row_grad = table_step, None
+        if table_step is not None:                                   # one RowGrad for every graph of the step
+            from .optim_rows import RowGrad
+            self.row_grad = RowGrad(model.embeds.weight)
+            optimizer.set_row_grad(model.embeds.weight, self.row_grad, table_step)
         # the longest bag among the nodes that occur as columns of rows: the one host read, and only here
         lens = attr_indptr[1:] - attr_indptr[:-1]
         cols = rows.col.long()
@@ -101,7 +125,8 @@ class MagTrainStep(TrainStep):
         S = self.samples
         X = self.model.emb_rows(*self.attr, self.rows, batch_rows=batch_rows, samples=S, dropnode_rate=self.dropnode_rate, seed=0,
                                 keep=self._node_keep, deterministic=self.deterministic,
-                                max_entries=self._max_entries(batch_rows.numel()), overflow=self._entries_flag)
+                                max_entries=self._max_entries(batch_rows.numel()), overflow=self._entries_flag,
+                                row_grad=self.row_grad)
         return X[None] if S == 1 else X
 
     def check_entries_flag(self):

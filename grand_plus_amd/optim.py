@@ -20,6 +20,7 @@ import torch
 
 from . import _native
 from ._common import _stream
+from .optim_rows import RowGrad, check_mode, clip_adam_rows, sqnorm
 
 __all__ = ["ClipAdam", "clip_grad_norm"]
 
@@ -117,6 +118,9 @@ class ClipAdam(torch.optim.Optimizer):
     for more than 8 parameter groups.  `state_dict()` reports `step` as the number torch.optim.Adam would hold (one host
     read of `tick`); `load_state_dict()` sets `tick` from it.  `lr` and the betas are read when the state advances: under a
     captured graph they are the values of the capture.
+
+    `set_row_grad(param, row_grad, mode)` steps one [V, H] embedding table from a row list instead of a dense
+    `.grad`: see there.  mode "lazy" is NOT the reference's dense Adam.
     """
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, clip_norm=0.0, *,
@@ -136,7 +140,33 @@ class ClipAdam(torch.optim.Optimizer):
         # torch.optim.Adam's own constructor checks the ranges (its messages) and names the keys of a parameter group
         probe = torch.optim.Adam([torch.nn.Parameter(torch.empty(0))], lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
         self.clip_norm = float(clip_norm)
+        self._row_grads = {}                                         # parameter -> (RowGrad, mode): set_row_grad
         super().__init__(params, dict(probe.defaults))
+
+    def set_row_grad(self, param, row_grad, mode):
+        """Steps `param`, a [V, H] embedding table of this optimiser, from `row_grad` (an optim_rows.RowGrad(param), filled by
+        the deterministic backward of `mag_prop_rows(..., row_grad=row_grad)`) instead of `param.grad`, which stays None.
+        The parameter counts as having a gradient: the one norm of `step()` includes its touched rows, and its state
+        (`step`, dense `exp_avg` and `exp_avg_sq`) and checkpoints are torch.optim.Adam's, unchanged.
+
+        mode "exact": every element gets the update the dense path gives it, bit for bit; an untouched row takes g = 0.0f.
+        mode "lazy": only the touched rows of the parameter and of its moments are read and written; every other row keeps
+        its bits.  This is NOT the reference's trajectory: under dense torch.optim.Adam (model_mag.py:312) an untouched row
+        still moves while its moments decay.  The group's weight_decay must be 0 in this mode (ValueError, here and in
+        `step()`): a decay applied to the touched rows alone is nobody's semantics.
+
+        A `step()` before any backward has filled the RowGrad is a RuntimeError."""
+        if not isinstance(row_grad, RowGrad):
+            raise TypeError(f"row_grad must be an optim_rows.RowGrad, got {type(row_grad).__name__}")
+        check_mode(mode)
+        group = next((g for g in self.param_groups if any(p is param for p in g["params"])), None)
+        if group is None:
+            raise ValueError("set_row_grad: param is not a parameter of this optimiser")
+        row_grad.check_weight(param)
+        if mode == "lazy" and float(group["weight_decay"]) != 0.0:
+            raise ValueError(f"mode 'lazy' takes weight_decay = 0, the parameter's group has {group['weight_decay']}: a decay "
+                             "applied to the touched rows alone is nobody's semantics")
+        self._row_grads[param] = (row_grad, mode)
 
     def load_state_dict(self, state_dict):
         if self.capturable:
@@ -168,6 +198,7 @@ class ClipAdam(torch.optim.Optimizer):
             with torch.enable_grad():
                 closure()
         todo, calls, dev = [], {}, None                              # calls: (group index, step count) -> entries
+        rows = []                                                    # (group index, parameter, RowGrad, mode): set_row_grad
         if self.capturable:
             self._check_capturable()
         for gi, group in enumerate(self.param_groups):
@@ -175,7 +206,17 @@ class ClipAdam(torch.optim.Optimizer):
                 raise ValueError("ClipAdam does not implement amsgrad, maximize or decoupled_weight_decay")
             for p in group["params"]:
                 g = p.grad
-                if g is None:
+                rg, mode = self._row_grads.get(p, (None, None))
+                if rg is not None:                                   # the gradient is the RowGrad's rows
+                    if g is not None:
+                        raise ValueError("a parameter with a row gradient (set_row_grad) also has a dense .grad")
+                    if mode == "lazy" and float(group["weight_decay"]) != 0.0:
+                        raise ValueError(f"mode 'lazy' takes weight_decay = 0, the parameter's group has {group['weight_decay']}")
+                    if not rg.filled():
+                        raise RuntimeError("ClipAdam.step(): no backward has filled the parameter's RowGrad yet (run the "
+                                           "deterministic backward of mag_prop_rows(..., row_grad=...) first)")
+                    g = rg.values
+                elif g is None:
                     continue
                 _check_tensor(g, "a gradient")
                 _check_tensor(p, "a parameter")
@@ -189,32 +230,77 @@ class ClipAdam(torch.optim.Optimizer):
                     _check_tensor(s, key)
                     if s.device != dev or s.shape != p.shape:
                         raise TypeError(f"{key} must have its parameter's device and shape, got {tuple(s.shape)} on {s.device}")
-                todo.append((gi, p, g))
+                if rg is not None:
+                    rows.append((gi, p, rg, mode))
+                else:
+                    todo.append((gi, p, g))
         if self.capturable:
-            return self._step_capturable(todo, dev)
+            return self._step_capturable(todo, dev, rows)
+        row_calls = []
+        for gi, p, rg, mode in rows:
+            state = self._init_state(p)
+            state["step"] = self._number(state["step"]) + 1
+            row_calls.append((gi, state["step"], p, rg, mode))
         for gi, p, g in todo:                                        # every check has passed: now the state may change
-            state = self.state[p]
-            if len(state) == 0:
-                state["step"] = 0
-                state["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-                state["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+            state = self._init_state(p)
             t = state["step"] = self._number(state["step"]) + 1
             calls.setdefault((gi, t), []).append((p, g, state["exp_avg"], state["exp_avg_sq"]))
         if dev is None:
             return _no_gradients([p for group in self.param_groups for p in group["params"]])
         ws, norm = _buffers(dev)
-        like = next(iter(calls.values()))[0][0]
-        flags = 0
-        if len(calls) > 1:                                           # one norm over everything, then an update per group
-            _call(dev, like, [e for entries in calls.values() for e in entries], _native.GP_OPTIM_NORM_ONLY, ws, norm)
-            flags = _native.GP_OPTIM_NORM_READY
+        like = next(iter(calls.values()))[0][0] if calls else row_calls[0][2]
+        flags = self._norm_first(dev, like, calls, [rg for _, _, _, rg, _ in row_calls], ws, norm)
         for (gi, t), entries in calls.items():
             group = self.param_groups[gi]
             lr, (beta1, beta2) = float(group["lr"]), group["betas"]
             _call(dev, like, entries, flags, ws, norm, max_norm=self.clip_norm, lr=lr, betas=(float(beta1), float(beta2)),
                   eps=float(group["eps"]), weight_decay=float(group["weight_decay"]),
                   step_size=lr / (1.0 - beta1 ** t), rsqrt_bc2=1.0 / math.sqrt(1.0 - beta2 ** t))
+        for gi, t, p, rg, mode in row_calls:
+            group = self.param_groups[gi]
+            lr, (beta1, beta2) = float(group["lr"]), group["betas"]
+            self._rows_update(gi, p, rg, mode, ws, norm, step_size=lr / (1.0 - beta1 ** t),
+                              rsqrt_bc2=1.0 / math.sqrt(1.0 - beta2 ** t))
         return norm
+
+    def _init_state(self, p):
+        """The Adam state of p, created on its first step as torch.optim.Adam creates it (a capturable optimiser leaves `step`
+        at what a checkpoint brought: its count is the state's tick)."""
+        state = self.state[p]
+        if len(state) == 0:
+            state["step"] = 0
+            state["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+            state["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+        return state
+
+    def _rows_update(self, gi, p, rg, mode, ws, norm, **corrections):
+        """The table's update from its RowGrad with the hyper-parameters of group gi; corrections: step_size and rsqrt_bc2 as
+        numbers, or d_step_size and d_rsqrt_bc2 as device addresses."""
+        group = self.param_groups[gi]
+        beta1, beta2 = group["betas"]
+        clip_adam_rows(rg, mode, self.state[p]["exp_avg"], self.state[p]["exp_avg_sq"], ws, norm, max_norm=self.clip_norm,
+                       lr=float(group["lr"]), betas=(float(beta1), float(beta2)), eps=float(group["eps"]),
+                       weight_decay=float(group["weight_decay"]), **corrections)
+
+    @staticmethod
+    def _norm_first(dev, like, calls, row_grads, ws, norm):
+        """The norm launches that come before the updates, and the flags of the dense updates after them.  Without a row
+        gradient: today's sequence (one norm-only launch when several calls share the norm).  With one: the dense
+        gradients' norm-only launch, if there is any dense gradient, then every RowGrad's rows added into the same
+        workspace; the updates then find the norm ready."""
+        if not row_grads:
+            if len(calls) > 1:                                       # one norm over everything, then an update per group
+                _call(dev, like, [e for entries in calls.values() for e in entries], _native.GP_OPTIM_NORM_ONLY, ws, norm)
+                return _native.GP_OPTIM_NORM_READY
+            return 0
+        first = True
+        if calls:
+            _call(dev, like, [e for entries in calls.values() for e in entries], _native.GP_OPTIM_NORM_ONLY, ws, norm)
+            first = False
+        for rg in row_grads:
+            sqnorm(rg, not first, ws)
+            first = False
+        return _native.GP_OPTIM_NORM_READY
 
     def _check_capturable(self):
         """What one device-resident step count cannot serve: ValueError before anything is launched or any state changes."""
@@ -224,37 +310,35 @@ class ClipAdam(torch.optim.Optimizer):
         steps = set()
         for group in self.param_groups:
             for p in group["params"]:
-                if p.grad is None:
+                if p.grad is None and p not in self._row_grads:
                     raise ValueError("ClipAdam(capturable=True) steps every parameter with one step count: a parameter has no "
                                      "gradient (give the optimiser only the parameters that are trained)")
                 steps.add(self._number((self.state.get(p) or {}).get("step", 0)))
         if len(steps) > 1:
             raise ValueError(f"ClipAdam(capturable=True) keeps one step count for all parameters: the loaded values are {sorted(steps)}")
 
-    def _step_capturable(self, todo, dev):
+    def _step_capturable(self, todo, dev, rows=()):
         """The launches of step() with the bias corrections of group gi read from the optimiser's gp_step_state."""
         calls = {}
+        for _gi, p, _rg, _mode in rows:
+            self._init_state(p)
         for gi, p, g in todo:
-            state = self.state[p]
-            if len(state) == 0:
-                state["step"] = 0                                    # the count itself is the state's tick
-                state["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-                state["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+            state = self._init_state(p)
             calls.setdefault(gi, []).append((p, g, state["exp_avg"], state["exp_avg_sq"]))
         if dev is None:
             return _no_gradients([p for group in self.param_groups for p in group["params"]])
         if self.step_state.device != dev:
             raise TypeError(f"the StepState is on {self.step_state.device}, the parameters on {dev}")
         ws, norm = _buffers(dev)
-        like = next(iter(calls.values()))[0][0]
-        flags = 0
-        if len(calls) > 1:
-            _call(dev, like, [e for entries in calls.values() for e in entries], _native.GP_OPTIM_NORM_ONLY, ws, norm)
-            flags = _native.GP_OPTIM_NORM_READY
+        like = next(iter(calls.values()))[0][0] if calls else rows[0][1]
+        flags = self._norm_first(dev, like, calls, [rg for _, _, rg, _ in rows], ws, norm)
         for gi, entries in calls.items():
             group = self.param_groups[gi]
             beta1, beta2 = group["betas"]
             d_step_size, d_rsqrt_bc2 = self.step_state.correction_ptrs(gi)
             _call_dev(dev, like, entries, flags, ws, norm, d_step_size, d_rsqrt_bc2, max_norm=self.clip_norm, lr=float(group["lr"]),
                       betas=(float(beta1), float(beta2)), eps=float(group["eps"]), weight_decay=float(group["weight_decay"]))
+        for gi, p, rg, mode in rows:
+            d_step_size, d_rsqrt_bc2 = self.step_state.correction_ptrs(gi)
+            self._rows_update(gi, p, rg, mode, ws, norm, d_step_size=d_step_size, d_rsqrt_bc2=d_rsqrt_bc2)
         return norm

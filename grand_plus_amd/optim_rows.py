@@ -1,0 +1,132 @@
+"""The embedding table's gradient as a row list, and the clip + Adam step over it: the binding of
+csrc/optim_rows_abi.hpp and `RowGrad`, the object that carries the touched rows from MAG's deterministic backward to
+`ClipAdam`.
+
+A MAG batch touches a small part of the [V, H] table, and the deterministic backward (mag_det.py, §7o) knows which: it
+holds the sorted key list, and its gather writes every touched row of dW exactly once.  Handed a `RowGrad`, that backward
+writes dW into the RowGrad's persistent buffer -- never zeroed, never read outside the touched rows -- hands over the key
+list, and gives the weight no `.grad`.  `ClipAdam.set_row_grad(param, row_grad, mode)` then steps the table from it:
+
+  * mode "exact": every element of the table gets the update the dense path gives it, bit for bit (an untouched row takes
+    g = 0.0f through the same expression).  What is saved is the zero-fill of dW and its two dense reads.
+  * mode "lazy": only the touched rows of the parameter, `exp_avg` and `exp_avg_sq` are read and written; every other
+    row keeps its bits.  THIS IS NOT THE REFERENCE'S TRAJECTORY: model_mag.py:312 uses dense torch.optim.Adam, under
+    which an untouched row still moves while its moments decay.  weight_decay must be 0 in this mode.
+
+The entry points are extern "C" symbols of libgrandplus.so declared in csrc/optim_rows_abi.hpp; they are not part of
+C ABI 4, so their binding (ABI below) lives here and not in `_native`, as mag_det's does.
+
+Left out: a row list for the atomic backward, amsgrad, lazy mode with weight decay.
+"""
+from __future__ import annotations
+
+import ctypes
+
+import torch
+
+from . import _native
+from ._common import _stream
+
+__all__ = ["RowGrad", "MODES", "check_mode"]
+
+# name -> (restype, argtypes), under the convention stated above _native.ABI; tests/test_host_optim_rows.py holds it against
+# optim_rows_abi.hpp.
+_int, _i32, _i64, _f, _d, _vp = ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_double, ctypes.c_void_p
+_table = [_int, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _int, _f, _f, _d, _d, _f, _f]   # device .. weight_decay
+ABI = {
+    "gp_optim_rows_sqnorm": (_int, [_int, _vp, _i64, _i64, _i32, _vp, _int, _vp, _vp]),
+    "gp_clip_adam_rows": (_int, _table + [_f, _f, _vp, _vp, _vp]),
+    "gp_clip_adam_rows_dev": (_int, _table + [_vp, _vp, _vp, _vp, _vp]),
+}
+MODES = {"exact": 1, "lazy": 2}           # GP_OPTIM_ROWS_EXACT, GP_OPTIM_ROWS_LAZY
+_BOUND = False
+
+
+def lib():
+    """_native.lib() with the entry points of optim_rows_abi.hpp declared on it.  A library without them is an error, not
+    a fallback."""
+    global _BOUND
+    L = _native.lib()
+    if not _BOUND:
+        for name, (restype, argtypes) in ABI.items():
+            if not hasattr(L, name):
+                raise RuntimeError(f"{_native.LIB_PATH} does not export {name} (an older build?): rebuild the library")
+            f = getattr(L, name)
+            f.restype, f.argtypes = restype, argtypes
+        _BOUND = True
+    return L
+
+
+def check_mode(mode):
+    """`mode` as "exact" or "lazy" (ValueError otherwise)."""
+    if not isinstance(mode, str) or mode not in MODES:
+        raise ValueError(f"the table step's mode must be 'exact' or 'lazy', got {mode!r}")
+    return mode
+
+
+class RowGrad:
+    """The gradient of one [V, H] embedding table as (values, keys): `values` is a persistent float32 [V, H] buffer on the
+    parameter's device that is never zeroed; after a deterministic backward of `mag_prop_rows(..., row_grad=this)`, `keys`
+    is that backward's sorted key list (int64 [n_sorted], ascending, sentinel V in the tail) and the rows of `values`
+    that occur in it hold the batch's dW.  Every other row of `values` holds anything at all and is never read.
+
+    `keys` and `n_sorted` are set when Python runs the backward: in an eager step, and once when a graph is captured.  A
+    captured graph carries its own key tensor and its own length in its launches, so replays are right whatever these
+    attributes say; but with several graphs over one RowGrad (`MagTrainStep.step_sampled`, a graph per batch shape, each
+    with its own `max_entries`) they describe the graph captured LAST, not the one replayed last.  Read them after a
+    replay only when the step has one graph; `values` is the one buffer of every graph.
+
+    param: the table, a contiguous float32 CUDA [V, H] tensor (TypeError / ValueError otherwise; no CPU fallback)."""
+
+    def __init__(self, param):
+        if not isinstance(param, torch.Tensor) or param.is_sparse or param.dtype != torch.float32 or not param.is_contiguous():
+            raise TypeError("RowGrad takes a dense contiguous float32 table")
+        if param.dim() != 2 or param.shape[0] < 1 or param.shape[1] < 1:
+            raise ValueError(f"RowGrad takes a 2-D [V, H] table, got shape {tuple(param.shape)}")
+        if not param.is_cuda:
+            raise TypeError("RowGrad takes a CUDA table: the row-list step runs on the GPU only (no CPU fallback)")
+        self.param = param
+        self.shape = tuple(param.shape)
+        self.device = param.device
+        self.values = torch.empty(self.shape, dtype=torch.float32, device=param.device)
+        self.keys = None
+        self.n_sorted = 0
+
+    def check_weight(self, weight):
+        """Refuses a weight that is not this RowGrad's table (before any device call)."""
+        if weight is not self.param:
+            raise ValueError("row_grad was made for another tensor: RowGrad(param) takes the weight itself")
+        if tuple(weight.shape) != self.shape or weight.device != self.device:
+            raise ValueError(f"row_grad holds a {self.shape} table on {self.device}, the weight is {tuple(weight.shape)} on "
+                             f"{weight.device}")
+
+    def fill(self, sorted_keys):
+        """What the backward calls once `values` holds the batch's rows: takes the key list over."""
+        self.keys = sorted_keys
+        self.n_sorted = sorted_keys.numel()
+
+    def filled(self):
+        return self.keys is not None
+
+
+def sqnorm(rg, accumulate, ws):
+    """gp_optim_rows_sqnorm of a filled RowGrad into the workspace `ws`, on the current stream."""
+    V, H = rg.shape
+    rc = lib().gp_optim_rows_sqnorm(rg.device.index, rg.keys.data_ptr(), rg.n_sorted, V, H, rg.values.data_ptr(),
+                                    int(bool(accumulate)), ws.data_ptr(), _stream(rg.values))
+    _native.raise_for_status(rc)
+
+
+def clip_adam_rows(rg, mode, exp_avg, exp_avg_sq, ws, norm, *, max_norm, lr, betas, eps, weight_decay, step_size=None,
+                   rsqrt_bc2=None, d_step_size=None, d_rsqrt_bc2=None):
+    """gp_clip_adam_rows (step_size, rsqrt_bc2 as numbers) or gp_clip_adam_rows_dev (their device addresses) of a filled
+    RowGrad: the workspace holds the norm's partials."""
+    V, H = rg.shape
+    head = (rg.device.index, rg.param.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), rg.values.data_ptr(),
+            rg.keys.data_ptr(), rg.n_sorted, V, H, MODES[mode], max_norm, lr, betas[0], betas[1], eps, weight_decay)
+    tail = (ws.data_ptr(), norm.data_ptr(), _stream(rg.values))
+    if d_step_size is None:
+        rc = lib().gp_clip_adam_rows(*head, step_size, rsqrt_bc2, *tail)
+    else:
+        rc = lib().gp_clip_adam_rows_dev(*head, d_step_size, d_rsqrt_bc2, *tail)
+    _native.raise_for_status(rc)
