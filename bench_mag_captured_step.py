@@ -2,7 +2,7 @@
 """bench_mag_captured_step.py -- a whole MAG training step, eager against captured, one JSON line.
 
 Not the driver's bench (that is bench.py = GFPush rows/s).  At bench_mag_rows.py's mag-train shape (V = 500 000, H = 64,
-B = 40, K = 32, S = 2, synthetic bags of mean 20, 2 000 000 nodes, input_droprate 0), five variants of one step (select a
+B = 40, K = 32, S = 2, synthetic bags of mean 20, 2 000 000 nodes, input_droprate 0), seven variants of one step (select a
 batch -> emb_rows -> MagMLP -> loss -> backward -> clip + Adam over the table and the layers), alternated window by window in
 one process:
   eager           what the project offered before MagTrainStep: emb_rows + MagMLP + grand_plus_loss + ClipAdam.step() with
@@ -13,6 +13,8 @@ one process:
                   bit replay-det's update, without the zero-fill of dW and its two dense reads
   replay-det-lazy   replay-det with table_step="lazy": the touched rows of the table and its moments alone -- NOT the reference's
                   dense Adam; the table sits in a parameter group of its own with weight_decay = 0, which lazy mode requires
+  replay-atomic-exact, replay-atomic-lazy   replay-atomic with row_list="bitmap"  and the same two table steps:
+                  the rows are listed from a bitmap, no sort and no gather, and dW is zeroed on the listed rows alone
 Every variant gets a fresh selection per step from the same pre-drawn list and uploads it the same way.
 Per variant: `<v>_us` wall clock per step (a window of --iters steps between two synchronisations, median [min, max] of
 --reps windows) and `<v>_host_us`, the host time per step to enqueue the same window.
@@ -43,7 +45,7 @@ from grand_plus_amd.step import step_weight  # noqa: E402
 S, P_NODE, TEM, C, N_L, N_U = 2, 0.5, 0.5, 8, 20, 20
 LAM, WARMUP, BASE_SEED, N_SELECTIONS = 1.0, 100, 0x5EED, 64
 ADAM = dict(lr=1e-2, weight_decay=5e-4, clip_norm=0.1)
-VARIANTS = ("eager", "replay-atomic", "replay-det", "replay-det-exact", "replay-det-lazy")
+VARIANTS = ("eager", "replay-atomic", "replay-det", "replay-det-exact", "replay-det-lazy", "replay-atomic-exact", "replay-atomic-lazy")
 
 
 def build(a, dev):
@@ -95,7 +97,8 @@ def variants(c, dev, only=None):
 
         out["eager"] = eager
     for key, det, table_step in (("replay-atomic", False, None), ("replay-det", True, None), ("replay-det-exact", True, "exact"),
-                                 ("replay-det-lazy", True, "lazy")):
+                                 ("replay-det-lazy", True, "lazy"), ("replay-atomic-exact", False, "exact"),
+                                 ("replay-atomic-lazy", False, "lazy")):
         if only not in (None, key):
             continue
         mm = make_model(c, dev)
@@ -103,6 +106,8 @@ def variants(c, dev, only=None):
         if table_step == "lazy":                                    # lazy mode takes no weight decay on the table
             params = [dict(params=params[:1], weight_decay=0.0), dict(params=params[1:])]
         kw = {} if table_step is None else dict(table_step=table_step)
+        if table_step is not None and not det:                      # the atomic backward's row list
+            kw["row_list"] = "bitmap"
         ts = MagTrainStep(mm, ClipAdam(params, capturable=True, state=StepState(dev), **ADAM), rm, *attrs,
                           c["labels"], c["idx_train"], c["idx_unlabel"], samples=S, dropnode_rate=P_NODE, lam=LAM, warmup=WARMUP,
                           tem=TEM, kind="l2", seed=BASE_SEED, capture=True, deterministic=det, **kw)
@@ -154,7 +159,9 @@ def main():
             wall[k].append(w)
             host[k].append(h)
     det = v["replay-det"].step
-    det.check_entries_flag()
+    for k in v:
+        if k != "eager":
+            v[k].step.check_entries_flag()
     rec = {"case": "mag-train-step", "S": S, "B": N_L + N_U, "K": a.K, "H": a.hidden, "C": C, "assumed_vocab": a.vocab,
            "assumed_bag_mean": a.bag, "assumed_nodes": a.nodes, "longest_bag": det.longest_bag,
            "max_entries": det._max_entries(N_L + N_U), "table_bytes": 4 * a.vocab * a.hidden, "iters": a.iters, "reps": a.reps}

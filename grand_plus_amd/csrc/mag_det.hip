@@ -24,24 +24,7 @@ namespace {
 constexpr int kBlock = 256;           // the length and key kernels
 constexpr int kScan = 1024;           // the scan: one workgroup
 
-// what finds a slot's node: the attribute CSR's row pointers, the resident rows and the batch
-struct SlotArgs {
-    const long long* indptr; const int* indices; long long N, V;
-    const int* col; const int* filled; long long n_rows; int K;
-    const int* batch_rows;
-};
-
-// whether slot e = b * K + k exists (mag_det_abi.hpp), and its node
-__device__ __forceinline__ bool slot_node(const SlotArgs& A, long long e, long long& node)
-{
-    const long long b = e / A.K;
-    const int k = (int)(e - b * A.K);
-    const long long row = A.batch_rows ? (long long)A.batch_rows[b] : b;
-    node = 0;
-    if (row < 0 || row >= A.n_rows || k >= row_len(A.filled, row, A.K)) return false;
-    node = A.col[row * (long long)A.K + k];
-    return node >= 0 && node < A.N;
-}
+// SlotArgs and slot_node -- what finds a slot's node -- are mag_stage.hpp's: row_mark.hip (§7u) enumerates the same slots.
 
 // ---- 1. slot_base[e] = len_e
 __global__ void __launch_bounds__(kBlock)

@@ -1,8 +1,8 @@
 // mag_stage.hpp -- what MAG's kernels share besides dropnode.hpp: the operands of a call (MagArgs), the staging of one
 // resident row's columns and DropNode weights in LDS, the workgroup shape and the entry points' argument check.
 // mag_prop.hip (§7k: the forward and the atomic backward) and mag_det.hip (§7o: the deterministic backward) call these
-// lines, so a slot is present, weighted and masked in the backward exactly as the forward had it.  Everything has
-// internal linkage, as in gp_common.hpp.
+// lines, so a slot is present, weighted and masked in the backward exactly as the forward had it; row_mark.hip (§7u)
+// finds a slot's node by mag_det.hip's rule.  Everything has internal linkage, as in gp_common.hpp.
 #pragma once
 
 #include "dropnode.hpp"
@@ -21,6 +21,26 @@ struct MagArgs {
     float p_node, p_in; int training; u64 seed;
     const unsigned char* keep; long long keep_stride;
 };
+
+// what finds a slot's node without the weights: the attribute CSR's row pointers, the resident rows and the batch
+// (mag_det.hip's key kernels and gather, row_mark.hip's mark kernel)
+struct SlotArgs {
+    const long long* indptr; const int* indices; long long N, V;
+    const int* col; const int* filled; long long n_rows; int K;
+    const int* batch_rows;
+};
+
+// whether slot e = b * K + k exists (mag_det_abi.hpp), and its node
+__device__ __forceinline__ bool slot_node(const SlotArgs& A, long long e, long long& node)
+{
+    const long long b = e / A.K;
+    const int k = (int)(e - b * A.K);
+    const long long row = A.batch_rows ? (long long)A.batch_rows[b] : b;
+    node = 0;
+    if (row < 0 || row >= A.n_rows || k >= row_len(A.filled, row, A.K)) return false;
+    node = A.col[row * (long long)A.K + k];
+    return node >= 0 && node < A.N;
+}
 
 // Stage the row's columns (first chunk) and the weights of samples s0 .. s0 + ns - 1; a column outside [0, N) makes
 // the slot absent (weight 0).  Called by every thread, between two barriers of the caller.

@@ -18,6 +18,10 @@ torch's deterministic mode) takes it -- keys, `torch.sort(stable=True)`, a seque
 same bits run to run.  Without `max_entries` such a call still raises and names the composed path.  With `max_entries` and
 the mode resolving to non-deterministic the atomic backward runs and `max_entries` is ignored, so a caller may pass it always
 and let torch's flag decide.  The forward is the same in every mode.  There is no CPU fallback.
+
+Either backward can hand the table's gradient to the optimiser as a row list instead of a dense tensor (`row_grad=`): the
+deterministic one its sorted keys (an `optim_rows.RowGrad`), the atomic one the rows it marked in a bitmap (an
+`optim_rows.BitmapRowGrad`).
 """
 from __future__ import annotations
 
@@ -65,13 +69,33 @@ def _backward(weight_shape, grad_out, call):
     return dW
 
 
+def _backward_rows(weight_shape, grad_out, call, capacity, overflow, row_grad):
+    """The atomic backward into a BitmapRowGrad: mark the rows the batch can touch, compact them into a list of
+    `capacity` keys, zero those rows of `row_grad.values`, then the atomic launch of `_backward` into that buffer.  Five
+    launches, no `torch.zeros` of [V, H], no host read.  Bit 0 of `overflow` is set when the batch marked more rows than
+    `capacity`; the adds into the rows past it land in memory nobody reads."""
+    from .optim_rows import mark_and_list
+    V, H = weight_shape
+    g = grad_out.contiguous()
+    if call.scalars[2] == 0:
+        row_grad.fill(torch.full((1,), V, dtype=torch.int64, device=g.device))   # the sentinel alone: no row is touched
+        return None
+    keys = mark_and_list(row_grad, call, capacity, overflow)
+    rc = _native.lib().gp_mag_prop_rows_backward(_dev_index(g), g.data_ptr(), V, H, *call.args(), row_grad.values.data_ptr(),
+                                                 _stream(g))
+    _native.raise_for_status(rc)
+    row_grad.fill(keys)
+    return None
+
+
 class _MagRowsFn(torch.autograd.Function):
     """mag_prop_rows with the gradient to weight (summed over the samples)."""
 
     @staticmethod
     def forward(ctx, weight, call, n_bad, det=None):
         """det: None for the atomic backward, (max_entries, overflow, row_grad) for the deterministic one
-        (mag_det.backward_det); with a row_grad the weight's gradient is None and dW goes to the RowGrad."""
+        (mag_det.backward_det); with a row_grad the weight's gradient is None and dW goes to the RowGrad.
+        (capacity, overflow, a BitmapRowGrad): the atomic backward into that row gradient (`_backward_rows`)."""
         ctx.save_for_backward(*call.tensors)
         ctx.args = (weight.shape, call.scalars, det)
         return _forward(weight, call, n_bad)
@@ -83,6 +107,9 @@ class _MagRowsFn(torch.autograd.Function):
         call = _Call(ctx.saved_tensors, *scalars)
         if det is None:
             return _backward(shape, grad_out, call), None, None, None
+        from .optim_rows import BitmapRowGrad
+        if isinstance(det[2], BitmapRowGrad):
+            return _backward_rows(shape, grad_out, call, *det), None, None, None
         from .mag_det import backward_det
         return backward_det(shape, grad_out, call, *det), None, None, None
 
@@ -111,7 +138,13 @@ def mag_prop_rows(weight, attr_indptr, attr_indices, attr_data, col, val, filled
     buffer instead of a fresh `torch.zeros`, hands it the sorted key list and returns no gradient for `weight`
     (`weight.grad` stays None): the table is stepped by `ClipAdam.set_row_grad`.  It needs the deterministic mode and
     `max_entries` (ValueError with the atomic mode or without a capacity) and must be the RowGrad of this very `weight`
-    (TypeError / ValueError).  The forward is the same."""
+    (TypeError / ValueError).  The forward is the same.
+    An `optim_rows.BitmapRowGrad(weight)` is the same for the ATOMIC backward: it needs the mode to resolve to
+    non-deterministic and `max_entries` (ValueError otherwise).  The backward marks the rows the batch's bags name in the
+    BitmapRowGrad's bitmap, compacts them into a fresh int64 [min(V, max_entries)] list, zeroes those rows of its buffer and
+    runs the atomic launch into it: no `torch.zeros` of [V, H], no host read, input dropout allowed.  The list holds every
+    row a slot of the batch names, dropped by DropNode or not.  If the batch names more rows than the list holds, bit 0 of
+    `overflow` is set and the list lacks the rows past it."""
     deterministic = _deterministic(deterministic)
     if max_entries is not None:
         from .mag_det import check_max_entries
@@ -122,10 +155,16 @@ def mag_prop_rows(weight, attr_indptr, attr_indices, attr_data, col, val, filled
     if weight.dim() != 2 or weight.shape[0] < 1 or weight.shape[1] < 1:
         raise TypeError("weight must be a 2-D [V, H] table")
     if row_grad is not None:
-        from .optim_rows import RowGrad
+        from .optim_rows import BitmapRowGrad, RowGrad
         if not isinstance(row_grad, RowGrad):
             raise TypeError(f"row_grad must be an optim_rows.RowGrad, got {type(row_grad).__name__}")
-        if not deterministic or max_entries is None:
+        if isinstance(row_grad, BitmapRowGrad):
+            if deterministic:
+                raise ValueError("a BitmapRowGrad is the atomic backward's row gradient: deterministic=False (and torch's "
+                                 "deterministic mode off); the deterministic backward takes a plain optim_rows.RowGrad")
+            if max_entries is None:
+                raise ValueError("a BitmapRowGrad needs max_entries=: the capacity of its row list is min(V, max_entries)")
+        elif not deterministic or max_entries is None:
             raise ValueError("row_grad needs the deterministic backward: deterministic=True (or torch's deterministic mode) and "
                              "max_entries=; the atomic backward keeps no list of the rows it touched (DESIGN §9)")
         row_grad.check_weight(weight)
@@ -176,6 +215,14 @@ def mag_prop_rows(weight, attr_indptr, attr_indices, attr_data, col, val, filled
         raise RuntimeError("mag_prop_rows has no deterministic backward (fp32 atomics into dW); for a reproducible gradient use the "
                            "composed path with deterministic=True: flatten_rows -> embedding_bag_csr(nodes=..., deterministic=True) "
                            "-> random_prop, or pass max_entries= for the deterministic backward of this op (DESIGN §7o)")
+    elif row_grad is not None and wants_grad:                          # a BitmapRowGrad: the atomic backward into its rows
+        from .mag_det import check_overflow
+        if B * K >= 2 ** 31:
+            raise ValueError(f"the row list of mag_prop_rows takes fewer than 2**31 slots, got {B} x {K}")
+        if overflow is not None:
+            check_overflow(overflow, weight.device)
+        det = (min(weight.shape[0], max_entries),
+               overflow if overflow is not None else torch.zeros(1, dtype=torch.int32, device=weight.device), row_grad)
     if seed is None:
         seed = _new_seed()
     call = _Call((attr_indptr, attr_indices, attr_data, col, val, filled, batch_rows, keep), S_rows, K, B, samples,

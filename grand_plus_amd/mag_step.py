@@ -12,8 +12,8 @@ host for a number, so the whole step is captured and a replay is bitwise the eag
 `max_entries` entries per batch row and slot: None means K * Lmax per batch row, Lmax the longest bag among the nodes that
 occur as columns of `rows` (read once here, the constructor's one host read), and then the buffer cannot overflow.
 
-`table_step="exact"` or `"lazy"` (deterministic mode only) steps the embedding table from the backward's row list
-instead of a dense gradient: no `torch.zeros` of [V, H] per step, no dense read of dW.  "exact" is bit for bit today's
+`table_step="exact"` or `"lazy"` (deterministic mode, or the atomic mode with `row_list="bitmap"`, §7u) steps
+the embedding table from the backward's row list instead of a dense gradient: no `torch.zeros` of [V, H] per step, no dense read of dW.  "exact" is bit for bit today's
 step.  "lazy" updates the touched rows alone and is NOT the reference's dense Adam (model_mag.py:312), under which an
 untouched row still moves while its moments decay.
 
@@ -61,12 +61,18 @@ class MagTrainStep(TrainStep):
     rounding of the norm, whose partial sums are cut differently).  "lazy": only the touched rows of the table and of its
     moments change -- NOT the reference's trajectory (dense Adam moves an untouched row while its moments decay); the table's
     group must have weight_decay = 0.
+    row_list: None, or "bitmap"  for a `table_step` over the ATOMIC backward: it needs a table_step and a mode
+    that resolves to non-deterministic (ValueError otherwise).  One optim_rows.BitmapRowGrad, shared by every graph, lists
+    the rows each batch's bags name (a bitmap of V bits, compacted without a sort) in min(V, max_entries) keys; with
+    max_entries=None that cannot overflow.  The table gradient is then as reproducible as the atomic backward is -- the row
+    list itself is the same run to run -- and with "exact" the step is the dense atomic step up to the order of the atomics.
 
     With capture=True and the deterministic mode the capture includes `torch.sort`; should a torch build refuse to capture it,
     the capture fails as every broken capture does here: a RuntimeError naming the call (backward), no retry, no fallback."""
 
     def __init__(self, model, optimizer, rows, attr_indptr, attr_indices, attr_data, labels, idx_train, idx_unlabel, *, samples,
-                 dropnode_rate, lam, warmup, tem, conf=None, kind="l2", seed, capture=True, deterministic=None, max_entries=None, table_step=None):
+                 dropnode_rate, lam, warmup, tem, conf=None, kind="l2", seed, capture=True, deterministic=None, max_entries=None, table_step=None,
+                 row_list=None):
         from .mlp import MagMLP
         if not isinstance(model, MagMLP):
             raise ValueError("MagTrainStep takes a MagMLP (a GrandPlusMLP goes to step.TrainStep)")
@@ -84,12 +90,20 @@ class MagTrainStep(TrainStep):
         if max_entries is not None:
             from .mag_det import check_max_entries
             check_max_entries(max_entries)
+        if row_list not in (None, "bitmap"):
+            raise ValueError(f"row_list must be None or 'bitmap', got {row_list!r}")
         if table_step is not None:
             from .optim_rows import check_mode
             check_mode(table_step)
-            if not self.deterministic:
+            if row_list == "bitmap":
+                if self.deterministic:
+                    raise ValueError("row_list='bitmap' is the atomic backward's row list: it needs deterministic=False (the "
+                                     "deterministic backward holds a key list of its own)")
+            elif not self.deterministic:
                 raise ValueError(f"table_step={table_step!r} needs the deterministic table gradient: deterministic=True (the atomic "
                                  "backward keeps no list of the rows it touched, DESIGN §9)")
+        elif row_list == "bitmap":
+            raise ValueError("row_list='bitmap' needs a table_step ('exact' or 'lazy'): without one the table takes a dense gradient")
         if not attr_indptr.is_cuda:
             raise ValueError("the step runs on the GPU only: the attribute CSR must be CUDA tensors (no CPU fallback)")
         dev = attr_indptr.device
@@ -104,10 +118,10 @@ class MagTrainStep(TrainStep):
         self._setup(model, optimizer, rows, labels, idx_train, idx_unlabel, dev, samples=samples, dropnode_rate=dropnode_rate,
                     lam=lam, warmup=warmup, tem=tem, conf=conf, kind=kind, seed=seed, capture=capture)
         self._entries_flag = torch.zeros(1, dtype=torch.int32, device=dev)   # bit 0: a backward had more entries than its buffer
-        self.table_step, self.row_grad = table_step, None
+        self.table_step, self.row_list, self.row_grad = table_step, row_list, None
         if table_step is not None:                                   # one RowGrad for every graph of the step
-            from .optim_rows import RowGrad
-            self.row_grad = RowGrad(model.embeds.weight)
+            from .optim_rows import BitmapRowGrad, RowGrad
+            self.row_grad = (BitmapRowGrad if row_list == "bitmap" else RowGrad)(model.embeds.weight)
             optimizer.set_row_grad(model.embeds.weight, self.row_grad, table_step)
         # the longest bag among the nodes that occur as columns of rows: the one host read, and only here
         lens = attr_indptr[1:] - attr_indptr[:-1]
@@ -130,7 +144,12 @@ class MagTrainStep(TrainStep):
         return X[None] if S == 1 else X
 
     def check_entries_flag(self):
-        """Raises if a deterministic backward had more entries than `max_entries` (one device-to-host copy)."""
+        """Raises if a deterministic backward had more entries than `max_entries`, or, with row_list="bitmap", if a batch
+        named more rows than min(V, max_entries) (one device-to-host copy)."""
         if int(self._entries_flag.item()) & 1:
+            if self.row_list == "bitmap":
+                raise RuntimeError(f"a step's batch named more table rows than max_entries = {self.max_entries}: the row list of "
+                                   "that step lacks the rows past it, and the table was not stepped on them (pass a larger "
+                                   "max_entries, or None)")
             raise RuntimeError(f"a step's batch had more entries than max_entries = {self.max_entries}: the table gradient of that "
                                "step lacks the entries past it (pass a larger max_entries, or None for B * K * Lmax)")

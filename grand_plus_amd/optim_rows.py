@@ -16,7 +16,12 @@ list, and gives the weight no `.grad`.  `ClipAdam.set_row_grad(param, row_grad, 
 The entry points are extern "C" symbols of libgrandplus.so declared in csrc/optim_rows_abi.hpp; they are not part of
 C ABI 4, so their binding (ABI below) lives here and not in `_native`, as mag_det's does.
 
-Left out: a row list for the atomic backward, amsgrad, lazy mode with weight decay.
+`BitmapRowGrad` is a RowGrad for the ATOMIC backward, which keeps no key list: the rows a batch can touch are
+marked in a bitmap of V bits (csrc/row_mark_abi.hpp, bound by MARK_ABI below), the bitmap is compacted into the same kind
+of list -- ascending, each row once, sentinel V in the tail -- and the listed rows of `values` are zeroed for the atomics
+to add into.  `ClipAdam.set_row_grad` and both row kernels take it unchanged.
+
+Left out: amsgrad, lazy mode with weight decay.
 """
 from __future__ import annotations
 
@@ -25,9 +30,9 @@ import ctypes
 import torch
 
 from . import _native
-from ._common import _stream
+from ._common import _ptr, _stream
 
-__all__ = ["RowGrad", "MODES", "check_mode"]
+__all__ = ["RowGrad", "BitmapRowGrad", "MODES", "check_mode"]
 
 # name -> (restype, argtypes), under the convention stated above _native.ABI; tests/test_host_optim_rows.py holds it against
 # optim_rows_abi.hpp.
@@ -38,17 +43,24 @@ ABI = {
     "gp_clip_adam_rows": (_int, _table + [_f, _f, _vp, _vp, _vp]),
     "gp_clip_adam_rows_dev": (_int, _table + [_vp, _vp, _vp, _vp, _vp]),
 }
+# the entry points of row_mark_abi.hpp; tests/test_host_row_mark.py holds this table against that header
+MARK_ABI = {
+    "gp_row_mark_mag": (_int, [_int, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _vp]),
+    "gp_row_list_compact": (_int, [_int, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "gp_row_list_zero": (_int, [_int, _vp, _i64, _i64, _i32, _vp, _vp]),
+}
+ROW_LIST_PARTIALS = 1024                  # GP_ROW_LIST_PARTIALS
 MODES = {"exact": 1, "lazy": 2}           # GP_OPTIM_ROWS_EXACT, GP_OPTIM_ROWS_LAZY
 _BOUND = False
 
 
 def lib():
-    """_native.lib() with the entry points of optim_rows_abi.hpp declared on it.  A library without them is an error, not
-    a fallback."""
+    """_native.lib() with the entry points of optim_rows_abi.hpp and row_mark_abi.hpp declared on it.  A library without
+    them is an error, not a fallback."""
     global _BOUND
     L = _native.lib()
     if not _BOUND:
-        for name, (restype, argtypes) in ABI.items():
+        for name, (restype, argtypes) in {**ABI, **MARK_ABI}.items():
             if not hasattr(L, name):
                 raise RuntimeError(f"{_native.LIB_PATH} does not export {name} (an older build?): rebuild the library")
             f = getattr(L, name)
@@ -107,6 +119,47 @@ class RowGrad:
 
     def filled(self):
         return self.keys is not None
+
+
+class BitmapRowGrad(RowGrad):
+    """A RowGrad that the ATOMIC backward of `mag_prop_rows(..., row_grad=this, deterministic=False, max_entries=M)` fills
+    (DESIGN §7u).  Besides `values` it holds `bitmap` (int32 [(V + 31) // 32], zeros, made once: one bit per row, all zero
+    between two backwards), `count` (int64 [1]: how many rows the last backward marked, unclamped) and `partials`, the
+    workspace of the compaction.  After a backward `keys` is int64 [min(V, M)]: the distinct rows of the batch's bags,
+    ascending, the sentinel V in the tail; the listed rows of `values` hold the batch's dW, every other row anything at all.
+    `values` is never zero-filled as a whole.
+
+    `reset()` zeroes the bitmap: for a caller whose backward raised between the mark and the compaction."""
+
+    def __init__(self, param):
+        super().__init__(param)
+        V = self.shape[0]
+        self.bitmap = torch.zeros((V + 31) // 32, dtype=torch.int32, device=self.device)
+        self.count = torch.zeros(1, dtype=torch.int64, device=self.device)
+        self.partials = torch.empty(ROW_LIST_PARTIALS, dtype=torch.int64, device=self.device)
+
+    def reset(self):
+        self.bitmap.zero_()
+
+
+def mark_and_list(rg, call, capacity, overflow):
+    """The row list of one batch for a BitmapRowGrad, on the current stream: gp_row_mark_mag over the batch of `call` (a
+    mag._Call), gp_row_list_compact into a fresh int64 [capacity] and gp_row_list_zero of the listed rows of `rg.values`.
+    Four launches, no host read.  Returns the keys; bit 0 of `overflow` is set when more than `capacity` rows were marked."""
+    attr_indptr, attr_indices, _, col, _, filled, batch_rows, _ = call.tensors
+    S_rows, K, B = call.scalars[:3]
+    V, H = rg.shape
+    dev, stream, L = rg.device.index, _stream(rg.values), lib()
+    keys = torch.empty(capacity, dtype=torch.int64, device=rg.device)
+    rc = L.gp_row_mark_mag(dev, V, attr_indptr.data_ptr(), attr_indices.data_ptr(), attr_indptr.numel() - 1, col.data_ptr(),
+                           _ptr(filled), S_rows, K, _ptr(batch_rows), B, rg.bitmap.data_ptr(), stream)
+    _native.raise_for_status(rc)
+    rc = L.gp_row_list_compact(dev, V, rg.bitmap.data_ptr(), capacity, keys.data_ptr(), rg.count.data_ptr(),
+                               rg.partials.data_ptr(), overflow.data_ptr(), stream)
+    _native.raise_for_status(rc)
+    rc = L.gp_row_list_zero(dev, keys.data_ptr(), capacity, V, H, rg.values.data_ptr(), stream)
+    _native.raise_for_status(rc)
+    return keys
 
 
 def sqnorm(rg, accumulate, ws):
