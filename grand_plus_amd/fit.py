@@ -16,8 +16,15 @@ synchronised at every validation.  Here
 The three entry points are part of the C ABI (include/grandplus_fit.h): `_native.ABI` binds them, and `_native` holds
 the GP_FIT_* constants and the two struct mirrors.  They are imported here so that `fit.GpFitTrack` and the like resolve.
 
-Left out: MagMLP, several steps in one graph, numpy's own shuffle stream, a checkpoint on disk
-(`tracker.restore()` then `torch.save` is the caller's line).
+`fit` takes a `mag_step.MagTrainStep` as it takes a `TrainStep`: the step says how it validates
+(`_valid_plan` / `_valid_pass`).  For a step built with `dirty_rows=True` the tracker snapshots the embedding table row by
+row: `gp_fit_rows_mark` collects the rows every backward hands over in a bitmap, `gp_fit_rows_snapshot` copies the marked
+rows when the rule takes a new best and clears the bitmap.  Those two are extern "C" symbols of libgrandplus.so declared
+in csrc/fit_rows_abi.hpp, outside C ABI 4; ROWS_ABI below binds them, as optim_rows.ABI binds its own.
+
+Left out: several steps in one graph, the validation pass as a captured graph, numpy's own shuffle stream, a
+dirty-row `restore` (it stays a full copy, once per run), Adam's moments in the snapshot (the reference saves the
+state_dict alone), a checkpoint on disk (`tracker.restore()` then `torch.save` is the caller's line).
 """
 from __future__ import annotations
 
@@ -37,6 +44,37 @@ __all__ = ["Sampler", "BestTracker", "FitLoop", "FitResult", "fit", "early_stop_
 
 STOP_MODES = {"acc": GP_FIT_STOP_ACC, "both": GP_FIT_STOP_BOTH}
 _MAX_SIZE = 2 ** 31
+
+# the entry points of fit_rows_abi.hpp: name -> (restype, argtypes), under the convention stated above _native.ABI;
+# tests/test_host_fit_rows.py holds this table against that header
+_int, _i32, _i64, _vp = ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p
+ROWS_ABI = {
+    "gp_fit_rows_mark": (_int, [_int, _vp, _i64, _i64, _vp, _vp]),
+    "gp_fit_rows_snapshot": (_int, [_int, _vp, _vp, _vp, _i64, _i32, _vp, _vp]),
+}
+_ROWS_BOUND = False
+
+
+def rows_lib():
+    """_native.lib() with the entry points of fit_rows_abi.hpp declared on it.  A library without them is an error, not a
+    fallback."""
+    global _ROWS_BOUND
+    L = _native.lib()
+    if not _ROWS_BOUND:
+        for name, (restype, argtypes) in ROWS_ABI.items():
+            if not hasattr(L, name):
+                raise RuntimeError(f"{_native.LIB_PATH} does not export {name} (an older build?): rebuild the library")
+            f = getattr(L, name)
+            f.restype, f.argtypes = restype, argtypes
+        _ROWS_BOUND = True
+    return L
+
+
+def rows_mark(keys, n_vocab, dirty):
+    """gp_fit_rows_mark on the current stream: the in-range keys of `keys` (int64 CUDA, a row list as `RowGrad.fill` takes
+    it) set their bits of `dirty` (int32 CUDA [(n_vocab + 31) // 32])."""
+    rc = rows_lib().gp_fit_rows_mark(dirty.device.index, keys.data_ptr(), keys.numel(), n_vocab, dirty.data_ptr(), _stream(dirty))
+    _native.raise_for_status(rc)
 
 
 def _int_in(v, name, lo, hi=None, what="an int"):
@@ -136,16 +174,36 @@ class BestTracker:
 
     Owns one gp_fit_track, one snapshot buffer per tensor of model.state_dict() (parameters, BatchNorm running statistics
     and num_batches_tracked alike) and the copy table.  `update(loss, acc, state)` enqueues the decision and the copy;
-    `read()` is one device-to-host copy of the struct; `restore()` copies the snapshot back into the model."""
+    `read()` is one device-to-host copy of the struct; `restore()` copies the snapshot back into the model.
 
-    def __init__(self, model, device, stop_mode="both", patience=100):
+    row_grad: an `optim_rows.RowGrad` with `track_dirty()` called, whose `param` is a tensor of the state_dict (ValueError
+    otherwise) -- the embedding table of a MAG step under the lazy table step.  That tensor then leaves the
+    copy table of gp_fit_snapshot: its snapshot starts as a clone of the table, so that every row whose dirty bit is 0 has
+    the same bits in both, and `update` issues gp_fit_rows_snapshot after gp_fit_snapshot, which copies the rows marked
+    since the last snapshot and clears their bits.  Whoever changes a row of the table must mark it: the backwards do,
+    through `RowGrad.fill`.  ONE tracker per RowGrad: the snapshot kernel is what clears the bitmap, so a second tracker
+    over the same RowGrad would miss the rows the first one cleared.  A stopped tracker never copies again; the bitmap
+    then only accumulates.  `restore()` stays a full copy."""
+
+    def __init__(self, model, device, stop_mode="both", patience=100, *, row_grad=None):
         if stop_mode not in STOP_MODES:
             raise ValueError(f"stop_mode must be 'acc' or 'both', got {stop_mode!r}")
         self.patience = _size(patience, "patience")
+        state = model.state_dict()
+        if row_grad is not None:
+            from .optim_rows import RowGrad
+            if not isinstance(row_grad, RowGrad) or row_grad.dirty is None:
+                raise ValueError("row_grad must be an optim_rows.RowGrad that tracks its dirty rows: call row_grad.track_dirty() "
+                                 "before the step is captured (MagTrainStep(dirty_rows=True) does)")
+            p = row_grad.param
+            if not any(t.data_ptr() == p.data_ptr() and t.shape == p.shape and t.dtype == p.dtype for t in state.values()):
+                raise ValueError("row_grad was made for a tensor that is not in model.state_dict(): the tracker snapshots the model's "
+                                 "own table")
+        self.row_grad = row_grad
         self.device = device = _cuda_device(device, "BestTracker")
         self.stop_mode = stop_mode
         self.tensors = []
-        for name, t in model.state_dict().items():
+        for name, t in state.items():
             if t.device != device:
                 raise ValueError(f"{name} is on {t.device}, the tracker on {device}")
             if not (t.dtype.is_floating_point or t.dtype in (torch.int8, torch.uint8, torch.int16, torch.int32, torch.int64)):
@@ -153,17 +211,25 @@ class BestTracker:
             if not t.is_contiguous() or (t.numel() * t.element_size()) % 4 or t.data_ptr() % 4:
                 raise ValueError(f"{name} must be contiguous, 4-byte aligned and a whole number of 4-byte words")
             self.tensors.append(t)
-        self.snapshot = [torch.zeros_like(t) for t in self.tensors]
-        self._copies = (GpFitCopy * max(len(self.tensors), 1))(*[
-            GpFitCopy(src=t.data_ptr(), dst=s.data_ptr(), n_words=t.numel() * t.element_size() // 4)
-            for t, s in zip(self.tensors, self.snapshot)])
+        self._table = None                                               # (table, its snapshot): copied row by row
+        if row_grad is not None:
+            at = [i for i, t in enumerate(self.tensors) if t.data_ptr() == row_grad.param.data_ptr() and t.shape == row_grad.param.shape]
+            self.snapshot = [t.detach().clone() if i == at[0] else torch.zeros_like(t) for i, t in enumerate(self.tensors)]
+            self._table = (self.tensors[at[0]], self.snapshot[at[0]])
+        else:
+            self.snapshot = [torch.zeros_like(t) for t in self.tensors]
+        whole = [(t, s) for t, s in zip(self.tensors, self.snapshot) if self._table is None or t is not self._table[0]]
+        self._n_copies = len(whole)
+        self._copies = (GpFitCopy * max(len(whole), 1))(*[
+            GpFitCopy(src=t.data_ptr(), dst=s.data_ptr(), n_words=t.numel() * t.element_size() // 4) for t, s in whole])
         init = GpFitTrack(best_loss=float("inf"))
         self.buf = torch.frombuffer(bytearray(bytes(init)), dtype=torch.int64).to(device)
         self._val = torch.zeros(2, dtype=torch.float32, device=device)
 
     def update(self, loss, acc, state):
         """The rule on (loss, acc) -- 0-dim float32 device tensors, as `valid` returns them -- at state's tick, then the
-        snapshot if the rule took a new best: two launches (more past 32 tensors) on the current stream, nothing read back."""
+        snapshot if the rule took a new best: two launches (more past 32 tensors; one more with a row_grad) on the current
+        stream, nothing read back."""
         for t, name in ((loss, "loss"), (acc, "acc")):
             if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.numel() != 1 or t.device != self.device:
                 raise TypeError(f"{name} must be a float32 tensor of one element on {self.device}")
@@ -177,8 +243,13 @@ class BestTracker:
         rc = L.gp_fit_track_update(self.device.index, self.buf.data_ptr(), val.data_ptr(), state.buf.data_ptr(),
                                    STOP_MODES[self.stop_mode], self.patience, _stream(self.buf))
         _native.raise_for_status(rc)
-        rc = L.gp_fit_snapshot(self.device.index, self.buf.data_ptr(), self._copies, len(self.tensors), _stream(self.buf))
+        rc = L.gp_fit_snapshot(self.device.index, self.buf.data_ptr(), self._copies, self._n_copies, _stream(self.buf))
         _native.raise_for_status(rc)
+        if self._table is not None:                                      # the table's dirty rows, and the bitmap cleared
+            table, snap = self._table
+            rc = rows_lib().gp_fit_rows_snapshot(self.device.index, self.buf.data_ptr(), table.data_ptr(), snap.data_ptr(),
+                                                 table.shape[0], table.shape[1], self.row_grad.dirty.data_ptr(), _stream(self.buf))
+            _native.raise_for_status(rc)
 
     def read(self):
         """The struct on the host (one device-to-host copy): best_loss, best_acc, best_tick, stop_tick, bad_counter,
@@ -209,28 +280,34 @@ class FitLoop:
     synchronisation of the steady state) and raises if a step ran with the wrong batch shape; `finish()` restores the best
     weights and returns the FitResult."""
 
-    def __init__(self, step, sampler, idx_val, *, eval_batch=10, stop_mode="both", patience=100):
-        from .evaluate import valid_plan
+    def __init__(self, step, sampler, idx_val, *, eval_batch=10, stop_mode="both", patience=100, valid_batch=None):
         from .step import TrainStep
         if not isinstance(step, TrainStep) or not isinstance(sampler, Sampler):
-            raise TypeError("fit takes a TrainStep and a Sampler")
+            raise TypeError("fit takes a TrainStep and a Sampler")                # a MagTrainStep is one
+        if valid_batch is not None:
+            valid_batch = _int_in(valid_batch, "valid_batch", 1, _MAX_SIZE, what="None or an int")
         step.check_sampler(sampler)
         self.step, self.sampler, self.eval_batch = step, sampler, _int_in(eval_batch, "eval_batch", 1)
-        # the reference validates in batches of the training batch size (model.py:337)
-        self.plan = valid_plan(step.model, step.rows, step.features, idx_val, step.labels, sampler.batch_size)
-        self.tracker = BestTracker(step.model, step.features.device, stop_mode, patience)
+        # the reference validates in batches of the training batch size (model.py:337); MAG's in batches of 100
+        # (model_mag.py:372 passes none, and the default of line 145 is 100)
+        if valid_batch is None:
+            valid_batch = step._valid_batch if step._valid_batch is not None else sampler.batch_size
+        self.valid_batch = valid_batch
+        self.plan = step._valid_plan(idx_val, valid_batch)
+        # a step built with dirty_rows=True: the table's snapshot goes row by row (DESIGN §7v)
+        self.tracker = BestTracker(step.model, step.device, stop_mode, patience,
+                                   row_grad=step.row_grad if getattr(step, "dirty_rows", False) else None)
         self.t = step.state.read().tick                                  # the one read of the tick
         self.steps = self.evals = 0
         self.last = None                                                 # the StepResult of the last step
 
     def advance(self):
-        from .evaluate import valid_pass
         self.t += 1
         self.last = self.step.step_sampled(self.sampler, self.t)
         self.steps += 1
         if (self.t - 1) % self.eval_batch:
             return False
-        loss, acc, _counts = valid_pass(self.plan, self.step.dropnode_rate)
+        loss, acc, _counts = self.step._valid_pass(self.plan)
         self.tracker.update(loss, acc, self.step.state)
         self.evals += 1
         return True
@@ -247,11 +324,16 @@ class FitLoop:
                          float(image.best_loss), float(image.best_acc))
 
 
-def fit(step, sampler, idx_val, *, epochs, eval_batch=10, stop_mode="both", patience=100, poll_every=1, max_steps=None):
-    """The reference's training loop (model.py:302-368) over a TrainStep: returns FitResult(steps, best_tick, stop_tick,
-    best_loss, best_acc) with the best weights restored into the model.
+def fit(step, sampler, idx_val, *, epochs, eval_batch=10, stop_mode="both", patience=100, poll_every=1, max_steps=None,
+        valid_batch=None):
+    """The reference's training loop (model.py:302-368) over a TrainStep, or MAG's (model_mag.py) over a MagTrainStep in any
+    mode it can be built in: returns FitResult(steps, best_tick, stop_tick, best_loss, best_acc) with the best weights
+    restored into the model.
 
     step: the TrainStep (model in train mode); sampler: the Sampler over its two pools; idx_val: the validation node ids.
+    valid_batch: the batch size of the validation pass; None is sampler.batch_size for a TrainStep (model.py:337) and 100
+    for a MagTrainStep (model_mag.py:145).  A MagTrainStep built with dirty_rows=True has the best table kept row by row
+    (BestTracker's row_grad): the same restored weights, less copied at every improvement.
     Runs the steps after the state's tick (read once here) up to step epochs * sampler.n_batches, at most max_steps of
     them.  Step t validates when (t - 1) % eval_batch == 0 (num_batch % eval_batch of the reference) and feeds the
     tracker; every poll_every-th validation the host reads the tracker and stops if the rule has.  With poll_every=1
@@ -261,7 +343,7 @@ def fit(step, sampler, idx_val, *, epochs, eval_batch=10, stop_mode="both", pati
     epochs, poll_every = _int_in(epochs, "epochs", 1), _int_in(poll_every, "poll_every", 1)
     if max_steps is not None:
         _int_in(max_steps, "max_steps", 0, what="None or an int")
-    loop = FitLoop(step, sampler, idx_val, eval_batch=eval_batch, stop_mode=stop_mode, patience=patience)
+    loop = FitLoop(step, sampler, idx_val, eval_batch=eval_batch, stop_mode=stop_mode, patience=patience, valid_batch=valid_batch)
     last = epochs * sampler.n_batches
     while loop.t < last and (max_steps is None or loop.steps < max_steps):
         if loop.advance() and loop.evals % poll_every == 0 and loop.poll().stopped:

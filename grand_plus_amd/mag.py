@@ -22,10 +22,14 @@ and let torch's flag decide.  The forward is the same in every mode.  There is n
 Either backward can hand the table's gradient to the optimiser as a row list instead of a dense tensor (`row_grad=`): the
 deterministic one its sorted keys (an `optim_rows.RowGrad`), the atomic one the rows it marked in a bitmap (an
 `optim_rows.BitmapRowGrad`).
+
+`valid_mag` is `valid_mag_pass(valid_mag_plan(...))`, as `evaluate.valid` is `valid_pass(valid_plan(...))`: the fit loop
+ plans once and passes at every validation.
 """
 from __future__ import annotations
 
 import ctypes
+from typing import NamedTuple
 
 import torch
 from torch.autograd.function import once_differentiable
@@ -245,7 +249,28 @@ def valid_mag(model, rows, attr_indptr, attr_indices, attr_data, idx_val, labels
     (one check, KeyError for a node that is no seed); then per batch `model.emb_rows` in eval mode (only the batch's
     neighbours are embedded, with the weights as they are now), the MLP and `eval_head` into one shared buffer, and one
     `eval_reduce`: nothing synchronises.  The model's training flag is restored.  Same returns as `valid`."""
-    from .evaluate import _NoSync, _node_ids, _on_gpu, eval_buffers, eval_head, eval_reduce
+    plan = valid_mag_plan(model, rows, attr_indptr, attr_indices, attr_data, idx_val, labels, batch_size)
+    loss, acc, counts = valid_mag_pass(plan, dropnode_rate)
+    return (loss, acc, counts) if return_counts else (loss, acc)
+
+
+class ValidMagPlan(NamedTuple):
+    """What `valid_mag` prepares once for a validation set: its arguments as checked, the node ids on the device, their
+    positions in `rows` and the evaluation buffers.  Nothing in it depends on the weights: `valid_mag_pass` runs over it any
+    number of times (the fit loop) and sees the table as it is at that moment."""
+    model: torch.nn.Module
+    rows: object
+    attr: tuple
+    labels: torch.Tensor
+    idx: torch.Tensor
+    pos: torch.Tensor
+    buf: object
+    batch_size: int
+
+
+def valid_mag_plan(model, rows, attr_indptr, attr_indices, attr_data, idx_val, labels, batch_size=100):
+    """The checks, the one position lookup (KeyError for a node that is no seed) and the buffers of `valid_mag`."""
+    from .evaluate import _node_ids, _on_gpu, eval_buffers
     from .rows import RowMatrix
     if not isinstance(model, torch.nn.Module) or not hasattr(model, "emb_rows"):
         raise TypeError("valid_mag: model must be a MagMLP")
@@ -261,14 +286,20 @@ def valid_mag(model, rows, attr_indptr, attr_indices, attr_data, idx_val, labels
     idx = _node_ids(idx_val, "idx_val", dev)
     n = idx.numel()
     pos = rows.batch_positions(idx, check=True) if n else None
-    buf = eval_buffers(n, dev)
+    return ValidMagPlan(model, rows, (attr_indptr, attr_indices, attr_data), labels, idx, pos, eval_buffers(n, dev), batch_size)
+
+
+def valid_mag_pass(plan, dropnode_rate=0.5):
+    """One validation pass over a ValidMagPlan: (loss, acc, counts) as device tensors.  Nothing synchronises."""
+    from .evaluate import _NoSync, eval_head, eval_reduce
+    model, rows, attr, labels, idx, pos, buf, batch_size = plan
+    n = idx.numel()
     with _NoSync(model):
         for start in range(0, n, batch_size):
             end = min(start + batch_size, n)
-            aug = model.emb_rows(attr_indptr, attr_indices, attr_data, rows, batch_rows=pos[start:end], dropnode_rate=dropnode_rate)
+            aug = model.emb_rows(*attr, rows, batch_rows=pos[start:end], dropnode_rate=dropnode_rate)
             eval_head(model(aug), labels, label_rows=idx[start:end], out=buf, offset=start)
-        loss, acc, counts = eval_reduce(buf)
-    return (loss, acc, counts) if return_counts else (loss, acc)
+        return eval_reduce(buf)
 
 
 def predict_mag(graph, attr_indptr, attr_indices, attr_data, model, idx_test, labels, prop_mode, order, alpha=0.2,

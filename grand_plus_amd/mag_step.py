@@ -17,7 +17,12 @@ the embedding table from the backward's row list instead of a dense gradient: no
 step.  "lazy" updates the touched rows alone and is NOT the reference's dense Adam (model_mag.py:312), under which an
 untouched row still moves while its moments decay.
 
-Left out: input dropout (`model.input_droprate` must be 0), `fit` for MAG, several steps in one graph.
+`fit.fit` takes a MagTrainStep as it takes a TrainStep: `_valid_plan` / `_valid_pass` are `mag.valid_mag_plan` /
+`valid_mag_pass` over the step's attribute CSR and rows.  `dirty_rows=True` (with `table_step="lazy"`) has every backward mark
+the rows it hands over in a bitmap, from which the loop's BestTracker copies only the rows that changed since its last snapshot.
+
+Left out: input dropout (`model.input_droprate` must be 0), several steps in one graph, the validation pass
+as a captured graph.
 """
 from __future__ import annotations
 
@@ -66,13 +71,17 @@ class MagTrainStep(TrainStep):
     the rows each batch's bags name (a bitmap of V bits, compacted without a sort) in min(V, max_entries) keys; with
     max_entries=None that cannot overflow.  The table gradient is then as reproducible as the atomic backward is -- the row
     list itself is the same run to run -- and with "exact" the step is the dense atomic step up to the order of the atomics.
+    dirty_rows: True needs table_step="lazy" (ValueError otherwise, before any device call: under None or "exact" every row of
+    the table moves in every step, so there is nothing to skip).  The step's RowGrad then tracks the rows every backward
+    hands over (`RowGrad.track_dirty()`, made here, before any capture: the mark is part of every graph of the step), and
+    `fit` snapshots the table row by row (`fit.BestTracker(row_grad=)`).
 
     With capture=True and the deterministic mode the capture includes `torch.sort`; should a torch build refuse to capture it,
     the capture fails as every broken capture does here: a RuntimeError naming the call (backward), no retry, no fallback."""
 
     def __init__(self, model, optimizer, rows, attr_indptr, attr_indices, attr_data, labels, idx_train, idx_unlabel, *, samples,
                  dropnode_rate, lam, warmup, tem, conf=None, kind="l2", seed, capture=True, deterministic=None, max_entries=None, table_step=None,
-                 row_list=None):
+                 row_list=None, dirty_rows=False):
         from .mlp import MagMLP
         if not isinstance(model, MagMLP):
             raise ValueError("MagTrainStep takes a MagMLP (a GrandPlusMLP goes to step.TrainStep)")
@@ -104,6 +113,9 @@ class MagTrainStep(TrainStep):
                                  "backward keeps no list of the rows it touched, DESIGN §9)")
         elif row_list == "bitmap":
             raise ValueError("row_list='bitmap' needs a table_step ('exact' or 'lazy'): without one the table takes a dense gradient")
+        if dirty_rows and table_step != "lazy":
+            raise ValueError(f"dirty_rows=True needs table_step='lazy', got table_step={table_step!r}: under None or 'exact' every "
+                             "row of the table moves in every step, so a snapshot has no row to skip")
         if not attr_indptr.is_cuda:
             raise ValueError("the step runs on the GPU only: the attribute CSR must be CUDA tensors (no CPU fallback)")
         dev = attr_indptr.device
@@ -123,6 +135,9 @@ class MagTrainStep(TrainStep):
             from .optim_rows import BitmapRowGrad, RowGrad
             self.row_grad = (BitmapRowGrad if row_list == "bitmap" else RowGrad)(model.embeds.weight)
             optimizer.set_row_grad(model.embeds.weight, self.row_grad, table_step)
+        self.dirty_rows = bool(dirty_rows)
+        if self.dirty_rows:
+            self.row_grad.track_dirty()                              # before any capture: every graph of the step marks
         # the longest bag among the nodes that occur as columns of rows: the one host read, and only here
         lens = attr_indptr[1:] - attr_indptr[:-1]
         cols = rows.col.long()
@@ -142,6 +157,17 @@ class MagTrainStep(TrainStep):
                                 max_entries=self._max_entries(batch_rows.numel()), overflow=self._entries_flag,
                                 row_grad=self.row_grad)
         return X[None] if S == 1 else X
+
+    # ---- what the fit loop validates with
+    _valid_batch = 100             # model_mag.py:372 calls `valid` without a batch size; its default (line 145) is 100
+
+    def _valid_plan(self, idx_val, batch_size):
+        from .mag import valid_mag_plan
+        return valid_mag_plan(self.model, self.rows, *self.attr, idx_val, self.labels, batch_size)
+
+    def _valid_pass(self, plan):
+        from .mag import valid_mag_pass
+        return valid_mag_pass(plan, self.dropnode_rate)
 
     def check_entries_flag(self):
         """Raises if a deterministic backward had more entries than `max_entries`, or, with row_list="bitmap", if a batch

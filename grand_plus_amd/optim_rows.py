@@ -21,7 +21,11 @@ marked in a bitmap of V bits (csrc/row_mark_abi.hpp, bound by MARK_ABI below), t
 of list -- ascending, each row once, sentinel V in the tail -- and the listed rows of `values` are zeroed for the atomics
 to add into.  `ClipAdam.set_row_grad` and both row kernels take it unchanged.
 
-Left out: amsgrad, lazy mode with weight decay.
+`RowGrad.track_dirty()` has every `fill` also mark the rows it is handed in a bitmap `dirty` that only
+accumulates here: `fit.BestTracker(row_grad=)` reads it to snapshot the table row by row, and clears it.
+
+Left out: amsgrad, lazy mode with weight decay, Adam's moments in the best-weights snapshot (the reference
+saves the state_dict alone).
 """
 from __future__ import annotations
 
@@ -103,6 +107,16 @@ class RowGrad:
         self.values = torch.empty(self.shape, dtype=torch.float32, device=param.device)
         self.keys = None
         self.n_sorted = 0
+        self.dirty = None
+
+    def track_dirty(self):
+        """Makes `dirty` (int32 [(V + 31) // 32], zeros, made once): from here on every `fill` sets the bits of the rows it is
+        handed (one gp_fit_rows_mark), and `fit.BestTracker(row_grad=this)`, the one reader, copies those rows
+        and clears the bits.  To be called before a step over this RowGrad is captured: the mark is a launch of the
+        backward, so a graph captured earlier lacks it.  Returns `dirty`."""
+        if self.dirty is None:
+            self.dirty = torch.zeros((self.shape[0] + 31) // 32, dtype=torch.int32, device=self.device)
+        return self.dirty
 
     def check_weight(self, weight):
         """Refuses a weight that is not this RowGrad's table (before any device call)."""
@@ -113,9 +127,14 @@ class RowGrad:
                              f"{weight.device}")
 
     def fill(self, sorted_keys):
-        """What the backward calls once `values` holds the batch's rows: takes the key list over."""
+        """What the backward calls once `values` holds the batch's rows: takes the key list over.  With `dirty` set it marks
+        the list's rows there, on the current stream: inside the backward, so inside every captured graph of the step, with
+        that graph's own key tensor and length."""
         self.keys = sorted_keys
         self.n_sorted = sorted_keys.numel()
+        if self.dirty is not None:
+            from .fit import rows_mark
+            rows_mark(sorted_keys, self.shape[0], self.dirty)
 
     def filled(self):
         return self.keys is not None

@@ -307,6 +307,17 @@ class TrainStep:
         graph.replay()
         return result
 
+    # ---- what the fit loop validates with (fit.FitLoop); mag_step.MagTrainStep swaps both
+    def _valid_plan(self, idx_val, batch_size):
+        from .evaluate import valid_plan
+        return valid_plan(self.model, self.rows, self.features, idx_val, self.labels, batch_size)
+
+    def _valid_pass(self, plan):
+        from .evaluate import valid_pass
+        return valid_pass(plan, self.dropnode_rate)
+
+    _valid_batch = None            # the validation batch size `fit` uses when it is given none: None is the sampler's
+
     # ---- the step with the selection drawn on the device
     def check_sampler(self, sampler):
         if (sampler.n_train, sampler.n_unlabel) != (self.n_train, self.n_unlabel):
