@@ -37,21 +37,30 @@ def alternate(atomic, det, iters, reps=5, warmup=3):
     return float(np.median(a)), float(np.median(d)), (min(a), max(a)), (min(d), max(d))
 
 
-def bag_case(name, dev, rng, V, H, bag, B, K, hub, iters, out):
+def bag_inputs(dev, rng, V, H, bag, B, K, hub, draw_ids=None):
+    """The embedding bag's backward operands at one shape: (L, nnz, G, args) for embedding._backward / _backward_det.
+    draw_ids(rng, n): the attribute ids of the n stored entries (default: uniform over V); bench_det_chunk.py builds its
+    cases here too."""
     n_nodes = 200_000
     lens = rng.integers(1, 2 * bag, n_nodes)
     indptr = np.zeros(n_nodes + 1, np.int64); np.cumsum(lens, out=indptr[1:])
-    indices = rng.integers(0, V, int(indptr[-1])).astype(np.int32)
+    n_stored = int(indptr[-1])
+    indices = (rng.integers(0, V, n_stored) if draw_ids is None else draw_ids(rng, n_stored)).astype(np.int32)
     if hub:
         indices[indptr[:-1]] = 13                                               # the first attribute of every node
-    data = (rng.random(int(indptr[-1]), dtype=np.float32) + 0.05).astype(np.float32)
+    data = (rng.random(n_stored, dtype=np.float32) + 0.05).astype(np.float32)
     ip, ix, dt = (torch.from_numpy(x).to(dev) for x in (indptr, indices, data))
     nodes = torch.from_numpy(rng.integers(0, n_nodes, B * K)).to(dev)            # the batch's B * K neighbour rows
     bl = ip[nodes + 1] - ip[nodes]
     L = embedding._Layout(ip, n_nodes, nodes, torch.cumsum(bl, 0) - bl, nodes.numel(), ix, dt)
     nnz = int(bl.sum())
     G = torch.randn((nodes.numel(), H), device=dev)
-    args = (0.5, True, 1234, None)
+    return L, nnz, G, (0.5, True, 1234, None)
+
+
+def bag_case(name, dev, rng, V, H, bag, B, K, hub, iters, out):
+    L, nnz, G, args = bag_inputs(dev, rng, V, H, bag, B, K, hub)
+    nodes = L.nodes
     atomic = lambda: embedding._backward((V, H), G, L, *args)                    # noqa: E731
     det = lambda: embedding._backward_det((V, H), G, L, nnz, *args)              # noqa: E731
     a, d, ar, dr = alternate(atomic, det, iters)
@@ -64,14 +73,20 @@ def bag_case(name, dev, rng, V, H, bag, B, K, hub, iters, out):
           "zeroing_dW_us": round(zero_only, 1), "windows": 5, "iters": iters}, out)
 
 
-def rows_case(name, dev, rng, N, F, B, K, S, hub, iters, out):
+def rows_inputs(dev, rng, N, F, B, K, S, hub):
+    """random_prop_rows' backward operands at one shape: (G, args) for augment._rows_backward / _rows_backward_det."""
     S_rows = 20_000
     col, val, filled = synthetic_rows(rng, dev, S_rows, K, N)
     if hub:
         col.view(S_rows, K)[:, 0] = 7
     rows = torch.from_numpy(rng.choice(S_rows, B, replace=False).astype(np.int32)).to(dev)
     G = torch.randn((S, B, F), device=dev)
-    args = (col, val, filled, K, rows, B, N, S, 0.5, True, 99, None)
+    return G, (col, val, filled, K, rows, B, N, S, 0.5, True, 99, None)
+
+
+def rows_case(name, dev, rng, N, F, B, K, S, hub, iters, out):
+    G, args = rows_inputs(dev, rng, N, F, B, K, S, hub)
+    col, _, filled, _, rows = args[:5]
     atomic = lambda: augment._rows_backward(G, *args)                            # noqa: E731
     det = lambda: augment._rows_backward_det(G, *args)                           # noqa: E731
     a, d, ar, dr = alternate(atomic, det, iters)

@@ -118,9 +118,11 @@ def _rows_det_order(col, filled, K, batch_rows, N):
     return order, keys
 
 
-def _rows_backward_det(grad_out, col, val, filled, K, batch_rows, B, N, samples, dropnode_rate, training, seed, keep):
+def _rows_backward_det(grad_out, col, val, filled, K, batch_rows, B, N, samples, dropnode_rate, training, seed, keep,
+                       segment_chunk=None):
     """_rows_backward without atomics (csrc/scatter_det.hip): the batch's slots ordered by column id
-    (_rows_det_order), one gather kernel that sums each gradient row in that order."""
+    (_rows_det_order), one gather kernel that sums each gradient row in that order.  segment_chunk = C: the chunked gather
+    of DESIGN §7w over the same order, two kernels and a scratch."""
     g = grad_out.contiguous()
     F = g.shape[-1]
     grad = torch.zeros((N, F), dtype=torch.float32, device=g.device)
@@ -129,10 +131,15 @@ def _rows_backward_det(grad_out, col, val, filled, K, batch_rows, B, N, samples,
     order, keys = _rows_det_order(col, filled, int(K), batch_rows, N)
     S = 1 if samples is None else samples
     inv_den = torch.empty(_native.scatter_rows_workspace_bytes(S, B) // 4, dtype=torch.float32, device=g.device)
-    rc = _native.lib().gp_random_prop_rows_backward_det(
-        _dev_index(g), g.data_ptr(), B, F, col.data_ptr(), val.data_ptr(), _ptr(filled), int(K), _ptr(batch_rows), S,
-        float(dropnode_rate), int(bool(training)), ctypes.c_uint64(seed), _ptr(keep), col.numel(), grad.data_ptr(), N,
-        order.data_ptr(), keys.data_ptr(), keys.numel(), inv_den.data_ptr(), _stream(g))
+    args = (_dev_index(g), g.data_ptr(), B, F, col.data_ptr(), val.data_ptr(), _ptr(filled), int(K), _ptr(batch_rows), S,
+            float(dropnode_rate), int(bool(training)), ctypes.c_uint64(seed), _ptr(keep), col.numel(), grad.data_ptr(), N,
+            order.data_ptr(), keys.data_ptr(), keys.numel(), inv_den.data_ptr())
+    if segment_chunk is None:
+        rc = _native.lib().gp_random_prop_rows_backward_det(*args, _stream(g))
+    else:
+        from . import gather_chunk
+        scratch, nbytes = gather_chunk.scratch(keys.numel(), segment_chunk, F, g.device)
+        rc = gather_chunk.lib().gp_random_prop_rows_backward_det_chunked(*args, segment_chunk, scratch.data_ptr(), nbytes, _stream(g))
     _native.raise_for_status(rc)
     return grad
 
@@ -163,10 +170,10 @@ class _RowsFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, features, col, val, filled, K, batch_rows, B, samples, dropnode_rate, training, seed, keep, stream,
-                deterministic=False):
+                deterministic=False, segment_chunk=None):
         ctx.save_for_backward(col, val, filled, batch_rows, keep)
         ctx.args = (K, B, features.shape[0], samples, dropnode_rate, training, seed)
-        ctx.deterministic = deterministic
+        ctx.deterministic, ctx.segment_chunk = deterministic, segment_chunk
         return _rows_forward(features, col, val, filled, K, batch_rows, B, samples, dropnode_rate, training, seed, keep, stream)
 
     @staticmethod
@@ -174,8 +181,11 @@ class _RowsFn(torch.autograd.Function):
     def backward(ctx, grad_out):
         col, val, filled, batch_rows, keep = ctx.saved_tensors
         K, B, *rest = ctx.args
-        backward = _rows_backward_det if ctx.deterministic else _rows_backward
-        return (backward(grad_out, col, val, filled, K, batch_rows, B, *rest, keep),) + (None,) * 13
+        if not ctx.deterministic:
+            grad = _rows_backward(grad_out, col, val, filled, K, batch_rows, B, *rest, keep)
+        else:
+            grad = _rows_backward_det(grad_out, col, val, filled, K, batch_rows, B, *rest, keep, ctx.segment_chunk)
+        return (grad,) + (None,) * 14
 
 
 def random_prop(feats, mat_scores, mat_idx, dropnode_rate, training=True, seed=None, keep=None, stream=None,
@@ -215,7 +225,7 @@ def random_prop(feats, mat_scores, mat_idx, dropnode_rate, training=True, seed=N
 
 
 def random_prop_rows(features, col, val, filled, K, batch_rows=None, dropnode_rate=0.5, training=True,
-                     seed=None, keep=None, stream=None, samples=1, deterministic=None):
+                     seed=None, keep=None, stream=None, samples=1, deterministic=None, segment_chunk=None):
     """Fused augmentation straight from the GFPush row matrix.
 
     features [N, F] float32 (node features resident on the GPU); col int32 [S*K], val float64 [S*K],
@@ -228,9 +238,15 @@ def random_prop_rows(features, col, val, filled, K, batch_rows=None, dropnode_ra
     batch's slots are sorted by column id and each gradient row is summed in a fixed order with plain stores (DESIGN §7i;
     slower, bitwise the same run to run, no host synchronisation).  None follows
     `torch.are_deterministic_algorithms_enabled()`.
+    `segment_chunk` = C (a power of two in [64, 4096]; None: off) cuts the deterministic backward's segment sums into
+    chunks of C entries summed by separate waves and folded in a fixed order: a node that sits in many rows is
+    no longer one serial chain.  Still bitwise the same run to run; a node with at most C entries gets the unchunked bits.
+    It needs the deterministic backward: ValueError when the mode resolves to False.
     `samples` = S > 1 returns [S, B, F] from one launch (keep: uint8 [S, S_rows * K]); see the module docstring.
     """
     deterministic = _deterministic(deterministic)
+    from .gather_chunk import resolve
+    segment_chunk = resolve(segment_chunk, deterministic, "random_prop_rows")
     _check_samples(samples)
     _check(features, torch.float32, "features")
     _check(col, torch.int32, "col")
@@ -248,7 +264,7 @@ def random_prop_rows(features, col, val, filled, K, batch_rows=None, dropnode_ra
     if keep is not None:
         _check_keep(keep, samples, col.numel())
     args = (features, col, val, filled, K, batch_rows, B, samples, dropnode_rate, training, seed, keep, stream)
-    return _RowsFn.apply(*args, deterministic) if _wants_grad(features) else _rows_forward(*args)
+    return _RowsFn.apply(*args, deterministic, segment_chunk) if _wants_grad(features) else _rows_forward(*args)
 
 
 def algorithmic_bytes(n_kept_entries: int, n_out: int, feat_dim: int) -> int:

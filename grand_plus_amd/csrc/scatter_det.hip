@@ -18,12 +18,15 @@
 // them per pass for wider rows) and walk the segment to its end: first through the window's prepared entries, passed
 // round with shuffles, then, when the segment runs past the window, through further groups of 64 prepared the same
 // way.  A position whose key is not a destination (the sentinel N / V, to which the caller keys what does not exist)
-// ends the walk.  A long segment is a serial chain of adds on one wave: the accepted cost of the mode (§7i).
+// ends the walk.  A long segment is a serial chain of adds on one wave: the accepted cost of the mode (§7i); the two
+// _chunked entry points at the end of this unit cut it into chunks (§7w, gather_chunk.hpp).
 //
 // The entry must be found exactly as the forward finds it: BagLayout, bag_of, attr_id, sample_weight and the
 // denominators are dropnode.hpp's, the lines augment.hip calls.
 #include "dropnode.hpp"
 #include "gather_sum.hpp"
+#include "gather_chunk.hpp"
+#include "gather_chunk_abi.hpp"
 
 #include <algorithm>
 
@@ -188,6 +191,11 @@ struct BagOp {
     }
 };
 
+// The grid of rows_inv_den_kernel for the chunked twin.  The cap is a SECOND COPY of the one in the launch line of
+// gp_random_prop_rows_backward_det, which stays as it is written because tests/second_trip_cases.source_caps() reads it
+// there; tests/test_host_gather_chunk.py holds this copy to that one.  Change both together.
+int rows_den_grid(int n_batch) { return std::min(n_batch, 65535); }
+
 }  // namespace
 
 extern "C" {
@@ -247,6 +255,68 @@ int gp_embedding_bag_backward_det(int device, const float* d_grad_out, int64_t n
     hipLaunchKernelGGL(gather_sum_kernel<BagOp>, dim3(gather_grid(n_sorted)), dim3(kGather), 0, s, op, (const long long*)d_order,
                        (const long long*)d_sorted_keys, (long long)n_sorted, (long long)n_vocab, dim, d_grad_weight);
     return launch_status("gather_sum_kernel<BagOp>");
+}
+
+// ---- the chunked twins (gather_chunk_abi.hpp states their contract): the same pre-pass and the same Op, the
+// gather cut into chunks of `chunk` sorted positions by gather_chunk.hpp.
+
+int gp_random_prop_rows_backward_det_chunked(int device, const float* d_grad_out, int32_t n_batch, int32_t feat_dim,
+                                             const int32_t* d_col, const double* d_val, const int32_t* d_filled, int32_t K,
+                                             const int32_t* d_batch_rows, int32_t n_samples, float dropnode_rate, int training,
+                                             uint64_t seed, const uint8_t* d_keep, int64_t keep_stride, float* d_grad_x,
+                                             int64_t n_nodes, const int64_t* d_order, const int64_t* d_sorted_keys,
+                                             int64_t n_sorted, float* d_inv_den, int32_t chunk, float* d_scratch,
+                                             int64_t scratch_bytes, void* stream)
+{
+    // The checks, the pre-pass launch and the RowsOp below are gp_random_prop_rows_backward_det's own lines, repeated here
+    // because that entry point stays byte for byte what it was.  tests/test_host_gather_chunk.py holds the two copies
+    // together; a change to one belongs in the other (a shared helper is the later remedy).
+    const char* where = "gp_random_prop_rows_backward_det_chunked";
+    if (n_samples < 1 || n_samples > kMaxSamples || !(dropnode_rate >= 0.0f && dropnode_rate <= 1.0f))
+        return fail(GP_ERR_INVALID_ARG, where, "n_samples outside [1, 16] or dropnode_rate outside [0, 1]");
+    if (n_batch < 0 || n_nodes < 1 || feat_dim < 1 || K < 1 || K > GP_MAX_K || n_sorted < 0 || (d_keep && keep_stride < 1))
+        return fail(GP_ERR_INVALID_ARG, where, "bad size, K outside [1, 1024] or keep_stride < 1 with a mask");
+    if (const int rc = chunk_check(where, chunk, n_batch == 0 ? 0 : n_sorted, feat_dim, d_scratch, scratch_bytes)) return rc;
+    if (n_batch == 0 || n_sorted == 0) return GP_OK;
+    if (!d_grad_out || !d_col || !d_val || !d_grad_x || !d_order || !d_sorted_keys || !d_inv_den)
+        return fail(GP_ERR_NULL, where, "a device pointer is NULL");
+    if (const int rc = set_device(device, where)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(rows_inv_den_kernel, dim3(rows_den_grid(n_batch)), dim3(kBlock), 0, s, d_val, d_filled, K, d_batch_rows,
+                       n_batch, n_samples, dropnode_rate, training, (u64)seed, d_keep, (long long)keep_stride, d_inv_den);
+    if (const int rc = launch_status("rows_inv_den_kernel")) return rc;
+    const RowsOp op = {d_grad_out, feat_dim, d_col, d_val, d_filled, K, d_batch_rows, n_batch, n_samples, dropnode_rate, training,
+                       (u64)seed, d_keep, (long long)keep_stride, d_inv_den};
+    return gather_chunked(op, "gather_chunk_kernel<RowsOp>", d_order, d_sorted_keys, n_sorted, n_nodes, feat_dim, chunk, d_grad_x,
+                          d_scratch, s);
+}
+
+int gp_embedding_bag_backward_det_chunked(int device, const float* d_grad_out, int64_t n_vocab, int32_t dim,
+                                          const int64_t* d_offsets, int64_t n_src, const int64_t* d_nodes,
+                                          const int64_t* d_entry_base, int64_t n_rows, const void* d_attr_idx, int idx_bytes,
+                                          const float* d_attr_data, float dropout_rate, int training, uint64_t seed,
+                                          const uint8_t* d_keep, float* d_grad_weight, int32_t* d_n_bad, const int64_t* d_order,
+                                          const int64_t* d_sorted_keys, const int64_t* d_sorted_rows, int64_t n_sorted,
+                                          float* d_inv_den, int32_t chunk, float* d_scratch, int64_t scratch_bytes, void* stream)
+{
+    const char* where = "gp_embedding_bag_backward_det_chunked";
+    if (n_vocab < 0 || dim < 1 || n_src < 0 || n_rows < 0 || n_sorted < 0 || (idx_bytes != 4 && idx_bytes != 8) ||
+        !(dropout_rate >= 0.0f && dropout_rate <= 1.0f))
+        return fail(GP_ERR_INVALID_ARG, where, "negative size, dim < 1, idx_bytes not 4 or 8, or dropout rate outside [0, 1]");
+    const bool gathers = n_rows > 0 && n_sorted > 0 && n_vocab > 0;
+    if (const int rc = chunk_check(where, chunk, gathers ? n_sorted : 0, dim, d_scratch, scratch_bytes)) return rc;
+    if (gathers && (!d_order || !d_sorted_keys || !d_sorted_rows)) return fail(GP_ERR_NULL, where, "a device pointer is NULL");
+    // The pre-pass is the twin's own: given no sorted positions it checks the remaining pointers, counts the bad ids, writes
+    // inv_den and stops before its gather.
+    if (const int rc = gp_embedding_bag_backward_det(device, d_grad_out, n_vocab, dim, d_offsets, n_src, d_nodes, d_entry_base, n_rows,
+                                                     d_attr_idx, idx_bytes, d_attr_data, dropout_rate, training, seed, d_keep,
+                                                     d_grad_weight, d_n_bad, nullptr, nullptr, nullptr, 0, d_inv_den, stream))
+        return rc;
+    if (!gathers) return GP_OK;
+    const BagLayout L = bag_layout(d_offsets, n_src, d_nodes, d_entry_base, n_rows, d_attr_idx, idx_bytes, d_attr_data);
+    const BagOp op = {d_grad_out, dim, L, dropout_rate, training, (u64)seed, d_keep, d_inv_den, (const long long*)d_sorted_rows};
+    return gather_chunked(op, "gather_chunk_kernel<BagOp>", d_order, d_sorted_keys, n_sorted, n_vocab, dim, chunk, d_grad_weight,
+                          d_scratch, (hipStream_t)stream);
 }
 
 }  // extern "C"

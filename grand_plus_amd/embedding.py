@@ -99,9 +99,10 @@ def _det_order(L, n_entries, V):
     return order, keys, m[order]
 
 
-def _backward_det(weight_shape, grad_out, L, n_entries, p, training, seed, keep):
+def _backward_det(weight_shape, grad_out, L, n_entries, p, training, seed, keep, segment_chunk=None):
     """_backward without atomics (csrc/scatter_det.hip): the entries ordered by attribute id (_det_order), one
-    gather kernel that sums each row of dW in that order."""
+    gather kernel that sums each row of dW in that order.  segment_chunk = C: the chunked gather of DESIGN §7w over the
+    same order, two kernels and a scratch."""
     V, H = weight_shape
     g = grad_out.contiguous()
     dW = torch.zeros((V, H), dtype=torch.float32, device=g.device)
@@ -109,20 +110,26 @@ def _backward_det(weight_shape, grad_out, L, n_entries, p, training, seed, keep)
         return dW
     order, keys, rows = _det_order(L, n_entries, V)
     inv_den = torch.empty(_native.scatter_bag_workspace_bytes(L.n_rows) // 4, dtype=torch.float32, device=g.device)
-    rc = _native.lib().gp_embedding_bag_backward_det(
-        _dev_index(g), g.data_ptr(), V, H, *L.args(), float(p), int(bool(training)), ctypes.c_uint64(seed),
-        _ptr(keep), dW.data_ptr(), None, order.data_ptr(), keys.data_ptr(), rows.data_ptr(), order.numel(),
-        inv_den.data_ptr(), _stream(g))
+    args = (_dev_index(g), g.data_ptr(), V, H, *L.args(), float(p), int(bool(training)), ctypes.c_uint64(seed),
+            _ptr(keep), dW.data_ptr(), None, order.data_ptr(), keys.data_ptr(), rows.data_ptr(), order.numel(),
+            inv_den.data_ptr())
+    if segment_chunk is None:
+        rc = _native.lib().gp_embedding_bag_backward_det(*args, _stream(g))
+    else:
+        from . import gather_chunk
+        scratch, nbytes = gather_chunk.scratch(order.numel(), segment_chunk, H, g.device)
+        rc = gather_chunk.lib().gp_embedding_bag_backward_det_chunked(*args, segment_chunk, scratch.data_ptr(), nbytes, _stream(g))
     _native.raise_for_status(rc)
     return dW
 
 
 class _BagFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, weight, L, p, training, seed, keep, n_bad, det_entries=None):
+    def forward(ctx, weight, L, p, training, seed, keep, n_bad, det_entries=None, segment_chunk=None):
         ctx.save_for_backward(*L.tensors(), keep)
         ctx.args = (weight.shape, L.n_src, L.n_rows, p, training, seed)
         ctx.det_entries = det_entries                                   # None: the atomic backward; else the entry count
+        ctx.segment_chunk = segment_chunk                               # the deterministic backward's chunk
         return _forward(weight, L, p, training, seed, keep, n_bad)
 
     @staticmethod
@@ -134,13 +141,13 @@ class _BagFn(torch.autograd.Function):
         if ctx.det_entries is None:
             dW = _backward(shape, grad_out, L, p, training, seed, keep)
         else:
-            dW = _backward_det(shape, grad_out, L, ctx.det_entries, p, training, seed, keep)
-        return dW, None, None, None, None, None, None, None
+            dW = _backward_det(shape, grad_out, L, ctx.det_entries, p, training, seed, keep, ctx.segment_chunk)
+        return dW, None, None, None, None, None, None, None, None
 
 
-def _run(weight, L, n_entries, input_droprate, training, seed, keep, validate, det_entries=None):
+def _run(weight, L, n_entries, input_droprate, training, seed, keep, validate, det_entries=None, segment_chunk=None):
     """det_entries: None for the atomic backward, else a callable that gives the number of entries the deterministic
-    backward sorts (called only when the gradient is wanted)."""
+    backward sorts (called only when the gradient is wanted).  segment_chunk: that backward's chunk, or None."""
     _check(weight, torch.float32, "weight")
     if weight.dim() != 2:
         raise TypeError("weight must be a 2-D [V, H] table")
@@ -155,7 +162,7 @@ def _run(weight, L, n_entries, input_droprate, training, seed, keep, validate, d
     n_bad = torch.zeros(1, dtype=torch.int32, device=weight.device)
     if torch.is_grad_enabled() and weight.requires_grad:
         out = _BagFn.apply(weight, L, float(input_droprate), bool(training), seed, keep, n_bad,
-                           det_entries() if det_entries is not None else None)
+                           det_entries() if det_entries is not None else None, segment_chunk)
     else:
         out = _forward(weight, L, input_droprate, training, seed, keep, n_bad)
     if validate:
@@ -166,7 +173,7 @@ def _run(weight, L, n_entries, input_droprate, training, seed, keep, validate, d
 
 
 def embedding_bag(weight, attr_idx, node_idx, attr_data, input_droprate=0.0, training=True, seed=None, keep=None,
-                  validate=True, deterministic=None, n_out=None):
+                  validate=True, deterministic=None, n_out=None, segment_chunk=None):
     """Drop-in for `MLP.emb(attr_idx, node_idx, attr_data)` (model_mag.py:48-55) on CUDA tensors.
 
     weight [V, H] float32 (the `nn.Embedding` table, on the GPU); attr_idx [nnz] int64; node_idx [nnz] int64
@@ -176,8 +183,12 @@ def embedding_bag(weight, attr_idx, node_idx, attr_data, input_droprate=0.0, tra
     (one host synchronisation); with validate=False such ids are skipped, never read or written.
     `deterministic` (None = torch.are_deterministic_algorithms_enabled()) chooses the backward: see the module docstring.
     `n_out` (optional) is the number of output rows; given, it saves the host read of node_idx[-1] (as random_prop's).
+    `segment_chunk` = C (a power of two in [64, 4096]; None: off) cuts the deterministic backward's sums into chunks of C
+    entries (gather_chunk.py): a hub attribute is no longer one serial chain.  ValueError with the atomic backward.
     """
     deterministic = _deterministic(deterministic)
+    from .gather_chunk import resolve
+    segment_chunk = resolve(segment_chunk, deterministic, "embedding_bag")
     _check(attr_idx, torch.int64, "attr_idx")
     _check(node_idx, torch.int64, "node_idx")
     _check(attr_data, torch.float32, "attr_data")
@@ -194,11 +205,12 @@ def embedding_bag(weight, attr_idx, node_idx, attr_data, input_droprate=0.0, tra
     n_out = int(n_out)
     offsets = torch.searchsorted(node_idx, torch.arange(n_out + 1, dtype=torch.int64, device=node_idx.device))
     L = _Layout(offsets, n_out, None, None, n_out, attr_idx, attr_data)
-    return _run(weight, L, lambda: nnz, input_droprate, training, seed, keep, validate, (lambda: nnz) if deterministic else None)
+    return _run(weight, L, lambda: nnz, input_droprate, training, seed, keep, validate, (lambda: nnz) if deterministic else None,
+                segment_chunk)
 
 
 def embedding_bag_csr(weight, attr_indptr, attr_indices, attr_data, nodes=None, input_droprate=0.0, training=True,
-                      seed=None, keep=None, validate=True, deterministic=None):
+                      seed=None, keep=None, validate=True, deterministic=None, segment_chunk=None):
     """`MLP.emb` over the bags of `nodes` in a node-attribute CSR resident on the GPU.
 
     attr_indptr [N + 1] int64, attr_indices [nnz] int32, attr_data [nnz] float32 (the scipy CSR's arrays);
@@ -210,8 +222,11 @@ def embedding_bag_csr(weight, attr_indptr, attr_indices, attr_data, nodes=None, 
     With `nodes` given the number of entries of the batch is data-dependent, and the deterministic backward needs it as
     a host number to size its sort: that one count is read back here, in the forward call (one host synchronisation;
     only when the gradient is wanted).  With nodes=None the count is `attr_indices.numel()`: no host read.
+    `segment_chunk`: as `embedding_bag`'s.
     """
     deterministic = _deterministic(deterministic)
+    from .gather_chunk import resolve
+    segment_chunk = resolve(segment_chunk, deterministic, "embedding_bag_csr")
     _check(attr_indptr, torch.int64, "attr_indptr")
     _check(attr_indices, torch.int32, "attr_indices")
     _check(attr_data, torch.float32, "attr_data")
@@ -230,7 +245,8 @@ def embedding_bag_csr(weight, attr_indptr, attr_indices, attr_data, nodes=None, 
         base = torch.cumsum(lens, 0) - lens                            # entry order: the bags one after another
         L = _Layout(attr_indptr, N, nodes, base, nodes.numel(), attr_indices, attr_data)
         n_entries = det_entries = lambda: int(lens.sum().item())       # noqa: E731
-    return _run(weight, L, n_entries, input_droprate, training, seed, keep, validate, det_entries if deterministic else None)
+    return _run(weight, L, n_entries, input_droprate, training, seed, keep, validate, det_entries if deterministic else None,
+                segment_chunk)
 
 
 def flatten_rows(col, val, filled, K, batch_rows):

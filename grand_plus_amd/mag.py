@@ -97,7 +97,7 @@ class _MagRowsFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, weight, call, n_bad, det=None):
-        """det: None for the atomic backward, (max_entries, overflow, row_grad) for the deterministic one
+        """det: None for the atomic backward, (max_entries, overflow, row_grad, segment_chunk) for the deterministic one
         (mag_det.backward_det); with a row_grad the weight's gradient is None and dW goes to the RowGrad.
         (capacity, overflow, a BitmapRowGrad): the atomic backward into that row gradient (`_backward_rows`)."""
         ctx.save_for_backward(*call.tensors)
@@ -120,7 +120,7 @@ class _MagRowsFn(torch.autograd.Function):
 
 def mag_prop_rows(weight, attr_indptr, attr_indices, attr_data, col, val, filled, K, batch_rows=None, *, samples=1,
                   dropnode_rate=0.5, input_droprate=0.0, training=True, seed=None, keep=None, validate=False, deterministic=None,
-                  max_entries=None, overflow=None, row_grad=None):
+                  max_entries=None, overflow=None, row_grad=None, segment_chunk=None):
     """The S augmented embeddings of a batch of resident rows, in one launch.
 
     weight [V, H] float32 (the `nn.Embedding` table); attr_indptr [N + 1] int64, attr_indices [nnz] int32, attr_data [nnz]
@@ -148,8 +148,14 @@ def mag_prop_rows(weight, attr_indptr, attr_indices, attr_data, col, val, filled
     BitmapRowGrad's bitmap, compacts them into a fresh int64 [min(V, max_entries)] list, zeroes those rows of its buffer and
     runs the atomic launch into it: no `torch.zeros` of [V, H], no host read, input dropout allowed.  The list holds every
     row a slot of the batch names, dropped by DropNode or not.  If the batch names more rows than the list holds, bit 0 of
-    `overflow` is set and the list lacks the rows past it."""
+    `overflow` is set and the list lacks the rows past it.
+    `segment_chunk` = C (a power of two in [64, 4096]; None: off) cuts the deterministic backward's sums into chunks of C
+    entries (gather_chunk.py): an attribute that sits in many bags of the batch is no longer one serial chain.
+    Still no host read and the same bits run to run; with `row_grad` the rows and the key list are the unchunked call's.  It
+    needs the mode to resolve to deterministic (ValueError otherwise)."""
     deterministic = _deterministic(deterministic)
+    from .gather_chunk import resolve
+    segment_chunk = resolve(segment_chunk, deterministic, "mag_prop_rows")
     if max_entries is not None:
         from .mag_det import check_max_entries
         check_max_entries(max_entries)
@@ -214,7 +220,8 @@ def mag_prop_rows(weight, attr_indptr, attr_indices, attr_data, col, val, filled
             raise ValueError(f"the deterministic backward of mag_prop_rows takes fewer than 2**31 slots, got {B} x {K}")
         if overflow is not None:
             check_overflow(overflow, weight.device)
-        det = (max_entries, overflow if overflow is not None else torch.zeros(1, dtype=torch.int32, device=weight.device), row_grad)
+        det = (max_entries, overflow if overflow is not None else torch.zeros(1, dtype=torch.int32, device=weight.device), row_grad,
+               segment_chunk)
     elif deterministic and wants_grad:
         raise RuntimeError("mag_prop_rows has no deterministic backward (fp32 atomics into dW); for a reproducible gradient use the "
                            "composed path with deterministic=True: flatten_rows -> embedding_bag_csr(nodes=..., deterministic=True) "

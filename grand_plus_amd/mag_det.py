@@ -12,7 +12,9 @@ captured graph.
 The entry points are extern "C" symbols of libgrandplus.so declared in csrc/mag_det_abi.hpp; they are not part of C ABI 4,
 so their binding (ABI below) lives here and not in `_native`.
 
-Left out: input dropout (the keyed mask would need S values of U per slot), hub segments cut into chunks.
+`segment_chunk=C` sums a hub attribute's segment in chunks of C entries (gather_chunk.py).
+
+Left out: input dropout (the keyed mask would need S values of U per slot).
 """
 from __future__ import annotations
 
@@ -66,12 +68,13 @@ def check_overflow(overflow, device):
     return overflow
 
 
-def backward_det(weight_shape, grad_out, call, max_entries, overflow, row_grad=None):
+def backward_det(weight_shape, grad_out, call, max_entries, overflow, row_grad=None, segment_chunk=None):
     """dW [V, H] of mag_prop_rows by the order contract of mag_det_abi.hpp.  call: mag._Call, the forward's operands;
     overflow: int32 [1], bit 0 is set when the batch has more than max_entries entries (the gradient then lacks the rest).
     Six launches, torch.sort between the third and the fourth; no host read.
     row_grad: an optim_rows.RowGrad.  The gather then writes the touched rows into `row_grad.values`, which
-    nobody zeroes, the RowGrad takes the sorted key list over, and None is returned in place of dW."""
+    nobody zeroes, the RowGrad takes the sorted key list over, and None is returned in place of dW.
+    segment_chunk: None, or the chunk C of the chunked gather: one launch and a scratch more, the same keys."""
     V, H = weight_shape
     attr_indptr, attr_indices, attr_data, col, val, filled, batch_rows, keep = call.tensors
     S_rows, K, B, S, p_node, p_in, training, seed = call.scalars
@@ -97,9 +100,14 @@ def backward_det(weight_shape, grad_out, call, max_entries, overflow, row_grad=N
     sorted_keys, order = torch.sort(keys, stable=True)
     U = torch.empty((B * K, H), dtype=torch.float32, device=dev)
     inv = torch.empty((S, B), dtype=torch.float32, device=dev)
-    rc = L.gp_mag_prop_rows_backward_det(_dev_index(g), g.data_ptr(), V, H, *call.args(), slot_base.data_ptr(), order.data_ptr(),
-                                         sorted_keys.data_ptr(), max_entries, U.data_ptr(), inv.data_ptr(), dW.data_ptr(),
-                                         _stream(g))
+    args = (_dev_index(g), g.data_ptr(), V, H, *call.args(), slot_base.data_ptr(), order.data_ptr(), sorted_keys.data_ptr(),
+            max_entries, U.data_ptr(), inv.data_ptr(), dW.data_ptr())
+    if segment_chunk is None:
+        rc = L.gp_mag_prop_rows_backward_det(*args, _stream(g))
+    else:
+        from . import gather_chunk
+        scratch, nbytes = gather_chunk.scratch(max_entries, segment_chunk, H, dev)
+        rc = gather_chunk.lib().gp_mag_prop_rows_backward_det_chunked(*args, segment_chunk, scratch.data_ptr(), nbytes, _stream(g))
     _native.raise_for_status(rc)
     if row_grad is None:
         return dW

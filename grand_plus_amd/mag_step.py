@@ -75,13 +75,16 @@ class MagTrainStep(TrainStep):
     the table moves in every step, so there is nothing to skip).  The step's RowGrad then tracks the rows every backward
     hands over (`RowGrad.track_dirty()`, made here, before any capture: the mark is part of every graph of the step), and
     `fit` snapshots the table row by row (`fit.BestTracker(row_grad=)`).
+    segment_chunk: None, or C (a power of two in [64, 4096]): the deterministic table gradient sums every
+    attribute's segment in chunks of C entries, so that an attribute that sits in many bags of a batch is no longer one
+    serial chain.  It needs the deterministic mode (ValueError otherwise) and goes with every table_step, dirty_rows and fit.
 
     With capture=True and the deterministic mode the capture includes `torch.sort`; should a torch build refuse to capture it,
     the capture fails as every broken capture does here: a RuntimeError naming the call (backward), no retry, no fallback."""
 
     def __init__(self, model, optimizer, rows, attr_indptr, attr_indices, attr_data, labels, idx_train, idx_unlabel, *, samples,
                  dropnode_rate, lam, warmup, tem, conf=None, kind="l2", seed, capture=True, deterministic=None, max_entries=None, table_step=None,
-                 row_list=None, dirty_rows=False):
+                 row_list=None, dirty_rows=False, segment_chunk=None):
         from .mlp import MagMLP
         if not isinstance(model, MagMLP):
             raise ValueError("MagTrainStep takes a MagMLP (a GrandPlusMLP goes to step.TrainStep)")
@@ -99,6 +102,8 @@ class MagTrainStep(TrainStep):
         if max_entries is not None:
             from .mag_det import check_max_entries
             check_max_entries(max_entries)
+        from .gather_chunk import resolve
+        self.segment_chunk = resolve(segment_chunk, self.deterministic, "MagTrainStep")
         if row_list not in (None, "bitmap"):
             raise ValueError(f"row_list must be None or 'bitmap', got {row_list!r}")
         if table_step is not None:
@@ -155,7 +160,7 @@ class MagTrainStep(TrainStep):
         X = self.model.emb_rows(*self.attr, self.rows, batch_rows=batch_rows, samples=S, dropnode_rate=self.dropnode_rate, seed=0,
                                 keep=self._node_keep, deterministic=self.deterministic,
                                 max_entries=self._max_entries(batch_rows.numel()), overflow=self._entries_flag,
-                                row_grad=self.row_grad)
+                                row_grad=self.row_grad, segment_chunk=self.segment_chunk)
         return X[None] if S == 1 else X
 
     # ---- what the fit loop validates with

@@ -413,26 +413,28 @@ class MagMLP(_MLPBase, nn.Module):
         self.node_norm = node_norm
         self.reset_param()
 
-    def emb(self, attr_idx, node_idx, attr_data, seed=None, keep=None, deterministic=None):
+    def emb(self, attr_idx, node_idx, attr_data, seed=None, keep=None, deterministic=None, segment_chunk=None):
         """MLP.emb (model_mag.py:48-55) through embedding.embedding_bag (the reference's COO arguments); `deterministic`
-        is passed through."""
+        and `segment_chunk` are passed through."""
         from .embedding import embedding_bag
         return embedding_bag(self.embeds.weight, attr_idx, node_idx, attr_data, self.input_droprate, self.training,
-                             seed, keep, deterministic=deterministic)
+                             seed, keep, deterministic=deterministic, segment_chunk=segment_chunk)
 
-    def emb_csr(self, attr_indptr, attr_indices, attr_data, nodes=None, seed=None, keep=None, deterministic=None):
+    def emb_csr(self, attr_indptr, attr_indices, attr_data, nodes=None, seed=None, keep=None, deterministic=None,
+                segment_chunk=None):
         """MLP.emb over the bags of `nodes` in a GPU-resident node-attribute CSR (embedding.embedding_bag_csr);
-        `deterministic` is passed through."""
+        `deterministic` and `segment_chunk` are passed through."""
         from .embedding import embedding_bag_csr
         return embedding_bag_csr(self.embeds.weight, attr_indptr, attr_indices, attr_data, nodes, self.input_droprate,
-                                 self.training, seed, keep, deterministic=deterministic)
+                                 self.training, seed, keep, deterministic=deterministic, segment_chunk=segment_chunk)
 
     def emb_rows(self, attr_indptr, attr_indices, attr_data, rows, batch_rows=None, samples=1, dropnode_rate=0.5, seed=None,
-                 keep=None, deterministic=None, max_entries=None, overflow=None, row_grad=None):
+                 keep=None, deterministic=None, max_entries=None, overflow=None, row_grad=None, segment_chunk=None):
         """MLP.emb of every neighbour of a batch of `rows` (a RowMatrix) and random_prop over them as one op
         (mag.mag_prop_rows): [B, H], or [S, B, H] for samples = S > 1, ready for `forward`.  `deterministic`,
         `max_entries` and `overflow` are passed through (the deterministic table gradient), and so is
-        `row_grad` (an optim_rows.RowGrad of `embeds.weight`: the table's gradient as a row list)."""
+        `row_grad` (an optim_rows.RowGrad of `embeds.weight`: the table's gradient as a row list) and
+        `segment_chunk` (the deterministic gradient's hub segments in chunks)."""
         from .mag import mag_prop_rows
         from .rows import RowMatrix
         if not isinstance(rows, RowMatrix):
@@ -440,7 +442,7 @@ class MagMLP(_MLPBase, nn.Module):
         return mag_prop_rows(self.embeds.weight, attr_indptr, attr_indices, attr_data, rows.col, rows.val, rows.filled, rows.K,
                              batch_rows, samples=samples, dropnode_rate=dropnode_rate, input_droprate=self.input_droprate,
                              training=self.training, seed=seed, keep=keep, deterministic=deterministic, max_entries=max_entries,
-                             overflow=overflow, row_grad=row_grad)
+                             overflow=overflow, row_grad=row_grad, segment_chunk=segment_chunk)
 
     def _layers(self):
         return [(fc, bn if self.use_bn else None, True, bool(self.node_norm), False, self.hidden_droprate)
