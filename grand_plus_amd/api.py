@@ -234,6 +234,11 @@ class Graph:
         return buf
 
     def set_option(self, key: str, value: int):
+        """gp_set_option (include/grandplus.h lists every key).  "kernel": 0 = choose per call, 1 = the general kernel, 2 = the
+        sketch kernel whenever the call allows it, 3 = the dense-LDS kernel on graphs of up to 6 720 nodes (Cora, Citeseer;
+        opt-in -- a call it cannot take runs what 0 would, `stats()["kernel"]` says which ran).  "dn_block_threads" (0, 256,
+        512, 1024) and "dn_csr_lds" (1 = stage the CSR into LDS when it fits) shape the dense kernel.  Raises ValueError for
+        an unknown key or a value out of range."""
         _native.raise_for_status(_native.lib().gp_set_option(self._h, key.encode(), int(value)))
 
 

@@ -12,6 +12,9 @@
 // CPU by tests/test_host_gfpush_plan.py).  This file gathers their inputs, calls them and applies the outcome with HIP calls.
 #include "gfpush_kernels.hpp"
 #include "gfpush_sketch.hpp"
+#ifndef GP_DIAG
+#include "gfpush_dense.hpp"
+#endif
 #include "gfpush_plan.hpp"
 #include "grandplus.h"
 
@@ -674,6 +677,84 @@ int enqueue_row_order(gp_graph* g, const CallArgs& a, bool acsr, hipStream_t s)
     return GP_OK;
 }
 
+// What every call does to the handle's per-call state before its launches: the recipe's coefficients go to the device, the
+// counters are zeroed -- in full for a timing run or after a reset, else the queue heads and retry counts (and the observed
+// maxima when they belong to another recipe).
+int begin_call_state(gp_graph* g, const CallArgs& a, u64* counters, bool timing)
+{
+    const hipStream_t s = a.s;
+    if (a.n_coef > g->coef_cap) {
+        if (g->d_coef) (void)hipFree(g->d_coef);
+        g->d_coef = nullptr; g->coef_cap = 0;
+        HIP_TRY(hipMalloc(&g->d_coef, sizeof(double) * (size_t)a.n_coef));
+        g->coef_cap = a.n_coef;
+    }
+    HIP_TRY(hipMemcpyAsync(g->d_coef, a.coef, sizeof(double) * (size_t)a.n_coef, hipMemcpyHostToDevice, s));
+    if (timing || g->reset_pending) {
+        HIP_TRY(hipMemsetAsync(counters, 0, sizeof(u64) * kNumCounters, s));
+        if (!timing) { g->reset_pending = false; g->rows_total = 0; }
+    } else {
+        HIP_TRY(hipMemsetAsync(counters, 0, sizeof(u64) * (kSkSlabFails + 1), s));  // the queue heads and the retry counts (per call: ADVICE r4)
+        if (g->est.recipe_changed)                                                          // maxima of another recipe must not size this one's slabs
+            HIP_TRY(hipMemsetAsync(counters + kMaxLevelEdges, 0, sizeof(u64) * 2, s));
+    }
+    g->est.recipe_changed = false;
+    return GP_OK;
+}
+
+#ifndef GP_DIAG
+static_assert(sizeof(DenseCtl) <= (size_t)kDenseCtlBytes, "DensePlan reserves kDenseCtlBytes for the dense kernel's control block");
+Kernel dense_kernel(int block, bool staged) {
+    return staged ? kernel_for<256, 512, 1024>(block, [](auto b) -> Kernel { return gfpush_dense_kernel<decltype(b)::value, true>; })
+                  : kernel_for<256, 512, 1024>(block, [](auto b) -> Kernel { return gfpush_dense_kernel<decltype(b)::value, false>; });
+}
+bool dense_takes(const gp_graph* g, const CallArgs& a) {
+    return dense_wanted(g->opt, g->n_nodes, g->nnz, a.n_coef, a.rmax, a.K, g->opt.lds_pad);
+}
+
+// One call on the dense kernel (option kernel = 3 on a graph within kDenseMaxNodes): no sketch or general plan, no workspace, no
+// row ordering -- the layout and shape are dense_plan's (gfpush_plan.hpp), the launch sits between the same two events.
+int enqueue_dense(gp_graph* g, const CallArgs& a, u64* counters, bool timing)
+{
+    const hipStream_t s = a.s;
+    DensePlan dn = dense_plan(g->opt, g->n_nodes, g->nnz, a.K, g->opt.lds_pad);
+    const Kernel k = dense_kernel(dn.block, dn.csr_lds);
+    int per_cu = 1;
+    int rc = resident_blocks(k, dn.block, dn.lds_bytes + g->opt.lds_pad, &per_cu);
+    if (rc) return rc;
+    dn = dense_plan(g->opt, g->n_nodes, g->nnz, a.K, g->opt.lds_pad, g->num_cus, per_cu, a.n_seeds);
+    rc = ensure_packed(g, s);                               // (column words are read under node_mask, packed or not)
+    if (rc) return rc;
+    rc = begin_call_state(g, a, counters, timing);
+    if (rc) return rc;
+    KParams kp = call_params(g, a, GeneralPlan(), counters);
+    kp.direct = 0; kp.queue_counter = kQueue; kp.retry_counter = kRetryRows;
+    kp.dn_hist = dn.off_hist; kp.dn_cur = dn.off_cur; kp.dn_next = dn.off_next; kp.dn_reserve = dn.off_reserve; kp.dn_marks = dn.off_marks;
+    kp.dn_indptr = dn.off_indptr; kp.dn_indices = dn.off_indices; kp.dn_npad = (u32)dn.n_pad; kp.dn_csr_lds = dn.csr_lds ? 1u : 0u;
+    HIP_TRY(hipEventRecord(g->ev0, s));
+    g->last_order_rows = 0;
+    if (a.n_seeds > 0) {
+        rc = launch_kernel(k, dn.block, kp, dn.workgroups, dn.lds_bytes + g->opt.lds_pad, s);
+        if (rc) return rc;
+    }
+    HIP_TRY(hipEventRecord(g->ev1, s));
+    HIP_TRY(hipMemcpyAsync(g->h_counters, counters, sizeof(u64) * kNumCounters, hipMemcpyDeviceToHost, s));
+    g->last_stream = s; g->est.last_call_rows = a.n_seeds; g->est.grown_for_call = false;
+    g->est.last_kind = 3; g->est.last_sk_soft = false;
+    if (timing) return GP_OK;
+    g->launched = true;
+    std::memset(&g->last, 0, sizeof g->last);
+    g->rows_total += a.n_seeds;
+    g->last.rows = g->rows_total;
+    g->last.kernel = 3;
+    g->last.workgroups = dn.workgroups; g->last.block_threads = dn.block; g->last.lds_bytes = dn.lds_bytes;
+    return GP_OK;
+}
+#else
+bool dense_takes(const gp_graph*, const CallArgs&) { return false; }          // (no dense kernel in the diagnostic build)
+int enqueue_dense(gp_graph*, const CallArgs&, u64*, bool) { return GP_OK; }
+#endif
+
 // Plans and enqueues one call on a.s: everything behind gp_gfpush_device's argument checks, for the caller's call and for
 // each timing run of calibrate_choice alike.
 int enqueue_call(gp_graph* g, const CallArgs& a, const CallShape& shape)
@@ -692,6 +773,8 @@ int enqueue_call(gp_graph* g, const CallArgs& a, const CallShape& shape)
         else if (qs != hipErrorNotReady) (void)hipGetLastError();
     }
 
+    if (dense_takes(g, a)) return enqueue_dense(g, a, counters, timing);
+
     SketchPlan sk; GeneralPlan gk;
     int rc = plan_sketch(g, a, shape, sk);
     if (rc) return rc;
@@ -701,22 +784,8 @@ int enqueue_call(gp_graph* g, const CallArgs& a, const CallShape& shape)
     if (rc) return rc;
     Workspace& w = g->ws;
 
-    if (a.n_coef > g->coef_cap) {
-        if (g->d_coef) (void)hipFree(g->d_coef);
-        g->d_coef = nullptr; g->coef_cap = 0;
-        HIP_TRY(hipMalloc(&g->d_coef, sizeof(double) * (size_t)a.n_coef));
-        g->coef_cap = a.n_coef;
-    }
-    HIP_TRY(hipMemcpyAsync(g->d_coef, a.coef, sizeof(double) * (size_t)a.n_coef, hipMemcpyHostToDevice, s));
-    if (timing || g->reset_pending) {
-        HIP_TRY(hipMemsetAsync(counters, 0, sizeof(u64) * kNumCounters, s));
-        if (!timing) { g->reset_pending = false; g->rows_total = 0; }
-    } else {
-        HIP_TRY(hipMemsetAsync(counters, 0, sizeof(u64) * (kSkSlabFails + 1), s));  // the queue heads and the retry counts (per call: ADVICE r4)
-        if (g->est.recipe_changed)                                                          // maxima of another recipe must not size this one's slabs
-            HIP_TRY(hipMemsetAsync(counters + kMaxLevelEdges, 0, sizeof(u64) * 2, s));
-    }
-    g->est.recipe_changed = false;
+    rc = begin_call_state(g, a, counters, timing);
+    if (rc) return rc;
     if (w.dirty) {
         hipLaunchKernelGGL(init_tables_kernel, dim3(4096), dim3(256), 0, s, w.est.resg, (u64)w.est.n_wg * w.est.resg_cap);
         if (w.big.n_wg > 0)
@@ -1079,8 +1148,13 @@ int gp_set_option(gp_graph* g, const char* key, int64_t value) {
         if (value < 0 || value > 120 * 1024) return fail(GP_ERR_INVALID_ARG, "lds_pad must be in [0, 122880]");
         g->opt.lds_pad = (int)(value & ~15ll);       // dynamic LDS the tables do not use: fewer workgroups per CU at the same table size (occupancy experiments)
     } else if (k == "kernel") {
-        if (value < 0 || value > 2) return fail(GP_ERR_INVALID_ARG, "kernel must be 0 (automatic), 1 (general) or 2 (sketch)");
+        if (value < 0 || value > 3) return fail(GP_ERR_INVALID_ARG, "kernel must be 0 (automatic), 1 (general), 2 (sketch) or 3 (dense)");
         g->opt.kernel = (int)value;
+    } else if (k == "dn_block_threads") {
+        if (value != 0 && value != 256 && value != 512 && value != 1024) return fail(GP_ERR_INVALID_ARG, "dn_block_threads must be 0, 256, 512 or 1024");
+        g->opt.dn_block = (int)value;
+    } else if (k == "dn_csr_lds") {
+        g->opt.dn_csr_lds = value ? 1 : 0;           // 1 = the dense kernel stages indptr + indices into LDS when they fit beside the row state
     } else if (k == "sk_block_threads") {
         if (value != 0 && value != 512 && value != 768 && value != 1024) return fail(GP_ERR_INVALID_ARG, "sk_block_threads must be 0, 512, 768 or 1024");
         g->opt.sk_block = (int)value;
@@ -1135,7 +1209,7 @@ int gp_set_option(gp_graph* g, const char* key, int64_t value) {
         return fail(GP_ERR_INVALID_ARG, "unknown option '%s'", key);
     }
     // what was measured holds for the launch shapes it was measured with
-    if (k == "max_workgroups" || k == "workspace_mb" || k == "lds_pad" || k == "est_level_edges" || k.rfind("sk_", 0) == 0 ||
+    if (k == "max_workgroups" || k == "workspace_mb" || k == "lds_pad" || k == "est_level_edges" || k.rfind("sk_", 0) == 0 || k.rfind("dn_", 0) == 0 ||
         k == "solo_levels" || k == "seedrow" || k == "direct_tables") g->choices.clear();
     return GP_OK;
 }

@@ -325,6 +325,9 @@ struct KParams {
     int diag_flags;                       // GP_DIAG builds only (instruction attribution by difference): bit 0 = skip TOP-K, bit 1 = run EXPAND twice, bit 2 = walk the drained table once more
     int pad_df;
     u64* wg_log;                          // -DGP_SK_TIMING only (else NULL): per workgroup of the sketch launch { stamp at entry, stamp at leaving the row loop } (tools/sk_phases.py)
+    // dense kernel (gfpush_dense.hpp): byte offsets of its LDS arrays (DensePlan, gfpush_plan.hpp), the node count rounded up to
+    // whole 64-node chunks, and whether indptr + indices are staged into LDS
+    u32 dn_hist, dn_cur, dn_next, dn_reserve, dn_marks, dn_indptr, dn_indices, dn_npad, dn_csr_lds, dn_pad;
 };
 // The launch parameters where the hardware put them: the kernel argument segment (KParams is the kernels' only argument),
 // read with scalar loads.  __builtin_amdgcn_kernarg_segment_ptr() is only meaningful inside the kernel function itself

@@ -42,6 +42,7 @@ struct Options {
     int64_t est_level_edges = 0;                                           // option: edges per level the first-launch slabs are sized for (0 = automatic)
     int measure_choice = 1;                                                // 0 = kernel and launch shape from the thresholds alone, never from a calibration
     int max_degree_bits = 31;                                              // most bits of a column word the packed degree may take (0 = plain column ids); set before the first gfpush call, which packs
+    int dn_block = 0; int dn_csr_lds = 0;                                  // options of the dense kernel (kernel = 3): threads per workgroup (0 = default; 256, 512, 1024); 1 = indptr + indices are staged into LDS when they fit beside the row state
 };
 
 // The running estimate of what a row of the recipe needs, with the memory of a recipe the sketch kernel was switched off for.
@@ -271,6 +272,7 @@ inline Held held_after(const Held& held, const WorkspacePlan& p) {
 inline void grow_estimate(Estimate& e, int64_t est_level_edges, int64_t rows_n, double outgrown, double handed_back) {
     if (est_level_edges != 0 || e.grown_for_call || rows_n <= 0) return;
     e.grown_for_call = true;
+    if (e.last_kind == 3) return;                                      // (the dense kernel used no slab: nothing to grow from)
     const double rows = (double)rows_n;
     if (outgrown > 0.02 * rows) e.edges = std::max(e.edges, 2.0 * e.cur_edges);
     else if (outgrown > 0.001 * rows) e.edges = std::max(e.edges, 1.5 * e.cur_edges);
@@ -470,6 +472,66 @@ inline bool prune_allowed(const Options& opt, const double* coef, int n_coef) {
 // the diagnostic build instruments the general kernel on the packed CSR only).
 inline bool general_wants_acsr(bool diag_build, const Options& opt, bool direct, int64_t n_nodes, int64_t n_seeds) {
     return !diag_build && opt.gk_acsr && !direct && !opt.force_global && n_nodes >= 65536 && n_seeds > 0;
+}
+
+// ------------------------------------------------------------------ the dense kernel (option kernel = 3)
+
+// The dense kernel (gfpush_dense.hpp) keeps a row's whole state in one workgroup's LDS, indexed by node id over the node count
+// rounded up to whole 64-node chunks (one wave's step):
+//   [ control block | select histogram | cur f64 | next f64 | reserve f64 | touched marks, one 64-bit word per chunk | indptr | indices ]
+// 24 bytes per node + 1 bit, the last two arrays only when the CSR is staged.  TOP-K's list of selected (value, column) pairs
+// -- min(K, N) entries of 16 bytes -- lives in cur | next, which are dead by then, so K does not enter the layout.
+constexpr int kDenseLds = 163840;              // LDS of a CU: the most one workgroup can own
+constexpr int kDenseCtlBytes = 512;            // control block (DenseCtl: the row, the select's state, statistics, coefficients)
+constexpr int kDenseHistBytes = 1024;          // 256 bins of the radix select
+constexpr int64_t kDenseMaxNodes = 6720;       // the largest multiple of 64 whose state fits: 1536 + 6720 * 24 + 6720 / 8 = 163 656 bytes
+static_assert(kDenseCtlBytes + kDenseHistBytes + kDenseMaxNodes * 24 + kDenseMaxNodes / 8 <= kDenseLds &&
+              kDenseCtlBytes + kDenseHistBytes + (kDenseMaxNodes + 64) * 24 + (kDenseMaxNodes + 64) / 8 > kDenseLds && kDenseMaxNodes >= 5120,
+              "kDenseMaxNodes is the cap the LDS layout gives");
+
+struct DensePlan {
+    bool fits = false;                         // the row state fits beside lds_pad (else nothing below is meaningful)
+    bool csr_lds = false;                      // indptr + indices are staged into LDS
+    int lds_bytes = 0, block = 0, workgroups = 0;
+    int64_t n_pad = 0;                         // nodes rounded up to whole chunks: the length of cur / next / reserve
+    unsigned off_hist = 0, off_cur = 0, off_next = 0, off_reserve = 0, off_marks = 0, off_indptr = 0, off_indices = 0, state_end = 0;   // byte offsets
+};
+
+// The layout and launch shape of a dense-kernel call.  per_cu = workgroups of that shape the shell has measured to fit a CU
+// (0: not asked yet -- workgroups stays 0).
+inline DensePlan dense_plan(const Options& opt, int64_t n_nodes, int64_t nnz, int K, int lds_pad, int num_cus = 0, int per_cu = 0, int64_t n_seeds = 0) {
+    DensePlan d;
+    (void)K;
+    if (n_nodes < 1 || n_nodes > kDenseMaxNodes || nnz < 0) return d;
+    d.n_pad = (n_nodes + 63) & ~(int64_t)63;
+    size_t q = (size_t)kDenseCtlBytes;
+    d.off_hist = (unsigned)q;    q += (size_t)kDenseHistBytes;
+    d.off_cur = (unsigned)q;     q += 8 * (size_t)d.n_pad;
+    d.off_next = (unsigned)q;    q += 8 * (size_t)d.n_pad;
+    d.off_reserve = (unsigned)q; q += 8 * (size_t)d.n_pad;
+    d.off_marks = (unsigned)q;   q += (size_t)d.n_pad / 8;
+    d.state_end = (unsigned)q;
+    const size_t room = (size_t)kDenseLds - (size_t)std::min(std::max(lds_pad, 0), kDenseLds);
+    if (q > room) return d;
+    d.fits = true;
+    const size_t csr = ((4 * (size_t)(n_nodes + 1) + 7) & ~(size_t)7) + ((4 * (size_t)nnz + 7) & ~(size_t)7);
+    if (opt.dn_csr_lds && q + csr <= room) {
+        d.csr_lds = true;
+        d.off_indptr = (unsigned)q;  q += (4 * (size_t)(n_nodes + 1) + 7) & ~(size_t)7;
+        d.off_indices = (unsigned)q; q += (4 * (size_t)nnz + 7) & ~(size_t)7;
+    }
+    d.lds_bytes = (int)((q + 15) & ~(size_t)15);
+    d.block = opt.dn_block ? opt.dn_block : 512;
+    if (per_cu > 0) d.workgroups = cap_workgroups(num_cus * per_cu, opt.max_workgroups, n_seeds);
+    return d;
+}
+
+// Whether the dense kernel takes the call: only when option kernel = 3 asks for it, the graph is within the node cap and its
+// state fits the LDS that lds_pad leaves.  Any sign of coef, any n_coef >= 1, K <= 1024 and rmax >= 0 are fine.
+inline bool dense_wanted(const Options& opt, int64_t n_nodes, int64_t nnz, int n_coef, double rmax, int K, int lds_pad) {
+    if (opt.kernel != 3 || n_nodes < 1 || n_nodes > kDenseMaxNodes) return false;
+    if (n_coef < 1 || K < 1 || K > 1024 || !(rmax >= 0.0)) return false;
+    return dense_plan(opt, n_nodes, nnz, K, lds_pad).fits;
 }
 
 // ------------------------------------------------------------------ measured choice

@@ -77,7 +77,11 @@ typedef struct gp_stats {
     /* ABI 3: which kernel ran the rows.  2 = the sketch-filtered kernel (csrc/gfpush_sketch.hpp: keyless fixed-point upper
      * bounds decide which targets get an exact fp64 accumulator; `frontier` and `support` are not counted by it and stay 0,
      * its log holds one record per pushed edge, so max_log_records counts edges), 1 = the general kernel
-     * (csrc/gfpush_kernels.hpp), which also re-runs the rows the sketch kernel hands back (retried_rows). */
+     * (csrc/gfpush_kernels.hpp), which also re-runs the rows the sketch kernel hands back (retried_rows).  3 = the dense-LDS
+     * kernel (csrc/gfpush_dense.hpp, option "kernel" = 3): pushes, edges, filled, frontier and support (the sum over rows of the
+     * nodes a row touched: the size of the reference's reserve map) are always exact, lds_levels counts the levels it swept,
+     * max_level_edges is the real maximum; global_levels, retried_rows, degree_lookups, max_log_records, workspace_bytes,
+     * lds_slots and the sketch fields stay 0; lds_bytes is what its layout needs, not the whole CU's. */
     int32_t kernel;
     int32_t sketch_pad;
     int64_t sketch_candidate_edges;  /* pushed edges whose target might push and went into the exact table (of `edges`) */
@@ -212,7 +216,17 @@ int gp_reset_stats(gp_graph* g);
  *                      level start to finish, the others park at one barrier)
  *   "kernel"          0 = choose per call (default), 1 = always the general kernel, 2 = the sketch-filtered kernel whenever
  *                      the call allows it (all coef >= 0, at most 40 levels, K <= 128, rmax > 0).  Automatic choice: the
- *                      sketch kernel for rmax >= 5e-6 on graphs of >= 65 536 nodes
+ *                      sketch kernel for rmax >= 5e-6 on graphs of >= 65 536 nodes.
+ *                      3 = the dense-LDS kernel on graphs of up to 6 720 nodes (Cora, Citeseer): a row's residues, reserve and
+ *                      touched marks are plain fp64 arrays indexed by node id in one workgroup's LDS -- no hash table, no push
+ *                      list, no reserve log, no workspace.  Any coef, n_coef >= 1, K <= 1024, rmax >= 0.  Opt-in: the
+ *                      automatic choice never picks it and it is never calibrated.  On a call it cannot take (a larger
+ *                      graph, "lds_pad" leaving no room for its state) kernel = 3 runs what kernel = 0 would; gp_stats.kernel
+ *                      says which kernel ran, and that is not an error.  Same contract as the other kernels: slots
+ *                      0..filled-1 by (value desc, column asc), last bits of sums depend on the order of the adds
+ *   "dn_block_threads" / "dn_csr_lds"   the dense kernel's shape: 0 (default: 512) | 256 | 512 | 1024 threads per workgroup;
+ *                      1 = indptr + indices are staged into LDS once per workgroup when they fit beside the row state (default
+ *                      0: the CSR is read from memory -- staging costs a workgroup per CU and measured slower)
  *   "sk_block_threads" / "sk_lg_mu" / "sk_lg_mr" / "sk_target"   geometry of the sketch kernel (0 = default): threads per
  *                      workgroup (512 = three per CU with 52 KB, 768 = two with 80 KB, 1024 = one with 160 KB: measurements
  *                      only), log2 cells of the level sketch and of the reserve sketch, cell rank of the first TOP-K
