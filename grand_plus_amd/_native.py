@@ -269,6 +269,39 @@ ABI = {
     },
 }
 
+# The entry points outside C ABI 4: extern "C" symbols of libgrandplus.so whose prototypes stand in the private headers
+# csrc/*_abi.hpp, not under include/, so GP_ABI_VERSION and ABI above stay what they are.  Private header -> entry point ->
+# (restype, argtypes, False), under the same convention; tests/test_host_abi.py holds both tables against their headers.  No
+# private name is required: lib() declares the ones the library has, and calling one it lacks raises (_missing).
+_rows_step = [_int, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _int, _f32, _f32, _f64, _f64, _f32, _f32]   # device .. weight_decay
+# a chunked twin takes its unchunked twin's arguments up to the stream, then chunk, d_scratch, scratch_bytes and the stream
+_scatter, _chunk = ABI["grandplus_scatter.h"], [_i32, _vp, _i64, _vp]
+PRIVATE_ABI = {
+    "mag_det_abi.hpp": {
+        "gp_mag_det_keys": (_int, [_int, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _i32, _i64, _vp, _vp, _vp, _vp], False),
+        "gp_mag_prop_rows_backward_det": (_int, [_int, _vp] + _mag + [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp], False),
+    },
+    "optim_rows_abi.hpp": {
+        "gp_optim_rows_sqnorm": (_int, [_int, _vp, _i64, _i64, _i32, _vp, _int, _vp, _vp], False),
+        "gp_clip_adam_rows": (_int, _rows_step + [_f32, _f32, _vp, _vp, _vp], False),
+        "gp_clip_adam_rows_dev": (_int, _rows_step + [_vp, _vp, _vp, _vp, _vp], False),
+    },
+    "row_mark_abi.hpp": {
+        "gp_row_mark_mag": (_int, [_int, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _vp], False),
+        "gp_row_list_compact": (_int, [_int, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp], False),
+        "gp_row_list_zero": (_int, [_int, _vp, _i64, _i64, _i32, _vp, _vp], False),
+    },
+    "fit_rows_abi.hpp": {
+        "gp_fit_rows_mark": (_int, [_int, _vp, _i64, _i64, _vp, _vp], False),
+        "gp_fit_rows_snapshot": (_int, [_int, _vp, _vp, _vp, _i64, _i32, _vp, _vp], False),
+    },
+    "gather_chunk_abi.hpp": {
+        "gp_random_prop_rows_backward_det_chunked": (_int, _scatter["gp_random_prop_rows_backward_det"][1][:-1] + _chunk, False),
+        "gp_embedding_bag_backward_det_chunked": (_int, _scatter["gp_embedding_bag_backward_det"][1][:-1] + _chunk, False),
+        "gp_mag_prop_rows_backward_det_chunked": (_int, [_int, _vp] + _mag + [_vp, _vp, _vp, _i64, _vp, _vp, _vp] + _chunk, False),
+    },
+}
+
 _LIB = None
 
 
@@ -297,7 +330,7 @@ def lib():
     except ImportError:
         pass
     L = ctypes.CDLL(LIB_PATH)
-    for entries in ABI.values():
+    for entries in (*ABI.values(), *PRIVATE_ABI.values()):
         for name, (restype, argtypes, required) in entries.items():
             if not required and not hasattr(L, name):
                 setattr(L, name, _missing(name))

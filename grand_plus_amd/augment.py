@@ -139,7 +139,7 @@ def _rows_backward_det(grad_out, col, val, filled, K, batch_rows, B, N, samples,
     else:
         from . import gather_chunk
         scratch, nbytes = gather_chunk.scratch(keys.numel(), segment_chunk, F, g.device)
-        rc = gather_chunk.lib().gp_random_prop_rows_backward_det_chunked(*args, segment_chunk, scratch.data_ptr(), nbytes, _stream(g))
+        rc = _native.lib().gp_random_prop_rows_backward_det_chunked(*args, segment_chunk, scratch.data_ptr(), nbytes, _stream(g))
     _native.raise_for_status(rc)
     return grad
 

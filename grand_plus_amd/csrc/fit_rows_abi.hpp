@@ -3,9 +3,9 @@
  * csrc/fit_rows.hip).
  *
  * NOT part of C ABI 4: these are extern "C" symbols of libgrandplus.so that no public header declares, as
- * mag_det_abi.hpp's, optim_rows_abi.hpp's and row_mark_abi.hpp's.  The one caller is grand_plus_amd/fit.py, which binds them
- * through its own table (fit.ROWS_ABI) under the convention of _native.ABI: d_* and void* travel as c_void_p, scalars map
- * one to one.  tests/test_host_fit_rows.py holds that table against this file.
+ * mag_det_abi.hpp's, optim_rows_abi.hpp's and row_mark_abi.hpp's.  The one caller is grand_plus_amd/fit.py;
+ * _native.PRIVATE_ABI binds them, under this file's name and the convention of _native.ABI: d_* and void* travel as
+ * c_void_p, scalars map one to one.  tests/test_host_abi.py holds that table against this file.
  *
  * gp_fit_snapshot (grandplus_fit.h) copies every tensor of the model whole when the early-stop rule takes a new best.
  * Under the lazy table step (optim_rows_abi.hpp) only the rows a batch's bags name ever change, and the row lists of

@@ -131,13 +131,16 @@ gather_fold_kernel(const long long* __restrict__ keys, long long n_sorted, long 
     }
 }
 
+// What a chunked entry point takes beyond its unchunked twin; a body that serves both takes a pointer to one, null for the twin.
+struct Chunking { int32_t chunk; float* d_scratch; int64_t scratch_bytes; };
+
 // The checks the three chunked entry points share: the chunk length and the caller's scratch.
-int chunk_check(const char* where, int32_t chunk, int64_t n_sorted, int32_t width, const void* d_scratch, int64_t scratch_bytes)
+int chunk_check(const char* where, const Chunking& c, int64_t n_sorted, int32_t width)
 {
-    if (!gp_gather_chunk::chunk_ok(chunk)) return fail(GP_ERR_INVALID_ARG, where, "chunk is not a power of two in [64, 4096]");
-    const int64_t need = n_sorted > 0 && width > 0 ? gp_gather_chunk::scratch_bytes(n_sorted, chunk, width) : 0;
-    if (scratch_bytes < need) return fail(GP_ERR_INVALID_ARG, where, "the scratch is smaller than GP_GATHER_CHUNK_SCRATCH_BYTES");
-    if (need > 0 && !d_scratch) return fail(GP_ERR_NULL, where, "the scratch pointer is NULL");
+    if (!gp_gather_chunk::chunk_ok(c.chunk)) return fail(GP_ERR_INVALID_ARG, where, "chunk is not a power of two in [64, 4096]");
+    const int64_t need = n_sorted > 0 && width > 0 ? gp_gather_chunk::scratch_bytes(n_sorted, c.chunk, width) : 0;
+    if (c.scratch_bytes < need) return fail(GP_ERR_INVALID_ARG, where, "the scratch is smaller than GP_GATHER_CHUNK_SCRATCH_BYTES");
+    if (need > 0 && !c.d_scratch) return fail(GP_ERR_NULL, where, "the scratch pointer is NULL");
     return GP_OK;
 }
 

@@ -2,10 +2,10 @@
  * gather_chunk_abi.hpp -- the entry points of the chunked deterministic gradients (implemented by
  * csrc/scatter_det.hip and csrc/mag_det.hip over the kernels of csrc/gather_chunk.hpp).
  *
- * NOT part of C ABI 4: these are extern "C" symbols of libgrandplus.so that no public header declares.  The one caller
- * is grand_plus_amd/gather_chunk.py, which binds them through its own table (gather_chunk.ABI) under the convention of
- * _native.ABI: d_* and void* travel as c_void_p, scalars map one to one.  tests/test_host_gather_chunk.py holds that table
- * against this file.
+ * NOT part of C ABI 4: these are extern "C" symbols of libgrandplus.so that no public header declares.  The callers are
+ * the three deterministic backwards (augment.py, embedding.py, mag_det.py, with gather_chunk.py's scratch);
+ * _native.PRIVATE_ABI binds them, under this file's name and the convention of _native.ABI: d_* and void* travel as
+ * c_void_p, scalars map one to one.  tests/test_host_abi.py holds that table against this file.
  *
  * Each is its unchunked twin (gp_random_prop_rows_backward_det and gp_embedding_bag_backward_det of grandplus_scatter.h,
  * gp_mag_prop_rows_backward_det of mag_det_abi.hpp) with three more arguments before the stream: chunk, d_scratch and

@@ -214,6 +214,50 @@ int slots_check(const char* where, int32_t K, int32_t n_batch, int64_t max_entri
     return GP_OK;
 }
 
+// gp_mag_prop_rows_backward_det and its chunked twin: the checks, U and inv and the Op are the same, the gather is
+// gather_sum_kernel, or with a Chunking gather_chunk.hpp's.  where: the entry point that was called.
+int mag_backward_det(const char* where, int device, const float* d_grad_out, int64_t n_vocab, int32_t dim,
+                     const int64_t* d_attr_indptr, const int32_t* d_attr_indices, const float* d_attr_data, int64_t n_nodes,
+                     const int32_t* d_col, const double* d_val, const int32_t* d_filled, int64_t n_rows, int32_t K,
+                     const int32_t* d_batch_rows, int32_t n_batch, int32_t n_samples, float dropnode_rate, float input_droprate,
+                     int training, uint64_t seed, const uint8_t* d_keep, int64_t keep_stride, const int64_t* d_slot_base,
+                     const int64_t* d_order, const int64_t* d_sorted_keys, int64_t max_entries, float* d_slot_grad, float* d_inv,
+                     float* d_dW, const Chunking* chunking, void* stream)
+{
+    if (const int rc = mag_check(where, n_vocab, dim, n_nodes, n_rows, K, n_batch, n_samples, dropnode_rate, input_droprate,
+                                 d_keep, keep_stride)) return rc;
+    if (training && input_droprate > 0.0f)
+        return fail(GP_ERR_INVALID_ARG, where, "input dropout is not supported by the deterministic backward (DESIGN §9)");
+    if (const int rc = slots_check(where, K, n_batch, max_entries)) return rc;
+    if (chunking)
+        if (const int rc = chunk_check(where, *chunking, n_batch == 0 ? 0 : max_entries, dim)) return rc;
+    if (n_batch == 0) return GP_OK;
+    if (!d_grad_out || !d_attr_indptr || !d_attr_indices || !d_attr_data || !d_col || !d_val || !d_slot_base || !d_order ||
+        !d_sorted_keys || !d_slot_grad || !d_inv || !d_dW)
+        return fail(GP_ERR_NULL, where, "a device pointer is NULL");
+    if (const int rc = set_device(device, where)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const int n_waves = waves_for(K);
+    const int nsc = std::min<int>(n_samples, (kLdsFloats - K - kMaxSamples) / K);
+    const size_t lds = (size_t)(K + kMaxSamples + nsc * K) * 4;
+    const MagArgs A = {n_vocab, dim, (const long long*)d_attr_indptr, d_attr_indices, d_attr_data, n_nodes, d_col, d_val, d_filled,
+                       n_rows, K, d_batch_rows, n_batch, n_samples, nsc, dropnode_rate, 0.0f, training, (u64)seed,
+                       d_keep, (long long)keep_stride};
+    hipLaunchKernelGGL(mag_slot_grad_kernel, dim3(std::min<int>(n_batch, kGridCap)), dim3(n_waves * 64), lds, s, d_grad_out, A,
+                       d_slot_grad, d_inv);
+    if (const int rc = launch_status("mag_slot_grad_kernel")) return rc;
+    const MagOp op = {d_slot_grad, dim, {(const long long*)d_attr_indptr, d_attr_indices, n_nodes, n_vocab, d_col, d_filled, n_rows, K,
+                                         d_batch_rows},
+                      d_attr_data, (const long long*)d_slot_base, (long long)n_batch * K, (long long)max_entries};
+    if (!chunking) {
+        hipLaunchKernelGGL(gather_sum_kernel<MagOp>, dim3(gather_grid(max_entries)), dim3(kGather), 0, s, op, (const long long*)d_order,
+                           (const long long*)d_sorted_keys, (long long)max_entries, (long long)n_vocab, dim, d_dW);
+        return launch_status("gather_sum_kernel<MagOp>");
+    }
+    return gather_chunked(op, "gather_chunk_kernel<MagOp>", d_order, d_sorted_keys, max_entries, n_vocab, dim, chunking->chunk, d_dW,
+                          chunking->d_scratch, s);
+}
+
 }  // namespace
 
 extern "C" {
@@ -254,33 +298,10 @@ int gp_mag_prop_rows_backward_det(int device, const float* d_grad_out, int64_t n
                                   const int64_t* d_order, const int64_t* d_sorted_keys, int64_t max_entries,
                                   float* d_slot_grad, float* d_inv, float* d_dW, void* stream)
 {
-    const char* where = "gp_mag_prop_rows_backward_det";
-    if (const int rc = mag_check(where, n_vocab, dim, n_nodes, n_rows, K, n_batch, n_samples, dropnode_rate, input_droprate,
-                                 d_keep, keep_stride)) return rc;
-    if (training && input_droprate > 0.0f)
-        return fail(GP_ERR_INVALID_ARG, where, "input dropout is not supported by the deterministic backward (DESIGN §9)");
-    if (const int rc = slots_check(where, K, n_batch, max_entries)) return rc;
-    if (n_batch == 0) return GP_OK;
-    if (!d_grad_out || !d_attr_indptr || !d_attr_indices || !d_attr_data || !d_col || !d_val || !d_slot_base || !d_order ||
-        !d_sorted_keys || !d_slot_grad || !d_inv || !d_dW)
-        return fail(GP_ERR_NULL, where, "a device pointer is NULL");
-    if (const int rc = set_device(device, where)) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    const int n_waves = waves_for(K);
-    const int nsc = std::min<int>(n_samples, (kLdsFloats - K - kMaxSamples) / K);
-    const size_t lds = (size_t)(K + kMaxSamples + nsc * K) * 4;
-    const MagArgs A = {n_vocab, dim, (const long long*)d_attr_indptr, d_attr_indices, d_attr_data, n_nodes, d_col, d_val, d_filled,
-                       n_rows, K, d_batch_rows, n_batch, n_samples, nsc, dropnode_rate, 0.0f, training, (u64)seed,
-                       d_keep, (long long)keep_stride};
-    hipLaunchKernelGGL(mag_slot_grad_kernel, dim3(std::min<int>(n_batch, kGridCap)), dim3(n_waves * 64), lds, s, d_grad_out, A,
-                       d_slot_grad, d_inv);
-    if (const int rc = launch_status("mag_slot_grad_kernel")) return rc;
-    const MagOp op = {d_slot_grad, dim, {(const long long*)d_attr_indptr, d_attr_indices, n_nodes, n_vocab, d_col, d_filled, n_rows, K,
-                                         d_batch_rows},
-                      d_attr_data, (const long long*)d_slot_base, (long long)n_batch * K, (long long)max_entries};
-    hipLaunchKernelGGL(gather_sum_kernel<MagOp>, dim3(gather_grid(max_entries)), dim3(kGather), 0, s, op, (const long long*)d_order,
-                       (const long long*)d_sorted_keys, (long long)max_entries, (long long)n_vocab, dim, d_dW);
-    return launch_status("gather_sum_kernel<MagOp>");
+    return mag_backward_det("gp_mag_prop_rows_backward_det", device, d_grad_out, n_vocab, dim, d_attr_indptr, d_attr_indices,
+                            d_attr_data, n_nodes, d_col, d_val, d_filled, n_rows, K, d_batch_rows, n_batch, n_samples, dropnode_rate,
+                            input_droprate, training, seed, d_keep, keep_stride, d_slot_base, d_order, d_sorted_keys, max_entries,
+                            d_slot_grad, d_inv, d_dW, nullptr, stream);
 }
 
 // The chunked twin (gather_chunk_abi.hpp states its contract): U and inv as above, the gather cut into chunks of
@@ -295,36 +316,11 @@ int gp_mag_prop_rows_backward_det_chunked(int device, const float* d_grad_out, i
                                           float* d_slot_grad, float* d_inv, float* d_dW, int32_t chunk, float* d_scratch,
                                           int64_t scratch_bytes, void* stream)
 {
-    // The checks, the LDS sizing, MagArgs / MagOp and the launch of mag_slot_grad_kernel below are
-    // gp_mag_prop_rows_backward_det's own lines, repeated here because that entry point stays byte for byte what it was.
-    // tests/test_host_gather_chunk.py holds the two copies together; a change to one belongs in the other (a shared helper
-    // is the later remedy).
-    const char* where = "gp_mag_prop_rows_backward_det_chunked";
-    if (const int rc = mag_check(where, n_vocab, dim, n_nodes, n_rows, K, n_batch, n_samples, dropnode_rate, input_droprate,
-                                 d_keep, keep_stride)) return rc;
-    if (training && input_droprate > 0.0f)
-        return fail(GP_ERR_INVALID_ARG, where, "input dropout is not supported by the deterministic backward (DESIGN §9)");
-    if (const int rc = slots_check(where, K, n_batch, max_entries)) return rc;
-    if (const int rc = chunk_check(where, chunk, n_batch == 0 ? 0 : max_entries, dim, d_scratch, scratch_bytes)) return rc;
-    if (n_batch == 0) return GP_OK;
-    if (!d_grad_out || !d_attr_indptr || !d_attr_indices || !d_attr_data || !d_col || !d_val || !d_slot_base || !d_order ||
-        !d_sorted_keys || !d_slot_grad || !d_inv || !d_dW)
-        return fail(GP_ERR_NULL, where, "a device pointer is NULL");
-    if (const int rc = set_device(device, where)) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    const int n_waves = waves_for(K);
-    const int nsc = std::min<int>(n_samples, (kLdsFloats - K - kMaxSamples) / K);
-    const size_t lds = (size_t)(K + kMaxSamples + nsc * K) * 4;
-    const MagArgs A = {n_vocab, dim, (const long long*)d_attr_indptr, d_attr_indices, d_attr_data, n_nodes, d_col, d_val, d_filled,
-                       n_rows, K, d_batch_rows, n_batch, n_samples, nsc, dropnode_rate, 0.0f, training, (u64)seed,
-                       d_keep, (long long)keep_stride};
-    hipLaunchKernelGGL(mag_slot_grad_kernel, dim3(std::min<int>(n_batch, kGridCap)), dim3(n_waves * 64), lds, s, d_grad_out, A,
-                       d_slot_grad, d_inv);
-    if (const int rc = launch_status("mag_slot_grad_kernel")) return rc;
-    const MagOp op = {d_slot_grad, dim, {(const long long*)d_attr_indptr, d_attr_indices, n_nodes, n_vocab, d_col, d_filled, n_rows, K,
-                                         d_batch_rows},
-                      d_attr_data, (const long long*)d_slot_base, (long long)n_batch * K, (long long)max_entries};
-    return gather_chunked(op, "gather_chunk_kernel<MagOp>", d_order, d_sorted_keys, max_entries, n_vocab, dim, chunk, d_dW, d_scratch, s);
+    const Chunking chunking = {chunk, d_scratch, scratch_bytes};
+    return mag_backward_det("gp_mag_prop_rows_backward_det_chunked", device, d_grad_out, n_vocab, dim, d_attr_indptr, d_attr_indices,
+                            d_attr_data, n_nodes, d_col, d_val, d_filled, n_rows, K, d_batch_rows, n_batch, n_samples, dropnode_rate,
+                            input_droprate, training, seed, d_keep, keep_stride, d_slot_base, d_order, d_sorted_keys, max_entries,
+                            d_slot_grad, d_inv, d_dW, &chunking, stream);
 }
 
 }  // extern "C"

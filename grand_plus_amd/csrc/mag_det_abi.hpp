@@ -2,9 +2,9 @@
  * mag_det_abi.hpp -- the entry points of MAG's deterministic table gradient (implemented by csrc/mag_det.hip).
  *
  * NOT part of C ABI 4: these are extern "C" symbols of libgrandplus.so that no public header declares.  The one caller
- * is grand_plus_amd/mag_det.py, which binds them through its own table (mag_det.ABI) under the convention of _native.ABI:
- * d_* and void* travel as c_void_p, scalars map one to one.  tests/test_host_mag_det.py holds that table against this
- * file.  Promoting them to a public header is a later change, together with the ABI test.
+ * is grand_plus_amd/mag_det.py; _native.PRIVATE_ABI binds them, under this file's name and the convention of _native.ABI:
+ * d_* and void* travel as c_void_p, scalars map one to one.  tests/test_host_abi.py holds that table against this file.
+ * Promoting them to a public header is a later change.
  *
  * They are the backward of gp_mag_prop_rows (grandplus_mag.h) without atomics on dW: sort-then-gather, as
  * grandplus_scatter.h's two.  The operands named as in grandplus_mag.h mean what they mean there, and the bounds rules are

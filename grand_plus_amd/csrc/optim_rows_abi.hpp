@@ -3,9 +3,9 @@
  * csrc/optim_rows.hip).
  *
  * NOT part of C ABI 4: these are extern "C" symbols of libgrandplus.so that no public header declares, as
- * mag_det_abi.hpp's.  The one caller is grand_plus_amd/optim_rows.py, which binds them through its own table
- * (optim_rows.ABI) under the convention of _native.ABI: d_* and void* travel as c_void_p, scalars map one to one.
- * tests/test_host_optim_rows.py holds that table against this file.
+ * mag_det_abi.hpp's.  The one caller is grand_plus_amd/optim_rows.py; _native.PRIVATE_ABI binds them, under this file's
+ * name and the convention of _native.ABI: d_* and void* travel as c_void_p, scalars map one to one.
+ * tests/test_host_abi.py holds that table against this file.
  *
  * The table is d_param float [n_vocab, dim] with Adam's d_exp_avg and d_exp_avg_sq of the same shape.  Its gradient is
  * d_dW float [n_vocab, dim] TOGETHER WITH d_keys int64 [n_sorted], ascending: the sorted key list of

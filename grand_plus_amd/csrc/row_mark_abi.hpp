@@ -3,9 +3,9 @@
  * csrc/row_mark.hip).
  *
  * NOT part of C ABI 4: these are extern "C" symbols of libgrandplus.so that no public header declares, as
- * mag_det_abi.hpp's and optim_rows_abi.hpp's.  The one caller is grand_plus_amd/optim_rows.py, which binds them through
- * its own table (optim_rows.MARK_ABI) under the convention of _native.ABI: d_* and void* travel as c_void_p, scalars map
- * one to one.  tests/test_host_row_mark.py holds that table against this file.
+ * mag_det_abi.hpp's and optim_rows_abi.hpp's.  The one caller is grand_plus_amd/optim_rows.py; _native.PRIVATE_ABI binds
+ * them, under this file's name and the convention of _native.ABI: d_* and void* travel as c_void_p, scalars map one to
+ * one.  tests/test_host_abi.py holds that table against this file.
  *
  * The atomic backward (gp_mag_prop_rows_backward, grandplus_mag.h) adds into a dense dW and keeps no list of the rows it
  * added into.  Here the rows a batch CAN touch are marked in a bitmap of n_vocab bits (csrc/row_mark_layout.hpp states

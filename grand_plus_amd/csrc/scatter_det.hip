@@ -191,10 +191,38 @@ struct BagOp {
     }
 };
 
-// The grid of rows_inv_den_kernel for the chunked twin.  The cap is a SECOND COPY of the one in the launch line of
-// gp_random_prop_rows_backward_det, which stays as it is written because tests/second_trip_cases.source_caps() reads it
-// there; tests/test_host_gather_chunk.py holds this copy to that one.  Change both together.
-int rows_den_grid(int n_batch) { return std::min(n_batch, 65535); }
+// gp_random_prop_rows_backward_det and its chunked twin: the checks, the pre-pass and the Op are the same, the
+// gather is gather_sum_kernel, or with a Chunking gather_chunk.hpp's.  where: the entry point that was called.
+int rows_backward_det(const char* where, int device, const float* d_grad_out, int32_t n_batch, int32_t feat_dim,
+                      const int32_t* d_col, const double* d_val, const int32_t* d_filled, int32_t K, const int32_t* d_batch_rows,
+                      int32_t n_samples, float dropnode_rate, int training, uint64_t seed, const uint8_t* d_keep,
+                      int64_t keep_stride, float* d_grad_x, int64_t n_nodes, const int64_t* d_order, const int64_t* d_sorted_keys,
+                      int64_t n_sorted, float* d_inv_den, const Chunking* chunking, void* stream)
+{
+    if (n_samples < 1 || n_samples > kMaxSamples || !(dropnode_rate >= 0.0f && dropnode_rate <= 1.0f))
+        return fail(GP_ERR_INVALID_ARG, where, "n_samples outside [1, 16] or dropnode_rate outside [0, 1]");
+    if (n_batch < 0 || n_nodes < 1 || feat_dim < 1 || K < 1 || K > GP_MAX_K || n_sorted < 0 || (d_keep && keep_stride < 1))
+        return fail(GP_ERR_INVALID_ARG, where, "bad size, K outside [1, 1024] or keep_stride < 1 with a mask");
+    if (chunking)
+        if (const int rc = chunk_check(where, *chunking, n_batch == 0 ? 0 : n_sorted, feat_dim)) return rc;
+    if (n_batch == 0 || n_sorted == 0) return GP_OK;
+    if (!d_grad_out || !d_col || !d_val || !d_grad_x || !d_order || !d_sorted_keys || !d_inv_den)
+        return fail(GP_ERR_NULL, where, "a device pointer is NULL");
+    if (const int rc = set_device(device, where)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(rows_inv_den_kernel, dim3(std::min(n_batch, 65535)), dim3(kBlock), 0, s, d_val, d_filled, K, d_batch_rows,
+                       n_batch, n_samples, dropnode_rate, training, (u64)seed, d_keep, (long long)keep_stride, d_inv_den);
+    if (const int rc = launch_status("rows_inv_den_kernel")) return rc;
+    const RowsOp op = {d_grad_out, feat_dim, d_col, d_val, d_filled, K, d_batch_rows, n_batch, n_samples, dropnode_rate, training,
+                       (u64)seed, d_keep, (long long)keep_stride, d_inv_den};
+    if (!chunking) {
+        hipLaunchKernelGGL(gather_sum_kernel<RowsOp>, dim3(gather_grid(n_sorted)), dim3(kGather), 0, s, op, (const long long*)d_order,
+                           (const long long*)d_sorted_keys, (long long)n_sorted, (long long)n_nodes, feat_dim, d_grad_x);
+        return launch_status("gather_sum_kernel<RowsOp>");
+    }
+    return gather_chunked(op, "gather_chunk_kernel<RowsOp>", d_order, d_sorted_keys, n_sorted, n_nodes, feat_dim, chunking->chunk,
+                          d_grad_x, chunking->d_scratch, s);
+}
 
 }  // namespace
 
@@ -207,24 +235,9 @@ int gp_random_prop_rows_backward_det(int device, const float* d_grad_out, int32_
                                      int64_t n_nodes, const int64_t* d_order, const int64_t* d_sorted_keys, int64_t n_sorted,
                                      float* d_inv_den, void* stream)
 {
-    const char* where = "gp_random_prop_rows_backward_det";
-    if (n_samples < 1 || n_samples > kMaxSamples || !(dropnode_rate >= 0.0f && dropnode_rate <= 1.0f))
-        return fail(GP_ERR_INVALID_ARG, where, "n_samples outside [1, 16] or dropnode_rate outside [0, 1]");
-    if (n_batch < 0 || n_nodes < 1 || feat_dim < 1 || K < 1 || K > GP_MAX_K || n_sorted < 0 || (d_keep && keep_stride < 1))
-        return fail(GP_ERR_INVALID_ARG, where, "bad size, K outside [1, 1024] or keep_stride < 1 with a mask");
-    if (n_batch == 0 || n_sorted == 0) return GP_OK;
-    if (!d_grad_out || !d_col || !d_val || !d_grad_x || !d_order || !d_sorted_keys || !d_inv_den)
-        return fail(GP_ERR_NULL, where, "a device pointer is NULL");
-    if (const int rc = set_device(device, where)) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(rows_inv_den_kernel, dim3(std::min(n_batch, 65535)), dim3(kBlock), 0, s, d_val, d_filled, K, d_batch_rows,
-                       n_batch, n_samples, dropnode_rate, training, (u64)seed, d_keep, (long long)keep_stride, d_inv_den);
-    if (const int rc = launch_status("rows_inv_den_kernel")) return rc;
-    const RowsOp op = {d_grad_out, feat_dim, d_col, d_val, d_filled, K, d_batch_rows, n_batch, n_samples, dropnode_rate, training,
-                       (u64)seed, d_keep, (long long)keep_stride, d_inv_den};
-    hipLaunchKernelGGL(gather_sum_kernel<RowsOp>, dim3(gather_grid(n_sorted)), dim3(kGather), 0, s, op, (const long long*)d_order,
-                       (const long long*)d_sorted_keys, (long long)n_sorted, (long long)n_nodes, feat_dim, d_grad_x);
-    return launch_status("gather_sum_kernel<RowsOp>");
+    return rows_backward_det("gp_random_prop_rows_backward_det", device, d_grad_out, n_batch, feat_dim, d_col, d_val, d_filled, K,
+                             d_batch_rows, n_samples, dropnode_rate, training, seed, d_keep, keep_stride, d_grad_x, n_nodes, d_order,
+                             d_sorted_keys, n_sorted, d_inv_den, nullptr, stream);
 }
 
 int gp_embedding_bag_backward_det(int device, const float* d_grad_out, int64_t n_vocab, int32_t dim,
@@ -268,27 +281,10 @@ int gp_random_prop_rows_backward_det_chunked(int device, const float* d_grad_out
                                              int64_t n_sorted, float* d_inv_den, int32_t chunk, float* d_scratch,
                                              int64_t scratch_bytes, void* stream)
 {
-    // The checks, the pre-pass launch and the RowsOp below are gp_random_prop_rows_backward_det's own lines, repeated here
-    // because that entry point stays byte for byte what it was.  tests/test_host_gather_chunk.py holds the two copies
-    // together; a change to one belongs in the other (a shared helper is the later remedy).
-    const char* where = "gp_random_prop_rows_backward_det_chunked";
-    if (n_samples < 1 || n_samples > kMaxSamples || !(dropnode_rate >= 0.0f && dropnode_rate <= 1.0f))
-        return fail(GP_ERR_INVALID_ARG, where, "n_samples outside [1, 16] or dropnode_rate outside [0, 1]");
-    if (n_batch < 0 || n_nodes < 1 || feat_dim < 1 || K < 1 || K > GP_MAX_K || n_sorted < 0 || (d_keep && keep_stride < 1))
-        return fail(GP_ERR_INVALID_ARG, where, "bad size, K outside [1, 1024] or keep_stride < 1 with a mask");
-    if (const int rc = chunk_check(where, chunk, n_batch == 0 ? 0 : n_sorted, feat_dim, d_scratch, scratch_bytes)) return rc;
-    if (n_batch == 0 || n_sorted == 0) return GP_OK;
-    if (!d_grad_out || !d_col || !d_val || !d_grad_x || !d_order || !d_sorted_keys || !d_inv_den)
-        return fail(GP_ERR_NULL, where, "a device pointer is NULL");
-    if (const int rc = set_device(device, where)) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(rows_inv_den_kernel, dim3(rows_den_grid(n_batch)), dim3(kBlock), 0, s, d_val, d_filled, K, d_batch_rows,
-                       n_batch, n_samples, dropnode_rate, training, (u64)seed, d_keep, (long long)keep_stride, d_inv_den);
-    if (const int rc = launch_status("rows_inv_den_kernel")) return rc;
-    const RowsOp op = {d_grad_out, feat_dim, d_col, d_val, d_filled, K, d_batch_rows, n_batch, n_samples, dropnode_rate, training,
-                       (u64)seed, d_keep, (long long)keep_stride, d_inv_den};
-    return gather_chunked(op, "gather_chunk_kernel<RowsOp>", d_order, d_sorted_keys, n_sorted, n_nodes, feat_dim, chunk, d_grad_x,
-                          d_scratch, s);
+    const Chunking chunking = {chunk, d_scratch, scratch_bytes};
+    return rows_backward_det("gp_random_prop_rows_backward_det_chunked", device, d_grad_out, n_batch, feat_dim, d_col, d_val, d_filled,
+                             K, d_batch_rows, n_samples, dropnode_rate, training, seed, d_keep, keep_stride, d_grad_x, n_nodes, d_order,
+                             d_sorted_keys, n_sorted, d_inv_den, &chunking, stream);
 }
 
 int gp_embedding_bag_backward_det_chunked(int device, const float* d_grad_out, int64_t n_vocab, int32_t dim,
@@ -304,7 +300,7 @@ int gp_embedding_bag_backward_det_chunked(int device, const float* d_grad_out, i
         !(dropout_rate >= 0.0f && dropout_rate <= 1.0f))
         return fail(GP_ERR_INVALID_ARG, where, "negative size, dim < 1, idx_bytes not 4 or 8, or dropout rate outside [0, 1]");
     const bool gathers = n_rows > 0 && n_sorted > 0 && n_vocab > 0;
-    if (const int rc = chunk_check(where, chunk, gathers ? n_sorted : 0, dim, d_scratch, scratch_bytes)) return rc;
+    if (const int rc = chunk_check(where, {chunk, d_scratch, scratch_bytes}, gathers ? n_sorted : 0, dim)) return rc;
     if (gathers && (!d_order || !d_sorted_keys || !d_sorted_rows)) return fail(GP_ERR_NULL, where, "a device pointer is NULL");
     // The pre-pass is the twin's own: given no sorted positions it checks the remaining pointers, counts the bad ids, writes
     // inv_den and stops before its gather.

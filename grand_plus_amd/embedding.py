@@ -118,7 +118,7 @@ def _backward_det(weight_shape, grad_out, L, n_entries, p, training, seed, keep,
     else:
         from . import gather_chunk
         scratch, nbytes = gather_chunk.scratch(order.numel(), segment_chunk, H, g.device)
-        rc = gather_chunk.lib().gp_embedding_bag_backward_det_chunked(*args, segment_chunk, scratch.data_ptr(), nbytes, _stream(g))
+        rc = _native.lib().gp_embedding_bag_backward_det_chunked(*args, segment_chunk, scratch.data_ptr(), nbytes, _stream(g))
     _native.raise_for_status(rc)
     return dW
 

@@ -20,7 +20,7 @@ the GP_FIT_* constants and the two struct mirrors.  They are imported here so th
 (`_valid_plan` / `_valid_pass`).  For a step built with `dirty_rows=True` the tracker snapshots the embedding table row by
 row: `gp_fit_rows_mark` collects the rows every backward hands over in a bitmap, `gp_fit_rows_snapshot` copies the marked
 rows when the rule takes a new best and clears the bitmap.  Those two are extern "C" symbols of libgrandplus.so declared
-in csrc/fit_rows_abi.hpp, outside C ABI 4; ROWS_ABI below binds them, as optim_rows.ABI binds its own.
+in csrc/fit_rows_abi.hpp, outside C ABI 4; `_native.PRIVATE_ABI` binds them, as it binds optim_rows' own.
 
 Left out: several steps in one graph, the validation pass as a captured graph, numpy's own shuffle stream, a
 dirty-row `restore` (it stays a full copy, once per run), Adam's moments in the snapshot (the reference saves the
@@ -44,36 +44,18 @@ __all__ = ["Sampler", "BestTracker", "FitLoop", "FitResult", "fit", "early_stop_
 
 STOP_MODES = {"acc": GP_FIT_STOP_ACC, "both": GP_FIT_STOP_BOTH}
 _MAX_SIZE = 2 ** 31
-
-# the entry points of fit_rows_abi.hpp: name -> (restype, argtypes), under the convention stated above _native.ABI;
-# tests/test_host_fit_rows.py holds this table against that header
-_int, _i32, _i64, _vp = ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p
-ROWS_ABI = {
-    "gp_fit_rows_mark": (_int, [_int, _vp, _i64, _i64, _vp, _vp]),
-    "gp_fit_rows_snapshot": (_int, [_int, _vp, _vp, _vp, _i64, _i32, _vp, _vp]),
-}
-_ROWS_BOUND = False
+ROWS_ABI = _native.PRIVATE_ABI["fit_rows_abi.hpp"]                # the sub-table itself: this module declares nothing
 
 
 def rows_lib():
-    """_native.lib() with the entry points of fit_rows_abi.hpp declared on it.  A library without them is an error, not a
-    fallback."""
-    global _ROWS_BOUND
-    L = _native.lib()
-    if not _ROWS_BOUND:
-        for name, (restype, argtypes) in ROWS_ABI.items():
-            if not hasattr(L, name):
-                raise RuntimeError(f"{_native.LIB_PATH} does not export {name} (an older build?): rebuild the library")
-            f = getattr(L, name)
-            f.restype, f.argtypes = restype, argtypes
-        _ROWS_BOUND = True
-    return L
+    """`_native.lib()`, looked up at each call: this module binds nothing, and a patch of `_native.lib` reaches it."""
+    return _native.lib()
 
 
 def rows_mark(keys, n_vocab, dirty):
     """gp_fit_rows_mark on the current stream: the in-range keys of `keys` (int64 CUDA, a row list as `RowGrad.fill` takes
     it) set their bits of `dirty` (int32 CUDA [(n_vocab + 31) // 32])."""
-    rc = rows_lib().gp_fit_rows_mark(dirty.device.index, keys.data_ptr(), keys.numel(), n_vocab, dirty.data_ptr(), _stream(dirty))
+    rc = _native.lib().gp_fit_rows_mark(dirty.device.index, keys.data_ptr(), keys.numel(), n_vocab, dirty.data_ptr(), _stream(dirty))
     _native.raise_for_status(rc)
 
 
@@ -247,8 +229,8 @@ class BestTracker:
         _native.raise_for_status(rc)
         if self._table is not None:                                      # the table's dirty rows, and the bitmap cleared
             table, snap = self._table
-            rc = rows_lib().gp_fit_rows_snapshot(self.device.index, self.buf.data_ptr(), table.data_ptr(), snap.data_ptr(),
-                                                 table.shape[0], table.shape[1], self.row_grad.dirty.data_ptr(), _stream(self.buf))
+            rc = L.gp_fit_rows_snapshot(self.device.index, self.buf.data_ptr(), table.data_ptr(), snap.data_ptr(),
+                                        table.shape[0], table.shape[1], self.row_grad.dirty.data_ptr(), _stream(self.buf))
             _native.raise_for_status(rc)
 
     def read(self):

@@ -1,5 +1,5 @@
-"""Chunked deterministic segment sums: the binding of csrc/gather_chunk_abi.hpp and what the three
-deterministic backwards share to use it.
+"""Chunked deterministic segment sums: what the three deterministic backwards share to use the entry points
+of csrc/gather_chunk_abi.hpp.
 
 The deterministic backwards of `random_prop_rows`, the embedding bag and `mag_prop_rows` sum every destination row's
 contributions left to right on one wave: a hub destination (a word that sits in a third of the bags, a node in every row's
@@ -11,11 +11,9 @@ the unchunked result.  Nothing is read back, so the path runs under `torch.cuda.
 captured graph.  The order contract is stated in csrc/gather_chunk_abi.hpp.
 
 The entry points are extern "C" symbols of libgrandplus.so declared in csrc/gather_chunk_abi.hpp; they are not part of
-C ABI 4, so their binding (ABI below) lives here and not in `_native`.
+C ABI 4, so `_native.PRIVATE_ABI` binds them, not `_native.ABI`.
 """
 from __future__ import annotations
-
-import ctypes
 
 import torch
 
@@ -25,33 +23,10 @@ __all__ = ["MIN_CHUNK", "MAX_CHUNK", "check_chunk", "resolve", "scratch_bytes", 
 
 MIN_CHUNK, MAX_CHUNK = 64, 4096
 
-# name -> (restype, argtypes), under the convention stated above _native.ABI; tests/test_host_gather_chunk.py holds it
-# against gather_chunk_abi.hpp.  Each is its unchunked twin's arguments up to the stream, then chunk, d_scratch,
-# scratch_bytes and the stream.
-_int, _i32, _i64, _vp = ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p
-_tail = [_i32, _vp, _i64, _vp]
-_scatter = _native.ABI["grandplus_scatter.h"]
-ABI = {
-    "gp_random_prop_rows_backward_det_chunked": (_int, _scatter["gp_random_prop_rows_backward_det"][1][:-1] + _tail),
-    "gp_embedding_bag_backward_det_chunked": (_int, _scatter["gp_embedding_bag_backward_det"][1][:-1] + _tail),
-    "gp_mag_prop_rows_backward_det_chunked": (_int, [_int, _vp] + _native._mag + [_vp, _vp, _vp, _i64, _vp, _vp, _vp] + _tail),
-}
-_BOUND = False
-
 
 def lib():
-    """_native.lib() with the entry points of gather_chunk_abi.hpp declared on it.  A library without them is an error, not
-    a fallback."""
-    global _BOUND
-    L = _native.lib()
-    if not _BOUND:
-        for name, (restype, argtypes) in ABI.items():
-            if not hasattr(L, name):
-                raise RuntimeError(f"{_native.LIB_PATH} does not export {name} (an older build?): rebuild the library")
-            f = getattr(L, name)
-            f.restype, f.argtypes = restype, argtypes
-        _BOUND = True
-    return L
+    """`_native.lib()`, looked up at each call: this module binds nothing, and a patch of `_native.lib` reaches it."""
+    return _native.lib()
 
 
 def check_chunk(segment_chunk):

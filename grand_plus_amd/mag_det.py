@@ -1,5 +1,5 @@
-"""The deterministic table gradient of `mag_prop_rows`: the binding of csrc/mag_det_abi.hpp and the backward
-built on it.
+"""The deterministic table gradient of `mag_prop_rows`: the backward built on the entry points of
+csrc/mag_det_abi.hpp.
 
 The atomic backward of mag.py adds one fp32 atomic per (entry, column) into dW: fast, capturable, not reproducible.  The
 composed path has a deterministic backward, but it asks the host how many entries the batch has.  Here the host never
@@ -10,15 +10,13 @@ right from 0.0f.  Nothing is read back, so the backward runs under `torch.cuda.s
 captured graph.
 
 The entry points are extern "C" symbols of libgrandplus.so declared in csrc/mag_det_abi.hpp; they are not part of C ABI 4,
-so their binding (ABI below) lives here and not in `_native`.
+so `_native.PRIVATE_ABI` binds them, not `_native.ABI`.
 
 `segment_chunk=C` sums a hub attribute's segment in chunks of C entries (gather_chunk.py).
 
 Left out: input dropout (the keyed mask would need S values of U per slot).
 """
 from __future__ import annotations
-
-import ctypes
 
 import torch
 
@@ -27,30 +25,12 @@ from ._common import _dev_index, _ptr, _stream
 
 __all__ = ["backward_det", "check_max_entries", "check_overflow"]
 
-# name -> (restype, argtypes), under the convention stated above _native.ABI; tests/test_host_mag_det.py holds it against
-# mag_det_abi.hpp.  _native._mag: gp_mag_prop_rows' arguments between the table and the outputs.
-_int, _i32, _i64, _vp = ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p
-ABI = {
-    "gp_mag_det_keys": (_int, [_int, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _i32, _i64, _vp, _vp, _vp, _vp]),
-    "gp_mag_prop_rows_backward_det": (_int, [_int, _vp] + _native._mag + [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
-}
-_BOUND = False
 _MAX_SLOTS = 2 ** 31
 
 
 def lib():
-    """_native.lib() with the entry points of mag_det_abi.hpp declared on it.  A library without them is an error, not a
-    fallback."""
-    global _BOUND
-    L = _native.lib()
-    if not _BOUND:
-        for name, (restype, argtypes) in ABI.items():
-            if not hasattr(L, name):
-                raise RuntimeError(f"{_native.LIB_PATH} does not export {name} (an older build?): rebuild the library")
-            f = getattr(L, name)
-            f.restype, f.argtypes = restype, argtypes
-        _BOUND = True
-    return L
+    """`_native.lib()`, looked up at each call: this module binds nothing, and a patch of `_native.lib` reaches it."""
+    return _native.lib()
 
 
 def check_max_entries(max_entries):
@@ -92,7 +72,7 @@ def backward_det(weight_shape, grad_out, call, max_entries, overflow, row_grad=N
         return None
     slot_base = torch.empty(B * K + 1, dtype=torch.int64, device=dev)
     keys = torch.empty(max_entries, dtype=torch.int64, device=dev)
-    L = lib()
+    L = _native.lib()
     rc = L.gp_mag_det_keys(_dev_index(g), V, attr_indptr.data_ptr(), attr_indices.data_ptr(), attr_indptr.numel() - 1,
                            col.data_ptr(), _ptr(filled), S_rows, K, _ptr(batch_rows), B, max_entries, slot_base.data_ptr(),
                            keys.data_ptr(), overflow.data_ptr(), _stream(g))
@@ -107,7 +87,7 @@ def backward_det(weight_shape, grad_out, call, max_entries, overflow, row_grad=N
     else:
         from . import gather_chunk
         scratch, nbytes = gather_chunk.scratch(max_entries, segment_chunk, H, dev)
-        rc = gather_chunk.lib().gp_mag_prop_rows_backward_det_chunked(*args, segment_chunk, scratch.data_ptr(), nbytes, _stream(g))
+        rc = L.gp_mag_prop_rows_backward_det_chunked(*args, segment_chunk, scratch.data_ptr(), nbytes, _stream(g))
     _native.raise_for_status(rc)
     if row_grad is None:
         return dW

@@ -1,6 +1,6 @@
-"""The embedding table's gradient as a row list, and the clip + Adam step over it: the binding of
-csrc/optim_rows_abi.hpp and `RowGrad`, the object that carries the touched rows from MAG's deterministic backward to
-`ClipAdam`.
+"""The embedding table's gradient as a row list, and the clip + Adam step over it: the calls of
+csrc/optim_rows_abi.hpp's entry points and `RowGrad`, the object that carries the touched rows from MAG's deterministic
+backward to `ClipAdam`.
 
 A MAG batch touches a small part of the [V, H] table, and the deterministic backward (mag_det.py, §7o) knows which: it
 holds the sorted key list, and its gather writes every touched row of dW exactly once.  Handed a `RowGrad`, that backward
@@ -14,12 +14,12 @@ list, and gives the weight no `.grad`.  `ClipAdam.set_row_grad(param, row_grad, 
     which an untouched row still moves while its moments decay.  weight_decay must be 0 in this mode.
 
 The entry points are extern "C" symbols of libgrandplus.so declared in csrc/optim_rows_abi.hpp; they are not part of
-C ABI 4, so their binding (ABI below) lives here and not in `_native`, as mag_det's does.
+C ABI 4, so `_native.PRIVATE_ABI` binds them, not `_native.ABI`, as it binds mag_det's.
 
 `BitmapRowGrad` is a RowGrad for the ATOMIC backward, which keeps no key list: the rows a batch can touch are
-marked in a bitmap of V bits (csrc/row_mark_abi.hpp, bound by MARK_ABI below), the bitmap is compacted into the same kind
-of list -- ascending, each row once, sentinel V in the tail -- and the listed rows of `values` are zeroed for the atomics
-to add into.  `ClipAdam.set_row_grad` and both row kernels take it unchanged.
+marked in a bitmap of V bits (csrc/row_mark_abi.hpp, bound by `_native.PRIVATE_ABI` too), the bitmap is compacted into the
+same kind of list -- ascending, each row once, sentinel V in the tail -- and the listed rows of `values` are zeroed for the
+atomics to add into.  `ClipAdam.set_row_grad` and both row kernels take it unchanged.
 
 `RowGrad.track_dirty()` has every `fill` also mark the rows it is handed in a bitmap `dirty` that only
 accumulates here: `fit.BestTracker(row_grad=)` reads it to snapshot the table row by row, and clears it.
@@ -29,8 +29,6 @@ saves the state_dict alone).
 """
 from __future__ import annotations
 
-import ctypes
-
 import torch
 
 from . import _native
@@ -38,39 +36,13 @@ from ._common import _ptr, _stream
 
 __all__ = ["RowGrad", "BitmapRowGrad", "MODES", "check_mode"]
 
-# name -> (restype, argtypes), under the convention stated above _native.ABI; tests/test_host_optim_rows.py holds it against
-# optim_rows_abi.hpp.
-_int, _i32, _i64, _f, _d, _vp = ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_double, ctypes.c_void_p
-_table = [_int, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _int, _f, _f, _d, _d, _f, _f]   # device .. weight_decay
-ABI = {
-    "gp_optim_rows_sqnorm": (_int, [_int, _vp, _i64, _i64, _i32, _vp, _int, _vp, _vp]),
-    "gp_clip_adam_rows": (_int, _table + [_f, _f, _vp, _vp, _vp]),
-    "gp_clip_adam_rows_dev": (_int, _table + [_vp, _vp, _vp, _vp, _vp]),
-}
-# the entry points of row_mark_abi.hpp; tests/test_host_row_mark.py holds this table against that header
-MARK_ABI = {
-    "gp_row_mark_mag": (_int, [_int, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _vp]),
-    "gp_row_list_compact": (_int, [_int, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
-    "gp_row_list_zero": (_int, [_int, _vp, _i64, _i64, _i32, _vp, _vp]),
-}
 ROW_LIST_PARTIALS = 1024                  # GP_ROW_LIST_PARTIALS
 MODES = {"exact": 1, "lazy": 2}           # GP_OPTIM_ROWS_EXACT, GP_OPTIM_ROWS_LAZY
-_BOUND = False
 
 
 def lib():
-    """_native.lib() with the entry points of optim_rows_abi.hpp and row_mark_abi.hpp declared on it.  A library without
-    them is an error, not a fallback."""
-    global _BOUND
-    L = _native.lib()
-    if not _BOUND:
-        for name, (restype, argtypes) in {**ABI, **MARK_ABI}.items():
-            if not hasattr(L, name):
-                raise RuntimeError(f"{_native.LIB_PATH} does not export {name} (an older build?): rebuild the library")
-            f = getattr(L, name)
-            f.restype, f.argtypes = restype, argtypes
-        _BOUND = True
-    return L
+    """`_native.lib()`, looked up at each call: this module binds nothing, and a patch of `_native.lib` reaches it."""
+    return _native.lib()
 
 
 def check_mode(mode):
@@ -168,7 +140,7 @@ def mark_and_list(rg, call, capacity, overflow):
     attr_indptr, attr_indices, _, col, _, filled, batch_rows, _ = call.tensors
     S_rows, K, B = call.scalars[:3]
     V, H = rg.shape
-    dev, stream, L = rg.device.index, _stream(rg.values), lib()
+    dev, stream, L = rg.device.index, _stream(rg.values), _native.lib()
     keys = torch.empty(capacity, dtype=torch.int64, device=rg.device)
     rc = L.gp_row_mark_mag(dev, V, attr_indptr.data_ptr(), attr_indices.data_ptr(), attr_indptr.numel() - 1, col.data_ptr(),
                            _ptr(filled), S_rows, K, _ptr(batch_rows), B, rg.bitmap.data_ptr(), stream)
@@ -184,8 +156,8 @@ def mark_and_list(rg, call, capacity, overflow):
 def sqnorm(rg, accumulate, ws):
     """gp_optim_rows_sqnorm of a filled RowGrad into the workspace `ws`, on the current stream."""
     V, H = rg.shape
-    rc = lib().gp_optim_rows_sqnorm(rg.device.index, rg.keys.data_ptr(), rg.n_sorted, V, H, rg.values.data_ptr(),
-                                    int(bool(accumulate)), ws.data_ptr(), _stream(rg.values))
+    rc = _native.lib().gp_optim_rows_sqnorm(rg.device.index, rg.keys.data_ptr(), rg.n_sorted, V, H, rg.values.data_ptr(),
+                                            int(bool(accumulate)), ws.data_ptr(), _stream(rg.values))
     _native.raise_for_status(rc)
 
 
@@ -198,7 +170,7 @@ def clip_adam_rows(rg, mode, exp_avg, exp_avg_sq, ws, norm, *, max_norm, lr, bet
             rg.keys.data_ptr(), rg.n_sorted, V, H, MODES[mode], max_norm, lr, betas[0], betas[1], eps, weight_decay)
     tail = (ws.data_ptr(), norm.data_ptr(), _stream(rg.values))
     if d_step_size is None:
-        rc = lib().gp_clip_adam_rows(*head, step_size, rsqrt_bc2, *tail)
+        rc = _native.lib().gp_clip_adam_rows(*head, step_size, rsqrt_bc2, *tail)
     else:
-        rc = lib().gp_clip_adam_rows_dev(*head, d_step_size, d_rsqrt_bc2, *tail)
+        rc = _native.lib().gp_clip_adam_rows_dev(*head, d_step_size, d_rsqrt_bc2, *tail)
     _native.raise_for_status(rc)

@@ -1,5 +1,6 @@
-"""The public headers as tests/test_host_abi.py reads them: the header reader, the prototype parser, the pointer convention
-of the binding (stated above _native.ABI) as a function, and the C compiler as the judge of macros, sizeof and offsetof."""
+"""The headers as the host tests read them -- the public ones under include/, the private csrc/*_abi.hpp --: the header
+reader, the prototype parser, the pointer convention of the binding (stated above _native.ABI) as a function, and the C
+compiler as the judge of macros, sizeof and offsetof."""
 import ctypes
 import os
 import re
@@ -10,11 +11,13 @@ from grand_plus_amd import _native
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INC = os.path.join(ROOT, "include")
+CSRC = os.path.join(ROOT, "grand_plus_amd", "csrc")
 
 
 def read(header):
-    """(text, code) of include/<header>: as written, and with /* */ and // comments removed."""
-    text = open(os.path.join(INC, header)).read()
+    """(text, code) of include/<header>, or of csrc/<header> for a private *.hpp: as written, and with /* */ and //
+    comments removed."""
+    text = open(os.path.join(CSRC if header.endswith(".hpp") else INC, header)).read()
     return text, re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
 
 

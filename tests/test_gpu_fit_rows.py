@@ -59,8 +59,8 @@ def _no_sync(call):
 @pytest.fixture(scope="module", autouse=True)
 def loaded():
     """One launch of either kernel before any test: loading the code object may synchronise, the kernels may not."""
-    from grand_plus_amd import _native, fit
-    L = fit.rows_lib()
+    from grand_plus_amd import _native
+    L = _native.lib()
     keys = torch.zeros(1, dtype=torch.int64, device="cuda")
     dirty = torch.zeros(1, dtype=torch.int32, device="cuda")
     track = torch.zeros(5, dtype=torch.int64, device="cuda")
@@ -77,8 +77,8 @@ def _track(copy_now):
 
 # ---- the mark
 def _mark(V, keys, before):
-    from grand_plus_amd import _native, fit
-    L = fit.rows_lib()
+    from grand_plus_amd import _native
+    L = _native.lib()
     dirty = _Words(before)
     k = torch.full((len(keys) + 2 * G,), 3 % V, dtype=torch.int64, device="cuda")   # the guards name a real row: read, they would mark
     k[G:G + len(keys)].copy_(torch.from_numpy(np.asarray(keys, np.int64)))
@@ -116,8 +116,8 @@ def test_more_keys_than_the_grid_has_threads():
 def _snapshot(V, dim, bm, copy_now, offset=0, tables=None):
     """gp_fit_rows_snapshot from the mirror's tables, both `offset` words into a 16-byte aligned block: (the destination,
     the bitmap) afterwards as uint32."""
-    from grand_plus_amd import _native, fit
-    L = fit.rows_lib()
+    from grand_plus_amd import _native
+    L = _native.lib()
     src, dst = tables if tables is not None else fr.tables(V, dim)
     s, d, dirty = _Words(src, offset), _Words(dst, offset), _Words(bm)
     assert (s.ptr() % 16 == 0) == (offset % 4 == 0) and (d.ptr() % 16 == 0) == (offset % 4 == 0)
@@ -182,7 +182,7 @@ def test_mark_then_snapshot_is_what_the_tracker_issues():
     """The two entry points back to back on one stream, as RowGrad.fill and BestTracker.update issue them: marks accumulate
     over two lists, one snapshot copies their union, a second one copies nothing."""
     from grand_plus_amd import _native, fit
-    L = fit.rows_lib()
+    L = _native.lib()
     V, dim = 4097, 64
     src, dst = fr.tables(V, dim)
     s, d, dirty = _Words(src), _Words(dst), _Words(np.zeros(rm.words(V), np.uint32))

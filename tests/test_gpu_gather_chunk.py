@@ -119,7 +119,7 @@ def _stream():
 def test_guard_bands_round_the_bag_gradient_and_its_scratch_keep_their_fill():
     """gp_embedding_bag_backward_det_chunked on the adjacent long segments (both scratch rows of one span in use) and on a
     long segment that ends the list."""
-    from grand_plus_amd import gather_chunk as gc
+    from grand_plus_amd import _native
     from grand_plus_amd.embedding import _det_order, _Layout
     H, C = 65, 64
     for name in ("adjacent_at10", "long_ends_the_list"):
@@ -131,7 +131,7 @@ def test_guard_bands_round_the_bag_gradient_and_its_scratch_keep_their_fill():
         assert np.array_equal(keys.cpu().numpy(), e["sorted_keys"])
         inv = torch.empty(n, device="cuda")
         G = torch.from_numpy(e["G"]).cuda()
-        _guarded(lambda dst, scratch, nbytes: gc.lib().gp_embedding_bag_backward_det_chunked(
+        _guarded(lambda dst, scratch, nbytes: _native.lib().gp_embedding_bag_backward_det_chunked(
             0, G.data_ptr(), V, H, *L.args(), 0.0, 0, ctypes.c_uint64(0), None, dst, None, order.data_ptr(), keys.data_ptr(),
             rows.data_ptr(), n, inv.data_ptr(), C, scratch, nbytes, _stream()), V, H, n, C, gcc.expected(name, H), e["sorted_keys"], name)
 
@@ -139,7 +139,7 @@ def test_guard_bands_round_the_bag_gradient_and_its_scratch_keep_their_fill():
 def test_guard_bands_round_the_rows_gradient_and_its_scratch_keep_their_fill():
     """gp_random_prop_rows_backward_det_chunked on the rows hub at F = 257 (two passes of kCols slabs): width = F,
     n_sorted = B * K."""
-    from grand_plus_amd import _native, gather_chunk as gc
+    from grand_plus_amd import _native
     from grand_plus_amd.augment import _rows_det_order
     F, C = 257, 64
     col, val, X, G, keep = _rows_hub(F)
@@ -148,7 +148,7 @@ def test_guard_bands_round_the_rows_gradient_and_its_scratch_keep_their_fill():
     n = keys.numel()
     assert n == ROWS_B * ROWS_K
     inv = torch.empty(_native.scatter_rows_workspace_bytes(ROWS_S, ROWS_B) // 4, device="cuda")
-    _guarded(lambda dst, scratch, nbytes: gc.lib().gp_random_prop_rows_backward_det_chunked(
+    _guarded(lambda dst, scratch, nbytes: _native.lib().gp_random_prop_rows_backward_det_chunked(
         0, Gc.data_ptr(), ROWS_B, F, cc.data_ptr(), vc.data_ptr(), None, ROWS_K, None, ROWS_S, 0.5, 1, ctypes.c_uint64(0),
         kc.data_ptr(), cc.numel(), dst, ROWS_N, order.data_ptr(), keys.data_ptr(), n, inv.data_ptr(), C, scratch, nbytes, _stream()),
         ROWS_N, F, n, C, _rows_walk(col, val, G, keep, 0.5, C, ROWS_N), keys.cpu().numpy(), "rows")
@@ -157,7 +157,7 @@ def test_guard_bands_round_the_rows_gradient_and_its_scratch_keep_their_fill():
 def test_guard_bands_round_the_mag_gradient_and_its_scratch_keep_their_fill():
     """gp_mag_prop_rows_backward_det_chunked on the MAG hub with max_entries above the total: n_sorted = max_entries, the
     scratch sized from it, a sentinel tail of 37 positions behind the entries."""
-    from grand_plus_amd import _native, gather_chunk as gc, mag_det as md
+    from grand_plus_amd import _native
     from grand_plus_amd.mag import _Call
     C = 64
     P, G, keep, E, _ = _mag_hub()
@@ -167,7 +167,7 @@ def test_guard_bands_round_the_mag_gradient_and_its_scratch_keep_their_fill():
     slot_base = torch.empty(MAG_B * K + 1, dtype=torch.int64, device="cuda")
     keys = torch.empty(cap, dtype=torch.int64, device="cuda")
     flag = torch.zeros(1, dtype=torch.int32, device="cuda")
-    _native.raise_for_status(md.lib().gp_mag_det_keys(0, MAG_V, indptr.data_ptr(), indices.data_ptr(), MAG_N, col.data_ptr(), None, MAG_B,
+    _native.raise_for_status(_native.lib().gp_mag_det_keys(0, MAG_V, indptr.data_ptr(), indices.data_ptr(), MAG_N, col.data_ptr(), None, MAG_B,
                                                       K, None, MAG_B, cap, slot_base.data_ptr(), keys.data_ptr(), flag.data_ptr(), _stream()))
     sorted_keys, order = torch.sort(keys, stable=True)
     want, walk_keys = _mag_want()
@@ -175,7 +175,7 @@ def test_guard_bands_round_the_mag_gradient_and_its_scratch_keep_their_fill():
     U = torch.empty((MAG_B * K, MAG_H), device="cuda")
     inv = torch.empty((MAG_S, MAG_B), device="cuda")
     Gc = G.cuda()
-    _guarded(lambda dst, scratch, nbytes: gc.lib().gp_mag_prop_rows_backward_det_chunked(
+    _guarded(lambda dst, scratch, nbytes: _native.lib().gp_mag_prop_rows_backward_det_chunked(
         0, Gc.data_ptr(), MAG_V, MAG_H, *call.args(), slot_base.data_ptr(), order.data_ptr(), sorted_keys.data_ptr(), cap, U.data_ptr(),
         inv.data_ptr(), dst, C, scratch, nbytes, _stream()), MAG_V, MAG_H, cap, C, want, sorted_keys.cpu().numpy(), "mag")
     assert int(flag.item()) == 0

@@ -59,7 +59,7 @@ def test_keys_and_slot_base_are_the_brute_force_entry_order(n_slots, slack):
     the total, equal to it, 130 and 1 000 past it (with one slot the grid is one workgroup of 256 threads, so the tail of
     1 000 sentinels takes four passes of the key kernel's tail loop).  Every buffer sits between guard bands that must keep
     their pattern."""
-    from grand_plus_amd import mag_det as md
+    from grand_plus_amd import _native
     P = dc.grid_problem(n_slots)
     E = dc.entry_order(P, None)
     cap = E["total"] + slack
@@ -68,7 +68,7 @@ def test_keys_and_slot_base_are_the_brute_force_entry_order(n_slots, slack):
     keys = torch.full((GUARD + cap + GUARD,), G64, dtype=torch.int64, device="cuda")
     flag = torch.full((GUARD + 1 + GUARD,), G32, dtype=torch.int32, device="cuda")
     flag[GUARD] = 4                                                            # bit 0 clear, another bit set: it has to survive
-    rc = md.lib().gp_mag_det_keys(0, P.V, ip.data_ptr(), ix.data_ptr(), P.N, col.data_ptr(), None if filled is None else filled.data_ptr(),
+    rc = _native.lib().gp_mag_det_keys(0, P.V, ip.data_ptr(), ix.data_ptr(), P.N, col.data_ptr(), None if filled is None else filled.data_ptr(),
                                   P.S_rows, K, None, P.S_rows, cap, base.data_ptr() + 8 * GUARD, keys.data_ptr() + 8 * GUARD,
                                   flag.data_ptr() + 4 * GUARD, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
     assert rc == 0
@@ -86,7 +86,7 @@ def test_keys_and_slot_base_are_the_brute_force_entry_order(n_slots, slack):
 
 
 def test_keys_of_a_batch_with_ids_columns_and_rows_out_of_range():
-    from grand_plus_amd import mag_det as md
+    from grand_plus_amd import _native
     c = dc.walk_case("bad_indices")
     P, E = c["P"], c["E"]
     n_sentinel = int((E["keys"] == P.V).sum())
@@ -97,7 +97,7 @@ def test_keys_of_a_batch_with_ids_columns_and_rows_out_of_range():
     base = torch.empty(batch.numel() * K + 1, dtype=torch.int64, device="cuda")
     keys = torch.empty(cap, dtype=torch.int64, device="cuda")
     flag = torch.zeros(1, dtype=torch.int32, device="cuda")
-    rc = md.lib().gp_mag_det_keys(0, P.V, ip.data_ptr(), ix.data_ptr(), P.N, col.data_ptr(), filled.data_ptr(), P.S_rows, K,
+    rc = _native.lib().gp_mag_det_keys(0, P.V, ip.data_ptr(), ix.data_ptr(), P.N, col.data_ptr(), filled.data_ptr(), P.S_rows, K,
                                   batch.data_ptr(), batch.numel(), cap, base.data_ptr(), keys.data_ptr(), flag.data_ptr(),
                                   ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
     assert rc == 0

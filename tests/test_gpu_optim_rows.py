@@ -78,7 +78,7 @@ def _rows_step(mode, p, m, v, dW, keys, h, t, dev=False, guard=GUARD, finite=Tru
     from grand_plus_amd import _native
     from grand_plus_amd import optim_rows as orows
     V, H = p.shape
-    L = orows.lib()
+    L = _native.lib()
     bp, bm, bv, bg = _Buf(p, guard), _Buf(m, guard), _Buf(v, guard), _Buf(dW, guard)
     bn = _Buf(np.zeros(1, np.float32))
     k = torch.from_numpy(np.concatenate([[-99], keys, [-99]]).astype(np.int64)).cuda()      # a list of 0 keys still has an address

@@ -45,7 +45,7 @@ def _compact(bm, V, cap, flag0=0, repeats=1):
     elements behind them, the count, the flag and the bitmap afterwards, of the last run; the runs are bit-equal."""
     from grand_plus_amd import _native
     from grand_plus_amd import optim_rows as orows
-    L = orows.lib()
+    L = _native.lib()
     bitmap = _Ints(bm.view(np.int32), -1)                                          # the guards hold set bits: they are not the map's
     keys = _Ints(np.full(cap + rm.GUARD, rm.POISON, np.int64), rm.POISON - 1)
     count = _Ints(np.full(1, -5, np.int64), -6)
@@ -104,14 +104,13 @@ def _mark(P, col, indices, batch, V):
     """gp_row_mark_mag over the problem's tensors (col and indices possibly spoilt), into a zeroed guarded bitmap: the marked
     rows, and the bitmap's words."""
     from grand_plus_amd import _native
-    from grand_plus_amd import optim_rows as orows
     bitmap = _Ints(np.zeros(rm.words(V), np.int32), 0)                             # a stray bit outside the map shows in the guards
     ip, ix, c = P.indptr.cuda(), indices.cuda(), col.reshape(-1).cuda()
     f = None if P.filled is None else P.filled.cuda()
     b = None if batch is None else batch.cuda()
     B = P.S_rows if batch is None else batch.numel()
     ptr = lambda t: None if t is None else t.data_ptr()                             # noqa: E731
-    _native.raise_for_status(orows.lib().gp_row_mark_mag(0, V, ip.data_ptr(), ix.data_ptr(), P.N, c.data_ptr(), ptr(f), P.S_rows, P.K,
+    _native.raise_for_status(_native.lib().gp_row_mark_mag(0, V, ip.data_ptr(), ix.data_ptr(), P.N, c.data_ptr(), ptr(f), P.S_rows, P.K,
                                                          ptr(b), B, bitmap.ptr(), _stream()))
     torch.cuda.synchronize()
     words = bitmap.get().view(np.uint32)
@@ -121,7 +120,7 @@ def _mark(P, col, indices, batch, V):
 
 def _det_keys(P, col, indices, batch, V):
     """The distinct in-range keys of gp_mag_det_keys with a capacity that cannot overflow."""
-    from grand_plus_amd import _native, mag_det
+    from grand_plus_amd import _native
     B = P.S_rows if batch is None else batch.numel()
     cap = B * P.K * P.longest + 1
     ip, ix, c = P.indptr.cuda(), indices.cuda(), col.reshape(-1).cuda()
@@ -131,7 +130,7 @@ def _det_keys(P, col, indices, batch, V):
     keys = torch.empty(cap, dtype=torch.int64, device="cuda")
     flag = torch.zeros(1, dtype=torch.int32, device="cuda")
     ptr = lambda t: None if t is None else t.data_ptr()                             # noqa: E731
-    _native.raise_for_status(mag_det.lib().gp_mag_det_keys(0, V, ip.data_ptr(), ix.data_ptr(), P.N, c.data_ptr(), ptr(f), P.S_rows,
+    _native.raise_for_status(_native.lib().gp_mag_det_keys(0, V, ip.data_ptr(), ix.data_ptr(), P.N, c.data_ptr(), ptr(f), P.S_rows,
                                                            P.K, ptr(b), B, cap, base.data_ptr(), keys.data_ptr(), flag.data_ptr(),
                                                            _stream()))
     k = keys.cpu().numpy()
@@ -210,13 +209,12 @@ def _zero(V, H, keys, offset=0):
     """gp_row_list_zero over a [V, H] buffer of NaN poison that starts `offset` floats into a 16-byte aligned block: the
     buffer afterwards as uint32 bits."""
     from grand_plus_amd import _native
-    from grand_plus_amd import optim_rows as orows
     full = torch.full((V * H + 2 * 64 + offset,), 0, dtype=torch.int32, device="cuda")
     full.fill_(NAN_BITS)
     at = 64 + offset
     assert full.data_ptr() % 16 == 0 and ((full.data_ptr() + 4 * at) % 16 == 0) == (offset % 4 == 0)
     k = _Ints(np.asarray(keys, np.int64), -99)
-    _native.raise_for_status(orows.lib().gp_row_list_zero(0, k.ptr(), len(keys), V, H, full.data_ptr() + 4 * at, _stream()))
+    _native.raise_for_status(_native.lib().gp_row_list_zero(0, k.ptr(), len(keys), V, H, full.data_ptr() + 4 * at, _stream()))
     torch.cuda.synchronize()
     assert np.array_equal(k.get(), np.asarray(keys, np.int64))
     bits = full.cpu().numpy().view(np.uint32)

@@ -71,7 +71,7 @@ def test_mag_atomic_backward_past_its_grid_gives_the_same_bits():
 def test_mag_keys_slot_base_and_tail_past_the_grid():
     """gp_mag_det_keys as tests/test_gpu_mag_det.py calls it: slot_base, the keys and the tail of 1 000 sentinels equal the
     vectorised entry order, between guard bands."""
-    from grand_plus_amd import mag_det as md
+    from grand_plus_amd import _native
     c = st.mag_case()
     P, n_slots, cap = c["P"], st.MAG_B * st.MAG_K, c["total"] + st.MAG_SLACK
     _, ip, ix, _dt, col, _val, _filled, K = P.cuda()
@@ -79,7 +79,7 @@ def test_mag_keys_slot_base_and_tail_past_the_grid():
     keys = torch.full((GUARD + cap + GUARD,), G64, dtype=torch.int64, device="cuda")
     flag = torch.full((GUARD + 1 + GUARD,), G32, dtype=torch.int32, device="cuda")
     flag[GUARD] = 4
-    rc = md.lib().gp_mag_det_keys(0, P.V, ip.data_ptr(), ix.data_ptr(), P.N, col.data_ptr(), None, P.S_rows, K, None, P.S_rows, cap,
+    rc = _native.lib().gp_mag_det_keys(0, P.V, ip.data_ptr(), ix.data_ptr(), P.N, col.data_ptr(), None, P.S_rows, K, None, P.S_rows, cap,
                                   base.data_ptr() + 8 * GUARD, keys.data_ptr() + 8 * GUARD, flag.data_ptr() + 4 * GUARD, _stream())
     assert rc == 0
     torch.cuda.synchronize()

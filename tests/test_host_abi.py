@@ -1,6 +1,7 @@
-"""CPU tests of the C ABI's ctypes binding, _native.ABI, header by header: every public header is wired into the one ABI
-and the one library, the table's entries are the header's prototypes, every type is the one the convention stated above
-the table gives, and the Python mirrors of the macros and structs equal what the C compiler makes of the headers."""
+"""CPU tests of the ctypes binding, _native.ABI and _native.PRIVATE_ABI, header by header: every public header is wired
+into the one ABI and the one library, the private headers csrc/*_abi.hpp stay outside it, each table's entries are its
+header's prototypes, every type is the one the convention stated above _native.ABI gives, and the Python mirrors of the
+macros and structs equal what the C compiler makes of the headers."""
 import ctypes
 import glob
 import os
@@ -13,6 +14,7 @@ import optim_cases as oc
 from grand_plus_amd import _native
 
 HEADERS = list(_native.ABI)
+PRIVATE = list(_native.PRIVATE_ABI)                                   # the headers of the entry points outside C ABI 4
 # header -> the translation units of libgrandplus.so that define its entry points
 UNITS = {"grandplus.h": ("gfpush.hip", "augment.hip", "propagate.hip", "objective.hip", "mlp.hip", "optim.hip"),
          "grandplus_eval.h": ("evaluate.hip",), "grandplus_scatter.h": ("scatter_det.hip",),
@@ -63,25 +65,50 @@ def test_the_header_is_part_of_the_one_abi_and_the_one_library(header):
     assert _native.lib().gp_strerror(2) == b"invalid CSR"
 
 
-@pytest.mark.parametrize("header", HEADERS)
+def _table(header):
+    return _native.PRIVATE_ABI[header] if header in PRIVATE else _native.ABI[header]
+
+
+def test_the_private_headers_stay_outside_the_public_abi():
+    # every entry name occurs exactly once across the two tables
+    names = [name for table in (_native.ABI, _native.PRIVATE_ABI) for entries in table.values() for name in entries]
+    assert len(names) == len(set(names))
+    assert sorted(PRIVATE) == sorted(os.path.basename(p) for p in glob.glob(os.path.join(ah.CSRC, "*_abi.hpp")))
+    public = "".join(open(p).read() for p in glob.glob(os.path.join(ah.INC, "*")))
+    for header in PRIVATE:
+        assert header not in public and not [name for name in _native.PRIVATE_ABI[header] if name in public], header
+
+
+def test_one_patch_of_the_binder_reaches_every_modules_loader(monkeypatch):
+    """mag_det.lib, optim_rows.lib, gather_chunk.lib and fit.rows_lib go through `_native.lib` at each call, so the one patch
+    by which the host tests prove "the native library was not reached" covers them; none holds a table of its own."""
+    from grand_plus_amd import fit, gather_chunk, mag_det, optim_rows
+    reached = object()
+    monkeypatch.setattr(_native, "lib", lambda: reached)
+    assert [f() for f in (mag_det.lib, optim_rows.lib, gather_chunk.lib, fit.rows_lib)] == [reached] * 4
+    assert fit.ROWS_ABI is _native.PRIVATE_ABI["fit_rows_abi.hpp"]
+    assert not [m.__name__ for m in (mag_det, optim_rows, gather_chunk) if hasattr(m, "ABI") or hasattr(m, "MARK_ABI")]
+
+
+@pytest.mark.parametrize("header", HEADERS + PRIVATE)
 def test_the_entries_are_the_headers_prototypes(header):
     protos = ah.prototypes(header)
-    assert sorted(protos) == sorted(_native.ABI[header])
+    assert sorted(protos) == sorted(_table(header))
     if header == "grandplus.h":
         assert len(protos) == N_MAIN
-    else:
+    elif header in HEADERS:                                           # a private header's names stand in its module's own test
         assert sorted(protos) == NAMES[header]
     built = ctypes.CDLL(_native.LIB_PATH)
     for name in protos:
         assert hasattr(built, name), f"libgrandplus.so does not export {name}"
 
 
-@pytest.mark.parametrize("header", HEADERS)
+@pytest.mark.parametrize("header", HEADERS + PRIVATE)
 def test_the_types_are_the_conventions_position_by_position(header):
     """Every entry of the table against the header's prototype: the count, and the one type the convention gives for each
     position; the loaded library carries exactly these."""
     for name, (ret, params) in ah.prototypes(header).items():
-        restype, argtypes, required = _native.ABI[header][name]
+        restype, argtypes, required = _table(header)[name]
         assert isinstance(required, bool) if header == "grandplus.h" else required is False, name
         assert restype is ah.expected_ctype(name, *ret), f"{name}: restype {restype} for {ret}"
         assert len(argtypes) == len(params) == N_PARAMS.get(name, len(params)), f"{name}: {len(argtypes)} argtypes for {len(params)} parameters"

@@ -1,7 +1,8 @@
 """CPU tests of the dirty-row snapshot and of `fit` over a MagTrainStep: csrc/fit_rows_layout.hpp itself
 (tests/native/fit_rows_check.cpp, built with the address and undefined-behaviour sanitizers and run as a program) against
-brute force, the binding of csrc/fit_rows_abi.hpp (fit.ROWS_ABI) against that header, the entry points' error codes before
-any GPU work, every refusal of the Python layer before a device call, and the grid cap the GPU cases were sized for."""
+brute force, what is particular to the entry points of csrc/fit_rows_abi.hpp in _native.PRIVATE_ABI (tests/test_host_abi.py
+holds the types), their error codes before any GPU work, every refusal of the Python layer before a device call, and the
+grid cap the GPU cases were sized for."""
 import ctypes
 import glob
 import inspect
@@ -20,7 +21,6 @@ import row_mark_cases as rm
 from grand_plus_amd import _native
 from grand_plus_amd import fit as gfit
 from grand_plus_amd import optim_rows as orows
-from grand_plus_amd.fit import ROWS_ABI, rows_lib  # noqa: F401  (the whole module is about these names)
 from test_host_mag_det import _mag_step
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -100,31 +100,10 @@ def test_the_copy_of_a_word_is_brute_force(checker, V):
 
 
 # ---- 2. the binding
-def _prototypes():
-    text = open(os.path.join(CSRC, "fit_rows_abi.hpp")).read()
-    code = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
-    protos = {}
-    for ret, name, params in re.findall(r"\b((?:const\s+)?\w+\s*\**)\s*\b(gp_[a-z_0-9]+)\s*\(([^)]*)\)\s*;", code):
-        assert name not in protos
-        params = [re.fullmatch(r"(.*?)(\w+)", p.strip(), flags=re.S).groups() for p in params.split(",")]
-        protos[name] = (ah._ctype(ret), [ah._ctype(decl) + (pname,) for decl, pname in params])
-    assert sorted(re.findall(r"\b(gp_[a-z_0-9]+)\s*\(", code)) == sorted(protos)
-    return protos
-
-
 def test_the_table_is_the_headers_prototypes_type_by_type():
-    protos = _prototypes()
-    assert sorted(protos) == sorted(gfit.ROWS_ABI) == NAMES
-    built = ctypes.CDLL(_native.LIB_PATH)
-    for name, (ret, params) in protos.items():
-        restype, argtypes = gfit.ROWS_ABI[name]
-        assert restype is ah.expected_ctype(name, *ret)
-        assert len(argtypes) == len(params), name
-        for i, (got, want) in enumerate(zip(argtypes, params)):
-            assert got is ah.expected_ctype(name, *want), f"{name}: argument {i} is {got} for {want}"
-        assert hasattr(built, name), f"libgrandplus.so does not export {name}"
-        f = getattr(gfit.rows_lib(), name)
-        assert f.argtypes == argtypes and f.restype is restype
+    """The generic part -- every type by the convention, the library's exports -- is tests/test_host_abi.py's."""
+    protos = ah.prototypes("fit_rows_abi.hpp")
+    assert sorted(protos) == sorted(_native.PRIVATE_ABI["fit_rows_abi.hpp"]) == NAMES
     assert [p[2] for p in protos["gp_fit_rows_mark"][1]] == ["device", "d_keys", "n_keys", "n_vocab", "d_dirty", "stream"]
     assert [p[2] for p in protos["gp_fit_rows_snapshot"][1]] == ["device", "d_track", "d_src", "d_dst", "n_vocab", "dim", "d_dirty", "stream"]
 
@@ -134,8 +113,6 @@ def test_the_unit_is_built_and_stays_outside_c_abi_4():
     assert "fit_rows.hip" in entry.LIB_UNITS and os.path.exists(os.path.join(CSRC, "fit_rows.hip"))
     for hdr in ("fit_rows_abi.hpp", "fit_rows_layout.hpp", "row_mark_layout.hpp"):
         assert os.path.join(CSRC, hdr) in entry.lib_sources()
-    names = {n for entries in _native.ABI.values() for n in entries}
-    assert not names & set(gfit.ROWS_ABI) and not set(orows.ABI) & set(gfit.ROWS_ABI) and not set(orows.MARK_ABI) & set(gfit.ROWS_ABI)
     public = "".join(open(p).read() for p in glob.glob(os.path.join(ROOT, "include", "*.h")))
     assert "fit_rows" not in public
     assert _native.lib().gp_abi_version() == 4
@@ -157,7 +134,7 @@ def test_the_unit_is_built_and_stays_outside_c_abi_4():
 def test_the_entries_return_their_error_codes_before_any_gpu_work():
     """No device pointer here is real: every call has to stop at its argument checks."""
     E, N, OK = _native.GP_ERR_INVALID_ARG, _native.GP_ERR_NULL, _native.GP_OK
-    L = gfit.rows_lib()
+    L = _native.lib()
     odd = ctypes.c_void_p(18)
 
     def mark(keys=P, n_keys=5, V=50, dirty=P):
@@ -195,8 +172,7 @@ class _Cuda(torch.Tensor):
 
 
 def _no_device(monkeypatch):
-    for mod, name in ((_native, "lib"), (orows, "lib"), (gfit, "rows_lib")):
-        monkeypatch.setattr(mod, name, lambda: pytest.fail("the native library was reached"))
+    monkeypatch.setattr(_native, "lib", lambda: pytest.fail("the native library was reached"))
 
 
 def test_dirty_rows_needs_the_lazy_table_step(monkeypatch):

@@ -1,8 +1,8 @@
-"""CPU tests of the chunked deterministic segment sums: the binding of csrc/gather_chunk_abi.hpp
-(gather_chunk.ABI) against that header, the entry points' error codes before any GPU work, every refusal of the Python layer
-before a device call, the audit of tests/gather_chunk_cases.py with deliberate mistakes, and csrc/gather_chunk_layout.hpp
-itself (tests/native/gather_chunk_check.cpp, built with the address and undefined-behaviour sanitizers and run as a program)
-against brute force."""
+"""CPU tests of the chunked deterministic segment sums: what is particular to the entry points of
+csrc/gather_chunk_abi.hpp in _native.PRIVATE_ABI (tests/test_host_abi.py holds the types), their error codes before any GPU
+work, every refusal of the Python layer before a device call, the audit of tests/gather_chunk_cases.py with deliberate
+mistakes, and csrc/gather_chunk_layout.hpp itself (tests/native/gather_chunk_check.cpp, built with the address and
+undefined-behaviour sanitizers and run as a program) against brute force."""
 import ctypes
 import glob
 import inspect
@@ -34,32 +34,13 @@ def _code(name):
     return re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
 
 
-def _prototypes(code):
-    protos = {}
-    for ret, name, params in re.findall(r"\b((?:const\s+)?\w+\s*\**)\s*\b(gp_[a-z_0-9]+)\s*\(([^)]*)\)\s*;", code):
-        assert name not in protos
-        params = [re.fullmatch(r"(.*?)(\w+)", p.strip(), flags=re.S).groups() for p in params.split(",")]
-        protos[name] = (ah._ctype(ret), [ah._ctype(decl) + (pname,) for decl, pname in params])
-    assert sorted(re.findall(r"\b(gp_[a-z_0-9]+)\s*\(", code)) == sorted(protos)
-    return protos
-
-
 def test_the_table_is_the_headers_prototypes_position_by_position():
-    protos = _prototypes(_code("gather_chunk_abi.hpp"))
-    assert sorted(protos) == sorted(gc.ABI) == NAMES
-    built = ctypes.CDLL(_native.LIB_PATH)
-    for name, (ret, params) in protos.items():
-        restype, argtypes = gc.ABI[name]
-        assert restype is ah.expected_ctype(name, *ret)
-        assert len(argtypes) == len(params), name
-        for i, (got, want) in enumerate(zip(argtypes, params)):
-            assert got is ah.expected_ctype(name, *want), f"{name}: argument {i} is {got} for {want}"
-        assert hasattr(built, name), f"libgrandplus.so does not export {name}"
-        f = getattr(gc.lib(), name)
-        assert f.argtypes == argtypes and f.restype is restype
+    """The generic part -- every type by the convention, the library's exports -- is tests/test_host_abi.py's."""
+    protos = ah.prototypes("gather_chunk_abi.hpp")
+    assert sorted(protos) == sorted(_native.PRIVATE_ABI["gather_chunk_abi.hpp"]) == NAMES
     # each takes its unchunked twin's arguments up to the stream, name by name, then chunk, d_scratch, scratch_bytes, stream
     scatter = ah.prototypes("grandplus_scatter.h")
-    mag = _prototypes(_code("mag_det_abi.hpp"))
+    mag = ah.prototypes("mag_det_abi.hpp")
     for name, twin in (("gp_random_prop_rows_backward_det_chunked", scatter["gp_random_prop_rows_backward_det"]),
                        ("gp_embedding_bag_backward_det_chunked", scatter["gp_embedding_bag_backward_det"]),
                        ("gp_mag_prop_rows_backward_det_chunked", mag["gp_mag_prop_rows_backward_det"])):
@@ -72,8 +53,6 @@ def test_the_entry_points_stay_outside_c_abi_4():
     import __graft_entry__ as entry
     for hdr in ("gather_chunk.hpp", "gather_chunk_abi.hpp", "gather_chunk_layout.hpp"):
         assert os.path.join(CSRC, hdr) in entry.lib_sources()
-    names = {n for entries in _native.ABI.values() for n in entries}
-    assert not names & set(gc.ABI)
     public = "".join(open(p).read() for p in glob.glob(os.path.join(ROOT, "include", "*.h")))
     assert "chunked" not in public and "GATHER_CHUNK" not in public
     assert not [n for n in vars(_native) if "CHUNKED" in n.upper() or "GATHER_CHUNK" in n.upper()]
@@ -103,22 +82,24 @@ def _body(text, name):
     return [ln.strip() for ln in text[text.index("\n{\n", i) + 3:text.index("\n}\n", i)].splitlines()]
 
 
-def test_the_chunked_twins_repeat_their_twins_lines_and_the_second_grid_cap_is_the_first():
-    """The unchunked entry points stay as they are written, so the rows and MAG chunked twins repeat their checks, pre-pass
-    and Op: every line of a twin's body stands in its chunked twin's body, but for its name, its gather launch and (rows)
-    the pre-pass launch line, whose grid the chunked twin takes from rows_den_grid(): that cap is source_caps()'s."""
+def test_each_deterministic_backward_has_one_body_and_its_entry_points_only_name_themselves():
+    """The rows pair and the MAG pair share one body each: the pre-pass is launched on one line of its unit, the Op and the
+    arguments are built once, and an entry point holds its own name and no launch.  The pre-pass's grid cap stands on that
+    one line, where source_caps() reads it."""
     import second_trip_cases as st
     scatter = open(os.path.join(CSRC, "scatter_det.hip")).read()
     mag = open(os.path.join(CSRC, "mag_det.hip")).read()
-    for text, twin, own in ((scatter, "gp_random_prop_rows_backward_det", 5), (mag, "gp_mag_prop_rows_backward_det", 4)):
-        theirs, mine = _body(text, twin), set(_body(text, twin + "_chunked"))
-        missing = [ln for ln in theirs if ln not in mine]
-        assert len(missing) == own, missing
-        assert all(twin + '";' in ln or "gather_sum_kernel" in ln or "(const long long*)d_sorted_keys" in ln or
-                   "rows_inv_den_kernel, dim3(std::min(n_batch," in ln for ln in missing), missing
-    assert "rows_inv_den_kernel, dim3(rows_den_grid(n_batch))" in scatter
-    cap = re.findall(r"int rows_den_grid\(int n_batch\) \{ return std::min\(n_batch, (\d+)\); \}", scatter)
-    assert [int(c) for c in cap] == [st.source_caps()["rows_den_grid"]]
+    assert len([ln for ln in scatter.splitlines() if "rows_inv_den_kernel," in ln]) == 1 and scatter.count("const RowsOp op") == 1
+    assert len([ln for ln in mag.splitlines() if "mag_slot_grad_kernel," in ln]) == 1
+    assert mag.count("const MagArgs A") == 1 and mag.count("const MagOp op") == 1
+    for path in glob.glob(os.path.join(CSRC, "*")):
+        assert "rows_den_grid" not in open(path, errors="replace").read(), path
+    for text, twin in ((scatter, "gp_random_prop_rows_backward_det"), (mag, "gp_mag_prop_rows_backward_det")):
+        for name in (twin, twin + "_chunked"):
+            body = "\n".join(_body(text, name))
+            assert f'"{name}"' in body and "hipLaunchKernelGGL" not in body, name
+            assert f'"{twin}_chunked"' not in body if name == twin else f'"{twin}"' not in body, name
+    assert st.source_caps()["rows_den_grid"] == 65535
     # the bag twin runs its pre-pass through the unchunked entry point itself: nothing is repeated there
     bag = "\n".join(_body(scatter, "gp_embedding_bag_backward_det_chunked"))
     assert "gp_embedding_bag_backward_det(device," in bag and "bag_inv_den_kernel" not in bag
@@ -141,7 +122,7 @@ def test_the_scratch_macro_is_the_layout_headers_and_the_bindings_figure(tmp_pat
 def test_the_entries_return_their_error_codes_before_any_gpu_work():
     """No device pointer here is real: every call has to stop at its argument checks."""
     E, N, OK = _native.GP_ERR_INVALID_ARG, _native.GP_ERR_NULL, _native.GP_OK
-    L = gc.lib()
+    L = _native.lib()
 
     def rows(g=P, B=4, F=7, col=P, val=P, K=5, S=2, p=0.5, gx=P, n_nodes=9, order=P, keys=P, n_sorted=20, inv=P, chunk=64,
              scratch=P, nbytes=None):

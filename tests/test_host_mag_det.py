@@ -1,7 +1,8 @@
-"""CPU tests of MAG's deterministic table gradient and its captured step: the binding of
-csrc/mag_det_abi.hpp (mag_det.ABI) against that header, the entry points' error codes before any GPU work, every refusal
-of the Python layer before a device call, and csrc/mag_det_layout.hpp itself (tests/native/mag_det_check.cpp, built with the
-address and undefined-behaviour sanitizers and run as a program) against the brute-force entry order."""
+"""CPU tests of MAG's deterministic table gradient and its captured step: what is particular to
+the entry points of csrc/mag_det_abi.hpp in _native.PRIVATE_ABI (tests/test_host_abi.py holds the types), their error codes
+before any GPU work, every refusal of the Python layer before a device call, and csrc/mag_det_layout.hpp itself
+(tests/native/mag_det_check.cpp, built with the address and undefined-behaviour sanitizers and run as a program) against the
+brute-force entry order."""
 import ctypes
 import glob
 import os
@@ -26,37 +27,11 @@ NAMES = ["gp_mag_det_keys", "gp_mag_prop_rows_backward_det"]
 
 
 # ---- 1. the binding
-def _header():
-    text = open(os.path.join(CSRC, "mag_det_abi.hpp")).read()
-    return text, re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
-
-
-def _prototypes():
-    """name -> (return type, parameters) of mag_det_abi.hpp, parsed as abi_header.prototypes parses a public header."""
-    _, code = _header()
-    protos = {}
-    for ret, name, params in re.findall(r"\b((?:const\s+)?\w+\s*\**)\s*\b(gp_[a-z_0-9]+)\s*\(([^)]*)\)\s*;", code):
-        assert name not in protos
-        params = [re.fullmatch(r"(.*?)(\w+)", p.strip(), flags=re.S).groups() for p in params.split(",")]
-        protos[name] = (ah._ctype(ret), [ah._ctype(decl) + (pname,) for decl, pname in params])
-    assert sorted(re.findall(r"\b(gp_[a-z_0-9]+)\s*\(", code)) == sorted(protos)
-    return protos
-
-
 def test_the_table_is_the_headers_prototypes_position_by_position():
-    protos = _prototypes()
-    assert sorted(protos) == sorted(md.ABI) == NAMES
-    built = ctypes.CDLL(_native.LIB_PATH)
-    for name, (ret, params) in protos.items():
-        restype, argtypes = md.ABI[name]
-        assert restype is ah.expected_ctype(name, *ret)
-        assert len(argtypes) == len(params), name
-        for i, (got, want) in enumerate(zip(argtypes, params)):
-            assert got is ah.expected_ctype(name, *want), f"{name}: argument {i} is {got} for {want}"
-        assert hasattr(built, name), f"libgrandplus.so does not export {name}"
-        f = getattr(md.lib(), name)
-        assert f.argtypes == argtypes and f.restype is restype
-    assert len(md.ABI["gp_mag_det_keys"][1]) == 16 and len(md.ABI["gp_mag_prop_rows_backward_det"][1]) == 30
+    """The generic part -- every type by the convention, the library's exports -- is tests/test_host_abi.py's."""
+    protos, table = ah.prototypes("mag_det_abi.hpp"), _native.PRIVATE_ABI["mag_det_abi.hpp"]
+    assert sorted(protos) == sorted(table) == NAMES
+    assert len(table["gp_mag_det_keys"][1]) == 16 and len(table["gp_mag_prop_rows_backward_det"][1]) == 30
     # the deterministic backward takes the atomic backward's arguments up to keep_stride, name by name
     atomic = ah.prototypes("grandplus_mag.h")["gp_mag_prop_rows_backward"][1]
     assert protos["gp_mag_prop_rows_backward_det"][1][:22] == atomic[:22] and atomic[21][2] == "keep_stride"
@@ -67,8 +42,6 @@ def test_the_entry_points_stay_outside_c_abi_4():
     assert "mag_det.hip" in entry.LIB_UNITS
     for hdr in ("mag_det_abi.hpp", "mag_det_layout.hpp", "gather_sum.hpp", "mag_stage.hpp"):
         assert os.path.join(CSRC, hdr) in entry.lib_sources()
-    names = {n for entries in _native.ABI.values() for n in entries}
-    assert not names & set(md.ABI)
     public = "".join(open(p).read() for p in glob.glob(os.path.join(ROOT, "include", "*.h")))
     assert "gp_mag_det" not in public and "backward_det(" not in public.replace("gp_random_prop_rows_backward_det(", "").replace(
         "gp_embedding_bag_backward_det(", "")
@@ -100,7 +73,7 @@ def test_the_units_share_their_lines_and_the_kernels_hold_no_atomics():
 def test_the_entries_return_their_error_codes_before_any_gpu_work():
     """No device pointer here is real: every call has to stop at its argument checks."""
     E, N, OK = _native.GP_ERR_INVALID_ARG, _native.GP_ERR_NULL, _native.GP_OK
-    L = md.lib()
+    L = _native.lib()
 
     def keys(V=50, indptr=P, indices=P, n_nodes=12, col=P, filled=P, n_rows=6, K=5, batch=P, B=4, cap=100, base=P, out=P, flag=P):
         return L.gp_mag_det_keys(0, V, indptr, indices, n_nodes, col, filled, n_rows, K, batch, B, cap, base, out, flag, None)

@@ -1,7 +1,8 @@
 """CPU tests of the embedding table's row-list step: csrc/optim_rows_layout.hpp itself
 (tests/native/optim_rows_check.cpp, built with the address and undefined-behaviour sanitizers and run as a program) against
-brute force, the binding of csrc/optim_rows_abi.hpp (optim_rows.ABI) against that header, the entry points' error codes
-before any GPU work, every refusal of the Python layer before a device call, and the numpy mirror's deliberate mistakes."""
+brute force, what is particular to the entry points of csrc/optim_rows_abi.hpp in _native.PRIVATE_ABI (tests/test_host_abi.py
+holds the types), their error codes before any GPU work, every refusal of the Python layer before a device call, and the
+numpy mirror's deliberate mistakes."""
 import ctypes
 import glob
 import os
@@ -79,32 +80,10 @@ def test_the_grid_holds_the_edges_it_names():
 
 
 # ---- 2. the binding
-def _prototypes():
-    """name -> (return type, parameters) of optim_rows_abi.hpp, parsed as abi_header.prototypes parses a public header."""
-    text = open(os.path.join(CSRC, "optim_rows_abi.hpp")).read()
-    code = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
-    protos = {}
-    for ret, name, params in re.findall(r"\b((?:const\s+)?\w+\s*\**)\s*\b(gp_[a-z_0-9]+)\s*\(([^)]*)\)\s*;", code):
-        assert name not in protos
-        params = [re.fullmatch(r"(.*?)(\w+)", p.strip(), flags=re.S).groups() for p in params.split(",")]
-        protos[name] = (ah._ctype(ret), [ah._ctype(decl) + (pname,) for decl, pname in params])
-    assert sorted(re.findall(r"\b(gp_[a-z_0-9]+)\s*\(", code)) == sorted(protos)
-    return protos, code
-
-
 def test_the_table_is_the_headers_prototypes_type_by_type():
-    protos, code = _prototypes()
-    assert sorted(protos) == sorted(orows.ABI) == NAMES
-    built = ctypes.CDLL(_native.LIB_PATH)
-    for name, (ret, params) in protos.items():
-        restype, argtypes = orows.ABI[name]
-        assert restype is ah.expected_ctype(name, *ret)
-        assert len(argtypes) == len(params), name
-        for i, (got, want) in enumerate(zip(argtypes, params)):
-            assert got is ah.expected_ctype(name, *want), f"{name}: argument {i} is {got} for {want}"
-        assert hasattr(built, name), f"libgrandplus.so does not export {name}"
-        f = getattr(orows.lib(), name)
-        assert f.argtypes == argtypes and f.restype is restype
+    """The generic part -- every type by the convention, the library's exports -- is tests/test_host_abi.py's."""
+    protos, code = ah.prototypes("optim_rows_abi.hpp"), ah.read("optim_rows_abi.hpp")[1]
+    assert sorted(protos) == sorted(_native.PRIVATE_ABI["optim_rows_abi.hpp"]) == NAMES
     # the pair mirrors the dense pair: the same arguments but for the two corrections, by value or by device pointer
     a, b = protos["gp_clip_adam_rows"][1], protos["gp_clip_adam_rows_dev"][1]
     assert len(a) == len(b) == 21 and [x for x, y in zip(a, b) if x != y] == [("float", 0, "step_size"), ("float", 0, "rsqrt_bc2")]
@@ -120,8 +99,6 @@ def test_the_entry_points_stay_outside_c_abi_4():
     assert "optim_rows.hip" in entry.LIB_UNITS
     for hdr in ("optim_rows_abi.hpp", "optim_rows_layout.hpp", "optim_math.hpp"):
         assert os.path.join(CSRC, hdr) in entry.lib_sources()
-    names = {n for entries in _native.ABI.values() for n in entries}
-    assert not names & set(orows.ABI)
     public = "".join(open(p).read() for p in glob.glob(os.path.join(ROOT, "include", "*.h")))
     assert "optim_rows" not in public and "adam_rows" not in public and "GP_OPTIM_ROWS" not in public
     mag_det_abi = open(os.path.join(CSRC, "mag_det_abi.hpp")).read()
@@ -159,7 +136,7 @@ def test_the_arithmetic_is_stated_once_and_the_unit_holds_no_atomics():
 def test_the_entries_return_their_error_codes_before_any_gpu_work():
     """No device pointer here is real: every call has to stop at its argument checks."""
     E, N, OK = _native.GP_ERR_INVALID_ARG, _native.GP_ERR_NULL, _native.GP_OK
-    L = orows.lib()
+    L = _native.lib()
 
     def sq(keys=P, n=10, V=50, H=7, dW=P, acc=0, ws=P):
         return L.gp_optim_rows_sqnorm(0, keys, n, V, H, dW, acc, ws, None)
@@ -207,7 +184,6 @@ def _fake(t):
 
 def _no_device(monkeypatch):
     monkeypatch.setattr(_native, "lib", lambda: pytest.fail("the native library was reached"))
-    monkeypatch.setattr(orows, "lib", lambda: pytest.fail("the native library was reached"))
 
 
 def test_row_grad_refuses_what_is_no_table(monkeypatch):

@@ -1,7 +1,7 @@
 """CPU tests of the atomic backward's row list: csrc/row_mark_layout.hpp itself (tests/native/row_mark_check.cpp,
-built with the address and undefined-behaviour sanitizers and run as a program) against brute force, the binding of
-csrc/row_mark_abi.hpp (optim_rows.MARK_ABI) against that header, the entry points' error codes before any GPU work, every
-refusal of the Python layer before a device call, and the numpy mirror's deliberate mistakes."""
+built with the address and undefined-behaviour sanitizers and run as a program) against brute force, what is particular to the
+entry points of csrc/row_mark_abi.hpp in _native.PRIVATE_ABI (tests/test_host_abi.py holds the types), their error codes
+before any GPU work, every refusal of the Python layer before a device call, and the numpy mirror's deliberate mistakes."""
 import ctypes
 import glob
 import inspect
@@ -86,31 +86,10 @@ def test_words_bits_and_chunks(checker):
 
 
 # ---- 2. the binding
-def _prototypes():
-    text = open(os.path.join(CSRC, "row_mark_abi.hpp")).read()
-    code = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
-    protos = {}
-    for ret, name, params in re.findall(r"\b((?:const\s+)?\w+\s*\**)\s*\b(gp_[a-z_0-9]+)\s*\(([^)]*)\)\s*;", code):
-        assert name not in protos
-        params = [re.fullmatch(r"(.*?)(\w+)", p.strip(), flags=re.S).groups() for p in params.split(",")]
-        protos[name] = (ah._ctype(ret), [ah._ctype(decl) + (pname,) for decl, pname in params])
-    assert sorted(re.findall(r"\b(gp_[a-z_0-9]+)\s*\(", code)) == sorted(protos)
-    return protos, code
-
-
 def test_the_table_is_the_headers_prototypes_type_by_type():
-    protos, code = _prototypes()
-    assert sorted(protos) == sorted(orows.MARK_ABI) == NAMES
-    built = ctypes.CDLL(_native.LIB_PATH)
-    for name, (ret, params) in protos.items():
-        restype, argtypes = orows.MARK_ABI[name]
-        assert restype is ah.expected_ctype(name, *ret)
-        assert len(argtypes) == len(params), name
-        for i, (got, want) in enumerate(zip(argtypes, params)):
-            assert got is ah.expected_ctype(name, *want), f"{name}: argument {i} is {got} for {want}"
-        assert hasattr(built, name), f"libgrandplus.so does not export {name}"
-        f = getattr(orows.lib(), name)
-        assert f.argtypes == argtypes and f.restype is restype
+    """The generic part -- every type by the convention, the library's exports -- is tests/test_host_abi.py's."""
+    protos, code = ah.prototypes("row_mark_abi.hpp"), ah.read("row_mark_abi.hpp")[1]
+    assert sorted(protos) == sorted(_native.PRIVATE_ABI["row_mark_abi.hpp"]) == NAMES
     # the mark takes gp_mag_det_keys' operands up to n_batch, name by name
     text = open(os.path.join(CSRC, "mag_det_abi.hpp")).read()
     det = re.search(r"int gp_mag_det_keys\(([^)]*)\)", text).group(1)
@@ -124,8 +103,6 @@ def test_the_entry_points_stay_outside_c_abi_4_and_share_the_slot_rule():
     assert "row_mark.hip" in entry.LIB_UNITS
     for hdr in ("row_mark_abi.hpp", "row_mark_layout.hpp", "mag_stage.hpp"):
         assert os.path.join(CSRC, hdr) in entry.lib_sources()
-    names = {n for entries in _native.ABI.values() for n in entries}
-    assert not names & set(orows.MARK_ABI) and not set(orows.ABI) & set(orows.MARK_ABI)
     public = "".join(open(p).read() for p in glob.glob(os.path.join(ROOT, "include", "*.h")))
     assert "row_mark" not in public and "row_list" not in public and "ROW_LIST" not in public
     assert _native.lib().gp_abi_version() == 4
@@ -149,7 +126,7 @@ def test_the_entry_points_stay_outside_c_abi_4_and_share_the_slot_rule():
 def test_the_entries_return_their_error_codes_before_any_gpu_work():
     """No device pointer here is real: every call has to stop at its argument checks."""
     E, N, OK = _native.GP_ERR_INVALID_ARG, _native.GP_ERR_NULL, _native.GP_OK
-    L = orows.lib()
+    L = _native.lib()
 
     def mark(V=50, indptr=P, indices=P, n_nodes=12, col=P, filled=P, n_rows=6, K=5, batch=P, B=4, bitmap=P):
         return L.gp_row_mark_mag(0, V, indptr, indices, n_nodes, col, filled, n_rows, K, batch, B, bitmap, None)
@@ -200,7 +177,6 @@ def _fake(t):
 
 def _no_device(monkeypatch):
     monkeypatch.setattr(_native, "lib", lambda: pytest.fail("the native library was reached"))
-    monkeypatch.setattr(orows, "lib", lambda: pytest.fail("the native library was reached"))
 
 
 def test_bitmap_row_grad_is_a_row_grad_with_a_bitmap(monkeypatch):

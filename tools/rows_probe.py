@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from grand_plus_amd import optim_rows as orows  # noqa: E402
+from grand_plus_amd import _native, optim_rows as orows  # noqa: E402
 
 V, H, N_SORTED, LIVE, CALLS = 500_000, 64, 49_920, 25_600, 50
 
@@ -37,7 +37,7 @@ def timed(fn):
 
 
 def main():
-    L = orows.lib()
+    L = _native.lib()
     rng = np.random.default_rng(0)
     dW = torch.randn(V, H, device="cuda")
     p, m, v = (torch.rand(V, H, device="cuda") + 0.1 for _ in range(3))
