@@ -276,6 +276,7 @@ ABI = {
 _rows_step = [_int, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _int, _f32, _f32, _f64, _f64, _f32, _f32]   # device .. weight_decay
 # a chunked twin takes its unchunked twin's arguments up to the stream, then chunk, d_scratch, scratch_bytes and the stream
 _scatter, _chunk = ABI["grandplus_scatter.h"], [_i32, _vp, _i64, _vp]
+_mag_dseed = _mag[:-3] + [_vp] + _mag[-2:]                            # _mag with d_seed, a device pointer, where seed stands
 PRIVATE_ABI = {
     "mag_det_abi.hpp": {
         "gp_mag_det_keys": (_int, [_int, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _i32, _i64, _vp, _vp, _vp, _vp], False),
@@ -299,6 +300,14 @@ PRIVATE_ABI = {
         "gp_random_prop_rows_backward_det_chunked": (_int, _scatter["gp_random_prop_rows_backward_det"][1][:-1] + _chunk, False),
         "gp_embedding_bag_backward_det_chunked": (_int, _scatter["gp_embedding_bag_backward_det"][1][:-1] + _chunk, False),
         "gp_mag_prop_rows_backward_det_chunked": (_int, [_int, _vp] + _mag + [_vp, _vp, _vp, _i64, _vp, _vp, _vp] + _chunk, False),
+    },
+    # the two forms of grandplus_mag.h's pair with a device pointer where those take the seed; the deterministic backward with
+    # input dropout takes gp_mag_prop_rows_backward_det's arguments with d_seed after seed and the chunk's three before the stream
+    "mag_drop_abi.hpp": {
+        "gp_mag_prop_rows_dseed": (_int, [_int, _vp] + _mag_dseed + [_vp, _vp, _vp], False),
+        "gp_mag_prop_rows_backward_dseed": (_int, [_int, _vp] + _mag_dseed + [_vp, _vp], False),
+        "gp_mag_prop_rows_backward_det_drop": (_int, [_int, _vp] + _mag[:-2] + [_vp] + _mag[-2:] + [_vp, _vp, _vp, _i64, _vp, _vp, _vp] + _chunk,
+                                               False),
     },
 }
 

@@ -108,6 +108,7 @@ mag_slot_grad_kernel(const float* __restrict__ grad_out, MagArgs A, float* __res
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n_waves = blockDim.x >> 6;
     const float scale_node = inv_keep(A.p_node);
     const size_t g_stride = (size_t)A.B * H;
+    const u64 seed = call_seed(A);
     for (int b = blockIdx.x; b < A.B; b += gridDim.x) {
         const long long row = A.batch_rows ? (long long)A.batch_rows[b] : (long long)b;
         if (row < 0 || row >= A.n_rows) {                                         // workgroup-uniform: no slot of b exists
@@ -120,7 +121,7 @@ mag_slot_grad_kernel(const float* __restrict__ grad_out, MagArgs A, float* __res
             const int ns = min(nsc, A.S - s0);
             const bool first = s0 == 0, last = s0 + ns >= A.S;
             __syncthreads();
-            stage_row(A, row, n, s0, ns, scale_node, s_col, nullptr, s_w, nullptr);
+            stage_row(A, seed, row, n, s0, ns, scale_node, s_col, nullptr, s_w, nullptr);
             __syncthreads();
             if (threadIdx.x < ns) {
                 float den = 0.0f;

@@ -64,7 +64,8 @@ int gp_mag_det_keys(int device, int64_t n_vocab, const int64_t* d_attr_indptr, c
  * inv, then the gather.  The gather finds every entry again from d_slot_base and the call's operands, as the forward found
  * it; a sorted position whose entry does not exist, lies at or past min(total, max_entries), or whose id is not its key
  * adds nothing.
- * Input dropout is not supported: training with input_droprate > 0 is GP_ERR_INVALID_ARG.  Otherwise the
+ * Input dropout is not supported here: training with input_droprate > 0 is GP_ERR_INVALID_ARG.  The entry point that takes it
+ * is gp_mag_prop_rows_backward_det_drop (mag_drop_abi.hpp), which keeps U per sample.  Otherwise the
  * checks are gp_mag_prop_rows_backward's, plus max_entries < 1 and n_batch * K >= 2^31 (GP_ERR_INVALID_ARG) and the
  * added pointers (GP_ERR_NULL).  n_batch = 0 is GP_OK with nothing launched.
  * ------------------------------------------------------------------------------------------ */

@@ -20,7 +20,12 @@ struct MagArgs {
     const int* batch_rows; int B; int S; int nsc;
     float p_node, p_in; int training; u64 seed;
     const unsigned char* keep; long long keep_stride;
+    const u64* d_seed;                                   // the seed in device memory; null: `seed` above
 };
+
+// The seed of a call: read once by every kernel, before its row loop; the DropNode hash (stage_row) and the input dropout's
+// slot seeds derive from this value alone.  A captured graph freezes the pointer, not the value behind it.
+__device__ __forceinline__ u64 call_seed(const MagArgs& A) { return A.d_seed ? *A.d_seed : A.seed; }
 
 // what finds a slot's node without the weights: the attribute CSR's row pointers, the resident rows and the batch
 // (mag_det.hip's key kernels and gather, row_mark.hip's mark kernel)
@@ -43,8 +48,8 @@ __device__ __forceinline__ bool slot_node(const SlotArgs& A, long long e, long l
 }
 
 // Stage the row's columns (first chunk) and the weights of samples s0 .. s0 + ns - 1; a column outside [0, N) makes
-// the slot absent (weight 0).  Called by every thread, between two barriers of the caller.
-__device__ __forceinline__ void stage_row(const MagArgs& A, long long row, int n, int s0, int ns, float scale_node,
+// the slot absent (weight 0).  seed: call_seed(A).  Called by every thread, between two barriers of the caller.
+__device__ __forceinline__ void stage_row(const MagArgs& A, u64 seed, long long row, int n, int s0, int ns, float scale_node,
                                           int* s_col, int* s_seen, float* s_w, int* n_bad)
 {
     for (int k = threadIdx.x; k < n; k += blockDim.x) {
@@ -58,7 +63,7 @@ __device__ __forceinline__ void stage_row(const MagArgs& A, long long row, int n
             if (!c_ok && n_bad) atomicAdd(n_bad, 1);
         }
         for (int s = 0; s < ns; ++s)
-            s_w[s * A.K + k] = c_ok ? sample_weight(w, e, s0 + s, A.p_node, scale_node, A.training, A.seed, A.keep, A.keep_stride) : 0.0f;
+            s_w[s * A.K + k] = c_ok ? sample_weight(w, e, s0 + s, A.p_node, scale_node, A.training, seed, A.keep, A.keep_stride) : 0.0f;
     }
 }
 

@@ -19,6 +19,9 @@ same bits run to run.  Without `max_entries` such a call still raises and names 
 the mode resolving to non-deterministic the atomic backward runs and `max_entries` is ignored, so a caller may pass it always
 and let torch's flag decide.  The forward is the same in every mode.  There is no CPU fallback.
 
+With input dropout the deterministic backward is mag_drop.py's (`det_input_dropout=True`), and `seed=` may be
+an int64 [1] device tensor that the kernels read when they run, so that a captured call draws fresh masks at every replay.
+
 Either backward can hand the table's gradient to the optimiser as a row list instead of a dense tensor (`row_grad=`): the
 deterministic one its sorted keys (an `optim_rows.RowGrad`), the atomic one the rows it marked in a bitmap (an
 `optim_rows.BitmapRowGrad`).
@@ -46,20 +49,30 @@ class _Call:
         self.tensors = tensors             # attr_indptr, attr_indices, attr_data, col, val, filled, batch_rows, keep
         self.scalars = (S_rows, K, B, samples, p_node, p_in, training, seed)
 
+    @property
+    def dseed(self):
+        """Whether the seed stands in device memory (an int64 [1] tensor): the call then goes to the entry
+        points of csrc/mag_drop_abi.hpp, which take its address where the value forms take the value."""
+        return isinstance(self.scalars[7], torch.Tensor)
+
+    def entry(self, name):
+        """The entry point `name` of grandplus_mag.h, or its device-seed form."""
+        return getattr(_native.lib(), name + "_dseed" if self.dseed else name)
+
     def args(self):
         attr_indptr, attr_indices, attr_data, col, val, filled, batch_rows, keep = self.tensors
         S_rows, K, B, samples, p_node, p_in, training, seed = self.scalars
         return (attr_indptr.data_ptr(), attr_indices.data_ptr(), attr_data.data_ptr(), attr_indptr.numel() - 1, col.data_ptr(),
                 val.data_ptr(), _ptr(filled), S_rows, K, _ptr(batch_rows), B, samples, float(p_node), float(p_in),
-                int(bool(training)), ctypes.c_uint64(seed), _ptr(keep), col.numel())
+                int(bool(training)), seed.data_ptr() if self.dseed else ctypes.c_uint64(seed), _ptr(keep), col.numel())
 
 
 def _forward(weight, call, n_bad):
     V, H = weight.shape
     _, _, B, S = call.scalars[:4]
     out = torch.empty((S, B, H), dtype=torch.float32, device=weight.device)
-    rc = _native.lib().gp_mag_prop_rows(_dev_index(weight), weight.data_ptr(), V, H, *call.args(), out.data_ptr(),
-                                        n_bad.data_ptr(), _stream(weight))
+    rc = call.entry("gp_mag_prop_rows")(_dev_index(weight), weight.data_ptr(), V, H, *call.args(), out.data_ptr(), n_bad.data_ptr(),
+                                        _stream(weight))
     _native.raise_for_status(rc)
     return out
 
@@ -68,7 +81,7 @@ def _backward(weight_shape, grad_out, call):
     V, H = weight_shape
     g = grad_out.contiguous()
     dW = torch.zeros((V, H), dtype=torch.float32, device=g.device)
-    rc = _native.lib().gp_mag_prop_rows_backward(_dev_index(g), g.data_ptr(), V, H, *call.args(), dW.data_ptr(), _stream(g))
+    rc = call.entry("gp_mag_prop_rows_backward")(_dev_index(g), g.data_ptr(), V, H, *call.args(), dW.data_ptr(), _stream(g))
     _native.raise_for_status(rc)
     return dW
 
@@ -85,7 +98,7 @@ def _backward_rows(weight_shape, grad_out, call, capacity, overflow, row_grad):
         row_grad.fill(torch.full((1,), V, dtype=torch.int64, device=g.device))   # the sentinel alone: no row is touched
         return None
     keys = mark_and_list(row_grad, call, capacity, overflow)
-    rc = _native.lib().gp_mag_prop_rows_backward(_dev_index(g), g.data_ptr(), V, H, *call.args(), row_grad.values.data_ptr(),
+    rc = call.entry("gp_mag_prop_rows_backward")(_dev_index(g), g.data_ptr(), V, H, *call.args(), row_grad.values.data_ptr(),
                                                  _stream(g))
     _native.raise_for_status(rc)
     row_grad.fill(keys)
@@ -97,8 +110,9 @@ class _MagRowsFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, weight, call, n_bad, det=None):
-        """det: None for the atomic backward, (max_entries, overflow, row_grad, segment_chunk) for the deterministic one
-        (mag_det.backward_det); with a row_grad the weight's gradient is None and dW goes to the RowGrad.
+        """det: None for the atomic backward, (max_entries, overflow, row_grad, segment_chunk, per_sample) for the
+        deterministic one (mag_det.backward_det, or with per_sample mag_drop.backward_det_drop: input dropout or a device
+        seed); with a row_grad the weight's gradient is None and dW goes to the RowGrad.
         (capacity, overflow, a BitmapRowGrad): the atomic backward into that row gradient (`_backward_rows`)."""
         ctx.save_for_backward(*call.tensors)
         ctx.args = (weight.shape, call.scalars, det)
@@ -114,13 +128,16 @@ class _MagRowsFn(torch.autograd.Function):
         from .optim_rows import BitmapRowGrad
         if isinstance(det[2], BitmapRowGrad):
             return _backward_rows(shape, grad_out, call, *det), None, None, None
+        if det[4]:
+            from .mag_drop import backward_det_drop
+            return backward_det_drop(shape, grad_out, call, *det[:4]), None, None, None
         from .mag_det import backward_det
-        return backward_det(shape, grad_out, call, *det), None, None, None
+        return backward_det(shape, grad_out, call, *det[:4]), None, None, None
 
 
 def mag_prop_rows(weight, attr_indptr, attr_indices, attr_data, col, val, filled, K, batch_rows=None, *, samples=1,
                   dropnode_rate=0.5, input_droprate=0.0, training=True, seed=None, keep=None, validate=False, deterministic=None,
-                  max_entries=None, overflow=None, row_grad=None, segment_chunk=None):
+                  max_entries=None, overflow=None, row_grad=None, segment_chunk=None, det_input_dropout=False):
     """The S augmented embeddings of a batch of resident rows, in one launch.
 
     weight [V, H] float32 (the `nn.Embedding` table); attr_indptr [N + 1] int64, attr_indices [nnz] int32, attr_data [nnz]
@@ -137,7 +154,14 @@ def mag_prop_rows(weight, attr_indptr, attr_indices, attr_data, col, val, filled
     raises RuntimeError.  It never reads the host: `overflow` (an int32 [1] tensor on weight's device; a private one
     that nobody reads when omitted) gets bit 0 set by the backward if the batch had more entries than `max_entries`, and
     the gradient then lacks the entries past it.  Input dropout (input_droprate > 0 while training) is not supported by that
-    backward: ValueError.  When the mode resolves to False `max_entries` is ignored.
+    backward: ValueError, unless `det_input_dropout=True` (below).  When the mode resolves to False `max_entries` is ignored.
+    `seed`: an int, or a contiguous int64 tensor of one element on weight's device: the kernels then read the
+    seed, as a uint64, from that address when they run, so a captured call draws the masks of the value that stands there at
+    each replay.  With the value v there the forward is bit for bit the call with seed=v.  Any other tensor: TypeError.
+    `det_input_dropout=True` lets the deterministic backward run with input dropout: it keeps the slot
+    gradient per sample (S times the scratch) and applies every sample's own mask in the gather (mag_drop.py).  It needs
+    the mode to resolve to deterministic and `max_entries` (ValueError otherwise), goes with `row_grad` and
+    `segment_chunk`, and changes nothing where no mask is drawn (input_droprate = 0, or eval mode).
     `row_grad`: an `optim_rows.RowGrad(weight)`.  The deterministic backward then writes dW into its persistent
     buffer instead of a fresh `torch.zeros`, hands it the sorted key list and returns no gradient for `weight`
     (`weight.grad` stays None): the table is stepped by `ClipAdam.set_row_grad`.  It needs the deterministic mode and
@@ -159,6 +183,11 @@ def mag_prop_rows(weight, attr_indptr, attr_indices, attr_data, col, val, filled
     if max_entries is not None:
         from .mag_det import check_max_entries
         check_max_entries(max_entries)
+    if not isinstance(det_input_dropout, bool):
+        raise TypeError(f"det_input_dropout must be True or False, got {det_input_dropout!r}")
+    if det_input_dropout and (not deterministic or max_entries is None):
+        raise ValueError("det_input_dropout=True is the deterministic backward's: it needs deterministic=True (or torch's "
+                         "deterministic mode) and max_entries= (DESIGN §7y)")
     if not isinstance(samples, int) or not 1 <= samples <= _native.GP_MAX_SAMPLES:
         raise ValueError(f"samples must be an int in [1, {_native.GP_MAX_SAMPLES}], got {samples!r}")
     _check(weight, torch.float32, "weight")
@@ -209,19 +238,27 @@ def mag_prop_rows(weight, attr_indptr, attr_indices, attr_data, col, val, filled
                     ("filled", filled), ("batch_rows", batch_rows), ("keep", keep)):
         if t is not None and t.device != weight.device:
             raise TypeError(f"{name} must be on {weight.device}, got {t.device} (no CPU fallback)")
+    device_seed = isinstance(seed, torch.Tensor)
+    if device_seed and (seed.dtype != torch.int64 or seed.numel() != 1 or not seed.is_contiguous() or seed.device != weight.device):
+        raise TypeError(f"seed must be an int, or a contiguous int64 tensor of one element on {weight.device} (DESIGN §7y)")
+    masked = bool(training) and float(input_droprate) > 0.0
+    if device_seed and not masked and (keep is not None or not training):
+        seed = 0                                                       # no mask is hashed: nothing reads the seed
+        device_seed = False
     wants_grad = torch.is_grad_enabled() and weight.requires_grad
     det = None
     if deterministic and wants_grad and max_entries is not None:
         from .mag_det import check_overflow
-        if training and float(input_droprate) > 0.0:
+        if masked and not det_input_dropout:
             raise ValueError("the deterministic backward of mag_prop_rows does not support input dropout (DESIGN §9): "
                              "input_droprate must be 0 in training")
         if B * K >= 2 ** 31:
             raise ValueError(f"the deterministic backward of mag_prop_rows takes fewer than 2**31 slots, got {B} x {K}")
         if overflow is not None:
             check_overflow(overflow, weight.device)
+        # the per-sample backward: a mask per sample, or a seed that only the entry points of mag_drop_abi.hpp read
         det = (max_entries, overflow if overflow is not None else torch.zeros(1, dtype=torch.int32, device=weight.device), row_grad,
-               segment_chunk)
+               segment_chunk, masked or device_seed)
     elif deterministic and wants_grad:
         raise RuntimeError("mag_prop_rows has no deterministic backward (fp32 atomics into dW); for a reproducible gradient use the "
                            "composed path with deterministic=True: flatten_rows -> embedding_bag_csr(nodes=..., deterministic=True) "

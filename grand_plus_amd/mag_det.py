@@ -14,7 +14,8 @@ so `_native.PRIVATE_ABI` binds them, not `_native.ABI`.
 
 `segment_chunk=C` sums a hub attribute's segment in chunks of C entries (gather_chunk.py).
 
-Left out: input dropout (the keyed mask would need S values of U per slot).
+Input dropout is not this backward's: its keyed mask needs S values of U per slot, which mag_drop.py keeps
+(`mag_prop_rows(..., det_input_dropout=True)`); `backward_det` and its two entry points refuse it.
 """
 from __future__ import annotations
 

@@ -21,17 +21,24 @@ untouched row still moves while its moments decay.
 `valid_mag_pass` over the step's attribute CSR and rows.  `dirty_rows=True` (with `table_step="lazy"`) has every backward mark
 the rows it hands over in a bitmap, from which the loop's BestTracker copies only the rows that changed since its last snapshot.
 
-Left out: input dropout (`model.input_droprate` must be 0), several steps in one graph, the validation pass
-as a captured graph.
+`input_dropout=True` takes a model with `input_droprate > 0`: the front end reads the step state's seed from
+device memory, so every replay draws a fresh input-dropout mask, and the deterministic table gradient keeps the samples apart
+(mag_drop.py).
+
+Left out: an explicit input-dropout mask, several steps in one graph, the validation pass as a captured graph.
 """
 from __future__ import annotations
 
 import torch
 
+from . import _native
 from ._common import _deterministic
 from .step import TrainStep, trained_parameters
 
 __all__ = ["MagTrainStep", "mag_trained_parameters"]
+
+
+_SEED_WORD = _native.GpStepState.seed.offset // 8      # gp_step_state.seed, as an index into StepState.buf (int64 words)
 
 
 def mag_trained_parameters(model):
@@ -48,8 +55,8 @@ def _csr(t, dtype, name):
 class MagTrainStep(TrainStep):
     """One MAG training step (model_mag.py's loop body) as one replayable object.
 
-    model: a MagMLP in train mode with input_droprate = 0; optimizer: a ClipAdam(capturable=True, state=StepState(device))
-    over `mag_trained_parameters(model)`; rows: the RowMatrix; attr_indptr int64 [N + 1], attr_indices int32 [nnz],
+    model: a MagMLP in train mode, with input_droprate = 0 unless input_dropout=True; optimizer: a
+    ClipAdam(capturable=True, state=StepState(device)) over `mag_trained_parameters(model)`; rows: the RowMatrix; attr_indptr int64 [N + 1], attr_indices int32 [nnz],
     attr_data float32 [nnz]: the node-attribute CSR on the GPU; labels, idx_train, idx_unlabel and the keywords up to
     `capture` as for TrainStep.  nlayers = 1 (no `fcs`: the embedding is the logits) is accepted.
 
@@ -79,18 +86,27 @@ class MagTrainStep(TrainStep):
     attribute's segment in chunks of C entries, so that an attribute that sits in many bags of a batch is no longer one
     serial chain.  It needs the deterministic mode (ValueError otherwise) and goes with every table_step, dirty_rows and fit.
 
+    input_dropout: True accepts a model with input_droprate > 0, in every mode above.  The front end is handed the
+    address of the step state's seed, which `gp_step_advance` rewrites at every step: the input-dropout mask of step t is
+    `mag_prop_rows`' for seed = step_seed(base, t), eager or replayed.  The deterministic table gradient then runs
+    `gp_mag_prop_rows_backward_det_drop`, whose scratch is S times as large and, like every buffer of the step, sized from the
+    batch shape before the capture.  With a model at input_droprate = 0 the step is bit for bit the step without the keyword.
+
     With capture=True and the deterministic mode the capture includes `torch.sort`; should a torch build refuse to capture it,
     the capture fails as every broken capture does here: a RuntimeError naming the call (backward), no retry, no fallback."""
 
     def __init__(self, model, optimizer, rows, attr_indptr, attr_indices, attr_data, labels, idx_train, idx_unlabel, *, samples,
                  dropnode_rate, lam, warmup, tem, conf=None, kind="l2", seed, capture=True, deterministic=None, max_entries=None, table_step=None,
-                 row_list=None, dirty_rows=False, segment_chunk=None):
+                 row_list=None, dirty_rows=False, segment_chunk=None, input_dropout=False):
         from .mlp import MagMLP
         if not isinstance(model, MagMLP):
             raise ValueError("MagTrainStep takes a MagMLP (a GrandPlusMLP goes to step.TrainStep)")
-        if float(model.input_droprate) != 0.0:
-            raise ValueError("MagTrainStep needs model.input_droprate = 0: input dropout in the step is left out (DESIGN §9), got "
-                             f"{model.input_droprate}")
+        if not isinstance(input_dropout, bool):
+            raise TypeError(f"input_dropout must be True or False, got {input_dropout!r}")
+        if float(model.input_droprate) != 0.0 and not input_dropout:
+            raise ValueError("MagTrainStep needs model.input_droprate = 0: input dropout in the step is left out (DESIGN §9) unless "
+                             f"input_dropout=True is passed (DESIGN §7y), got {model.input_droprate}")
+        self.input_dropout = input_dropout and float(model.input_droprate) > 0.0
         self._check_optimizer_and_rows(optimizer, rows)
         _csr(attr_indptr, torch.int64, "attr_indptr")
         _csr(attr_indices, torch.int32, "attr_indices")
@@ -157,10 +173,13 @@ class MagTrainStep(TrainStep):
     def _front(self, batch_rows):
         self._where = "mag_prop_rows"
         S = self.samples
-        X = self.model.emb_rows(*self.attr, self.rows, batch_rows=batch_rows, samples=S, dropnode_rate=self.dropnode_rate, seed=0,
+        # with input dropout the kernels read the state's seed where it stands: the step's, at every replay
+        seed = self.state.buf[_SEED_WORD:_SEED_WORD + 1] if self.input_dropout else 0
+        X = self.model.emb_rows(*self.attr, self.rows, batch_rows=batch_rows, samples=S, dropnode_rate=self.dropnode_rate, seed=seed,
                                 keep=self._node_keep, deterministic=self.deterministic,
                                 max_entries=self._max_entries(batch_rows.numel()), overflow=self._entries_flag,
-                                row_grad=self.row_grad, segment_chunk=self.segment_chunk)
+                                row_grad=self.row_grad, segment_chunk=self.segment_chunk,
+                                det_input_dropout=self.input_dropout and self.deterministic)
         return X[None] if S == 1 else X
 
     # ---- what the fit loop validates with

@@ -429,12 +429,14 @@ class MagMLP(_MLPBase, nn.Module):
                                  self.training, seed, keep, deterministic=deterministic, segment_chunk=segment_chunk)
 
     def emb_rows(self, attr_indptr, attr_indices, attr_data, rows, batch_rows=None, samples=1, dropnode_rate=0.5, seed=None,
-                 keep=None, deterministic=None, max_entries=None, overflow=None, row_grad=None, segment_chunk=None):
+                 keep=None, deterministic=None, max_entries=None, overflow=None, row_grad=None, segment_chunk=None,
+                 det_input_dropout=False):
         """MLP.emb of every neighbour of a batch of `rows` (a RowMatrix) and random_prop over them as one op
         (mag.mag_prop_rows): [B, H], or [S, B, H] for samples = S > 1, ready for `forward`.  `deterministic`,
         `max_entries` and `overflow` are passed through (the deterministic table gradient), and so is
         `row_grad` (an optim_rows.RowGrad of `embeds.weight`: the table's gradient as a row list) and
-        `segment_chunk` (the deterministic gradient's hub segments in chunks)."""
+        `segment_chunk` (the deterministic gradient's hub segments in chunks).  `seed` may be an int64 [1] device
+        tensor and `det_input_dropout=True` lets the deterministic gradient run with `input_droprate > 0`."""
         from .mag import mag_prop_rows
         from .rows import RowMatrix
         if not isinstance(rows, RowMatrix):
@@ -442,7 +444,7 @@ class MagMLP(_MLPBase, nn.Module):
         return mag_prop_rows(self.embeds.weight, attr_indptr, attr_indices, attr_data, rows.col, rows.val, rows.filled, rows.K,
                              batch_rows, samples=samples, dropnode_rate=dropnode_rate, input_droprate=self.input_droprate,
                              training=self.training, seed=seed, keep=keep, deterministic=deterministic, max_entries=max_entries,
-                             overflow=overflow, row_grad=row_grad, segment_chunk=segment_chunk)
+                             overflow=overflow, row_grad=row_grad, segment_chunk=segment_chunk, det_input_dropout=det_input_dropout)
 
     def _layers(self):
         return [(fc, bn if self.use_bn else None, True, bool(self.node_norm), False, self.hidden_droprate)
