@@ -5,8 +5,8 @@ include/grandplus.h), the ctypes binding (`_native`), the host-side mirror of th
 reference's `propagation.Graph` (`api.Graph`), the caller-side recipe helpers (`recipes`),
 the multi-GPU seed-sharding driver (`sharded`), the tie-aware parity comparator (`parity`)
 and the synthetic workload generator (`synth`).  The training-step pieces (`augment`, `mlp`, `objective`, `optim`) need
-torch and are imported on demand; `ClipAdam` and `clip_grad_norm` of `optim` and `valid`, `predict`, `local_logits`, `eval_head` and
-`eval_reduce` of `evaluate`, `mag_prop_rows`, `valid_mag`, `valid_mag_plan`, `valid_mag_pass` and `predict_mag` of `mag`, `StepState` and `TrainStep` of `step`, `MagTrainStep` and `mag_trained_parameters` of `mag_step`, `RowGrad` and `BitmapRowGrad` of `optim_rows` and `fit`, `Sampler` and `BestTracker` of `fit` are reachable from here by name, and stay out of `__all__` so that `from grand_plus_amd import *` loads neither torch nor the native library.
+torch and are imported on demand; `ClipAdam` and `clip_grad_norm` of `optim` and `valid`, `predict`, `local_logits`, `eval_head`,
+`eval_reduce`, `eval_tail` and `ValidGraph` of `evaluate`, `mag_prop_rows`, `valid_mag`, `valid_mag_plan`, `valid_mag_pass` and `predict_mag` of `mag`, `StepState` and `TrainStep` of `step`, `MagTrainStep` and `mag_trained_parameters` of `mag_step`, `RowGrad` and `BitmapRowGrad` of `optim_rows` and `fit`, `Sampler` and `BestTracker` of `fit` are reachable from here by name, and stay out of `__all__` so that `from grand_plus_amd import *` loads neither torch nor the native library.
 """
 from .api import Graph, algorithmic_bytes          # noqa: F401
 from .recipes import RECIPES, Recipe, make_coef    # noqa: F401
@@ -18,7 +18,7 @@ def __getattr__(name):                              # these need torch: loaded w
     if name in ("ClipAdam", "clip_grad_norm"):
         from . import optim
         return getattr(optim, name)
-    if name in ("valid", "predict", "local_logits", "eval_head", "eval_reduce"):
+    if name in ("valid", "predict", "local_logits", "eval_head", "eval_reduce", "eval_tail", "ValidGraph"):
         from . import evaluate
         return getattr(evaluate, name)
     if name in ("mag_prop_rows", "valid_mag", "valid_mag_plan", "valid_mag_pass", "predict_mag"):

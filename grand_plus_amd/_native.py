@@ -45,6 +45,12 @@ def eval_workspace_bytes() -> int:
     return 1024 * 40
 
 
+# GP_EVAL_TAIL_MAX_ROWS and GP_EVAL_TAIL_WORKSPACE_BYTES of csrc/eval_tail_abi.hpp, a private header: the names with a GP_ prefix
+# and the *_bytes functions of this module are the public headers' (the workspace is the ticket counter, padded)
+EVAL_TAIL_MAX_ROWS = 65536
+EVAL_TAIL_WORKSPACE_BYTES = 64
+
+
 def scatter_rows_workspace_bytes(n_samples: int, n_batch: int) -> int:
     """GP_SCATTER_ROWS_WORKSPACE_BYTES of grandplus_scatter.h."""
     return 4 * n_samples * n_batch
@@ -308,6 +314,10 @@ PRIVATE_ABI = {
         "gp_mag_prop_rows_backward_dseed": (_int, [_int, _vp] + _mag_dseed + [_vp, _vp], False),
         "gp_mag_prop_rows_backward_det_drop": (_int, [_int, _vp] + _mag[:-2] + [_vp] + _mag[-2:] + [_vp, _vp, _vp, _i64, _vp, _vp, _vp] + _chunk,
                                                False),
+    },
+    # gp_eval_head's arguments without the offset and the capacity, then gp_eval_reduce's from the workspace on
+    "eval_tail_abi.hpp": {
+        "gp_eval_tail": (_int, [_int, _vp, _i64, _i32, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp], False),
     },
 }
 

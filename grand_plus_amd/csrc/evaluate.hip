@@ -13,75 +13,20 @@
 //                       workgroup sums the slots in index order with one fixed tree and writes loss, acc and the counts.
 // The slices depend on the number of rows only, so the result is bitwise the same run to run and however the rows were
 // split into head calls.
-#include "gp_common.hpp"
+#include "eval_head.hpp"                                     // the row arithmetic, shared with eval_tail.hip
+#include "eval_plan.hpp"                                     // the slices of the reduction, shared with it too
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kWaves = kBlock / 64;
-constexpr int kMaxC = 4096;
 constexpr int kSlots = GP_EVAL_WORKSPACE_BYTES / 40;         // per slot: the f64 sum of nll and four int64 counts
-constexpr int kMinSlice = 1024;                              // rows of a stage-1 workgroup, at least
 
 static_assert(kSlots == kBlock * 4, "stage 2 reads four slots per thread");
-
-enum { kWrong = GP_EVAL_WRONG, kCorrect = GP_EVAL_CORRECT, kIgnored = GP_EVAL_IGNORED, kBad = GP_EVAL_BAD };   // a row's flag
-
-struct HeadArgs {
-    const float* z;                 // [n_z x C]
-    long long n_z; int C;
-    const long long* row_idx;       // [n] or NULL
-    const long long* labels;        // [n_labels]
-    long long n_labels;
-    const long long* label_idx;     // [n] or NULL
-    long long n, ignore, offset;
-};
-
-// torch.argmax / numpy.argmax: the first index of the largest value, where a NaN is larger than every number
-__device__ __forceinline__ bool better(float a, int ia, float b, int ib)
-{
-    if (a != a) return b != b ? ia < ib : true;
-    if (b != b) return false;
-    return a > b || (a == b && ia < ib);
-}
+static_assert(kSlots == gp_eval::kSlots, "eval_plan.hpp cuts the rows for this many slots");
 
 __global__ void __launch_bounds__(kBlock)
 eval_head_kernel(HeadArgs a, float* __restrict__ nll, int* __restrict__ pred, unsigned char* __restrict__ flag)
 {
-    const int lane = threadIdx.x & 63;
-    const long long n_waves = (long long)gridDim.x * kWaves;
-    for (long long i = (long long)blockIdx.x * kWaves + (threadIdx.x >> 6); i < a.n; i += n_waves) {   // wave-uniform
-        const long long r = a.row_idx ? a.row_idx[i] : i;
-        const long long l = a.label_idx ? a.label_idx[i] : i;
-        float loss = 0.0f; int arg = -1; int fl = kBad;
-        if (r >= 0 && r < a.n_z) {                            // an index outside its array is never used as an address
-            const float* __restrict__ zr = a.z + (size_t)r * a.C;
-            // the first 64 classes stay in a register: one read of the row for C <= 64
-            const float z0 = lane < a.C ? zr[lane] : -INFINITY;
-            float best = z0; arg = lane < a.C ? lane : 0x7FFFFFFF;
-            for (int c = lane + 64; c < a.C; c += 64) {
-                const float v = zr[c];
-                if (better(v, c, best, arg)) { best = v; arg = c; }
-            }
-            for (int o = 32; o > 0; o >>= 1) {
-                const float ob = __shfl_xor(best, o); const int oa = __shfl_xor(arg, o);
-                if (better(ob, oa, best, arg)) { best = ob; arg = oa; }
-            }
-            if (l >= 0 && l < a.n_labels) {
-                const long long y = a.labels[l];
-                if (y == a.ignore) fl = kIgnored;
-                else if (y >= 0 && y < a.C) {
-                    // (z - max) - log sum exp(z - max), the objective's order; a NaN in the row is the max: NaN, as torch
-                    float e = lane < a.C ? expf(z0 - best) : 0.0f;
-                    for (int c = lane + 64; c < a.C; c += 64) e += expf(zr[c] - best);
-                    const float ls = logf(wave_sum(e));
-                    loss = -((zr[y] - best) - ls);
-                    fl = arg == y ? kCorrect : kWrong;
-                }
-            }
-        }
-        if (lane == 0) { nll[a.offset + i] = loss; pred[a.offset + i] = arg; flag[a.offset + i] = (unsigned char)fl; }
-    }
+    GP_EVAL_HEAD_ROWS(a, nll, pred, flag)
 }
 
 // Workspace: sums[kSlots] (f64), then counts[4][kSlots] (int64) = valid, correct, ignored, bad.
@@ -168,10 +113,8 @@ int gp_eval_reduce(int device, const float* d_nll, const uint8_t* d_flag, int64_
     hipStream_t s = (hipStream_t)stream;
     double* sums = static_cast<double*>(d_workspace);
     long long* counts = reinterpret_cast<long long*>(sums + kSlots);
-    // the slices follow from n_rows alone: at least kMinSlice rows each, at most kSlots of them
-    long long grid = (n_rows + kMinSlice - 1) / kMinSlice;
-    grid = grid < 1 ? 1 : grid > kSlots ? kSlots : grid;
-    const long long slice = (n_rows + grid - 1) / grid;
+    const gp_eval::ReducePlan plan = gp_eval::reduce_plan(n_rows);          // the slices follow from n_rows alone
+    const long long grid = plan.grid, slice = plan.slice;
     hipLaunchKernelGGL(eval_reduce_kernel, dim3((int)grid), dim3(kBlock), 0, s, 1, d_nll, (const unsigned char*)d_flag,
                        (long long)n_rows, slice, sums, counts, (float*)nullptr, (long long*)nullptr);
     if (const int rc = launch_status("eval_reduce_kernel (stage 1)")) return rc;

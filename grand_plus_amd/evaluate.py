@@ -18,6 +18,10 @@ Labels equal to `ignore_index` are left out of the loss as in `F.nll_loss`; othe
 outside their array are never used as an address: they are flagged, left out and counted.  The accuracy divides by the
 number of rows, ignored ones included, as the reference's `accuracy` divides by `len(labels)`
 (utils/data_loader.py:165).  There is no CPU fallback.
+
+Opt-in: `eval_tail` is `eval_head` + `eval_reduce` as one launch with the same bits; `valid_plan(one_pass=True)`
+validates in one gather, one `model.infer` and one tail; `ValidGraph` replays a pass and the tracker's update from one
+captured graph.
 """
 from __future__ import annotations
 
@@ -131,6 +135,80 @@ def eval_reduce(buffers):
     return out[0], out[1], counts
 
 
+def eval_tail_workspace(device):
+    """The workspace of `eval_tail` on `device`: the ticket counter, zeroed here once; every call leaves it zero."""
+    return torch.zeros(_native.EVAL_TAIL_WORKSPACE_BYTES, dtype=torch.uint8, device=device)
+
+
+def eval_tail(logits, labels, *, rows=None, label_rows=None, ignore_index=-100, out=None, workspace=None, result=None):
+    """`eval_head` over all n rows at offset 0 and `eval_reduce` over them as ONE launch (gp_eval_tail): returns
+    (loss, acc, counts, EvalBuffers), every one bit for bit what the two calls give.
+
+    The arguments and host checks are `eval_head`'s (no offset: the buffers are filled from 0, `out` may be longer than n
+    and only its first n rows are written and reduced).  workspace: the uint8 tensor of `eval_tail_workspace(device)`, kept
+    by the caller between calls on one stream; None allocates and zeroes one.  result: None, or (out2, counts) -- a float32
+    [2] and an int64 [4] tensor on the device that the call writes (a plan's static tensors); loss and acc are views of
+    out2.  Above _native.EVAL_TAIL_MAX_ROWS rows the two calls run instead (three launches, the same bits).  No host
+    synchronisation."""
+    if not isinstance(logits, torch.Tensor) or logits.dtype != torch.float32 or logits.dim() != 2:
+        raise TypeError("logits must be a float32 [R, C] CUDA tensor")
+    R, C = logits.shape
+    if not 1 <= C <= _native.GP_MAX_CLASSES:
+        raise ValueError(f"the number of classes must be in [1, {_native.GP_MAX_CLASSES}], got {C}")
+    labels = _index(labels, "labels")
+    if labels is None:
+        raise TypeError("labels must be an int64 CUDA tensor")
+    rows = _index(rows, "rows")
+    label_rows = _index(label_rows, "label_rows")
+    if rows is not None and label_rows is not None and rows.numel() != label_rows.numel():
+        raise ValueError(f"rows has {rows.numel()} entries, label_rows {label_rows.numel()}")
+    n = rows.numel() if rows is not None else label_rows.numel() if label_rows is not None else R
+    if rows is None and n > R:
+        raise ValueError(f"label_rows has {n} entries, logits {R} rows (pass rows to pick them)")
+    if label_rows is None and n > labels.numel():
+        raise ValueError(f"labels has {labels.numel()} entries for {n} rows (pass label_rows to pick them)")
+    if workspace is not None and (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or
+                                  not workspace.is_contiguous() or workspace.numel() < _native.EVAL_TAIL_WORKSPACE_BYTES):
+        raise TypeError(f"workspace must be a contiguous uint8 tensor of at least {_native.EVAL_TAIL_WORKSPACE_BYTES} bytes "
+                        "(eval_tail_workspace)")
+    if result is not None:
+        if not isinstance(result, tuple) or len(result) != 2:
+            raise TypeError("result must be (out2, counts): a float32 [2] and an int64 [4] tensor")
+        for t, dtype, k, name in zip(result, (torch.float32, torch.int64), (2, 4), ("out2", "counts")):
+            if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.shape != (k,) or not t.is_contiguous():
+                raise TypeError(f"result.{name} must be a contiguous {dtype} tensor of {k} elements")
+    extra = dict(workspace=workspace, out2=result[0] if result else None, counts=result[1] if result else None)
+    if out is not None:
+        cap = _check_buffers(out)
+        if n > cap:
+            raise ValueError(f"n = {n} rows do not fit the out buffers of {cap}")
+        _on_gpu("eval_tail", logits, labels=labels, rows=rows, label_rows=label_rows, nll=out[0], pred=out[1], flag=out[2], **extra)
+    else:
+        _on_gpu("eval_tail", logits, labels=labels, rows=rows, label_rows=label_rows, **extra)
+        out = eval_buffers(n, logits.device)
+    out = EvalBuffers(*out)
+    if n > _native.EVAL_TAIL_MAX_ROWS:                    # one workgroup would walk too many slices: the unfused pair
+        eval_head(logits, labels, rows=rows, label_rows=label_rows, ignore_index=ignore_index, out=out)
+        used = out if out[0].numel() == n else EvalBuffers(out[0][:n], out[1][:n], out[2][:n])
+        loss, acc, counts = eval_reduce(used)
+        if result is not None:
+            result[0][0].copy_(loss)
+            result[0][1].copy_(acc)
+            result[1].copy_(counts)
+            loss, acc, counts = result[0][0], result[0][1], result[1]
+        return loss, acc, counts, out
+    if workspace is None:
+        workspace = eval_tail_workspace(logits.device)
+    out2, counts = result if result is not None else (torch.empty(2, dtype=torch.float32, device=logits.device),
+                                                      torch.empty(4, dtype=torch.int64, device=logits.device))
+    z = logits.contiguous()
+    rc = _native.lib().gp_eval_tail(z.device.index, z.data_ptr(), R, C, _ptr(rows), labels.data_ptr(), labels.numel(), _ptr(label_rows),
+                                    n, int(ignore_index), out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(),
+                                    workspace.data_ptr(), out2.data_ptr(), counts.data_ptr(), _stream(z))
+    _native.raise_for_status(rc)
+    return out2[0], out2[1], counts, out
+
+
 def _node_ids(idx, name, device):
     """A list of node ids (tensor or anything numpy converts) as an int64 tensor on `device`."""
     if isinstance(idx, torch.Tensor):
@@ -176,7 +254,8 @@ class _NoSync:
         return False
 
 
-def valid(model, rows, features, idx_val, labels, batch_size=10000, dropnode_rate=0.5, return_counts=False):
+def valid(model, rows, features, idx_val, labels, batch_size=10000, dropnode_rate=0.5, return_counts=False, one_pass=False,
+          fused=False):
     """The reference's `valid` (model.py:143-166) on the GPU: (loss, acc) as 0-dim float32 device tensors.
 
     rows: the RowMatrix that holds `topk_adj`; features float32 CUDA [N, F]; idx_val: the validation node ids (every one
@@ -186,14 +265,28 @@ def valid(model, rows, features, idx_val, labels, batch_size=10000, dropnode_rat
     n_ignored, n_bad (labels outside [0, C) are counted there, not raised).
 
     model: a GrandPlusMLP, or a MagMLP with `features` = the [N, H] embedding the caller computed in eval mode
-    (`model.emb_csr(...)` over all nodes): the MLP is then applied to the propagated embedding, as model_mag.py does."""
-    loss, acc, counts = valid_pass(valid_plan(model, rows, features, idx_val, labels, batch_size), dropnode_rate)
+    (`model.emb_csr(...)` over all nodes): the MLP is then applied to the propagated embedding, as model_mag.py does.
+
+    one_pass=True: one gather over the whole set, `model.infer` (fused= is its) and one `eval_tail`, see
+    `valid_plan`."""
+    loss, acc, counts = valid_pass(valid_plan(model, rows, features, idx_val, labels, batch_size, one_pass=one_pass, fused=fused),
+                                   dropnode_rate)
     return (loss, acc, counts) if return_counts else (loss, acc)
+
+
+class OnePass(NamedTuple):
+    """What a one-pass plan owns beside the evaluation buffers, allocated once."""
+    logits: torch.Tensor       # float32 [n, C]: `infer` writes its chunks into row slices of it
+    out2: torch.Tensor         # float32 [2]: loss, acc
+    counts: torch.Tensor       # int64 [4]
+    workspace: torch.Tensor    # eval_tail's ticket counter
+    fused: bool                # `infer`'s fused=
 
 
 class ValidPlan(NamedTuple):
     """What `valid` prepares once for a validation set: its arguments as checked, the node ids on the device, their
-    positions in `rows` and the evaluation buffers.  `valid_pass` runs over it any number of times (the fit loop)."""
+    positions in `rows` and the evaluation buffers.  `valid_pass` runs over it any number of times (the fit loop).
+    `one` is None, or the OnePass of a plan made with one_pass=True (an attribute, not a field: the tuple stays what it was)."""
     model: torch.nn.Module
     rows: object
     features: torch.Tensor
@@ -202,10 +295,53 @@ class ValidPlan(NamedTuple):
     pos: torch.Tensor
     buf: EvalBuffers
     batch_size: int
+    one = None
 
 
-def valid_plan(model, rows, features, idx_val, labels, batch_size=10000):
-    """The checks, the one position lookup (KeyError for a node that is no seed) and the buffers of `valid`."""
+class _OnePassValidPlan(ValidPlan):
+    """A ValidPlan whose instances carry `one` (a subclass of a NamedTuple has a __dict__)."""
+
+
+def n_classes_of(model):
+    """The width of the model's logits: the last layer's, or the embedding's for a MagMLP that is its embedding alone."""
+    layers = model._layers()
+    return int(layers[-1][0].weight.shape[0] if layers else model.embeds.weight.shape[1])
+
+
+def check_one_pass(model, one_pass, fused, what):
+    """The refusals of one_pass= / fused=, before any device call: the number of classes of a one-pass plan, else None."""
+    if not isinstance(one_pass, bool) or not isinstance(fused, bool):
+        raise TypeError(f"{what}: one_pass and fused must be bools")
+    if not one_pass:
+        if fused:
+            raise ValueError(f"{what}: fused=True needs one_pass=True (the fused kernel is an inference path)")
+        return None
+    if not hasattr(model, "infer") or not hasattr(model, "_layers"):
+        raise TypeError(f"{what}: one_pass=True needs a GrandPlusMLP or MagMLP (it runs model.infer)")
+    C = n_classes_of(model)
+    if not 1 <= C <= _native.GP_MAX_CLASSES:
+        raise ValueError(f"the number of classes must be in [1, {_native.GP_MAX_CLASSES}], got {C}")
+    return C
+
+
+def one_pass_buffers(n, C, device, fused):
+    """The OnePass of n rows of C classes, or None for C None."""
+    if C is None:
+        return None
+    return OnePass(torch.empty((n, C), dtype=torch.float32, device=device), torch.empty(2, dtype=torch.float32, device=device),
+                   torch.empty(4, dtype=torch.int64, device=device), eval_tail_workspace(device), fused)
+
+
+def valid_plan(model, rows, features, idx_val, labels, batch_size=10000, *, one_pass=False, fused=False):
+    """The checks, the one position lookup (KeyError for a node that is no seed) and the buffers of `valid`.
+
+    one_pass=True: `valid_pass` then runs one `random_prop_rows(training=False)` over all positions, one
+    `model.infer` into the plan's [n, C] logits and one `eval_tail`; batch_size is a memory bound only -- for n above it the
+    gather and `infer` go chunk by chunk into row slices of the one logits buffer, and the tail still runs once (above
+    _native.EVAL_TAIL_MAX_ROWS rows: `eval_head` + `eval_reduce`).  The result is bit for bit the eager composition
+    random_prop_rows -> infer -> eval_head -> eval_reduce and does not depend on batch_size.  The rows get `infer`'s bits,
+    not the block path's (the trade of `predict(..., infer=True)`): it is NOT promised bit-equal to one_pass=False.
+    fused=True is `infer`'s (the same bits) and needs one_pass=True."""
     from .rows import RowMatrix
     if not isinstance(rows, RowMatrix):
         raise TypeError("rows must be a RowMatrix")
@@ -216,23 +352,125 @@ def valid_plan(model, rows, features, idx_val, labels, batch_size=10000):
     if batch_size < 1:
         raise ValueError(f"batch_size must be >= 1, got {batch_size}")
     dev = features.device
+    C = check_one_pass(model, one_pass, fused, "valid")
     idx = _node_ids(idx_val, "idx_val", dev)
     n = idx.numel()
+    one = one_pass_buffers(n, C, dev, fused)
     pos = rows.batch_positions(idx, check=True) if n else None
-    return ValidPlan(model, rows, features, labels, idx, pos, eval_buffers(n, dev), batch_size)
+    fields = (model, rows, features, labels, idx, pos, eval_buffers(n, dev), batch_size)
+    if one is None:
+        return ValidPlan(*fields)
+    plan = _OnePassValidPlan(*fields)
+    plan.one = one
+    return plan
 
 
-def valid_pass(plan, dropnode_rate=0.5):
-    """One validation pass over a ValidPlan: (loss, acc, counts) as device tensors.  Nothing synchronises."""
+def one_pass_body(plan, gather):
+    """The one-pass validation over a plan with `one` set (inside _NoSync): gather(pos) gives the augmented rows of a chunk."""
+    model, labels, idx, pos, buf, batch_size, one = plan.model, plan.labels, plan.idx, plan.pos, plan.buf, plan.batch_size, plan.one
+    n = idx.numel()
+    for start in range(0, n, batch_size):
+        end = min(start + batch_size, n)
+        model.infer(gather(pos if end - start == n else pos[start:end]), out=one.logits[start:end], fused=one.fused)
+    loss, acc, counts, _ = eval_tail(one.logits, labels, label_rows=idx, out=buf, workspace=one.workspace, result=(one.out2, one.counts))
+    return loss, acc, counts
+
+
+def _resolve_one_pass(plan, one_pass):
+    if one_pass is None:
+        return plan.one is not None
+    if not isinstance(one_pass, bool):
+        raise TypeError("one_pass must be None (the plan's) or a bool")
+    if one_pass and plan.one is None:
+        raise ValueError("one_pass=True needs a plan made with one_pass=True (it owns the logits and the tail's workspace)")
+    return one_pass
+
+
+def valid_pass(plan, dropnode_rate=0.5, one_pass=None):
+    """One validation pass over a ValidPlan: (loss, acc, counts) as device tensors.  Nothing synchronises.  one_pass: None
+    reads it from the plan; False runs the batches over a one-pass plan too."""
     from .augment import random_prop_rows
     model, rows, features, labels, idx, pos, buf, batch_size = plan
+    one_pass = _resolve_one_pass(plan, one_pass)
     with _NoSync(model):
+        if one_pass:
+            return one_pass_body(plan, lambda p: random_prop_rows(features, rows.col, rows.val, rows.filled, rows.K, batch_rows=p,
+                                                                  dropnode_rate=dropnode_rate, training=False))
         for start in range(0, idx.numel(), batch_size):
             end = min(start + batch_size, idx.numel())
             aug = random_prop_rows(features, rows.col, rows.val, rows.filled, rows.K, batch_rows=pos[start:end],
                                    dropnode_rate=dropnode_rate, training=False)
             eval_head(model(aug), labels, label_rows=idx[start:end], out=buf, offset=start)
         return eval_reduce(buf)
+
+
+class ValidGraph:
+    """A validation pass and the tracker's update as one replayed graph.
+
+    plan: a ValidPlan or a mag.ValidMagPlan, one_pass or batched; tracker: None, or the fit.BestTracker that takes the
+    pass's loss and accuracy at `state`'s tick (state: the StepState; a tracker without one is a ValueError).  The first
+    `run()` executes the body eagerly (it loads code), the second captures it with torch.cuda.graph, every later one is one
+    replay; each returns (loss, acc, counts), from the capture on the static tensors of the graph.  With a row_grad tracker
+    gp_fit_rows_snapshot is part of the graph.  The body is one stream, a linear chain of launches.
+
+    A replay reads the weights, the BatchNorm running statistics, the step state and the tracker's struct through the
+    pointers of the capture: every tensor of model.state_dict() has to stay where it is, which run() checks (RuntimeError
+    for a tensor that moved).  The model's training flag, the grad mode and the sync-debug mode are as the pass leaves
+    them (_NoSync) on every path.  A capture that raises is re-raised with the name of the call that broke it."""
+
+    def __init__(self, plan, dropnode_rate=0.5, tracker=None, state=None):
+        if not isinstance(plan, tuple) or not hasattr(plan, "one") or not hasattr(plan, "model"):
+            raise TypeError("ValidGraph takes a ValidPlan (valid_plan) or a ValidMagPlan (mag.valid_mag_plan)")
+        if not 0.0 <= float(dropnode_rate) <= 1.0:
+            raise ValueError(f"dropnode_rate must be in [0, 1], got {dropnode_rate}")
+        if tracker is not None:
+            if not hasattr(tracker, "update") or not hasattr(tracker, "buf"):
+                raise TypeError("tracker must be a fit.BestTracker")
+            if state is None or not hasattr(state, "buf"):
+                raise ValueError("a tracker needs the StepState whose tick its update reads: pass state=")
+        self.plan, self.dropnode_rate, self.tracker, self.state = plan, float(dropnode_rate), tracker, state
+        if isinstance(plan, ValidPlan):
+            self._pass = valid_pass
+        else:
+            from .mag import valid_mag_pass
+            self._pass = valid_mag_pass
+        self.runs = 0
+        self._graph = self._result = self._ptrs = self._where = None
+
+    def _body(self):
+        self._where = "valid_pass"
+        result = self._pass(self.plan, self.dropnode_rate)
+        if self.tracker is not None:
+            self._where = "tracker.update"
+            self.tracker.update(result[0], result[1], self.state)
+        self._where = None
+        return result
+
+    def _pointers(self):
+        return [(name, t.data_ptr()) for name, t in self.plan.model.state_dict().items()]
+
+    def run(self):
+        self.runs += 1
+        if self.runs == 1:                                               # a real, eager pass
+            return self._body()
+        if self._graph is None:
+            ptrs = self._pointers()
+            graph = torch.cuda.CUDAGraph()
+            try:
+                with torch.cuda.graph(graph):                            # one side stream; nothing runs until the replay
+                    result = self._body()
+            except Exception as e:
+                where, self._where = self._where, None
+                self.runs -= 1
+                raise RuntimeError(f"capturing the validation pass broke in {where}: {e}") from e
+            self._graph, self._result, self._ptrs = graph, tuple(result), ptrs
+        else:
+            for (name, was), (_name, now) in zip(self._ptrs, self._pointers()):
+                if was != now:
+                    raise RuntimeError(f"{name} moved since the validation pass was captured: the graph reads the model's tensors "
+                                       "through the pointers of the capture (change them in place)")
+        self._graph.replay()
+        return self._result
 
 
 def local_logits(model, attr_mat, batch_size=10000, out=None, fused=False):

@@ -22,7 +22,11 @@ row: `gp_fit_rows_mark` collects the rows every backward hands over in a bitmap,
 rows when the rule takes a new best and clears the bitmap.  Those two are extern "C" symbols of libgrandplus.so declared
 in csrc/fit_rows_abi.hpp, outside C ABI 4; `_native.PRIVATE_ABI` binds them, as it binds optim_rows' own.
 
-Left out: several steps in one graph, the validation pass as a captured graph, numpy's own shuffle stream, a
+`valid_one_pass=True` validates in one gather, one `infer` and one `eval_tail` (`infer`'s bits, not promised equal to
+the batched pass); `valid_capture=True` replays the validation pass and the tracker's update from one captured graph
+(`evaluate.ValidGraph`): the same kernels on the same shapes, bit for bit the uncaptured run.  Both are off by default.
+
+Left out: several steps or several validations in one graph, numpy's own shuffle stream, a
 dirty-row `restore` (it stays a full copy, once per run), Adam's moments in the snapshot (the reference saves the
 state_dict alone), a checkpoint on disk (`tracker.restore()` then `torch.save` is the caller's line).
 """
@@ -262,12 +266,15 @@ class FitLoop:
     synchronisation of the steady state) and raises if a step ran with the wrong batch shape; `finish()` restores the best
     weights and returns the FitResult."""
 
-    def __init__(self, step, sampler, idx_val, *, eval_batch=10, stop_mode="both", patience=100, valid_batch=None):
+    def __init__(self, step, sampler, idx_val, *, eval_batch=10, stop_mode="both", patience=100, valid_batch=None,
+                 valid_one_pass=False, valid_capture=False):
         from .step import TrainStep
         if not isinstance(step, TrainStep) or not isinstance(sampler, Sampler):
             raise TypeError("fit takes a TrainStep and a Sampler")                # a MagTrainStep is one
         if valid_batch is not None:
             valid_batch = _int_in(valid_batch, "valid_batch", 1, _MAX_SIZE, what="None or an int")
+        if not isinstance(valid_one_pass, bool) or not isinstance(valid_capture, bool):
+            raise ValueError("valid_one_pass and valid_capture must be bools")
         step.check_sampler(sampler)
         self.step, self.sampler, self.eval_batch = step, sampler, _int_in(eval_batch, "eval_batch", 1)
         # the reference validates in batches of the training batch size (model.py:337); MAG's in batches of 100
@@ -275,10 +282,14 @@ class FitLoop:
         if valid_batch is None:
             valid_batch = step._valid_batch if step._valid_batch is not None else sampler.batch_size
         self.valid_batch = valid_batch
-        self.plan = step._valid_plan(idx_val, valid_batch)
+        self.plan = step._valid_plan(idx_val, valid_batch, one_pass=True) if valid_one_pass else step._valid_plan(idx_val, valid_batch)
         # a step built with dirty_rows=True: the table's snapshot goes row by row
         self.tracker = BestTracker(step.model, step.device, stop_mode, patience,
                                    row_grad=step.row_grad if getattr(step, "dirty_rows", False) else None)
+        self.valid_graph = None                                          # the pass and the tracker's update as one graph (§7z)
+        if valid_capture:
+            from .evaluate import ValidGraph
+            self.valid_graph = ValidGraph(self.plan, step.dropnode_rate, self.tracker, step.state)
         self.t = step.state.read().tick                                  # the one read of the tick
         self.steps = self.evals = 0
         self.last = None                                                 # the StepResult of the last step
@@ -289,8 +300,11 @@ class FitLoop:
         self.steps += 1
         if (self.t - 1) % self.eval_batch:
             return False
-        loss, acc, _counts = self.step._valid_pass(self.plan)
-        self.tracker.update(loss, acc, self.step.state)
+        if self.valid_graph is not None:
+            self.valid_graph.run()
+        else:
+            loss, acc, _counts = self.step._valid_pass(self.plan)
+            self.tracker.update(loss, acc, self.step.state)
         self.evals += 1
         return True
 
@@ -307,7 +321,7 @@ class FitLoop:
 
 
 def fit(step, sampler, idx_val, *, epochs, eval_batch=10, stop_mode="both", patience=100, poll_every=1, max_steps=None,
-        valid_batch=None):
+        valid_batch=None, valid_one_pass=False, valid_capture=False):
     """The reference's training loop (model.py:302-368) over a TrainStep, or MAG's (model_mag.py) over a MagTrainStep in any
     mode it can be built in: returns FitResult(steps, best_tick, stop_tick, best_loss, best_acc) with the best weights
     restored into the model.
@@ -321,11 +335,15 @@ def fit(step, sampler, idx_val, *, epochs, eval_batch=10, stop_mode="both", pati
     tracker; every poll_every-th validation the host reads the tracker and stops if the rule has.  With poll_every=1
     that is the reference's step; a larger value may run further steps, whose validations the stopped tracker ignores,
     so the restored weights are the same.  Between polls nothing synchronises.  best_tick is None when no validation
-    took a best (the model is then left as trained), stop_tick None when the rule never stopped the run."""
+    took a best (the model is then left as trained), stop_tick None when the rule never stopped the run.
+    valid_one_pass / valid_capture: the validation as one gather, one `infer` and one `eval_tail`; the pass and
+    the tracker's update replayed from one captured graph (the first validation runs eagerly, the second captures).  With
+    valid_capture alone the run is bit for bit the run without it."""
     epochs, poll_every = _int_in(epochs, "epochs", 1), _int_in(poll_every, "poll_every", 1)
     if max_steps is not None:
         _int_in(max_steps, "max_steps", 0, what="None or an int")
-    loop = FitLoop(step, sampler, idx_val, eval_batch=eval_batch, stop_mode=stop_mode, patience=patience, valid_batch=valid_batch)
+    loop = FitLoop(step, sampler, idx_val, eval_batch=eval_batch, stop_mode=stop_mode, patience=patience, valid_batch=valid_batch,
+                   valid_one_pass=valid_one_pass, valid_capture=valid_capture)
     last = epochs * sampler.n_batches
     while loop.t < last and (max_steps is None or loop.steps < max_steps):
         if loop.advance() and loop.evals % poll_every == 0 and loop.poll().stopped:

@@ -292,7 +292,8 @@ def valid_mag(model, rows, attr_indptr, attr_indices, attr_data, idx_val, labels
     validation node ids (every one a seed of `rows`); labels int64 CUDA [N].  The positions of idx_val are looked up once
     (one check, KeyError for a node that is no seed); then per batch `model.emb_rows` in eval mode (only the batch's
     neighbours are embedded, with the weights as they are now), the MLP and `eval_head` into one shared buffer, and one
-    `eval_reduce`: nothing synchronises.  The model's training flag is restored.  Same returns as `valid`."""
+    `eval_reduce`: nothing synchronises.  The model's training flag is restored.  Same returns as `valid`.  The one-pass
+    form is `valid_mag_pass(valid_mag_plan(..., one_pass=True))`."""
     plan = valid_mag_plan(model, rows, attr_indptr, attr_indices, attr_data, idx_val, labels, batch_size)
     loss, acc, counts = valid_mag_pass(plan, dropnode_rate)
     return (loss, acc, counts) if return_counts else (loss, acc)
@@ -301,7 +302,8 @@ def valid_mag(model, rows, attr_indptr, attr_indices, attr_data, idx_val, labels
 class ValidMagPlan(NamedTuple):
     """What `valid_mag` prepares once for a validation set: its arguments as checked, the node ids on the device, their
     positions in `rows` and the evaluation buffers.  Nothing in it depends on the weights: `valid_mag_pass` runs over it any
-    number of times (the fit loop) and sees the table as it is at that moment."""
+    number of times (the fit loop) and sees the table as it is at that moment.  `one` is None, or the
+    evaluate.OnePass of a plan made with one_pass=True (an attribute, not a field)."""
     model: torch.nn.Module
     rows: object
     attr: tuple
@@ -310,11 +312,21 @@ class ValidMagPlan(NamedTuple):
     pos: torch.Tensor
     buf: object
     batch_size: int
+    one = None
 
 
-def valid_mag_plan(model, rows, attr_indptr, attr_indices, attr_data, idx_val, labels, batch_size=100):
-    """The checks, the one position lookup (KeyError for a node that is no seed) and the buffers of `valid_mag`."""
-    from .evaluate import _node_ids, _on_gpu, eval_buffers
+class _OnePassValidMagPlan(ValidMagPlan):
+    """A ValidMagPlan whose instances carry `one`."""
+
+
+def valid_mag_plan(model, rows, attr_indptr, attr_indices, attr_data, idx_val, labels, batch_size=100, *, one_pass=False, fused=False):
+    """The checks, the one position lookup (KeyError for a node that is no seed) and the buffers of `valid_mag`.
+
+    one_pass=True: `valid_mag_pass` runs one eval `mag_prop_rows` over all positions, `model.infer` into the
+    plan's [n, C] logits and one `eval_tail`; batch_size is a memory bound only (chunks of it go into row slices of the one
+    logits buffer, the tail runs once).  Bit for bit the eager composition emb_rows -> infer -> eval_head -> eval_reduce,
+    whatever batch_size; `infer`'s bits, NOT promised bit-equal to one_pass=False.  fused= is `infer`'s."""
+    from .evaluate import _node_ids, _on_gpu, check_one_pass, eval_buffers, one_pass_buffers
     from .rows import RowMatrix
     if not isinstance(model, torch.nn.Module) or not hasattr(model, "emb_rows"):
         raise TypeError("valid_mag: model must be a MagMLP")
@@ -326,19 +338,30 @@ def valid_mag_plan(model, rows, attr_indptr, attr_indices, attr_data, idx_val, l
     if batch_size < 1:
         raise ValueError(f"batch_size must be >= 1, got {batch_size}")
     _on_gpu("valid_mag", model.embeds.weight, labels=labels, attr_indptr=attr_indptr, col=rows.col)
+    C = check_one_pass(model, one_pass, fused, "valid_mag")
     dev = rows.col.device
     idx = _node_ids(idx_val, "idx_val", dev)
     n = idx.numel()
+    one = one_pass_buffers(n, C, dev, fused)
     pos = rows.batch_positions(idx, check=True) if n else None
-    return ValidMagPlan(model, rows, (attr_indptr, attr_indices, attr_data), labels, idx, pos, eval_buffers(n, dev), batch_size)
+    fields = (model, rows, (attr_indptr, attr_indices, attr_data), labels, idx, pos, eval_buffers(n, dev), batch_size)
+    if one is None:
+        return ValidMagPlan(*fields)
+    plan = _OnePassValidMagPlan(*fields)
+    plan.one = one
+    return plan
 
 
-def valid_mag_pass(plan, dropnode_rate=0.5):
-    """One validation pass over a ValidMagPlan: (loss, acc, counts) as device tensors.  Nothing synchronises."""
-    from .evaluate import _NoSync, eval_head, eval_reduce
+def valid_mag_pass(plan, dropnode_rate=0.5, one_pass=None):
+    """One validation pass over a ValidMagPlan: (loss, acc, counts) as device tensors.  Nothing synchronises.  one_pass: None
+    reads it from the plan; False runs the batches over a one-pass plan too."""
+    from .evaluate import _NoSync, _resolve_one_pass, eval_head, eval_reduce, one_pass_body
     model, rows, attr, labels, idx, pos, buf, batch_size = plan
     n = idx.numel()
+    one_pass = _resolve_one_pass(plan, one_pass)
     with _NoSync(model):
+        if one_pass:
+            return one_pass_body(plan, lambda p: model.emb_rows(*attr, rows, batch_rows=p, dropnode_rate=dropnode_rate))
         for start in range(0, n, batch_size):
             end = min(start + batch_size, n)
             aug = model.emb_rows(*attr, rows, batch_rows=pos[start:end], dropnode_rate=dropnode_rate)

@@ -185,9 +185,9 @@ class MagTrainStep(TrainStep):
     # ---- what the fit loop validates with
     _valid_batch = 100             # model_mag.py:372 calls `valid` without a batch size; its default (line 145) is 100
 
-    def _valid_plan(self, idx_val, batch_size):
+    def _valid_plan(self, idx_val, batch_size, one_pass=False):
         from .mag import valid_mag_plan
-        return valid_mag_plan(self.model, self.rows, *self.attr, idx_val, self.labels, batch_size)
+        return valid_mag_plan(self.model, self.rows, *self.attr, idx_val, self.labels, batch_size, one_pass=one_pass)
 
     def _valid_pass(self, plan):
         from .mag import valid_mag_pass

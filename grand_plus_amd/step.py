@@ -308,9 +308,9 @@ class TrainStep:
         return result
 
     # ---- what the fit loop validates with (fit.FitLoop); mag_step.MagTrainStep swaps both
-    def _valid_plan(self, idx_val, batch_size):
+    def _valid_plan(self, idx_val, batch_size, one_pass=False):
         from .evaluate import valid_plan
-        return valid_plan(self.model, self.rows, self.features, idx_val, self.labels, batch_size)
+        return valid_plan(self.model, self.rows, self.features, idx_val, self.labels, batch_size, one_pass=one_pass)
 
     def _valid_pass(self, plan):
         from .evaluate import valid_pass
