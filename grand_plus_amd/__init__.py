@@ -6,7 +6,7 @@ reference's `propagation.Graph` (`api.Graph`), the caller-side recipe helpers (`
 the multi-GPU seed-sharding driver (`sharded`), the tie-aware parity comparator (`parity`)
 and the synthetic workload generator (`synth`).  The training-step pieces (`augment`, `mlp`, `objective`, `optim`) need
 torch and are imported on demand; `ClipAdam` and `clip_grad_norm` of `optim` and `valid`, `predict`, `local_logits`, `eval_head`,
-`eval_reduce`, `eval_tail` and `ValidGraph` of `evaluate`, `mag_prop_rows`, `valid_mag`, `valid_mag_plan`, `valid_mag_pass` and `predict_mag` of `mag`, `StepState` and `TrainStep` of `step`, `MagTrainStep` and `mag_trained_parameters` of `mag_step`, `RowGrad` and `BitmapRowGrad` of `optim_rows` and `fit`, `Sampler` and `BestTracker` of `fit` are reachable from here by name, and stay out of `__all__` so that `from grand_plus_amd import *` loads neither torch nor the native library.
+`eval_reduce`, `eval_tail` and `ValidGraph` of `evaluate`, `mag_prop_rows`, `valid_mag`, `valid_mag_plan`, `valid_mag_pass` and `predict_mag` of `mag`, `StepState` and `TrainStep` of `step`, `MagTrainStep` and `mag_trained_parameters` of `mag_step`, `RowGrad`, `BitmapRowGrad` and `DeferredRows` of `optim_rows` and `fit`, `Sampler` and `BestTracker` of `fit` are reachable from here by name, and stay out of `__all__` so that `from grand_plus_amd import *` loads neither torch nor the native library.
 """
 from .api import Graph, algorithmic_bytes          # noqa: F401
 from .recipes import RECIPES, Recipe, make_coef    # noqa: F401
@@ -30,7 +30,7 @@ def __getattr__(name):                              # these need torch: loaded w
     if name in ("MagTrainStep", "mag_trained_parameters"):
         from . import mag_step
         return getattr(mag_step, name)
-    if name in ("RowGrad", "BitmapRowGrad"):
+    if name in ("RowGrad", "BitmapRowGrad", "DeferredRows"):
         from . import optim_rows
         return getattr(optim_rows, name)
     if name in ("fit", "Sampler", "BestTracker"):

@@ -282,6 +282,7 @@ ABI = {
 _rows_step = [_int, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _int, _f32, _f32, _f64, _f64, _f32, _f32]   # device .. weight_decay
 # a chunked twin takes its unchunked twin's arguments up to the stream, then chunk, d_scratch, scratch_bytes and the stream
 _scatter, _chunk = ABI["grandplus_scatter.h"], [_i32, _vp, _i64, _vp]
+_defer = [_vp, _vp, _vp, _i32, _vp]                                   # d_tick, d_last, d_hist, capacity, d_flag
 _mag_dseed = _mag[:-3] + [_vp] + _mag[-2:]                            # _mag with d_seed, a device pointer, where seed stands
 PRIVATE_ABI = {
     "mag_det_abi.hpp": {
@@ -292,6 +293,15 @@ PRIVATE_ABI = {
         "gp_optim_rows_sqnorm": (_int, [_int, _vp, _i64, _i64, _i32, _vp, _int, _vp, _vp], False),
         "gp_clip_adam_rows": (_int, _rows_step + [_f32, _f32, _vp, _vp, _vp], False),
         "gp_clip_adam_rows_dev": (_int, _rows_step + [_vp, _vp, _vp, _vp, _vp], False),
+    },
+    # the deferred exact step: table, moments[, dW], [keys, n_sorted,] V, H, the group's constants, then the
+    # tick's address, last, the ring, its capacity and the flag; the step also takes gp_clip_adam_rows_dev's two corrections
+    # and its tail
+    "optim_defer_abi.hpp": {
+        "gp_optim_defer_catch_up": (_int, [_int, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _f64, _f64, _f32, _f32] + _defer + [_vp], False),
+        "gp_optim_defer_step": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _f32, _f32, _f64, _f64, _f32, _f32, _vp, _vp] +
+                                _defer + [_vp, _vp, _vp], False),
+        "gp_optim_defer_flush": (_int, [_int, _vp, _vp, _vp, _i64, _i32, _f64, _f64, _f32, _f32] + _defer + [_vp], False),
     },
     "row_mark_abi.hpp": {
         "gp_row_mark_mag": (_int, [_int, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _vp], False),

@@ -15,6 +15,7 @@
 // optim_math.hpp's, the lines optim.hip runs.  No atomics, no host read; every argument travels by value.
 #include "optim_math.hpp"
 #include "optim_rows_layout.hpp"
+#include "optim_rows_heads.hpp"
 #include "optim_rows_abi.hpp"
 
 namespace {
@@ -36,25 +37,6 @@ struct RowsArgs {
     long long n_sorted, V;
     int H;
 };
-
-// The next head rows of a window, up to R at a time: `heads` is the ballot of the window's heads, consumed lowest first;
-// returns how many rows were taken (wave-uniform).
-template <int R>
-__device__ __forceinline__ int take_heads(u64& heads, long long key, long long (&rows)[R])
-{
-    int n = 0;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        rows[r] = 0;
-        if (heads) {
-            const int l = __builtin_ctzll(heads);
-            heads &= heads - 1;
-            rows[r] = __shfl(key, l);
-            n = r + 1;
-        }
-    }
-    return n;
-}
 
 __device__ __forceinline__ u64 window_heads(const RowsArgs& R, long long win, int lane, long long& key)
 {

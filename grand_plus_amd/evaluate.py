@@ -411,7 +411,9 @@ class ValidGraph:
     pass's loss and accuracy at `state`'s tick (state: the StepState; a tracker without one is a ValueError).  The first
     `run()` executes the body eagerly (it loads code), the second captures it with torch.cuda.graph, every later one is one
     replay; each returns (loss, acc, counts), from the capture on the static tensors of the graph.  With a row_grad tracker
-    gp_fit_rows_snapshot is part of the graph.  The body is one stream, a linear chain of launches.
+    gp_fit_rows_snapshot is part of the graph.  The body is one stream, a linear chain of launches.  `before` (an attribute,
+    None by default) is a callable whose launches run in front of the pass and are captured with it: `fit` sets it to
+    `MagTrainStep.flush_table` for a deferred table.
 
     A replay reads the weights, the BatchNorm running statistics, the step state and the tracker's struct through the
     pointers of the capture: every tensor of model.state_dict() has to stay where it is, which run() checks (RuntimeError
@@ -421,6 +423,9 @@ class ValidGraph:
     def __init__(self, plan, dropnode_rate=0.5, tracker=None, state=None):
         if not isinstance(plan, tuple) or not hasattr(plan, "one") or not hasattr(plan, "model"):
             raise TypeError("ValidGraph takes a ValidPlan (valid_plan) or a ValidMagPlan (mag.valid_mag_plan)")
+        # None, or a callable whose launches belong in front of the pass and are captured with it; to be set before the second
+        # run().  `fit` sets MagTrainStep.flush_table for a deferred table
+        self.before = None
         if not 0.0 <= float(dropnode_rate) <= 1.0:
             raise ValueError(f"dropnode_rate must be in [0, 1], got {dropnode_rate}")
         if tracker is not None:
@@ -438,6 +443,9 @@ class ValidGraph:
         self._graph = self._result = self._ptrs = self._where = None
 
     def _body(self):
+        if self.before is not None:
+            self._where = "before"
+            self.before()
         self._where = "valid_pass"
         result = self._pass(self.plan, self.dropnode_rate)
         if self.tracker is not None:

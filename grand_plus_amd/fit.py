@@ -290,6 +290,8 @@ class FitLoop:
         if valid_capture:
             from .evaluate import ValidGraph
             self.valid_graph = ValidGraph(self.plan, step.dropnode_rate, self.tracker, step.state)
+            if getattr(step, "deferred", None) is not None:              # a deferred table is flushed in front of
+                self.valid_graph.before = step.flush_table               # the pass, inside the graph
         self.t = step.state.read().tick                                  # the one read of the tick
         self.steps = self.evals = 0
         self.last = None                                                 # the StepResult of the last step
@@ -302,6 +304,8 @@ class FitLoop:
             return False
         if self.valid_graph is not None:
             self.valid_graph.run()
+            if getattr(self.step, "deferred", None) is not None:
+                self.step._since_flush = 0                               # a replay flushed without running flush_table
         else:
             loss, acc, _counts = self.step._valid_pass(self.plan)
             self.tracker.update(loss, acc, self.step.state)
@@ -314,6 +318,8 @@ class FitLoop:
         return image
 
     def finish(self):
+        if getattr(self.step, "deferred", None) is not None:
+            self.step.flush_table()                                      # the moments stay the dense step's under the restored table
         image = self.tracker.restore()
         self.step.check_selection_flag()
         return FitResult(self.steps, image.best_tick or None, image.stop_tick if image.stopped else None,

@@ -15,7 +15,8 @@ occur as columns of `rows` (read once here, the constructor's one host read), an
 `table_step="exact"` or `"lazy"` (deterministic mode, or the atomic mode with `row_list="bitmap"`, §7u) steps
 the embedding table from the backward's row list instead of a dense gradient: no `torch.zeros` of [V, H] per step, no dense read of dW.  "exact" is bit for bit today's
 step.  "lazy" updates the touched rows alone and is NOT the reference's dense Adam (model_mag.py:312), under which an
-untouched row still moves while its moments decay.
+untouched row still moves while its moments decay.  "deferred"  is "exact"'s trajectory with "lazy"'s traffic: the
+untouched rows' updates are replayed when a row is next read and by `flush_table()`; between flushes the table shows lagging rows.
 
 `fit.fit` takes a MagTrainStep as it takes a TrainStep: `_valid_plan` / `_valid_pass` are `mag.valid_mag_plan` /
 `valid_mag_pass` over the step's attribute CSR and rows.  `dirty_rows=True` (with `table_step="lazy"`) has every backward mark
@@ -82,6 +83,15 @@ class MagTrainStep(TrainStep):
     the table moves in every step, so there is nothing to skip).  The step's RowGrad then tracks the rows every backward
     hands over (`RowGrad.track_dirty()`, made here, before any capture: the mark is part of every graph of the step), and
     `fit` snapshots the table row by row (`fit.BestTracker(row_grad=)`).
+    table_step="deferred" (DESIGN §7za), with either backward: the trajectory of "exact", bit for bit with the deterministic
+    backward, at the memory traffic of "lazy"; weight decay is allowed.  The zero-gradient update dense Adam gives an
+    untouched row at every step is put off: before the forward the step lists the rows the batch's bags name (the bitmap
+    kernels of §7u, min(V, max_entries) keys, the same overflow bit) and replays on them the steps they missed, in order,
+    through the dense step's own element update; `flush_table()` does so for every row.  defer_capacity: the steps of
+    history kept, a power of two in [4, 65536] (None: 1024; a ValueError with any other table_step); the step flushes by
+    itself before a row could lag further.  BETWEEN FLUSHES `model.embeds.weight` AND ITS MOMENTS SHOW LAGGING ROWS: call
+    `flush_table()` before reading them (`fit`, `_valid_pass` and `optimizer.state_dict()` do).  dirty_rows=True is refused
+    as for "exact": every row moves.
     segment_chunk: None, or C (a power of two in [64, 4096]): the deterministic table gradient sums every
     attribute's segment in chunks of C entries, so that an attribute that sits in many bags of a batch is no longer one
     serial chain.  It needs the deterministic mode (ValueError otherwise) and goes with every table_step, dirty_rows and fit.
@@ -97,7 +107,7 @@ class MagTrainStep(TrainStep):
 
     def __init__(self, model, optimizer, rows, attr_indptr, attr_indices, attr_data, labels, idx_train, idx_unlabel, *, samples,
                  dropnode_rate, lam, warmup, tem, conf=None, kind="l2", seed, capture=True, deterministic=None, max_entries=None, table_step=None,
-                 row_list=None, dirty_rows=False, segment_chunk=None, input_dropout=False):
+                 row_list=None, dirty_rows=False, segment_chunk=None, input_dropout=False, defer_capacity=None):
         from .mlp import MagMLP
         if not isinstance(model, MagMLP):
             raise ValueError("MagTrainStep takes a MagMLP (a GrandPlusMLP goes to step.TrainStep)")
@@ -137,6 +147,11 @@ class MagTrainStep(TrainStep):
         if dirty_rows and table_step != "lazy":
             raise ValueError(f"dirty_rows=True needs table_step='lazy', got table_step={table_step!r}: under None or 'exact' every "
                              "row of the table moves in every step, so a snapshot has no row to skip")
+        if table_step == "deferred":
+            from .optim_rows import check_capacity
+            defer_capacity = check_capacity(defer_capacity)
+        elif defer_capacity is not None:
+            raise ValueError(f"defer_capacity belongs to table_step='deferred', got table_step={table_step!r}")
         if not attr_indptr.is_cuda:
             raise ValueError("the step runs on the GPU only: the attribute CSR must be CUDA tensors (no CPU fallback)")
         dev = attr_indptr.device
@@ -152,10 +167,16 @@ class MagTrainStep(TrainStep):
                     lam=lam, warmup=warmup, tem=tem, conf=conf, kind=kind, seed=seed, capture=capture)
         self._entries_flag = torch.zeros(1, dtype=torch.int32, device=dev)   # bit 0: a backward had more entries than its buffer
         self.table_step, self.row_list, self.row_grad = table_step, row_list, None
+        self.deferred, self._since_flush = None, 0                   # table_step="deferred": the DeferredRows; steps since a flush
         if table_step is not None:                                   # one RowGrad for every graph of the step
             from .optim_rows import BitmapRowGrad, RowGrad
             self.row_grad = (BitmapRowGrad if row_list == "bitmap" else RowGrad)(model.embeds.weight)
-            optimizer.set_row_grad(model.embeds.weight, self.row_grad, table_step)
+            if table_step == "deferred":                             # the step's flag word takes the unserved-row bit too
+                optimizer.set_row_grad(model.embeds.weight, self.row_grad, table_step, capacity=defer_capacity,
+                                       flag=self._entries_flag)
+                self.deferred = optimizer.deferred_rows(model.embeds.weight)
+            else:
+                optimizer.set_row_grad(model.embeds.weight, self.row_grad, table_step)
         self.dirty_rows = bool(dirty_rows)
         if self.dirty_rows:
             self.row_grad.track_dirty()                              # before any capture: every graph of the step marks
@@ -175,12 +196,55 @@ class MagTrainStep(TrainStep):
         S = self.samples
         # with input dropout the kernels read the state's seed where it stands: the step's, at every replay
         seed = self.state.buf[_SEED_WORD:_SEED_WORD + 1] if self.input_dropout else 0
+        if self.deferred is not None:
+            self._catch_up(batch_rows)
+            self._where = "mag_prop_rows"
         X = self.model.emb_rows(*self.attr, self.rows, batch_rows=batch_rows, samples=S, dropnode_rate=self.dropnode_rate, seed=seed,
                                 keep=self._node_keep, deterministic=self.deterministic,
                                 max_entries=self._max_entries(batch_rows.numel()), overflow=self._entries_flag,
                                 row_grad=self.row_grad, segment_chunk=self.segment_chunk,
                                 det_input_dropout=self.input_dropout and self.deterministic)
         return X[None] if S == 1 else X
+
+    # ---- table_step="deferred" 
+    def _catch_up(self, batch_rows):
+        """Before the forward: the rows of the table that the batch's bags name, listed with the bitmap kernels of §7u
+        (min(V, max_entries) keys, the step's overflow bit), are brought through the step before.  With row_list="bitmap" the
+        backward takes this list over instead of marking a second time: the same batch and capacity, so the list it makes today."""
+        self._where = "gp_row_mark_mag"
+        V = self.model.embeds.weight.shape[0]
+        rows = self.rows
+        keys = self.deferred.list_batch(self.attr[0], self.attr[1], rows.col, rows.filled, rows.col.numel() // rows.K, rows.K,
+                                        batch_rows, min(V, self._max_entries(batch_rows.numel())), self._entries_flag)
+        self._where = "gp_optim_defer_catch_up"
+        self.deferred.catch_up(keys)
+        if self.row_list == "bitmap":
+            self.row_grad.prelisted = keys
+
+    def flush_table(self):
+        """With table_step="deferred": brings every row of the table and of its moments through the current step (one launch
+        on the current stream, capturable, no host read); afterwards they hold what table_step="exact" holds.  Between
+        flushes `model.embeds.weight` shows lagging rows.  `fit` calls it before every validation and before the best weights
+        are restored, `optimizer.state_dict()` before a checkpoint, and `step()` / `step_sampled()` themselves from a host
+        count of the steps since the last flush, before the ring of `defer_capacity` steps could be overrun.  With any other
+        table_step there is nothing to do."""
+        if self.deferred is not None:
+            self.deferred.flush()
+            self._since_flush = 0
+
+    def _before_step(self):
+        if self.deferred is not None:
+            if self._since_flush >= self.deferred.capacity:          # a row may lag by `capacity` steps, and no further
+                self.flush_table()
+            self._since_flush += 1
+
+    def step(self, train_sel, unlabel_sel):
+        self._before_step()
+        return super().step(train_sel, unlabel_sel)
+
+    def step_sampled(self, sampler, t):
+        self._before_step()
+        return super().step_sampled(sampler, t)
 
     # ---- what the fit loop validates with (DESIGN §7v)
     _valid_batch = 100             # model_mag.py:372 calls `valid` without a batch size; its default (line 145) is 100
@@ -191,12 +255,19 @@ class MagTrainStep(TrainStep):
 
     def _valid_pass(self, plan):
         from .mag import valid_mag_pass
+        self.flush_table()                                           # the pass reads the whole table: no row may lag (§7za)
         return valid_mag_pass(plan, self.dropnode_rate)
 
     def check_entries_flag(self):
         """Raises if a deterministic backward had more entries than `max_entries`, or, with row_list="bitmap", if a batch
-        named more rows than min(V, max_entries) (one device-to-host copy)."""
-        if int(self._entries_flag.item()) & 1:
+        named more rows than min(V, max_entries), or, with table_step="deferred", if a row lagged further than the ring of
+        `defer_capacity` steps serves (one device-to-host copy)."""
+        flag = int(self._entries_flag.item())
+        if flag & 2:
+            raise RuntimeError(f"a row of the table lagged more than defer_capacity = {self.deferred.capacity} steps behind the step "
+                               "count (or the count moved without DeferredRows.reset()): it was left as it was and is NOT on the "
+                               "dense trajectory; call flush_table() at least every defer_capacity steps")
+        if flag & 1:
             if self.row_list == "bitmap":
                 raise RuntimeError(f"a step's batch named more table rows than max_entries = {self.max_entries}: the row list of "
                                    "that step lacks the rows past it, and the table was not stepped on them (pass a larger "

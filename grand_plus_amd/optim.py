@@ -20,7 +20,7 @@ import torch
 
 from . import _native
 from ._common import _stream
-from .optim_rows import RowGrad, check_mode, clip_adam_rows, sqnorm
+from .optim_rows import DeferredRows, RowGrad, check_capacity, check_mode, clip_adam_rows, sqnorm
 
 __all__ = ["ClipAdam", "clip_grad_norm"]
 
@@ -120,7 +120,9 @@ class ClipAdam(torch.optim.Optimizer):
     captured graph they are the values of the capture.
 
     `set_row_grad(param, row_grad, mode)` steps one [V, H] embedding table from a row list instead of a dense
-    `.grad`: see there.  mode "lazy" is NOT the reference's dense Adam.
+    `.grad`: see there.  mode "lazy" is NOT the reference's dense Adam.  mode "deferred"  is, bit for bit, at
+    "lazy"'s memory traffic: it needs capturable=True, and `flush_rows()` brings its lagging rows up to date (`state_dict()`
+    calls it first; `load_state_dict()` makes every row current through the loaded step).
     """
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, clip_norm=0.0, *,
@@ -141,9 +143,10 @@ class ClipAdam(torch.optim.Optimizer):
         probe = torch.optim.Adam([torch.nn.Parameter(torch.empty(0))], lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
         self.clip_norm = float(clip_norm)
         self._row_grads = {}                                         # parameter -> (RowGrad, mode): set_row_grad
+        self._deferred = {}                                          # parameter -> DeferredRows, for mode "deferred"
         super().__init__(params, dict(probe.defaults))
 
-    def set_row_grad(self, param, row_grad, mode):
+    def set_row_grad(self, param, row_grad, mode, capacity=None, flag=None):
         """Steps `param`, a [V, H] embedding table of this optimiser, from `row_grad` (an optim_rows.RowGrad(param), filled by
         the deterministic backward of `mag_prop_rows(..., row_grad=row_grad)`) instead of `param.grad`, which stays None.
         The parameter counts as having a gradient: the one norm of `step()` includes its touched rows, and its state
@@ -154,11 +157,24 @@ class ClipAdam(torch.optim.Optimizer):
         its bits.  This is NOT the reference's trajectory: under dense torch.optim.Adam (model_mag.py:312) an untouched row
         still moves while its moments decay.  The group's weight_decay must be 0 in this mode (ValueError, here and in
         `step()`): a decay applied to the touched rows alone is nobody's semantics.
+        mode "deferred" (DESIGN §7za): the trajectory of "exact", bit for bit, at the memory traffic of "lazy".  The
+        zero-gradient update of an untouched row is put off and replayed, step by step through the same element update,
+        when the row is next read (`deferred_rows(param).catch_up(keys)`, before the forward) and by `flush_rows()`.
+        Weight decay is allowed.  It needs capturable=True (ValueError otherwise): the step number is read on the device.
+        capacity: the steps of history kept, a power of two in [4, 65536] (None: 1024); `flush_rows()` is due at least that
+        often.  flag: an int32 [1] tensor whose bit 1 a row that could not be served sets (None: a private one).
+        BETWEEN FLUSHES THE TABLE AND ITS MOMENTS SHOW LAGGING ROWS; `state_dict()` flushes first.
 
         A `step()` before any backward has filled the RowGrad is a RuntimeError."""
         if not isinstance(row_grad, RowGrad):
             raise TypeError(f"row_grad must be an optim_rows.RowGrad, got {type(row_grad).__name__}")
         check_mode(mode)
+        if mode == "deferred":
+            if not self.capturable:
+                raise ValueError("mode 'deferred' reads the step count on the device: it needs ClipAdam(capturable=True, state=...)")
+            capacity = check_capacity(capacity)
+        elif capacity is not None or flag is not None:
+            raise ValueError(f"capacity= and flag= belong to mode 'deferred', got mode {mode!r}")
         group = next((g for g in self.param_groups if any(p is param for p in g["params"])), None)
         if group is None:
             raise ValueError("set_row_grad: param is not a parameter of this optimiser")
@@ -166,7 +182,20 @@ class ClipAdam(torch.optim.Optimizer):
         if mode == "lazy" and float(group["weight_decay"]) != 0.0:
             raise ValueError(f"mode 'lazy' takes weight_decay = 0, the parameter's group has {group['weight_decay']}: a decay "
                              "applied to the touched rows alone is nobody's semantics")
+        self._deferred.pop(param, None)
+        if mode == "deferred":
+            self._deferred[param] = DeferredRows(self, param, self.param_groups.index(group), capacity, flag)
         self._row_grads[param] = (row_grad, mode)
+
+    def deferred_rows(self, param):
+        """The optim_rows.DeferredRows of a parameter set to mode "deferred" (KeyError otherwise)."""
+        return self._deferred[param]
+
+    def flush_rows(self):
+        """Brings every row of every table in mode "deferred" through the current step (one launch per table, capturable, no
+        host read): afterwards the tables and their moments hold what the dense step holds.  Nothing to do without one."""
+        for deferred in self._deferred.values():
+            deferred.flush()
 
     def load_state_dict(self, state_dict):
         if self.capturable:
@@ -179,8 +208,11 @@ class ClipAdam(torch.optim.Optimizer):
                 s["step"] = self._number(s["step"])
         if self.capturable:
             self.step_state.set_tick(steps.pop() if steps else 0)
+            for deferred in self._deferred.values():                 # the loaded table is current through the loaded tick
+                deferred.reset()
 
     def state_dict(self):
+        self.flush_rows()                                            # a checkpoint holds no lagging row
         out = super().state_dict()
         if self.capturable and out["state"]:
             # in self.state `step` is what a checkpoint brought (the same for all, 0 without one) and never moves
@@ -340,5 +372,8 @@ class ClipAdam(torch.optim.Optimizer):
                       betas=(float(beta1), float(beta2)), eps=float(group["eps"]), weight_decay=float(group["weight_decay"]))
         for gi, p, rg, mode in rows:
             d_step_size, d_rsqrt_bc2 = self.step_state.correction_ptrs(gi)
-            self._rows_update(gi, p, rg, mode, ws, norm, d_step_size=d_step_size, d_rsqrt_bc2=d_rsqrt_bc2)
+            if mode == "deferred":
+                self._deferred[p].step(rg, ws, norm, self.clip_norm, d_step_size, d_rsqrt_bc2)
+            else:
+                self._rows_update(gi, p, rg, mode, ws, norm, d_step_size=d_step_size, d_rsqrt_bc2=d_rsqrt_bc2)
         return norm

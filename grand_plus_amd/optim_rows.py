@@ -24,6 +24,11 @@ atomics to add into.  `ClipAdam.set_row_grad` and both row kernels take it uncha
 `RowGrad.track_dirty()` has every `fill` also mark the rows it is handed in a bitmap `dirty` that only
 accumulates here: `fit.BestTracker(row_grad=)` reads it to snapshot the table row by row, and clears it.
 
+`DeferredRows` is the state of mode "deferred": the trajectory of "exact", bit for bit, at the memory traffic of
+"lazy".  The zero-gradient update of an untouched row is put off and replayed, step by step through the dense step's own
+element update, when the row is next read and by a flush (csrc/optim_defer_abi.hpp, bound by `_native.PRIVATE_ABI` too).
+Between flushes the table and its moments show lagging rows.
+
 Left out: amsgrad, lazy mode with weight decay, Adam's moments in the best-weights snapshot (the reference
 saves the state_dict alone).
 """
@@ -34,10 +39,13 @@ import torch
 from . import _native
 from ._common import _ptr, _stream
 
-__all__ = ["RowGrad", "BitmapRowGrad", "MODES", "check_mode"]
+__all__ = ["RowGrad", "BitmapRowGrad", "DeferredRows", "MODES", "check_mode"]
 
 ROW_LIST_PARTIALS = 1024                  # GP_ROW_LIST_PARTIALS
-MODES = {"exact": 1, "lazy": 2}           # GP_OPTIM_ROWS_EXACT, GP_OPTIM_ROWS_LAZY
+# GP_OPTIM_ROWS_EXACT, GP_OPTIM_ROWS_LAZY; "deferred" has entry points of its own (csrc/optim_defer_abi.hpp) and no C constant
+MODES = {"exact": 1, "lazy": 2, "deferred": 3}
+DEFER_MIN_CAPACITY, DEFER_MAX_CAPACITY, DEFER_CAPACITY = 4, 65536, 1024   # kMinCapacity, kMaxCapacity; the default ring
+DEFER_FLAG_BIT = 2                        # gp_optim_defer::kFlagBit: bit 1 of the flag word, a row that could not be served
 
 
 def lib():
@@ -46,10 +54,21 @@ def lib():
 
 
 def check_mode(mode):
-    """`mode` as "exact" or "lazy" (ValueError otherwise)."""
+    """`mode` as "exact", "lazy" or "deferred" (ValueError otherwise)."""
     if not isinstance(mode, str) or mode not in MODES:
-        raise ValueError(f"the table step's mode must be 'exact' or 'lazy', got {mode!r}")
+        raise ValueError(f"the table step's mode must be 'exact' or 'lazy', or 'deferred', got {mode!r}")
     return mode
+
+
+def check_capacity(capacity):
+    """`capacity` of a DeferredRows ring as an int: a power of two in [4, 65536] (ValueError otherwise; None: 1024)."""
+    if capacity is None:
+        return DEFER_CAPACITY
+    if isinstance(capacity, bool) or not isinstance(capacity, int) or not DEFER_MIN_CAPACITY <= capacity <= DEFER_MAX_CAPACITY or \
+            capacity & (capacity - 1):
+        raise ValueError(f"the deferred step's capacity must be a power of two in [{DEFER_MIN_CAPACITY}, {DEFER_MAX_CAPACITY}], "
+                         f"got {capacity!r}")
+    return capacity
 
 
 class RowGrad:
@@ -128,29 +147,130 @@ class BitmapRowGrad(RowGrad):
         self.bitmap = torch.zeros((V + 31) // 32, dtype=torch.int32, device=self.device)
         self.count = torch.zeros(1, dtype=torch.int64, device=self.device)
         self.partials = torch.empty(ROW_LIST_PARTIALS, dtype=torch.int64, device=self.device)
+        self.prelisted = None                                        # the batch's row list, when it was made before the forward (§7za)
 
     def reset(self):
         self.bitmap.zero_()
+        self.prelisted = None
+
+
+def list_rows(marks, V, attr_indptr, attr_indices, col, filled, S_rows, K, batch_rows, B, capacity, overflow):
+    """The rows of the table that a batch's bags name, as a fresh int64 [capacity] list (ascending, each row once, sentinel V
+    in the tail), on the current stream: gp_row_mark_mag, then gp_row_list_compact.  marks: what owns `bitmap`, `count` and
+    `partials` (a BitmapRowGrad, a DeferredRows).  Bit 0 of `overflow` is set when more than `capacity` rows were marked."""
+    dev, stream, L = marks.device.index, _stream(marks.bitmap), _native.lib()
+    keys = torch.empty(capacity, dtype=torch.int64, device=marks.device)
+    rc = L.gp_row_mark_mag(dev, V, attr_indptr.data_ptr(), attr_indices.data_ptr(), attr_indptr.numel() - 1, col.data_ptr(),
+                           _ptr(filled), S_rows, K, _ptr(batch_rows), B, marks.bitmap.data_ptr(), stream)
+    _native.raise_for_status(rc)
+    rc = L.gp_row_list_compact(dev, V, marks.bitmap.data_ptr(), capacity, keys.data_ptr(), marks.count.data_ptr(),
+                               marks.partials.data_ptr(), overflow.data_ptr(), stream)
+    _native.raise_for_status(rc)
+    return keys
 
 
 def mark_and_list(rg, call, capacity, overflow):
     """The row list of one batch for a BitmapRowGrad, on the current stream: gp_row_mark_mag over the batch of `call` (a
     mag._Call), gp_row_list_compact into a fresh int64 [capacity] and gp_row_list_zero of the listed rows of `rg.values`.
-    Four launches, no host read.  Returns the keys; bit 0 of `overflow` is set when more than `capacity` rows were marked."""
+    Four launches, no host read.  Returns the keys; bit 0 of `overflow` is set when more than `capacity` rows were marked.
+    A list that `rg.prelisted` holds (the deferred step made it before the forward, DESIGN §7za: the same batch, the same
+    capacity, so the same list) is taken over instead of marking again: the zeroing alone is launched."""
     attr_indptr, attr_indices, _, col, _, filled, batch_rows, _ = call.tensors
     S_rows, K, B = call.scalars[:3]
     V, H = rg.shape
-    dev, stream, L = rg.device.index, _stream(rg.values), _native.lib()
-    keys = torch.empty(capacity, dtype=torch.int64, device=rg.device)
-    rc = L.gp_row_mark_mag(dev, V, attr_indptr.data_ptr(), attr_indices.data_ptr(), attr_indptr.numel() - 1, col.data_ptr(),
-                           _ptr(filled), S_rows, K, _ptr(batch_rows), B, rg.bitmap.data_ptr(), stream)
-    _native.raise_for_status(rc)
-    rc = L.gp_row_list_compact(dev, V, rg.bitmap.data_ptr(), capacity, keys.data_ptr(), rg.count.data_ptr(),
-                               rg.partials.data_ptr(), overflow.data_ptr(), stream)
-    _native.raise_for_status(rc)
-    rc = L.gp_row_list_zero(dev, keys.data_ptr(), capacity, V, H, rg.values.data_ptr(), stream)
+    keys, rg.prelisted = rg.prelisted, None
+    if keys is None or keys.numel() != capacity:
+        keys = list_rows(rg, V, attr_indptr, attr_indices, col, filled, S_rows, K, batch_rows, B, capacity, overflow)
+    rc = _native.lib().gp_row_list_zero(rg.device.index, keys.data_ptr(), capacity, V, H, rg.values.data_ptr(), _stream(rg.values))
     _native.raise_for_status(rc)
     return keys
+
+
+class DeferredRows:
+    """The deferred exact Adam step of one [V, H] embedding table: the dense trajectory, bit for bit, at the
+    memory traffic of the touched rows.  Made by `ClipAdam.set_row_grad(param, row_grad, "deferred", capacity=)`; one per table.
+
+    Under dense Adam a row no batch touches still takes the zero-gradient update of every step.  Here that update is put off
+    until the row is next read: `last` (int32 [V]) says which step each row is current through, `hist` is a ring of
+    `capacity` 16-byte entries {step_size, rsqrt_bc2, coef, tag} with the entry of step s in slot s % capacity, and the
+    missed steps are replayed in order through the dense step's own element update.  The step number is the optimiser's
+    StepState tick, read on the device: the mode needs ClipAdam(capturable=True).  All state is device memory owned here;
+    `bitmap`, `count` and `partials` are the workspace of `list_batch`.
+
+      * `catch_up(keys)`: before the forward of a step (after `state.advance`), the rows listed in `keys` -- either kind
+        of list: the deterministic backward's keys or the bitmap list -- are brought through the step before.
+      * `step(...)`: what `ClipAdam.step()` calls in place of gp_clip_adam_rows_dev.
+      * `flush()`: every row through the current tick; afterwards the table and both moments hold the dense step's bits.
+        BETWEEN FLUSHES `param` AND THE MOMENTS SHOW LAGGING ROWS: flush before reading them.
+
+    A row is served while tick - last[r] <= capacity, so a flush is due at least every `capacity` steps; a row that is not
+    served keeps its bits and sets bit 1 of `flag` (int32 [1]; a caller's own flag word may be passed in)."""
+
+    def __init__(self, optimizer, param, group_index, capacity=None, flag=None):
+        self.capacity = check_capacity(capacity)
+        self.optimizer, self.param, self.group_index = optimizer, param, group_index
+        self.shape, self.device = tuple(param.shape), param.device
+        if flag is not None and (not isinstance(flag, torch.Tensor) or flag.dtype != torch.int32 or flag.numel() != 1 or
+                                 flag.device != param.device):
+            raise TypeError(f"flag must be an int32 tensor of one element on {param.device}")
+        V = self.shape[0]
+        dev = param.device
+        self.flag = flag if flag is not None else torch.zeros(1, dtype=torch.int32, device=dev)
+        self.last = torch.zeros(V, dtype=torch.int32, device=dev)
+        self.hist = torch.zeros(self.capacity * 4, dtype=torch.int32, device=dev)
+        self.bitmap = torch.zeros((V + 31) // 32, dtype=torch.int32, device=dev)
+        self.count = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.partials = torch.empty(ROW_LIST_PARTIALS, dtype=torch.int64, device=dev)
+        self.reset()
+
+    def reset(self):
+        """Every row is current through the state's tick as it stands and the ring is empty: at construction and after a
+        checkpoint was loaded.  Device copies on the current stream, no host read."""
+        tick = self.optimizer.step_state.buf[:1]
+        self.last.copy_(tick.to(torch.int32).expand_as(self.last))
+        self.hist.zero_()
+
+    def _head(self):
+        """The arguments every entry point begins with, and the ones every entry point ends with."""
+        state = self.optimizer._init_state(self.param)
+        return (self.device.index, self.param.data_ptr(), state["exp_avg"].data_ptr(), state["exp_avg_sq"].data_ptr())
+
+    def _constants(self):
+        group = self.optimizer.param_groups[self.group_index]
+        beta1, beta2 = group["betas"]
+        return float(beta1), float(beta2), float(group["eps"]), float(group["weight_decay"])
+
+    def _tail(self):
+        return (self.optimizer.step_state.buf.data_ptr(), self.last.data_ptr(), self.hist.data_ptr(), self.capacity,
+                self.flag.data_ptr())
+
+    def list_batch(self, attr_indptr, attr_indices, col, filled, S_rows, K, batch_rows, capacity, overflow):
+        """`list_rows` of a batch over this object's bitmap: the list that `catch_up` takes before the forward."""
+        B = S_rows if batch_rows is None else batch_rows.numel()
+        return list_rows(self, self.shape[0], attr_indptr, attr_indices, col, filled, S_rows, K, batch_rows, B, capacity, overflow)
+
+    def catch_up(self, keys):
+        """gp_optim_defer_catch_up of an ascending int64 list on the current stream."""
+        V, H = self.shape
+        rc = _native.lib().gp_optim_defer_catch_up(*self._head(), keys.data_ptr(), keys.numel(), V, H, *self._constants(),
+                                                   *self._tail(), _stream(self.param))
+        _native.raise_for_status(rc)
+
+    def step(self, rg, ws, norm, max_norm, d_step_size, d_rsqrt_bc2):
+        """gp_optim_defer_step of a filled RowGrad: the workspace holds the norm's partials."""
+        V, H = self.shape
+        group = self.optimizer.param_groups[self.group_index]
+        beta1, beta2, eps, weight_decay = self._constants()
+        rc = _native.lib().gp_optim_defer_step(*self._head(), rg.values.data_ptr(), rg.keys.data_ptr(), rg.n_sorted, V, H, max_norm,
+                                               float(group["lr"]), beta1, beta2, eps, weight_decay, d_step_size, d_rsqrt_bc2,
+                                               *self._tail(), ws.data_ptr(), norm.data_ptr(), _stream(self.param))
+        _native.raise_for_status(rc)
+
+    def flush(self):
+        """gp_optim_defer_flush on the current stream: one launch, capturable."""
+        V, H = self.shape
+        rc = _native.lib().gp_optim_defer_flush(*self._head(), V, H, *self._constants(), *self._tail(), _stream(self.param))
+        _native.raise_for_status(rc)
 
 
 def sqnorm(rg, accumulate, ws):
