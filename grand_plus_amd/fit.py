@@ -129,7 +129,8 @@ def fit_select(state, sampler, n_labeled, sel, flag):
 
 def early_stop_rule(track, loss, acc, tick, stop_mode, patience):
     """The rule of gp_fit_track_update on the host, over a dict with the fields of gp_fit_track (updated in place): the
-    model the GPU tests hold the kernel to, itself held to a transcription of model.py:344-359.  loss, acc: float32."""
+    model the GPU tests hold the kernel to, itself held to the saves and the stop that the reference's own loop
+    (model.py:336-362) made on scripted validations, recorded in tests/golden/train_stop.npz.  loss, acc: float32."""
     if track["stopped"]:
         track["copy_now"] = 0
         return track
@@ -150,6 +151,13 @@ def new_track():
     """The initial image of gp_fit_track as the dict early_stop_rule takes."""
     return dict(best_loss=np.float32(np.inf), best_acc=np.float32(0), best_tick=0, stop_tick=0, bad_counter=0, n_evals=0,
                 copy_now=0, stopped=0)
+
+
+def validates_at(t, eval_batch):
+    """Whether the loop validates after step t >= 1: the reference tests `num_batch % eval_batch == 0` after the step and
+    before it advances num_batch (model.py:336, 360), so num_batch = t - 1 and steps 1, 1 + eval_batch, ... validate.
+    Held to the recorded `num_batch`es of the reference's own runs (tests/test_host_reference_training.py)."""
+    return (t - 1) % eval_batch == 0
 
 
 TrackImage = collections.namedtuple("TrackImage", [n for n, _ in GpFitTrack._fields_])
@@ -300,7 +308,7 @@ class FitLoop:
         self.t += 1
         self.last = self.step.step_sampled(self.sampler, self.t)
         self.steps += 1
-        if (self.t - 1) % self.eval_batch:
+        if not validates_at(self.t, self.eval_batch):
             return False
         if self.valid_graph is not None:
             self.valid_graph.run()

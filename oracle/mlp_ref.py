@@ -5,6 +5,9 @@ tests/test_gpu_mlp.py), never imported by the product.
 The submodule names are the reference's, so a state_dict moves between these and grand_plus_amd.mlp's modules.
 forward(X, keeps) takes one sample, as the reference calls it once per sample; keeps[i] is layer i's 0/1 mask (unused
 in eval mode).  `last_a` is the input of the last Linear, which the tests scale their output tolerance by.
+
+Pinned to the reference itself by tests/golden/train_pieces.npz (keys mlp_*) and tests/golden/train_mag.npz:
+tests/test_host_reference_training.py.
 """
 import torch
 import torch.nn as nn

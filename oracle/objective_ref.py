@@ -4,6 +4,9 @@ in tests/test_gpu_mlp.py and tests/test_gpu_embedding.py, and the timed comparis
 bench_mlp_step.py), never imported by the product.
 
 Works in the dtype and on the device of its inputs: float64 leaves give the reference gradients through autograd.
+
+Pinned to the reference itself by tests/golden/train_pieces.npz (keys cl_*) and by the step losses of
+tests/golden/train_run_*.npz: tests/test_host_reference_training.py.
 """
 import torch
 import torch.nn.functional as Fn

@@ -1,9 +1,10 @@
 """numpy/scipy float64 restatement of the propagation inside the reference's predict()
 (model.py:181-224, lines 186-210) -- TEST INFRASTRUCTURE, the checker of tests/test_gpu_propagate.py.
 
-predict() itself cannot be imported here (model.py:14 imports the un-vendored torch_scatter), and the
-reference has no test or golden vector for it: parity is unpinned by the reference and pinned by this
-line-by-line restatement with the same scipy/numpy calls.
+model.py:14 imports the un-vendored torch_scatter, so predict() is not imported by any test; with a stand-in for that
+module the reference does import and run on the CPU, and tests/golden/make_training_golden.py records what its predict()
+propagated inside whole runs of main() (tests/golden/train_run_*.npz, key `propagated`).  This restatement is pinned to
+that record by tests/test_host_reference_training.py.
 """
 import numpy as np
 

@@ -6,6 +6,8 @@ requirements.txt:7, not installed here).  Its published semantics for dim=0 are
 out[index[i]] += src[i]; `index_add_` states exactly that.  The dropout mask is an argument
 (the reference draws it from torch's global generator inside F.dropout, model.py:82), so that
 both sides of a parity test use the same mask.
+
+Pinned to the reference itself by tests/golden/train_pieces.npz (keys rp_*): tests/test_host_reference_training.py.
 """
 import torch
 

@@ -420,3 +420,20 @@ def assert_case(b, got, ref, what=None):
         assert v <= 1.0, f"{c.name}: {name} is {v:.3g} bounds off"
     assert got.nbt == ref.nbt, f"{c.name}: num_batches_tracked {got.nbt}, expected {ref.nbt}"
     return sh
+
+
+# ---- the rule of the whole model (tests/test_gpu_mlp.py, tests/test_gpu_reference_training.py)
+def model_assert_out(got, ref_out, last_a, fc):
+    """The logits of a whole model: |d| <= 2e-5 * (|a| |W|^T + |b|) + 1e-6 with a the last Linear's input, and finite."""
+    scale = last_a.detach().abs() @ fc.weight.detach().abs().t() + fc.bias.detach().abs()
+    err = (got.double() - ref_out.detach()).abs()
+    bad = err > 2e-5 * scale + 1e-6
+    assert not bool(bad.any()), f"{int(bad.sum())} outputs off, max err {float(err.max()):.3g}"
+    assert bool(torch.isfinite(got).all())
+
+
+def model_assert_grad(got, ref, name):
+    """A gradient of a whole model: rtol 1e-4, atol 1e-4 max|ref| + 1e-9."""
+    assert got is not None, name
+    scale = float(ref.abs().max())
+    torch.testing.assert_close(got.double(), ref, rtol=1e-4, atol=1e-4 * scale + 1e-9, msg=name)

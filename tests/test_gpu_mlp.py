@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 from augment_cases import rows_to_coo
-from mlp_block_cases import hashed_keep
+from mlp_block_cases import hashed_keep, model_assert_grad, model_assert_out
 from oracle.mlp_ref import RefMagMLP, RefMLP
 from oracle.objective_ref import grand_loss_ref
 
@@ -62,20 +62,7 @@ def _run_ref(ref, X64, keeps):
     return torch.stack(outs), torch.stack(lasts)
 
 
-def _assert_out(got, ref_out, last_a, fc):
-    import torch
-    scale = last_a.detach().abs() @ fc.weight.detach().abs().t() + fc.bias.detach().abs()
-    err = (got.double() - ref_out.detach()).abs()
-    bad = err > 2e-5 * scale + 1e-6
-    assert not bool(bad.any()), f"{int(bad.sum())} outputs off, max err {float(err.max()):.3g}"
-    assert bool(torch.isfinite(got).all())
-
-
-def _assert_grad(got, ref, name):
-    import torch
-    assert got is not None, name
-    scale = float(ref.abs().max())
-    torch.testing.assert_close(got.double(), ref, rtol=1e-4, atol=1e-4 * scale + 1e-9, msg=name)
+_assert_out, _assert_grad = model_assert_out, model_assert_grad       # the rule of this file, stated in mlp_block_cases
 
 
 @pytest.mark.parametrize("S", [1, 2, 4])
